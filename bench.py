@@ -35,8 +35,14 @@ next.  Every step is still one complete frame: reset, 8 spp, gather, read-back.
 Order of a run: scene and tree build on the first renderer; at N = 1 the launch-alone leg on it (Job.alone: the same frames one
 at a time before any other renderer exists -- the top level of `roofline`, `one_in_flight_*`); the other renderers of the ring
 and one frame on each so that its buffers exist and its bounce schedule has been learnt (preparation per renderer, like the
-build); W warm-up steps; then the timed region of exactly K steps.  The region is repeated (`--repeats`, default: until >= 2 s have been timed) and the line reports the MEDIAN
-region; min / max ride in `spread`.
+build); W warm-up steps; then the timed region of exactly K steps.  A plain run times that region once; with --full it is repeated
+(`--repeats`, default: until >= 2 s have been timed) and the line reports the MEDIAN region; min / max ride in `spread`.
+
+Plain run and --full: `bench.py --gpus 1 --steps K --warmup W` does only what the headline needs -- set-up, warm-up, ONE region of
+K steps, the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  --full adds everything else: the
+launch-alone leg and `roofline`, the rate without read-back, the CPU baseline, the repeated regions, the `configs` /
+`north_star` / `stand_ins_8spp` children (each a --full run of its own), the weak-scaling figure of N > 1, and bench_detail.json.
+--dump-outputs DIR writes what the timed path computed in its last step, the frame read back to the host (dump_outputs()).
 
 Launch:  python bench.py --gpus N --steps K --warmup W           (N = 1)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
@@ -748,10 +754,11 @@ def claim_stdout():
     return _REAL_STDOUT
 
 
-def emit(full, compact=True):
-    """Write the full record to bench_detail.json, then the compact line as the last (and only) line of the real stdout."""
+def emit(full, compact=True, write_detail=True):
+    """Write the full record to bench_detail.json (write_detail: --full runs), then the compact line as the last (and only) line of
+    the real stdout."""
     detail = None
-    if compact:
+    if compact and write_detail:
         for path in (os.path.join(REPO, "bench_detail.json"), os.path.join(REPO, "gpurun_out", "bench_detail.json")):
             if os.path.isdir(os.path.dirname(path)):
                 try:
@@ -791,23 +798,45 @@ def self_launch(n):
     return p.returncode
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: bytes of all the files together
+
+
+def dump_outputs(outdir, img, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the frame the timed path handed its caller in its last step (the RGBA32F sum read back to the host) as
+    DIR/accumulation.npy, float32 H x W x 4.  A frame above the limit is stored as a fixed sample instead: the same seeded set of
+    pixels in every run, accumulation_sample.npy (n x 4, float32) and their row-major pixel indices as float64 in
+    accumulation_sample_index.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes + 4096 <= limit:
+        np.save(os.path.join(outdir, "accumulation.npy"), img)
+        return
+    flat = img.reshape(-1, img.shape[-1])
+    n = (limit - 4096) // (flat.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(20240601).choice(flat.shape[0], n, replace=False))
+    np.save(os.path.join(outdir, "accumulation_sample.npy"), flat[idx])
+    np.save(os.path.join(outdir, "accumulation_sample_index.npy"), idx.astype(np.float64))
+
+
 def scene_line(args, pkg, torch, dist, orc, name, rank, world, local_rank, steps, warmup, min_seconds, with_cpu, digest):
-    """Measure one scene: the read-back-inclusive rate (value), the rate without read-back, roofline, CPU baseline."""
+    """Measure one scene: the read-back-inclusive rate (value); with --full also the rate without read-back, roofline, CPU baseline."""
     shard = tuple(int(x) for x in args.shard.split("/")) if args.shard else None
-    job = Job(args, pkg, torch, dist, name, rank, world, local_rank, shard=shard, alone_steps=3 if world == 1 and args.backend == "wavefront" else 0)
+    job = Job(args, pkg, torch, dist, name, rank, world, local_rank, shard=shard,
+              alone_steps=3 if args.full and world == 1 and args.backend == "wavefront" else 0)
     W, H = job.W, job.H
     spp = args.spp
     share = shard[1] if shard else 1  # a rank's share of a tile-sharded job renders 1 / share of the pixels
     med, regions, stats = job.measure(spp, steps, warmup, args.repeats, min_seconds, readback=True)
-    med_nr, regions_nr, _ = job.measure(spp, steps, 0, max(1, min(len(regions), 3)), 0.0, readback=False)
+    img = job.last_image().copy() if rank == 0 else None  # the frame of the last timed step
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, img)
+    med_nr = job.measure(spp, steps, 0, max(1, min(len(regions), 3)), 0.0, readback=False)[0] if args.full else None
     stats_x = job.alone_stats
     line = None
     if rank == 0:
         samples = W * H * spp * steps / share
-        img = job.last_image()
         line = {
             "value": samples / med / 1e6, "unit": "Msamples/s", "ms_per_step": med / steps * 1e3, "steps": steps,
-            "no_readback": {"value": samples / med_nr / 1e6, "ms_per_step": med_nr / steps * 1e3},
             "spread": {"regions": len(regions), "timed_s": float(sum(regions)), "min_ms_per_step": min(regions) / steps * 1e3,
                        "max_ms_per_step": max(regions) / steps * 1e3},
             "config": {
@@ -822,7 +851,9 @@ def scene_line(args, pkg, torch, dist, orc, name, rank, world, local_rank, steps
                 "frame_checksum": [float(img[..., :3].astype(np.float64).sum()), bool(np.isfinite(img).all()), bool((img[..., 3] == 1).all())],
             },
         }
-        if args.backend == "wavefront" and stats["trace_ms"] > 0:
+        if med_nr is not None:
+            line["no_readback"] = {"value": samples / med_nr / 1e6, "ms_per_step": med_nr / steps * 1e3}
+        if args.full and args.backend == "wavefront" and stats["trace_ms"] > 0:
             line["roofline"] = roofline(job, stats, digest, stats_x, line["ms_per_step"], line["config"]["segments_per_sample"])
         if stats_x:
             # latency of ONE frame batch (reset -> 8 spp -> done, nothing else on the machine); `value` is the pipelined rate
@@ -842,8 +873,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of K steps; 0 = until --min-seconds have been timed")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of K steps; 0 = until --min-seconds have been timed (default: 1, with --full or --emulate-shard 0)")
     ap.add_argument("--min-seconds", type=float, default=2.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: launch-alone leg and roofline, rate without read-back, CPU baseline, repeated "
+                         "regions, the `configs` / `north_star` children, weak scaling for N > 1, bench_detail.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes the frame of the last step, as read back to the host, to DIR (dump_outputs())")
     ap.add_argument("--scene", default="chess_like")
     ap.add_argument("--detail", type=float, default=1.0)
     ap.add_argument("--width", type=int, default=1920)
@@ -908,6 +945,8 @@ def main():
                     help="testing, N > 1: rank 0 saves EVERY host frame of the job's frame store after the strong-scaling run (npy, [L, H, W, 4]): "
                          "frame j was composed by rank j %% N")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 0 if (args.full or args.emulate_shard) else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))  # before anything touches the GPU: the ranks are CHILD processes, never an exec
     claim_stdout()
@@ -947,7 +986,7 @@ def main():
         n_ranks_seen = int(t.item())
 
     pkg = graft.load_package()  # after torch: one HIP runtime in the process
-    orc = graft.load_oracle() if (rank == 0 and not args.no_cpu_baseline) else None
+    orc = graft.load_oracle() if (rank == 0 and args.full and not args.no_cpu_baseline) else None
     digest = source_digest(pkg)
     W, H = args.width, args.height
     metric = "Msamples/s (paths*spp/s) at 1920x1080, 8spp, depth 8"
@@ -971,10 +1010,10 @@ def main():
 
     if world == 1 and not args.force_gather:
         line = scene_line(args, pkg, torch, dist, orc, args.scene, 0, 1, local_rank, args.steps, args.warmup, args.min_seconds,
-                          not args.no_cpu_baseline, digest)
+                          args.full and not args.no_cpu_baseline, digest)
         out = dict(common, scaling="strong", **line)  # N = 1 of the strong-scaling series: the named 8-spp frame
         out["config"]["parallelism"] = "pixel-tile shard x1"
-        if not args.no_extra_scenes and args.scene == "chess_like":
+        if args.full and not args.no_extra_scenes and args.scene == "chess_like":
             # Every other line is measured in a process of its own, as `bench.py --scene NAME ...` runs it (behind another scene's
             # job in THIS process atrium_like reads 10 % lower: its 460 MB tree lands in memory the first job used and freed).
             #   stand_ins_8spp  the other stand-ins at the headline's shape (1080p, 8 spp, depth 8), the same
@@ -987,7 +1026,7 @@ def main():
             mine = set(common) | {"scaling"}
 
             def child(extra, what, cpu=True):
-                cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extra-scenes", "--child", "--detail", str(args.detail),
+                cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extra-scenes", "--child", "--detail", str(args.detail),
                        "--tile", str(args.tile), "--backend", args.backend, "--cpu-seconds", str(min(args.cpu_seconds, CHILD_CPU_SECONDS))]
                 cmd += (["--no-cpu-baseline"] if args.no_cpu_baseline or not cpu else []) + [a for a in extra if a != "--no-cpu-baseline"]
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
@@ -1015,24 +1054,24 @@ def main():
             # the WHOLE frame on this GPU at the headline's shape
             out["north_star"] = child(["--scene", NORTH_STAR_SCENE, "--steps", "10", "--warmup", "2", "--repeats", "2", "--min-seconds", "0",
                                        "--width", "1920", "--height", "1080", "--spp", "8", "--depth", "8"], "north_star")
-        emit(out, compact=not args.child)
+        emit(out, compact=not args.child, write_detail=args.full)
         return
 
-    # ---- N > 1: strong scaling of the named frame is the metric; weak scaling beside it
-    job = Job(args, pkg, torch, dist, args.scene, rank, world, local_rank, alone_steps=3 if args.backend == "wavefront" else 0)
+    # ---- N > 1: strong scaling of the named frame is the metric; weak scaling beside it (--full)
+    job = Job(args, pkg, torch, dist, args.scene, rank, world, local_rank, alone_steps=3 if args.full and args.backend == "wavefront" else 0)
     med_s, regions_s, stats_s = job.measure(args.spp, args.steps, args.warmup, args.repeats, args.min_seconds, readback=True)
     img = job.last_image().copy() if rank == 0 else None  # from the job's frame store: composed by the rank that owned the last step
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, img)
     if rank == 0 and args.dump_frames:
         np.save(args.dump_frames, np.stack([job.frames.image(j, H, W) for j in range(job.L)]))
     weak_spp = args.spp * world
-    med_w, regions_w, stats_w = job.measure(weak_spp, args.steps, 1, args.repeats, args.min_seconds, readback=True)
+    med_w = job.measure(weak_spp, args.steps, 1, args.repeats, args.min_seconds, readback=True)[0] if args.full else None
     if rank == 0:
         samples = W * H * args.spp * args.steps
         out = dict(common, scaling="strong", steps=args.steps, value=samples / med_s / 1e6, ms_per_step=med_s / args.steps * 1e3,
                    spread={"regions": len(regions_s), "timed_s": float(sum(regions_s)), "min_ms_per_step": min(regions_s) / args.steps * 1e3,
                            "max_ms_per_step": max(regions_s) / args.steps * 1e3},
-                   weak={"scaling": "weak", "value": W * H * weak_spp * args.steps / med_w / 1e6, "ms_per_step": med_w / args.steps * 1e3,
-                         "workload": f"{weak_spp} spp in total = {args.spp} spp per GPU"},
                    config={"workload": f"{args.scene} (procedural stand-in for BASELINE {STAND_IN.get(args.scene, 'scenes')}), {W}x{H}, "
                                        f"{args.spp} spp, depth {args.depth}",
                            "triangles": job.n_tris, "backend": args.backend, "tile": args.tile, "frames_in_flight": job.F,
@@ -1043,7 +1082,10 @@ def main():
                                                         "k_trace_shadow": stats_s["shadow_ms"] / args.steps, "k_tail": stats_s["tail_ms"] / args.steps},
                            "frame_checksum": [float(img[..., :3].astype(np.float64).sum()), bool(np.isfinite(img).all()), bool((img[..., 3] == 1).all())]})
         out["n_ranks_seen"] = n_ranks_seen
-        if args.backend == "wavefront" and stats_s["trace_ms"] > 0:
+        if med_w is not None:
+            out["weak"] = {"scaling": "weak", "value": W * H * weak_spp * args.steps / med_w / 1e6, "ms_per_step": med_w / args.steps * 1e3,
+                           "workload": f"{weak_spp} spp in total = {args.spp} spp per GPU"}
+        if args.full and args.backend == "wavefront" and stats_s["trace_ms"] > 0:
             # as at N = 1: the launch ALONE on rank 0's GPU (its tile shard of the frame, before the other frames in flight exist)
             out["roofline"] = roofline(job, stats_s, digest, job.alone_stats)
             out["roofline"]["measured_on"] = f"rank 0's 1 / {world} tile shard of the frame, launch alone on its GPU"
@@ -1056,7 +1098,7 @@ def main():
     dist.barrier()
     dist.destroy_process_group()
     if rank == 0:  # after the process group is gone: nothing prints behind the line
-        emit(out)
+        emit(out, write_detail=args.full)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -26,6 +28,23 @@ def build(force: bool = False) -> None:
     src = [os.path.join(HERE, f) for f in ("pt_oracle.c", "pt_oracle_post.c", "pt_oracle.h", "pt_oracle_math.h")]
     if force or not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in src):
         subprocess.check_call(["make", "-C", HERE, "-B" if force else "-s", "libpt_oracle.so"])
+
+
+REF_DIR = os.path.join(HERE, "_ref")  # reference binaries (git-ignored): what build_ref() compiles from the reference tree
+
+
+def build_ref() -> None:
+    """The generators of tests/golden/ -- the reference's own shader arithmetic compiled by tools/gen_golden.py -- kept as
+    oracle/_ref/golden_{libm,fixed}, so that the fixtures can be regenerated where the reference tree is absent.  Nothing to do
+    where the reference tree is absent; rebuilt when the generator's sources are newer than the binaries."""
+    tools = os.path.join(os.path.dirname(HERE), "tools")
+    src = [os.path.join(tools, f) for f in ("gen_golden.py", "glsl_shim.hpp", "golden_main.inc")]
+    exes = [os.path.join(REF_DIR, "golden_" + m) for m in ("libm", "fixed")]
+    newest = max(os.path.getmtime(f) for f in src)
+    if all(os.path.exists(e) and os.path.getmtime(e) >= newest for e in exes):
+        return
+    with tempfile.TemporaryDirectory(prefix="ptgolden_") as tmp:
+        subprocess.check_call([sys.executable, src[0], "--if-present", "--out", tmp, "--bin", REF_DIR], stdout=subprocess.DEVNULL)
 
 
 _lib = None

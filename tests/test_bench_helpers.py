@@ -223,3 +223,52 @@ def test_fetch_size_factor_follows_the_measured_calibration(tmp_path):
     doc = json.load(open(out))
     assert doc["k_trace_closest"]["hbm_bytes_per_launch"] == (1000.0 + 100.0) * 1024 and doc["k_trace_closest"]["hbm_bytes_per_launch_upper"] == 2100.0 * 1024
     assert doc["k_generate"]["hbm_bytes_per_launch"] == (2 * 10.0 + 2000.0) * 1024 and doc["k_generate"]["fetch_factor"] == 2.0
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: a frame under the limit is stored whole (float32); above it the same seeded pixels are stored every run, with
+    their indices, and the files together stay within the limit."""
+    import numpy as np
+
+    img = np.random.default_rng(3).random((40, 50, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    back = np.load(tmp_path / "whole" / "accumulation.npy")
+    assert back.dtype == np.float32 and (back == img).all()
+    limit = 20000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, limit=limit)
+        assert not (tmp_path / d / "accumulation.npy").exists()
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    sample, index = np.load(tmp_path / "a" / "accumulation_sample.npy"), np.load(tmp_path / "a" / "accumulation_sample_index.npy")
+    assert sample.dtype == np.float32 and index.dtype == np.float64 and len(sample) == len(index) > 100
+    assert (sample == img.reshape(-1, 4)[index.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "b" / "accumulation_sample_index.npy") == index).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_k_steps_and_dumps_the_last_frame(pkg, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one region of exactly K steps, the headline keys and nothing that
+    needs runs of its own (no CPU leg, no roofline, no `configs` children, no detail file); --dump-outputs writes the frame of the
+    last step, which is the frame one renderer computes for the same scene and shape, bit for bit."""
+    import numpy as np
+
+    W, H = 328, 200
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--scene", "chess_like",
+                        "--detail", "0.05", "--width", str(W), "--height", str(H), "--spp", "4", "--depth", "6", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in line, k
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert not {"cpu_baseline", "roofline", "configs", "north_star", "no_readback_value", "detail"} & set(line)
+    got = np.load(tmp_path / "out" / "accumulation.npy")
+    scene = pkg.Scene("chess_like", 0.05)
+    r = pkg.Renderer()
+    r.upload(scene)
+    r.resize(W, H)
+    r.render_frames(scene.uniform(W, H, bounces=6), scene.lights, 0, 4)
+    ref = r.readback()
+    r.close()
+    assert got.dtype == np.float32 and got.shape == (H, W, 4) and (got.view(np.uint32) == ref.view(np.uint32)).all()

@@ -147,7 +147,7 @@ def _run_bench_two_ranks(tmp_path, backend, extra=(), launcher=True):
     cmd = [sys.executable]
     if launcher:  # as the driver starts an N > 1 run
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-    cmd += [os.path.join(REPO, "bench.py"), "--gpus", "2", "--single-device", "--dist-backend", backend,
+    cmd += [os.path.join(REPO, "bench.py"), "--gpus", "2", "--single-device", "--dist-backend", backend, "--full",
             "--steps", "2", "--warmup", "1", "--repeats", "1", "--scene", "chess_like", "--detail", "0.05", "--width", "328", "--height", "200",
             "--spp", "4", "--depth", "6", "--cpu-seconds", "1", "--dump-image", str(out), "--dump-frames", str(tmp_path / f"frames_{backend}.npy"), *extra]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -226,7 +226,7 @@ def test_rccl_gather_branch_runs_with_one_rank(pkg, tmp_path, collective):
     out = tmp_path / "gathered_rccl1.npy"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", NCCL_DEBUG="WARN", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-gather", "--dist-backend", "nccl", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--full", "--force-gather", "--dist-backend", "nccl", "--steps", "3", "--warmup", "1",
            "--repeats", "1", "--scene", "chess_like", "--detail", "0.05", "--width", "328", "--height", "200", "--spp", "4", "--depth", "6",
            "--in-flight", "3", "--cpu-seconds", "1", "--dump-image", str(out), "--collective", collective]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)

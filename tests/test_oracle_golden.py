@@ -367,20 +367,27 @@ def test_analytic_checks(orc, pkg):
     assert np.abs(gram - np.eye(3)).max() < 1e-5
 
 
-def test_golden_fixtures_regenerate_byte_for_byte_from_the_reference(tmp_path):
-    """The committed fixtures ARE what tools/gen_golden.py makes of the reference's shader text today: wherever /root/reference
-    exists (this container; not the GPU box) the generator runs into a scratch directory and every archive must come out
-    byte-identical to tests/golden/.  A fixture edited by hand, a generator that drifted from the committed vectors, or a
-    reference that changed under them fails here."""
+def test_golden_fixtures_regenerate_byte_for_byte_from_the_reference(tmp_path, orc):
+    """The committed fixtures ARE what tools/gen_golden.py makes of the reference's shader text: where the reference tree is
+    present the generator runs into a scratch directory, elsewhere the generators build() compiled from that text into oracle/_ref
+    (oracle.build_ref) run, and every archive must come out byte-identical to tests/golden/.  A fixture edited by hand, a
+    generator that drifted from the committed vectors, or a reference that changed under them fails here."""
     import gzip
     import subprocess
     import sys
 
-    ref = "/root/reference/Path-Tracing/Shaders"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree is not present (GPU box)")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(repo, "tools", "gen_golden.py"), "--out", str(tmp_path)], capture_output=True, text=True, timeout=900)
+    gen = os.path.join(repo, "tools", "gen_golden.py")
+    sys.path.insert(0, os.path.join(repo, "tools"))
+    import gen_golden
+
+    if os.path.isdir(gen_golden.REF):
+        cmd = [sys.executable, gen, "--out", str(tmp_path)]
+    elif all(os.path.exists(os.path.join(orc.REF_DIR, "golden_" + m)) for m, _ in gen_golden.MODES):
+        cmd = [sys.executable, gen, "--from-bin", orc.REF_DIR, "--out", str(tmp_path)]
+    else:
+        pytest.skip("neither the reference tree nor the generators compiled from it (oracle/_ref) are present")
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     made = sorted(f for f in os.listdir(tmp_path) if f.endswith(".json") or f.endswith(".json.gz"))
     committed = sorted(f for f in os.listdir(util.GOLDEN_DIR) if f.endswith(".json.gz"))

@@ -7,7 +7,7 @@ for r in $(seq 1 $ROUNDS); do
   for n in "$@"; do
     for s in $SCENES; do
       if [ "$n" = product ]; then unset PTX_HIP_LIB; else export PTX_HIP_LIB=$PWD/tools/ab/libptx_$n.so; fi
-      python3 bench.py --no-extra-scenes --no-cpu-baseline --scene $s --steps 20 --warmup 3 ${AB_ARGS} > /dev/null 2>&1; python3 -c "
+      python3 bench.py --full --no-extra-scenes --no-cpu-baseline --scene $s --steps 20 --warmup 3 ${AB_ARGS} > /dev/null 2>&1; python3 -c "
 import json,sys
 d=json.load(open('bench_detail.json'))   # the full record of the run that has just ended
 rf=d.get('roofline',{})

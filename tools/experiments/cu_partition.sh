@@ -8,7 +8,7 @@ val() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('   v
 for s in ${SCENES:-chess_like atrium_like temple_like street_like}; do
   for m in ${MODES:-0 1 2 3 4 5 6 7}; do
     echo "$s PTX_CU_PARTITION=$m whole frame"
-    PTX_CU_PARTITION=$m python3 bench.py --scene $s --no-extra-scenes --no-cpu-baseline --steps 20 --warmup 4 --min-seconds 1.5 2>/dev/null | tail -1 | val
+    PTX_CU_PARTITION=$m python3 bench.py --full --scene $s --no-extra-scenes --no-cpu-baseline --steps 20 --warmup 4 --min-seconds 1.5 2>/dev/null | tail -1 | val
   done
 done
 for m in ${MODES:-0 1 2 3 4 5 6 7}; do

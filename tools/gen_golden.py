@@ -22,6 +22,7 @@ Only inputs/outputs (uint32 bit patterns) are committed.
 """
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -31,6 +32,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "..", "tests", "golden")
 if "--out" in sys.argv:  # tests/test_oracle_golden.py regenerates into a scratch directory and compares with the committed archives
     OUT = sys.argv[sys.argv.index("--out") + 1]
+# --bin DIR: also keep the two compiled generators (golden_libm, golden_fixed) in DIR -- oracle.build_ref() puts them in oracle/_ref/;
+# --from-bin DIR: no reference needed, the kept generators write the vectors (the test where only oracle/_ref/ exists)
+BIN = sys.argv[sys.argv.index("--bin") + 1] if "--bin" in sys.argv else None
+FROM_BIN = sys.argv[sys.argv.index("--from-bin") + 1] if "--from-bin" in sys.argv else None
+MODES = (("libm", []), ("fixed", ["-DSHIM_FIXED"]))
 
 # (file, [(first_line, last_line), ...])  1-based inclusive
 SOURCES = [
@@ -89,7 +95,23 @@ def write_gz(dst, data):
         f.write(data)
 
 
+def write_vectors(exe, mode):
+    """Run one compiled generator: the function-level cases, then the stage-level cases into their own file."""
+    for arg, name in (([], "golden_%s.json.gz"), (["stage"], "golden_stage_%s.json.gz")):
+        data = subprocess.check_output([exe] + arg)
+        dst = os.path.join(OUT, name % mode)
+        write_gz(dst, data)
+        print("wrote", os.path.relpath(dst), len(data), "bytes")
+
+
 def main():
+    if FROM_BIN:
+        os.makedirs(OUT, exist_ok=True)
+        for mode, _ in MODES:
+            write_vectors(os.path.join(FROM_BIN, "golden_" + mode), mode)
+        return
+    if not os.path.isdir(REF) and "--if-present" in sys.argv:
+        return  # oracle.build_ref(): nothing to build where the reference tree is absent
     if not os.path.isdir(REF):
         raise SystemExit("reference not present; golden vectors can only be regenerated in the build container")
     os.makedirs(OUT, exist_ok=True)
@@ -184,18 +206,14 @@ def main():
         open(cpp, "w").write("\n".join(parts))
         if os.environ.get("PT_GOLDEN_KEEP"):  # debugging the shim: a copy of the generated file OUTSIDE the repository
             open(os.environ["PT_GOLDEN_KEEP"], "w").write("\n".join(parts))
-        for mode, flag in (("libm", []), ("fixed", ["-DSHIM_FIXED"])):
+        for mode, flag in MODES:
             exe = os.path.join(tmp, "golden_" + mode)
             cmd = ["g++", "-std=c++20", "-O1", "-ffp-contract=off", "-fno-fast-math", "-w"] + flag + [cpp, "-o", exe, "-lm"]
             subprocess.check_call(cmd)
-            data = subprocess.check_output([exe])
-            dst = os.path.join(OUT, "golden_%s.json.gz" % mode)
-            write_gz(dst, data)
-            print("wrote", os.path.relpath(dst), len(data), "bytes")
-            data = subprocess.check_output([exe, "stage"])  # the stage-level cases go into their own file
-            dst = os.path.join(OUT, "golden_stage_%s.json.gz" % mode)
-            write_gz(dst, data)
-            print("wrote", os.path.relpath(dst), len(data), "bytes")
+            write_vectors(exe, mode)
+            if BIN:
+                os.makedirs(BIN, exist_ok=True)
+                shutil.copy2(exe, os.path.join(BIN, "golden_" + mode))
 
 
 if __name__ == "__main__":

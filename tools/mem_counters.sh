@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 SC=${1:-chess_like}
-CMD="python3 bench.py --scene $SC --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline --no-extra-scenes --in-flight 1"
+CMD="python3 bench.py --full --scene $SC --steps 3 --warmup 1 --repeats 1 --no-cpu-baseline --no-extra-scenes --in-flight 1"
 i=0
 for set in "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum" \
            "TA_TA_BUSY_sum GRBM_GUI_ACTIVE" \

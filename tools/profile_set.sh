@@ -14,6 +14,7 @@ for a in "$@"; do
   [ "$prev" = "--depth" ] && DEPTH=$a; [ "$prev" = "--shard" ] && SHARD=$a; prev=$a
 done
 SHAPE="${W}x${H}/${SPP}spp/d${DEPTH}/shard${SHARD%/*}of${SHARD#*/}"   # bench.py shape_key()
+set -- --full "$@"   # every bench.py run of the set, profiled or not, is the full benchmark (launch-alone leg, roofline, ...)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
