@@ -552,7 +552,13 @@ PTX_API int ptx_bind_accumulation(PtxRenderer *r, void *devPtr, size_t bytes);
 /* traceRayEXT stand-in on explicit rays, 8 floats each (ox,oy,oz,tmin, dx,dy,dz,tmax):
  * closest hit (anyHit = 0, gl_RayFlagsNoneEXT, raygen.rgen:68) or occlusion (anyHit = 1,
  * TerminateOnFirstHit, raygen.rgen:31).  hits: 4 floats per ray (t, u, v, hit ? 1 : 0);
- * ids: 2 uints per ray ((instance,mesh) pair index, primitive index; 0xffffffff = miss). */
+ * ids: 2 uints per ray ((instance,mesh) pair index, primitive index; 0xffffffff = miss).
+ * A ray whose walk needs more traversal-stack entries than the stack holds fails the call
+ * with PTX_ERROR_DEVICE (as ptx_render does) instead of returning its hit.
+ * Diagnostic modes (closest hit, one thread per ray, no overflow check; hits as above):
+ *   anyHit = 2: ids = (node visits, triangle tests)
+ *   anyHit = 3: ids = (deepest traversal-stack position, node visits); the position counts
+ *               on past the stack's capacity, so a value above it means the walk overflowed. */
 PTX_API int ptx_trace_rays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, float *hits, uint32_t *ids);
 
 /* ------------------------------------------------------------------------- */

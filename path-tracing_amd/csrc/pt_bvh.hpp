@@ -380,7 +380,9 @@ PT_DEV int visitNode(const BvhNode *__restrict__ np, f3 o, f3 id, float tmin, fl
 // Culling against the current best leaves room for the triangle test's own error in t (Moeller-Trumbore from a far
 // origin: ~1e-5 relative): two triangles in one plane can report the SAME t while the point o + t d lies a few 1e-5
 // outside the second one's padded box; it must still be visited for the id tie-break (seen by the oracle's tree on
-// street_like at 1920x1080; this tree's quantisation margin happened to cover it).
+// street_like at 1920x1080; this tree's quantisation margin happened to cover it).  No test scene reaches this case today:
+// with the boxes' padding and quantisation, tests/test_tree_adversarial.py's overlapping coplanar quads 100-1000 units from
+// the ray origins pass with a slack of 1.0 as well.
 constexpr float kCullSlack = 1.0001f;
 
 // A ray whose origin/direction is not finite, whose direction is zero or whose interval is
@@ -399,9 +401,11 @@ PT_DEV f3 fastInverse(f3 d) { return F3(__builtin_amdgcn_rcpf(d.x), __builtin_am
 
 // Closest hit = min t over all triangles the ray hits in (tmin, tmax); ties go to the
 // smaller (pair, prim), i.e. the smaller global triangle id -- independent of tree shape.
+// STATS: counts node visits and triangle tests, and with stackDepth the deepest stack position the walk reached (entries held
+// at once, counted on past the capacity of the stack: a walk that overflowed reports more than it can hold).
 template <bool ANY_HIT, bool STATS = false, bool ALPHA = false>
 PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, Stack &st, Hit &best, uint32_t *nodeVisits = nullptr,
-                     uint32_t *triTests = nullptr, Decal *decalOut = nullptr)
+                     uint32_t *triTests = nullptr, Decal *decalOut = nullptr, uint32_t *stackDepth = nullptr)
 {
     Decal decal = noDecal();
     if (ALPHA && decalOut)
@@ -442,6 +446,8 @@ PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, S
                 if (h > 1) st.push((uint32_t)r1);
                 ref = h > 0 ? r0 : kRefNone;
             }
+            if (STATS && stackDepth && (uint32_t)st.sp > *stackDepth)
+                *stackDepth = (uint32_t)st.sp;
             if (ref == kRefNone)
             {
                 if (st.sp == 0)

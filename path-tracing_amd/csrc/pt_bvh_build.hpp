@@ -90,6 +90,9 @@ __global__ void k_tri_setup(uint32_t n, uint32_t pairCount, const uint32_t *__re
     {
         const float q1 = p0[a] + a1[a], q2 = p0[a] + a2[a];
         const float mn = fminf(p0[a], fminf(q1, q2)), mx = fmaxf(p0[a], fmaxf(q1, q2));
+        // (A nearly degenerate triangle -- edge cross product not exactly zero, area ~1e-8 -- is live, but its det is a rounding
+        // residue and the triangle test can accept points far outside this box: brute force then reports hits no tree walk
+        // reaches.  Exactly zero-area triangles are inert above; the adversarial tests build theirs exactly collinear.)
         const float pad = 1e-5f * fmaxf(fabsf(mn), fabsf(mx)) + 5e-4f * (mx - mn) + 1e-7f;
         l[a] = mn - pad;
         h[a] = mx + pad;
@@ -719,8 +722,12 @@ __global__ void k_ploc_init(uint32_t n, const uint32_t *__restrict__ vals, const
     cHi[i] = boxHi[g];
 }
 
-// pairs are ordered by (union area, lower position, higher position): a strict total order, so the globally
-// smallest pair is always mutual and every iteration merges at least once
+// pairs are ordered by (union area, distance, parity of the lower position, lower position): a strict total order (distance and
+// lower position fix the pair), so the globally smallest pair is always mutual and every iteration merges at least once.  Among
+// equal areas -- clusters with bit-identical boxes, e.g. duplicated geometry -- a position pairs with a neighbour, and with the
+// one that makes the lower position even: (0 1) (2 3) ... merge in the same iteration and N duplicates become a balanced subtree.
+// (Ordering ties by (lower, higher) position alone had every position choose the pair (first, first + 1) of its window: one merge
+// per iteration, N duplicates a chain N leaves deep that no traversal stack could hold.)
 // `shape`: weight of a compactness term in the merge metric, area + shape * (longest extent)^2 -- the surface area of the union of
 // two flat boxes does not tell a square from a strip.  Symmetric in (i, j) like the area, so the order stays total.
 __global__ void k_ploc_nearest(uint32_t count, uint32_t radius, float shape, const float4 *__restrict__ cLo, const float4 *__restrict__ cHi, uint32_t *__restrict__ nn)
@@ -732,7 +739,7 @@ __global__ void k_ploc_nearest(uint32_t count, uint32_t radius, float shape, con
     const uint32_t first = i > radius ? i - radius : 0u;
     const uint32_t last = i + radius < count ? i + radius : count - 1u;
     float best = 3.0e38f;
-    uint32_t bestJ = i == first ? last : first, bestA = 0xffffffffu, bestB = 0xffffffffu;
+    uint32_t bestJ = i == first ? last : first, bestA = 0xffffffffu, bestD = 0xffffffffu;
     for (uint32_t j = first; j <= last; j++)
     {
         if (j == i)
@@ -741,13 +748,14 @@ __global__ void k_ploc_nearest(uint32_t count, uint32_t radius, float shape, con
         const float dx = fmaxf(hi.x, h.x) - fminf(lo.x, l.x), dy = fmaxf(hi.y, h.y) - fminf(lo.y, l.y), dz = fmaxf(hi.z, h.z) - fminf(lo.z, l.z);
         const float longest = fmaxf(dx, fmaxf(dy, dz));
         const float area = (dx * dy + dy * dz + dz * dx) + shape * longest * longest;
-        const uint32_t a = i < j ? i : j, b = i < j ? j : i;
-        if (area < best || (area == best && (a < bestA || (a == bestA && b < bestB))) || bestA == 0xffffffffu)
+        const uint32_t a = i < j ? i : j, d = i < j ? j - i : i - j;
+        const bool tieWins = d < bestD || (d == bestD && ((a & 1u) < (bestA & 1u) || ((a & 1u) == (bestA & 1u) && a < bestA)));
+        if (area < best || (area == best && tieWins) || bestA == 0xffffffffu)
         {
             best = area;
             bestJ = j;
             bestA = a;
-            bestB = b;
+            bestD = d;
         }
     }
     nn[i] = bestJ;

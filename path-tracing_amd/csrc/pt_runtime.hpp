@@ -2679,9 +2679,11 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
     HIP_TRY(r, hipSetDevice(r->device));
     DevBuf<float4> dRays, dHits;
     DevBuf<uint2> dIds;
+    DevBuf<uint32_t> dOverflow; // the call's own count: a render whose counters are still to be collected keeps its C_OVERFLOW
     HIP_TRY(r, dRays.alloc((size_t)n * 2));
     HIP_TRY(r, dHits.alloc(n));
     HIP_TRY(r, dIds.alloc(n));
+    HIP_TRY(r, dOverflow.alloc(1));
     TraceScene sc;
     sc = makeTraceScene(r);
     hipError_t e = hipMemcpyAsync(dRays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice, r->stream);
@@ -2689,15 +2691,21 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
     {
         (void)hipEventRecord(r->evT0, r->stream);
         (void)hipMemsetAsync(&r->counters.p[C_CHUNK], 0, sizeof(uint32_t), r->stream);
+        (void)hipMemsetAsync(dOverflow.p, 0, sizeof(uint32_t), r->stream);
         if (sceneOf(r)->anyNonOpaque)
-            k_trace_rays<true><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p);
+            k_trace_rays<true><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p,
+                                                                     dOverflow.p);
         else
-            k_trace_rays<false><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p);
+            k_trace_rays<false><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p,
+                                                                      dOverflow.p);
         (void)hipEventRecord(r->evT1, r->stream);
         e = hipMemcpyAsync(hits, dHits.p, (size_t)n * 16, hipMemcpyDeviceToHost, r->stream);
     }
     if (e == hipSuccess)
         e = hipMemcpyAsync(ids, dIds.p, (size_t)n * 8, hipMemcpyDeviceToHost, r->stream);
+    uint32_t overflowed = 0;
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(&overflowed, dOverflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(r->stream);
     if (e == hipSuccess)
@@ -2705,8 +2713,10 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, r->evT0, r->evT1);
     r->stats.lastTraceMs = ms;
-    dRays.release(); dHits.release(); dIds.release();
+    dRays.release(); dHits.release(); dIds.release(); dOverflow.release();
     if (e != hipSuccess)
         return fail(r, PTX_ERROR_DEVICE, "ptx_trace_rays: %s", hipGetErrorString(e));
+    if (overflowed)
+        return fail(r, PTX_ERROR_DEVICE, "ptx_trace_rays: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
     return PTX_OK;
 }

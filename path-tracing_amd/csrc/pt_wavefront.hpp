@@ -1278,27 +1278,30 @@ struct RaysIO
 
 template <bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_rays(TraceScene sc, const float4 *__restrict__ rays, uint32_t n, int anyHit,
-                                                        float4 *__restrict__ outHit, uint2 *__restrict__ outIds, uint32_t *chunkCounter, uint32_t *spill)
+                                                        float4 *__restrict__ outHit, uint2 *__restrict__ outIds, uint32_t *chunkCounter, uint32_t *spill,
+                                                        uint32_t *overflowCount)
 {
     PT_DECLARE_STACK(st, kLdsStack, spill)
-    if (anyHit == 2) // diagnostics: closest hit, returning (node visits, triangle tests) instead of ids
+    if (anyHit >= 2) // diagnostics (include/ptx.h): closest hit, returning (node visits, triangle tests) or (deepest stack position, node visits)
     {
         for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
         {
             const float4 o = rays[2 * i], d = rays[2 * i + 1];
             Hit h;
-            uint32_t nv = 0, nt = 0;
-            const bool hitAny = traceRay<false, true, ALPHA>(sc, F3(o.x, o.y, o.z), F3(d.x, d.y, d.z), o.w, d.w, st, h, &nv, &nt);
+            uint32_t nv = 0, nt = 0, depth = 0;
+            const bool hitAny = traceRay<false, true, ALPHA>(sc, F3(o.x, o.y, o.z), F3(d.x, d.y, d.z), o.w, d.w, st, h, &nv, &nt, nullptr, &depth);
             outHit[i] = make_float4(h.t, h.u, h.v, hitAny ? 1.0f : 0.0f);
-            outIds[i] = make_uint2(nv, nt);
+            outIds[i] = anyHit == 2 ? make_uint2(nv, nt) : make_uint2(depth, nv);
         }
-        return;
+        return; // a walk past the stack shows in its depth: the diagnostic modes do not fail on it
     }
     RaysIO io = { rays, outHit, outIds };
     if (anyHit)
         persistentTrace<true, ALPHA>(sc, io, n, chunkCounter, st);
     else
         persistentTrace<false, ALPHA>(sc, io, n, chunkCounter, st);
+    if (st.overflow)
+        atomicAdd(overflowCount, 1u);
 }
 
 // shard pack / unpack: tile-major dense buffer [ownedTile][tileSize^2] of RGBA32F

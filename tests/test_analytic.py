@@ -116,51 +116,9 @@ def test_reflection_lobes_are_reciprocal(pkg, orc):
 # ---------------------------------------------------------------------------------------
 # image level: hand-built scenes with closed-form pixels
 # ---------------------------------------------------------------------------------------
-def _mr_material(color=(1, 1, 1), roughness=1.0, metalness=0.0, ior=1.5, transmission=0.0, att_color=(1, 1, 1), att_dist=1e32):
-    m = np.zeros(24, np.float32)
-    m[4:8] = (*color, 1.0)
-    m[8], m[9], m[10], m[11] = roughness, metalness, ior, transmission
-    m[12:15] = att_color
-    m[15] = att_dist
-    m.view(np.uint32)[19:24] = (4, 0, 1, 2, 3)  # default emissive / colour / normal / roughness / metallic texels
-    return m
-
-
-class _HandScene:
-    """A PtxSceneDesc assembled from numpy arrays (kept alive here): quads in world space, one material each."""
-
-    def __init__(self, pkg, quads, materials):
-        verts, inds, geos, meshes = [], [], [], []
-        for q, (corners, normal) in enumerate(quads):
-            corners = np.asarray(corners, np.float32)
-            n = np.asarray(normal, np.float32)
-            assert np.cross(corners[1] - corners[0], corners[2] - corners[0]) @ n > 0, "winding must agree with the normal"
-            t = corners[1] - corners[0]
-            t /= np.linalg.norm(t)
-            b = np.cross(n, t)
-            for k in range(4):
-                verts.append(np.concatenate([corners[k], [k in (1, 2), k in (2, 3)], n, t, b]))
-            geos.append((4 * q, 4, 6 * q, 6, 1, 0, (0, 0)))
-            inds += [0, 1, 2, 2, 3, 0]
-            meshes.append((q, (q << 8) | 0, 0))
-        self.vertices = np.asarray(verts, np.float32)
-        self.indices = np.asarray(inds, np.uint32)
-        self.transforms = np.float32([[1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]])
-        self.geometries = np.array(geos, util.GEOMETRY_DT)
-        self.materials = np.ascontiguousarray(np.stack(materials), np.float32)
-        self.meshes = np.array(meshes, util.MESH_DT)
-        self.models = np.array([(0, len(quads))], util.MODEL_DT)
-        self.instances = np.array([(0, self.transforms[0])], util.INSTANCE_DT)
-        d = pkg.SceneDesc()
-        d.vertices, d.vertexCount = self.vertices.ctypes.data, len(self.vertices)
-        d.indices, d.indexCount = self.indices.ctypes.data, len(self.indices)
-        d.transforms, d.transformCount = self.transforms.ctypes.data, 1
-        d.geometries, d.geometryCount = self.geometries.ctypes.data, len(self.geometries)
-        d.metallicRoughnessMaterials, d.metallicRoughnessMaterialCount = self.materials.ctypes.data, len(self.materials)
-        d.meshes, d.meshCount = self.meshes.ctypes.data, len(self.meshes)
-        d.models, d.modelCount = self.models.ctypes.data, 1
-        d.instances, d.instanceCount = self.instances.ctypes.data, 1
-        self.desc = d
+def _hand_scene(pkg, quads, material):
+    """Quads in world space (corners, normal), one mesh each, all with one material."""
+    return util.TriangleSoup(pkg, [[util.quad_mesh(c, n) for c, n in quads]], material=material)
 
 
 def _lights(pkg, color, direction, dark_point_lights=0):
@@ -194,7 +152,7 @@ def test_direct_light_pixel_in_closed_form(pkg, orc, dark_lights):
     S = 6.0
     plane = ([[-S, 0, -S], [-S, 0, S], [S, 0, S], [S, 0, -S]], [0, 1, 0])
     albedo = np.float64([0.8, 0.5, 0.3])
-    hs = _HandScene(pkg, [plane], [_mr_material(color=albedo, roughness=1.0)])
+    hs = _hand_scene(pkg, [plane], util.mr_material(color=albedo, roughness=1.0))
     osc = orc.OracleScene(hs.desc)
     cam = pkg.Scene("default")
     pos, look = np.float32([0.0, 3.0, -4.0]), np.float32([0.0, -0.6, 0.8])
@@ -253,8 +211,8 @@ def test_beer_lambert_slab_in_closed_form(pkg, orc):
     front = ([[-S, -S, 0], [-S, S, 0], [S, S, 0], [S, -S, 0]], [0, 0, -1])   # outward normals, winding to match
     back = ([[-S, -S, T], [S, -S, T], [S, S, T], [-S, S, T]], [0, 0, 1])
     att_color, att_dist = np.float64([0.3, 0.6, 0.9]), 0.4
-    glass = _mr_material(color=(1, 1, 1), roughness=0.0, transmission=1.0, ior=1.5, att_color=att_color, att_dist=att_dist)
-    hs = _HandScene(pkg, [front, back], [glass, glass])
+    glass = util.mr_material(color=(1, 1, 1), roughness=0.0, transmission=1.0, ior=1.5, att_color=att_color, att_dist=att_dist)
+    hs = _hand_scene(pkg, [front, back], glass)
     osc = orc.OracleScene(hs.desc)
     cam = pkg.Scene("default")
     cam.set_camera_pose(np.float32([0.0, 0.0, -5.0]), np.float32([0.0, 0.0, 1.0]))
@@ -272,8 +230,8 @@ def test_beer_lambert_slab_in_closed_form(pkg, orc):
     expect = sky * (F + (1 - F) ** 2 * a / (1 - F * a))               # k internal reflections: (1 - F)^2 a (F a)^k, every exit sees the sky
     assert np.abs(got / expect - 1).max() <= 0.03, (got, expect, got / sky)
     # without attenuation the slab is invisible against a constant sky (white furnace through two interfaces)
-    clear = _mr_material(color=(1, 1, 1), roughness=0.0, transmission=1.0, ior=1.5)
-    hs2 = _HandScene(pkg, [front, back], [clear, clear])
+    clear = util.mr_material(color=(1, 1, 1), roughness=0.0, transmission=1.0, ior=1.5)
+    hs2 = _hand_scene(pkg, [front, back], clear)
     img2, _ = orc.OracleScene(hs2.desc).render(u, lights, W, H)
     got2 = img2[c, c, :3].astype(np.float64).mean(axis=(0, 1)) / spp
     assert np.abs(got2 / sky - 1).max() <= 0.02, got2 / sky
@@ -287,59 +245,10 @@ def test_closest_hit_query_against_float64_geometry(pkg, orc):
     t, u, v agree to float precision."""
     scene = pkg.Scene("chess_like", 0.05)
     d = scene.desc
-    a = util.desc_arrays(d)
-    # world-space triangles in the global order (instance, mesh, primitive)
-    tris = []
-    for inst in a["instances"]:
-        it = np.float64(inst["Transform"]).reshape(3, 4)
-        m = a["models"][inst["ModelIndex"]]
-        for k in range(m["MeshCount"]):
-            rec = a["meshes"][m["MeshOffset"] + k]
-            g = a["geometries"][rec["GeometryIndex"]]
-            mt = np.float64(a["transforms"][rec["TransformIndex"]]).reshape(3, 4)
-            M = np.vstack([it, [0, 0, 0, 1]]) @ np.vstack([mt, [0, 0, 0, 1]])
-            v = np.float64(a["vertices"][g["VertexOffset"]:g["VertexOffset"] + g["VertexLength"], 0:3])
-            idx = a["indices"][g["IndexOffset"]:g["IndexOffset"] + g["IndexLength"]].reshape(-1, 3)
-            w = v @ M[:3, :3].T + M[:3, 3]
-            tris.append(w[idx])
-    T = np.concatenate(tris)
+    T = util.world_triangles(d)  # world-space triangles in the global order (instance, mesh, primitive)
     assert len(T) == scene.triangle_count and len(T) < 200000
     rng = np.random.default_rng(21)
     rays = util.random_rays(rng, 3000, -6.0, 6.0)
     got = orc.OracleScene(d, build_bvh=False).trace_closest(rays, brute_force=True)
-    o, dr, tmin, tmax = np.float64(rays[:, 0:3]), np.float64(rays[:, 4:7]), np.float64(rays[:, 3]), np.float64(rays[:, 7])
-    v0, e1, e2 = T[:, 0], T[:, 1] - T[:, 0], T[:, 2] - T[:, 0]
-    hits = agree = close = 0
-    for r in range(len(rays)):
-        p = np.cross(dr[r], e2)
-        det = np.einsum("ij,ij->i", e1, p)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = 1.0 / det
-            s = o[r] - v0
-            u = np.einsum("ij,ij->i", s, p) * inv
-            q = np.cross(s, e1)
-            v = (q @ dr[r]) * inv
-            t = np.einsum("ij,ij->i", e2, q) * inv
-        inside = (u >= 0) & (v >= 0) & (u + v <= 1) & (t > tmin[r]) & (t < tmax[r]) & (np.abs(det) > 1e-300)
-        margin = np.minimum(np.minimum(u, v), 1 - u - v)
-        if not inside.any():
-            # a miss in float64: the oracle may only report a hit that grazes an edge
-            if got["tri"][r] != 0xFFFFFFFF:
-                k = int(got["tri"][r])
-                assert abs(margin[k]) < 1e-5, (r, margin[k])
-            continue
-        hits += 1
-        tb = np.where(inside, t, np.inf)
-        k = int(np.argmin(tb))
-        if got["tri"][r] == 0xFFFFFFFF:
-            assert margin[k] < 1e-5, (r, margin[k])   # the only float64 hit grazes an edge
-            continue
-        kg = int(got["tri"][r])
-        if kg == k:
-            agree += 1
-            assert abs(got["t"][r] - t[k]) <= 2e-5 * max(1.0, t[k]) and abs(got["u"][r] - u[k]) < 1e-4 and abs(got["v"][r] - v[k]) < 1e-4
-        else:
-            # another triangle: it must be a genuine float64 hit at (nearly) the same distance, or an edge case
-            close += 1
-            assert (inside[kg] and abs(t[kg] - t[k]) < 1e-4 * max(1.0, t[k])) or margin[k] < 1e-5 or abs(margin[kg]) < 1e-5, (r, t[k], t[kg])
+    hits, agree, close = util.check_closest_against_float64(T, rays, got)
     assert hits > 500 and agree > 0.98 * hits, (hits, agree, close)

@@ -164,3 +164,199 @@ def reciprocal_spec(b):
         r = np.where(ab > np.float32(8.50705917e37), np.copysign(np.float32(0.0), b), r)
         r = np.where(np.isnan(b), b, r)
     return r.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------
+# hand-built scenes and the closest-hit comparisons that use them
+# ---------------------------------------------------------------------------------------
+IDENTITY_3X4 = np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])
+
+
+def mr_material(color=(1, 1, 1), roughness=1.0, metalness=0.0, ior=1.5, transmission=0.0, att_color=(1, 1, 1), att_dist=1e32):
+    """One metallic-roughness material record (24 words) with the default texels."""
+    m = np.zeros(24, np.float32)
+    m[4:8] = (*color, 1.0)
+    m[8], m[9], m[10], m[11] = roughness, metalness, ior, transmission
+    m[12:15] = att_color
+    m[15] = att_dist
+    m.view(np.uint32)[19:24] = (4, 0, 1, 2, 3)  # default emissive / colour / normal / roughness / metallic texels
+    return m
+
+
+def quad_mesh(corners, normal):
+    """A planar quad as a mesh of two triangles (0 1 2, 2 3 0) over four shared vertices, with the given normal and the
+    tangent frame of its first edge."""
+    corners = np.asarray(corners, np.float32)
+    n = np.asarray(normal, np.float32)
+    assert np.cross(corners[1] - corners[0], corners[2] - corners[0]) @ n > 0, "winding must agree with the normal"
+    return {"positions": corners, "indices": np.uint32([0, 1, 2, 2, 3, 0]), "normal": n,
+            "uv": np.float32([[k in (1, 2), k in (2, 3)] for k in range(4)])}
+
+
+def _mesh_vertices(mesh):
+    """Rows of 14 floats (position, uv, normal, tangent, bitangent) and the index list of one mesh: a dict from quad_mesh
+    or an (n, 3, 3) array of triangles (own vertices each, the geometric normal; +z / +x for a zero-area triangle)."""
+    if isinstance(mesh, dict):
+        p, idx = np.asarray(mesh["positions"], np.float32), np.asarray(mesh["indices"], np.uint32)
+        n = np.broadcast_to(np.asarray(mesh["normal"], np.float32), p.shape)
+        t = p[1] - p[0]
+        t = np.broadcast_to(t / np.linalg.norm(t), p.shape)
+        uv = np.asarray(mesh["uv"], np.float32)
+    else:
+        tri = np.asarray(mesh, np.float32).reshape(-1, 3, 3)
+        p, idx = tri.reshape(-1, 3), np.arange(3 * len(tri), dtype=np.uint32)
+        e1, e2 = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+        nn = np.cross(e1, e2)
+        ln, lt = np.linalg.norm(nn, axis=1, keepdims=True), np.linalg.norm(e1, axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nn = np.where(ln > 0, nn / ln, np.float32([0, 0, 1]))
+            tt = np.where((lt > 0) & (ln > 0), e1 / lt, np.float32([1, 0, 0]))
+        n, t = np.repeat(nn, 3, axis=0), np.repeat(tt, 3, axis=0)
+        uv = np.tile(np.float32([[0, 0], [1, 0], [0, 1]]), (len(tri), 1))
+    b = np.cross(n, t)
+    return np.concatenate([p, uv, n, t, b], axis=1).astype(np.float32), idx
+
+
+class TriangleSoup:
+    """A PtxSceneDesc assembled from numpy arrays that this object keeps alive: `models` is a list of models, each a list of
+    meshes (world-space (n, 3, 3) triangle arrays or quad_mesh dicts); `instances` a list of (model index, 3x4 transform),
+    by default one identity instance per model; every mesh uses the one metallic-roughness `material`."""
+
+    def __init__(self, pkg, models, instances=None, material=None):
+        verts, inds, geos, meshes, model_rows = [], [], [], [], []
+        nv = ni = 0
+        for model in models:
+            model_rows.append((len(meshes), len(model)))
+            for mesh in model:
+                v, idx = _mesh_vertices(mesh)
+                geos.append((nv, len(v), ni, len(idx), 1, 0, (0, 0)))
+                meshes.append((len(geos) - 1, 0, 0))
+                verts.append(v)
+                inds.append(idx)
+                nv, ni = nv + len(v), ni + len(idx)
+        if instances is None:
+            instances = [(m, IDENTITY_3X4) for m in range(len(models))]
+        self.vertices = np.ascontiguousarray(np.concatenate(verts), np.float32)
+        self.indices = np.ascontiguousarray(np.concatenate(inds), np.uint32)
+        self.transforms = IDENTITY_3X4.reshape(1, 12).copy()
+        self.geometries = np.array(geos, GEOMETRY_DT)
+        self.materials = np.ascontiguousarray(mr_material() if material is None else material, np.float32).reshape(1, 24)
+        self.meshes = np.array(meshes, MESH_DT)
+        self.models = np.array(model_rows, MODEL_DT)
+        self.instances = np.array([(m, np.asarray(x, np.float32).reshape(12)) for m, x in instances], INSTANCE_DT)
+        d = pkg.SceneDesc()
+        d.vertices, d.vertexCount = self.vertices.ctypes.data, len(self.vertices)
+        d.indices, d.indexCount = self.indices.ctypes.data, len(self.indices)
+        d.transforms, d.transformCount = self.transforms.ctypes.data, 1
+        d.geometries, d.geometryCount = self.geometries.ctypes.data, len(self.geometries)
+        d.metallicRoughnessMaterials, d.metallicRoughnessMaterialCount = self.materials.ctypes.data, 1
+        d.meshes, d.meshCount = self.meshes.ctypes.data, len(self.meshes)
+        d.models, d.modelCount = self.models.ctypes.data, len(self.models)
+        d.instances, d.instanceCount = self.instances.ctypes.data, len(self.instances)
+        self.desc = d
+
+
+def world_triangles(desc, instance_transforms=None):
+    """Every triangle of a scene in world space, float64, in the global order (instance, mesh, primitive): (n, 3, 3)."""
+    a = desc_arrays(desc)
+    tris = []
+    for i, inst in enumerate(a["instances"]):
+        x = inst["Transform"] if instance_transforms is None else np.asarray(instance_transforms, np.float32).reshape(-1, 12)[i]
+        it = np.float64(x).reshape(3, 4)
+        m = a["models"][inst["ModelIndex"]]
+        for k in range(m["MeshCount"]):
+            rec = a["meshes"][m["MeshOffset"] + k]
+            g = a["geometries"][rec["GeometryIndex"]]
+            mt = np.float64(a["transforms"][rec["TransformIndex"]]).reshape(3, 4)
+            M = np.vstack([it, [0, 0, 0, 1]]) @ np.vstack([mt, [0, 0, 0, 1]])
+            v = np.float64(a["vertices"][g["VertexOffset"]:g["VertexOffset"] + g["VertexLength"], 0:3])
+            idx = a["indices"][g["IndexOffset"]:g["IndexOffset"] + g["IndexLength"]].reshape(-1, 3)
+            w = v @ M[:3, :3].T + M[:3, 3]
+            tris.append(w[idx])
+    return np.concatenate(tris) if tris else np.zeros((0, 3, 3))
+
+
+def moller_trumbore_f64(T, ray):
+    """The textbook Moeller-Trumbore test in float64 of one ray (8 floats) against every triangle of T (n, 3, 3):
+    (inside, t, u, v, margin) per triangle, margin = the smallest barycentric (negative outside)."""
+    o, dr, tmin, tmax = np.float64(ray[0:3]), np.float64(ray[4:7]), np.float64(ray[3]), np.float64(ray[7])
+    v0, e1, e2 = T[:, 0], T[:, 1] - T[:, 0], T[:, 2] - T[:, 0]
+    p = np.cross(dr, e2)
+    det = np.einsum("ij,ij->i", e1, p)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / det
+        s = o - v0
+        u = np.einsum("ij,ij->i", s, p) * inv
+        q = np.cross(s, e1)
+        v = (q @ dr) * inv
+        t = np.einsum("ij,ij->i", e2, q) * inv
+    inside = (u >= 0) & (v >= 0) & (u + v <= 1) & (t > tmin) & (t < tmax) & (np.abs(det) > 1e-300)
+    margin = np.minimum(np.minimum(u, v), 1 - u - v)
+    return inside, t, u, v, margin
+
+
+def global_ids(desc, ids):
+    """(pair, prim) pairs of ptx_trace_rays -> global triangle ids (0xffffffff = miss), the oracle's numbering."""
+    first = pair_first(desc)
+    miss = ids[:, 0] == 0xFFFFFFFF
+    pair = ids[:, 0].astype(np.int64)
+    assert (pair[~miss] < len(first) - 1).all(), "a hit names an (instance, mesh) pair the scene does not have"
+    prim = ids[:, 1].astype(np.int64)
+    assert (prim[~miss] < (first[1:] - first[:-1])[pair[~miss]]).all(), "a hit names a primitive its pair does not have"
+    return np.where(miss, 0xFFFFFFFF, first[np.where(miss, 0, pair)] + prim).astype(np.uint32)
+
+
+def check_trace_against_bruteforce(r, orc, desc, rays, min_hits, instance_transforms=None, label=""):
+    """Closest-hit and occlusion queries of renderer `r` (its tree over `desc`) against the oracle's brute force: the same
+    global triangle per ray, t / u / v bit for bit on hits, the same occlusion flag -- and at least `min_hits` hits, so that a
+    scene every ray misses cannot pass.  Returns the brute-force closest hits."""
+    osc = orc.OracleScene(desc, build_bvh=False, instance_transforms=instance_transforms)
+    want = osc.trace_closest(rays, brute_force=True)
+    occ_want = osc.trace_any(rays, brute_force=True)
+    osc.close()
+    hits, ids = r.trace_rays(rays, any_hit=False)
+    gid = global_ids(desc, ids)
+    bad = np.flatnonzero(gid != want["tri"])
+    assert not len(bad), f"{label}: {len(bad)} rays hit a different triangle, first ray {bad[0]}: {gid[bad[0]]} != {want['tri'][bad[0]]}"
+    h = want["tri"] != 0xFFFFFFFF
+    assert int(h.sum()) >= min_hits, f"{label}: only {int(h.sum())} hits"
+    for k, f in enumerate(("t", "u", "v")):
+        diff = np.flatnonzero(hits[h, k].view(np.uint32) != want[f][h].view(np.uint32))
+        assert not len(diff), f"{label}: {f} differs on {len(diff)} hits"
+    occ, _ = r.trace_rays(rays, any_hit=True)
+    assert ((occ[:, 3] != 0) == (occ_want != 0)).all(), f"{label}: occlusion differs on {int(((occ[:, 3] != 0) != (occ_want != 0)).sum())} rays"
+    return want
+
+
+def check_closest_against_float64(T, rays, got, t_slack=0.0, bary_slack=0.0):
+    """Closest hits `got` (the oracle's trace_closest record) against moller_trumbore_f64 over the world-space triangles T:
+    hit / miss agrees except where the float64 barycentrics sit within 1e-5 of an edge; the nearest triangle agrees except
+    between hits closer than 1e-4 of t; t, u, v agree to float precision.  Far from the origin the float32 arithmetic works on
+    coordinates whose ulp is no longer small: t_slack (world units) and bary_slack (barycentric units) widen every bound by
+    that much.  Returns (float64 hits, same triangle, other triangle)."""
+    hits = agree = close = 0
+    for r in range(len(rays)):
+        inside, t, u, v, margin = moller_trumbore_f64(T, rays[r])
+        if not inside.any():
+            # a miss in float64: the oracle may only report a hit that grazes an edge
+            if got["tri"][r] != 0xFFFFFFFF:
+                k = int(got["tri"][r])
+                assert abs(margin[k]) < 1e-5 + bary_slack, (r, margin[k])
+            continue
+        hits += 1
+        tb = np.where(inside, t, np.inf)
+        k = int(np.argmin(tb))
+        if got["tri"][r] == 0xFFFFFFFF:
+            assert margin[k] < 1e-5 + bary_slack, (r, margin[k])   # the only float64 hit grazes an edge
+            continue
+        kg = int(got["tri"][r])
+        if kg == k:
+            agree += 1
+            assert abs(got["t"][r] - t[k]) <= 2e-5 * max(1.0, t[k]) + t_slack and abs(got["u"][r] - u[k]) < 1e-4 + bary_slack and \
+                abs(got["v"][r] - v[k]) < 1e-4 + bary_slack, (r, got[r], t[k], u[k], v[k])
+        else:
+            # another triangle: it must be a genuine float64 hit at (nearly) the same distance, or an edge case
+            close += 1
+            assert (inside[kg] and abs(t[kg] - t[k]) < 1e-4 * max(1.0, t[k]) + t_slack) or margin[k] < 1e-5 + bary_slack or \
+                abs(margin[kg]) < 1e-5 + bary_slack, (r, t[k], t[kg])
+    return hits, agree, close
