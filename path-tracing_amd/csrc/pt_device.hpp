@@ -435,38 +435,57 @@ PT_DEV float SchlickFresnel(float VdotH) // :50-53
     return x2 * x2 * x;
 }
 
-PT_DEV f3 EvaluateReflection(f3 V, f3 L, f3 F, float alpha, float &pdf) // :56-77
+// EvaluateReflection without its F factor.  evaluateBSDF's glossy and metallic lobes share V, L and alpha, so everything but F
+// -- H = normalize(V + L), D, G, the pdf, 1 / (4 V.z) -- is computed once per evaluation (the compiler does not merge the two
+// inlined copies), and Gv = GGXSmith(V, alpha) once per hit.  Same operations on the same operands: the same bits.
+struct ReflectionTerms
 {
-    if (L.z < 0.00001f)
-    {
-        pdf = 0.0f;
-        return F3s(0.0f);
-    }
-    const f3 H = normalize(V + L);
-    const float VdotH = dot(V, H);
+    bool above;   // L.z >= 1e-5; below, the lobe is F3s(0) with pdf 0 whatever F is
+    float DG;     // D * G
+    float rcp4Vz; // rcp_(4 V.z): operator/(f3, 4 V.z) is this reciprocal and three multiplies
+    float pdf;
+};
+PT_DEV ReflectionTerms reflectionTerms(f3 V, f3 L, f3 H, float VdotH, float Gv, float alpha) // :56-77, H = normalize(V + L)
+{
+    ReflectionTerms r;
+    r.above = !(L.z < 0.00001f);
+    r.DG = r.rcp4Vz = r.pdf = 0.0f;
+    if (!r.above)
+        return r;
     const float D = GGXDistribution(H, alpha);
-    const float Gv = GGXSmith(V, alpha);
     const float Gl = GGXSmith(L, alpha);
     const float G = Gv * Gl;
     const float Dv = div_(Gv * fmax_(VdotH, 0.0f) * D, V.z);
-    pdf = div_(Dv, 4.0f * VdotH);
-    return (F * (D * G)) / (4.0f * V.z);
+    r.pdf = div_(Dv, 4.0f * VdotH);
+    r.DG = D * G;
+    r.rcp4Vz = rcp_(4.0f * V.z);
+    return r;
+}
+PT_DEV f3 reflectionLobe(const ReflectionTerms &r, f3 F) { return r.above ? (F * r.DG) * r.rcp4Vz : F3s(0.0f); }
+PT_DEV f3 reflectionLobe(const ReflectionTerms &r) { return r.above ? F3s(r.DG * r.rcp4Vz) : F3s(0.0f); } // F = F3s(1): 1 * DG = DG
+
+PT_DEV f3 EvaluateReflection(f3 V, f3 L, f3 F, float alpha, float &pdf) // :56-77
+{
+    const f3 H = normalize(V + L);
+    const ReflectionTerms r = reflectionTerms(V, L, H, dot(V, H), GGXSmith(V, alpha), alpha);
+    pdf = r.pdf;
+    return reflectionLobe(r, F);
 }
 
-PT_DEV f3 EvaluateRefraction(f3 V, f3 L, f3 F, float alpha, float eta, float &pdf) // :80-108
+// :80-108; Hn = normalize(V * eta + L) before it is turned to the upper hemisphere, Gv = GGXSmith(V, alpha)
+PT_DEV f3 evaluateRefraction(f3 V, f3 L, f3 Hn, f3 F, float Gv, float alpha, float eta, float &pdf)
 {
     if (L.z > -0.00001f)
     {
         pdf = 0.0f;
         return F3s(0.0f);
     }
-    f3 H = normalize(V * eta + L);
+    f3 H = Hn;
     if (H.z < 0.0f)
         H = -H;
     const float VdotH = dot(V, H);
     const float LdotH = dot(L, H);
     const float D = GGXDistribution(H, alpha);
-    const float Gv = GGXSmith(V, alpha);
     const float Gl = GGXSmith(L, alpha);
     const float G = Gv * Gl;
     const float Dv = div_(Gv * abs_(VdotH) * D, V.z);
@@ -474,6 +493,10 @@ PT_DEV f3 EvaluateRefraction(f3 V, f3 L, f3 F, float alpha, float eta, float &pd
     const float jacobian = div_((eta * eta) * abs_(LdotH), denominator * denominator);
     pdf = Dv * jacobian;
     return ((F * (D * G)) * (div_(abs_(VdotH), abs_(V.z)))) * jacobian;
+}
+PT_DEV f3 EvaluateRefraction(f3 V, f3 L, f3 F, float alpha, float eta, float &pdf) // :80-108
+{
+    return evaluateRefraction(V, L, normalize(V * eta + L), F, GGXSmith(V, alpha), alpha, eta, pdf);
 }
 
 PT_DEV f3 SampleGGX(f2 u, f3 V, float alpha) // :111-129
@@ -516,11 +539,13 @@ struct BSDFSample
     f3 Color;
 };
 
-PT_DEV f3 evaluateBSDF(const MaterialSample &m, f3 V, f3 L, float &outPdf) // :72-103
+// Gv = GGXSmith(V, m.Roughness^2), the same at every evaluation of one hit: closestHit computes it once for both
+PT_DEV f3 evaluateBSDF(const MaterialSample &m, f3 V, f3 L, float Gv, float &outPdf) // :72-103
 {
     const bool isReflection = L.z > 0.0f;
     const f3 H = isReflection ? normalize(V + L) : normalize(V * m.Eta + L);
-    const float FD = DielectricFresnel(abs_(dot(V, H)), m.Eta);
+    const float VdotH = dot(V, H);
+    const float FD = DielectricFresnel(abs_(VdotH), m.Eta);
     // sampleLobePdfs, :62-70
     const float pDiffuse = (1.0f - m.Metalness) * (1.0f - FD) * (1.0f - m.Transmission);
     const float pGlossy = (1.0f - m.Metalness) * FD;
@@ -537,25 +562,30 @@ PT_DEV f3 evaluateBSDF(const MaterialSample &m, f3 V, f3 L, float &outPdf) // :7
         pdf = div_(L.z * 1.0f, PT_PI);
         bsdf = bsdf + ((m.Color * L.z) / PT_PI) * pDiffuse;
         outPdf += pdf * pDiffuse;
+        // the glossy and the metallic lobe are EvaluateReflection at the same V, L, alpha (and H): its terms once, F per lobe
+        const ReflectionTerms rt = reflectionTerms(V, L, H, VdotH, Gv, alpha);
         // evaluateGlossyBSDF, :22-25
-        bsdf = bsdf + EvaluateReflection(V, L, F3s(1.0f), alpha, pdf) * pGlossy;
-        outPdf += pdf * pGlossy;
-        // evaluateMetallicBRDF, :32-37
-        const f3 Hm = normalize(V + L);
-        const f3 F0 = mix(m.Color, F3s(1.0f), SchlickFresnel(dot(V, Hm)));
-        bsdf = bsdf + EvaluateReflection(V, L, F0, alpha, pdf) * pMetallic;
-        outPdf += pdf * pMetallic;
+        bsdf = bsdf + reflectionLobe(rt) * pGlossy;
+        outPdf += rt.pdf * pGlossy;
+        // evaluateMetallicBRDF, :32-37 (its own H is normalize(V + L) again)
+        const f3 F0 = mix(m.Color, F3s(1.0f), SchlickFresnel(VdotH));
+        bsdf = bsdf + reflectionLobe(rt, F0) * pMetallic;
+        outPdf += rt.pdf * pMetallic;
     }
     else
     {
         // evaluateBTDF, :44-47
-        bsdf = bsdf + EvaluateRefraction(V, L, m.Color, alpha, m.Eta, pdf) * pTransmissive;
+        bsdf = bsdf + evaluateRefraction(V, L, H, m.Color, Gv, alpha, m.Eta, pdf) * pTransmissive;
         outPdf += pdf * pTransmissive;
     }
     return bsdf;
 }
+PT_DEV f3 evaluateBSDF(const MaterialSample &m, f3 V, f3 L, float &outPdf)
+{
+    return evaluateBSDF(m, V, L, GGXSmith(V, m.Roughness * m.Roughness), outPdf);
+}
 
-PT_DEV BSDFSample sampleBSDF(const MaterialSample &m, f3 V, uint32_t &rngState) // :105-132
+PT_DEV BSDFSample sampleBSDF(const MaterialSample &m, f3 V, float Gv, uint32_t &rngState) // :105-132; Gv as evaluateBSDF's
 {
     const float alpha = m.Roughness * m.Roughness;
     f2 u;
@@ -586,8 +616,12 @@ PT_DEV BSDFSample sampleBSDF(const MaterialSample &m, f3 V, uint32_t &rngState) 
     }
     BSDFSample ret;
     ret.Direction = L;
-    ret.Color = evaluateBSDF(m, V, L, ret.Pdf);
+    ret.Color = evaluateBSDF(m, V, L, Gv, ret.Pdf);
     return ret;
+}
+PT_DEV BSDFSample sampleBSDF(const MaterialSample &m, f3 V, uint32_t &rngState)
+{
+    return sampleBSDF(m, V, GGXSmith(V, m.Roughness * m.Roughness), rngState);
 }
 
 // ---- ray.glsl ------------------------------------------------------------------------------
@@ -1718,7 +1752,8 @@ PT_DEV void closestHit(const SceneView &sv, f3 rayDirW, float t, float hu, float
     const mat3 invTBN = inverse(TBN);
     const f3 V = normalize(mul(invTBN, normalize(-rayDirW)));
 
-    BSDFSample bsdf = sampleBSDF(material, V, rngState);
+    const float Gv = GGXSmith(V, material.Roughness * material.Roughness); // V and alpha are those of both evaluations below
+    BSDFSample bsdf = sampleBSDF(material, V, Gv, rngState);
 
     if (isHitFromInside) // :123-128
     {
@@ -1739,7 +1774,7 @@ PT_DEV void closestHit(const SceneView &sv, f3 rayDirW, float t, float hu, float
     u3.z = rnd(rngState);
     const LightSample light = sampleLight(sv.lights, u3, rayOrigin, lightPdf);
     const f3 L = normalize(mul(invTBN, -light.Direction));
-    const f3 lightBsdf = evaluateBSDF(material, V, L, lightSmplPdf);
+    const f3 lightBsdf = evaluateBSDF(material, V, L, Gv, lightSmplPdf);
 
     out.Direction = normalize(mul(TBN, bsdf.Direction));
     if (isRefracted)

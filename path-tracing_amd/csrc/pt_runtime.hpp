@@ -1976,7 +1976,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
     const bool textured = pl.mode >= 1, alpha = pl.mode == 2;
     hipStream_t S = r->stream, X = r->auxStream;
     PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
-    const BounceCtl ctl = { b, skipBelow, pl.sortShade };
+    const BounceCtl ctl = { b, skipBelow };
     const int qout = qin ^ 1;
     k_prologue<<<1, 1, 0, S>>>(pl.wf, qin, ctl);
     HIP_TRY(r, hipEventRecord(ev.t0, S));
@@ -1988,8 +1988,12 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
     if (b > 1) // shade reads rad[slot]: the previous bounce's shadow adds must have landed
         HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
     const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
-    if (textured)
+    if (textured && pl.sortShade)
+        k_shade_sorted<true><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+    else if (textured)
         k_shade<true><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+    else if (pl.sortShade)
+        k_shade_sorted<false><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
     else
         k_shade<false><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
     HIP_TRY(r, hipEventRecord(ev.t2, S));
@@ -2008,7 +2012,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
         // per path (blocks beyond the queue return at once), anything beyond that strides.
         const uint32_t room = tail == 2 ? 4u * pl.tailBelow : pl.tailBelow;
         const uint32_t most = est < room ? est : room;
-        const BounceCtl tctl = { b, tail == 2 ? 0xffffffffu : pl.tailBelow, 0u };
+        const BounceCtl tctl = { b, tail == 2 ? 0xffffffffu : pl.tailBelow };
         const dim3 grid(gridFor(most, kBlock, kMaxPersistentThreads / kBlock));
         if (pl.mode == 2)
             k_tail<2><<<grid, kBlock, 0, X>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qout, tctl);
@@ -2080,7 +2084,7 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
             {
                 // the queue is short: k_tail finishes it, behind the shadow kernel of this bounce on its stream
                 PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
-                const BounceCtl tctl = { b, 0xffffffffu, 0u };
+                const BounceCtl tctl = { b, 0xffffffffu };
                 const dim3 grid(gridFor(est, kBlock, kMaxPersistentThreads / kBlock));
                 if (pl.mode == 2)
                     k_tail<2><<<grid, kBlock, 0, r->auxStream>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qin, tctl);

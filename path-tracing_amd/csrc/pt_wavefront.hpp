@@ -131,7 +131,6 @@ struct BounceCtl
 {
     uint32_t bounce;    // 1-based index inside the round
     uint32_t tailBelow; // queues of at most this many paths go to k_tail (never the first bounce of a round)
-    uint32_t sortShade; // k_shade puts its block's queue entries in material-type order first (scenes that mix types)
 };
 PT_DEV bool bounceRuns(const BounceCtl &c, uint32_t count) { return count != 0u && (c.bounce <= 1u || count > c.tailBelow); }
 
@@ -489,19 +488,30 @@ PT_DEV void pushRestarts(const Wavefront &wf, bool restart, uint32_t slot)
         wf.restartQueue[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = slot;
 }
 
-template <bool TEX>
+// SORT: the material-sorted shade queue (below), chosen on the host for scenes that mix material types.  The plain kernels
+// carry neither its code nor its LDS: a kernel argument that switched it kept the sort's state live across the item loop.
+template <bool TEX, bool SORT>
 PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefront &wf, int qin, const BounceCtl &ctl);
 template <bool TEX>
 __global__ void __launch_bounds__(kBlock) k_shade(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
-// 178 VGPRs by itself (195 with the SLP vectoriser); held at 168 = three waves per SIMD, which costs nothing now (15 spilled
-// dwords before round 3).  Four waves (128 VGPRs, 49 spilled) lose: chess_like 2,290 / 2,324 -> 2,164 / 2,185 Msamples/s.
+template <bool TEX>
+__global__ void __launch_bounds__(kBlock) k_shade_sorted(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
+// Three waves per SIMD (168 VGPRs): no VGPR spilled, no scratch; 4,703 static VALU instructions with the BSDF terms computed
+// once and the sort in its own kernel (6,162 before, 169 SGPRs spilled into VGPR lanes then, 82 now).  Four waves (128 VGPRs)
+// spill 31 VGPRs to 116 B of scratch per lane in this kernel; an older kernel at four waves (49 spilled) lost: chess_like
+// 2,290 / 2,324 -> 2,164 / 2,185 Msamples/s.
 #ifndef PT_SHADE_ATTR
 #define PT_SHADE_ATTR __attribute__((amdgpu_waves_per_eu(3, 3)))
 #endif
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade<false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<false>(p, sv, wf, qin, ctl);
+    shadeBody<false, false>(p, sv, wf, qin, ctl);
+}
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade_sorted<false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<false, true>(p, sv, wf, qin, ctl);
 }
 // the textured variant: 221 VGPRs = two waves per SIMD (round 1: a few registers past 256, i.e. ONE wave, held at two for four
 // spilled registers).  Three waves (168 VGPRs, 54 spilled, 164 B scratch) measure flat: atrium_like 725 / 730 -> 723 / 724.
@@ -511,9 +521,14 @@ __global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade<false>(LaunchPar
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade<true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<true>(p, sv, wf, qin, ctl);
+    shadeBody<true, false>(p, sv, wf, qin, ctl);
 }
-template <bool TEX>
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade_sorted<true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<true, true>(p, sv, wf, qin, ctl);
+}
+template <bool TEX, bool SORT>
 PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefront &wf, int qin, const BounceCtl &ctl)
 {
     __shared__ uint32_t s_cnt[2], s_base[2];
@@ -539,10 +554,10 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
       // inside a key is the queue order.
       // Measured (1 MI355X, 1080p, 8 spp, one frame in flight): materials_test (three material types + an unknown one side
       // by side) 1,313 -> 1,536 Msamples/s, k_shade 8.06 -> 6.29 ms; scenes of ONE material type pay for the sort and get
-      // nothing back (temple_like 614 -> 600, chess_like +-0.5 %), hence the switch.
-      __shared__ uint32_t s_sorted[kBlock * kShadeItems];
+      // nothing back (temple_like 614 -> 600, chess_like +-0.5 %), hence the two kernels (k_shade_sorted for mixed scenes).
+      __shared__ uint32_t s_sorted[SORT ? kBlock * kShadeItems : 1];
       constexpr uint32_t kPadSlot = 0xffffffffu; // never a slot: 184 B of state per slot bound the count far below
-      if (ctl.sortShade)
+      if (SORT)
       {
         constexpr uint32_t kKeys = 9, kWaves = kBlock / 64;
         __shared__ uint32_t s_keyCount[kWaves][kKeys], s_keyBase[kWaves][kKeys];
@@ -619,7 +634,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
         if (i < count)
         {
             // entries past the block's share of the queue were sorted last, with the dead slots
-            slot = ctl.sortShade ? s_sorted[item * blockDim.x + threadIdx.x] : wf.queue[qin][i];
+            slot = SORT ? s_sorted[item * blockDim.x + threadIdx.x] : wf.queue[qin][i];
             if (slot != kPadSlot)
                 pair = wf.hitPair[slot];
             else
