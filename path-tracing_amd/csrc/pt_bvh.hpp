@@ -18,8 +18,11 @@
 //                   the traversal kernels were bound by the per-CU address/L1 pipeline (every
 //                   lane fetches its own node: 4 divergent dwordx4 per visit), not by HBM.
 //   Tri       48 B  v0, e1, e2 (Moeller-Trumbore form) + (pair, prim) ids, in leaf order
-// child ref >= 0: internal node index; < 0: leaf, ~ref = triangle slot (bits 0..29) | kLeafNonOpaque for a triangle of a
-// non-opaque geometry (so that its any-hit record can be fetched WITH the triangle, not after it); kEmptyRef: no child.
+// child ref >= 0: internal node index; < 0: leaf, ~ref = triangle slot (bits 0..28) | kLeafPair for a leaf of two triangles
+// (slot and slot + 1) | kLeafNonOpaque for a triangle of a non-opaque geometry (so that its any-hit record can be fetched WITH
+// the triangle, not after it); kEmptyRef: no child.  The slot field was narrowed from 30 to 29 bits for kLeafPair.
+// Pair leaves: the two triangles of a quad -- consecutive indices of one (instance, mesh) pair that share an edge, both live and
+// opaque (k_pair_links) -- sit in one leaf and are tested in the same leaf phase; the second one's prim id is the first's + 1.
 #pragma once
 
 #include "pt_device.hpp"
@@ -49,8 +52,8 @@ struct Tri
 };
 static_assert(sizeof(Tri) == 48, "Tri is 48 B");
 constexpr uint32_t kTriNonOpaque = 0x80000000u; // Tri::c.w
-constexpr uint32_t kLeafNonOpaque = 0x40000000u, kLeafSlotMask = 0x3fffffffu; // ~ref of a leaf
-constexpr uint32_t kMaxTriangles = 0x3fffffffu;
+constexpr uint32_t kLeafNonOpaque = 0x40000000u, kLeafPair = 0x20000000u, kLeafSlotMask = 0x1fffffffu; // ~ref of a leaf
+constexpr uint32_t kMaxTriangles = 0x1fffffffu;
 
 struct Hit
 {
@@ -401,8 +404,8 @@ PT_DEV f3 fastInverse(f3 d) { return F3(__builtin_amdgcn_rcpf(d.x), __builtin_am
 
 // Closest hit = min t over all triangles the ray hits in (tmin, tmax); ties go to the
 // smaller (pair, prim), i.e. the smaller global triangle id -- independent of tree shape.
-// STATS: counts node visits and triangle tests, and with stackDepth the deepest stack position the walk reached (entries held
-// at once, counted on past the capacity of the stack: a walk that overflowed reports more than it can hold).
+// STATS: counts node visits and triangle tests (two for a pair leaf), and with stackDepth the deepest stack position the walk
+// reached (entries held at once, counted on past the capacity of the stack: a walk that overflowed reports more than it can hold).
 template <bool ANY_HIT, bool STATS = false, bool ALPHA = false>
 PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, Stack &st, Hit &best, uint32_t *nodeVisits = nullptr,
                      uint32_t *triTests = nullptr, Decal *decalOut = nullptr, uint32_t *stackDepth = nullptr)
@@ -457,32 +460,39 @@ PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, S
         }
         else
         {
+            // a pair leaf (kLeafPair) is one visit and two tests, slot first
+            const uint32_t leafBits = (uint32_t)~ref, firstSlot = leafBits & kLeafSlotMask;
+            const uint32_t tests = (leafBits & kLeafPair) ? 2u : 1u;
             if (STATS)
-                (*triTests)++;
-            const uint32_t leafSlot = ALPHA ? (uint32_t)~ref & kLeafSlotMask : (uint32_t)~ref;
-            const Tri *tp = &sc.tris[leafSlot];
-            const float4 ta = tp->a, tb = tp->b, tc = tp->c;
-            float t, u, v;
-            if (intersectTri(F3(ta.x, ta.y, ta.z), F3(ta.w, tb.x, tb.y), F3(tb.z, tb.w, tc.x), o, d, tmin, tmax, t, u, v) &&
-                (!ALPHA || !(__float_as_uint(tc.w) & kTriNonOpaque) ||
-                 anyHitKeeps<ANY_HIT>(sc, __float_as_uint(tc.y), __float_as_uint(tc.z), leafSlot, __float_as_uint(tc.w), t, u, v, decal)))
+                (*triTests) += tests;
+#pragma nounroll
+            for (uint32_t k = 0; k < tests; k++)
             {
-                const uint32_t pair = __float_as_uint(tc.y), prim = __float_as_uint(tc.z);
-                if (ANY_HIT)
+                const uint32_t leafSlot = firstSlot + k;
+                const Tri *tp = &sc.tris[leafSlot];
+                const float4 ta = tp->a, tb = tp->b, tc = tp->c;
+                float t, u, v;
+                if (intersectTri(F3(ta.x, ta.y, ta.z), F3(ta.w, tb.x, tb.y), F3(tb.z, tb.w, tc.x), o, d, tmin, tmax, t, u, v) &&
+                    (!ALPHA || !(__float_as_uint(tc.w) & kTriNonOpaque) ||
+                     anyHitKeeps<ANY_HIT>(sc, __float_as_uint(tc.y), __float_as_uint(tc.z), leafSlot, __float_as_uint(tc.w), t, u, v, decal)))
                 {
-                    best.pair = pair;
-                    best.prim = prim;
-                    best.slot = leafSlot;
-                    return true;
-                }
-                if (t < best.t || (t == best.t && (pair < best.pair || (pair == best.pair && prim < best.prim))))
-                {
-                    best.t = t;
-                    best.u = u;
-                    best.v = v;
-                    best.pair = pair;
-                    best.prim = prim;
-                    best.slot = leafSlot;
+                    const uint32_t pair = __float_as_uint(tc.y), prim = __float_as_uint(tc.z);
+                    if (ANY_HIT)
+                    {
+                        best.pair = pair;
+                        best.prim = prim;
+                        best.slot = leafSlot;
+                        return true;
+                    }
+                    if (t < best.t || (t == best.t && (pair < best.pair || (pair == best.pair && prim < best.prim))))
+                    {
+                        best.t = t;
+                        best.u = u;
+                        best.v = v;
+                        best.pair = pair;
+                        best.prim = prim;
+                        best.slot = leafSlot;
+                    }
                 }
             }
             if (st.sp == 0)
@@ -667,13 +677,14 @@ PT_DEV void persistentTrace(const TraceScene &sc, IO &io, uint32_t count, uint32
             }
         }
 
-        // ---- leaf phase (single-triangle leaves: ~ref = slot, with kLeafNonOpaque where the any-hit stage runs)
+        // ---- leaf phase (~ref = slot, with kLeafNonOpaque where the any-hit stage runs and kLeafPair for two triangles)
         if (have && ref < 0)
         {
             const uint32_t leafBits = (uint32_t)~ref;
-            const uint32_t leafSlot = ALPHA ? leafBits & kLeafSlotMask : leafBits;
+            uint32_t leafSlot = leafBits & kLeafSlotMask;
             const Tri *tp = &sc.tris[leafSlot];
             const float4 ta = tp->a, tb = tp->b, tc = tp->c;
+            const bool pairLeaf = (leafBits & kLeafPair) != 0u;
             // the any-hit record of a non-opaque triangle travels with the triangle: five independent loads, one wait
             float4 aa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ab = aa;
             const bool nonOpaque = ALPHA && (leafBits & kLeafNonOpaque) != 0u;
@@ -689,6 +700,22 @@ PT_DEV void persistentTrace(const TraceScene &sc, IO &io, uint32_t count, uint32
                 ref = st.sp ? (int)st.pop() : kRefDone;
             bool candidate = intersectTri(F3(ta.x, ta.y, ta.z), F3(ta.w, tb.x, tb.y), F3(tb.z, tb.w, tc.x), o, d, PT_TMIN, PT_TMAX, t, u, v);
             uint32_t pair = __float_as_uint(tc.y), prim = __float_as_uint(tc.z);
+            if (pairLeaf && !(ANY_HIT && candidate)) // (an occlusion query ends at its first candidate)
+            {
+                // the second triangle of a pair leaf (slot + 1, opaque, prim + 1 of the same pair), loaded behind the first test in
+                // the same round: loaded with the first, its nine registers cost the closest kernel six spilled VGPRs.  The nearer
+                // of the two stays; on a tie in t the first (smaller prim), as if they had been tested one by one.
+                // (the first hit's t as the limit: intersectTri accepts t < limit only, i.e. strictly nearer, and writes t, u, v
+                // only when it accepts)
+                const float4 sa = tp[1].a, sb = tp[1].b;
+                const float sc2 = tp[1].c.x;
+                if (intersectTri(F3(sa.x, sa.y, sa.z), F3(sa.w, sb.x, sb.y), F3(sb.z, sb.w, sc2), o, d, PT_TMIN, candidate ? t : PT_TMAX, t, u, v))
+                {
+                    candidate = true;
+                    prim++;
+                    leafSlot++;
+                }
+            }
             if (ALPHA && candidate && nonOpaque)
             {
                 // the any-hit stage; the nearest ignored candidate of a closest ray (the decal) is the IO's business: it keeps

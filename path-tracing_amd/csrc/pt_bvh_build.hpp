@@ -125,6 +125,112 @@ __global__ void k_tri_setup(uint32_t n, uint32_t pairCount, const uint32_t *__re
     }
 }
 
+// ---- pair leaves ----------------------------------------------------------------------------------------------------
+// Most stand-in geometry is quads written as two consecutive triangles that share an edge: a ray that reaches one nearly always
+// tests the other as well, one round of the persistent walk later.  Such a pair becomes ONE reference with the union box, one
+// leaf whose triangles sit in consecutive slots (kLeafPair) and are tested in the same leaf phase.
+//   link      g links to g + 1: same (instance, mesh) pair, two equal vertex indices, both live, both opaque, and the union box's
+//             area at most kPairAreaFactor x the sum of the two boxes' areas
+//   chains    a run of links pairs its 1st and 2nd triangle, its 3rd and 4th, ... : the start of the run by pointer jumping
+//             (k_pair_jump), so the result depends on the scene alone
+// Morton, PLOC, reinsertion, the level lists and the collapse then run over references; k_emit writes a reference's triangles at
+// an exclusive scan of the reference sizes in sorted order (k_slot_sizes), so tris / shadeTris keep one record per triangle.
+constexpr float kPairAreaFactor = 1.0f;
+
+PT_DEV float boxArea4(float4 lo, float4 hi)
+{
+    const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
+    return dx * dy + dy * dz + dz * dx;
+}
+
+__global__ void k_pair_links(uint32_t n, const Tri *__restrict__ triTmp, const DevPair *__restrict__ pairs, const uint32_t *__restrict__ indices,
+                             const float4 *__restrict__ boxLo, const float4 *__restrict__ boxHi, const uint8_t *__restrict__ inert,
+                             uint8_t *__restrict__ link)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n)
+        return;
+    bool ok = false;
+    if (g + 1 < n && !inert[g] && !inert[g + 1])
+    {
+        const float4 c0 = triTmp[g].c, c1 = triTmp[g + 1].c;
+        const uint32_t p = __float_as_uint(c0.y), prim = __float_as_uint(c0.z);
+        ok = p == __float_as_uint(c1.y) && !((__float_as_uint(c0.w) | __float_as_uint(c1.w)) & kTriNonOpaque);
+        if (ok)
+        {
+            const uint32_t *ia = &indices[pairs[p].indexOffset + prim * 3];
+            uint32_t shared = 0;
+            for (int a = 0; a < 3; a++)
+                for (int b = 0; b < 3; b++)
+                    shared += ia[a] == ia[3 + b] ? 1u : 0u;
+            const float4 l0 = boxLo[g], h0 = boxHi[g], l1 = boxLo[g + 1], h1 = boxHi[g + 1];
+            const float4 lu = make_float4(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z), 0.0f);
+            const float4 hu = make_float4(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z), 0.0f);
+            ok = shared >= 2 && boxArea4(lu, hu) <= kPairAreaFactor * (boxArea4(l0, h0) + boxArea4(l1, h1));
+        }
+    }
+    link[g] = ok ? 1 : 0;
+}
+
+// start of g's run of links: in == null sets up one step (g - 1 if g - 1 links to g), otherwise out[g] = in[in[g]]
+__global__ void k_pair_jump(uint32_t n, const uint8_t *__restrict__ link, const uint32_t *__restrict__ in, uint32_t *__restrict__ out)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n)
+        return;
+    out[g] = in ? in[in[g]] : (g > 0 && link[g - 1] ? g - 1 : g);
+}
+
+// g pairs with g + 1 when it links to it at an even position of its run; head[g] = 1 when g starts a reference
+PT_DEV bool pairsWithNext(uint32_t g, const uint8_t *link, const uint32_t *start) { return link[g] && ((g - start[g]) & 1u) == 0u; }
+__global__ void k_pair_heads(uint32_t n, const uint8_t *__restrict__ link, const uint32_t *__restrict__ start, uint32_t *__restrict__ head)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n)
+        return;
+    head[g] = (g > 0 && pairsWithNext(g - 1, link, start)) ? 0u : 1u;
+}
+
+// one thread per triangle that starts a reference (refIndex: the exclusive scan of the heads)
+__global__ void k_pair_write(uint32_t n, const uint8_t *__restrict__ link, const uint32_t *__restrict__ start, const uint32_t *__restrict__ refIndex,
+                             const uint8_t *__restrict__ inert, uint32_t *__restrict__ refTri, uint8_t *__restrict__ refPair, uint8_t *__restrict__ refInert)
+{
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n || refIndex[g + 1] == refIndex[g])
+        return;
+    const uint32_t r = refIndex[g];
+    refTri[r] = g;
+    refPair[r] = pairsWithNext(g, link, start) ? 1 : 0;
+    refInert[r] = inert[g];
+}
+
+// a reference's box: its triangle's, or the union of the two of a pair (full builds and refits)
+__global__ void k_ref_boxes(uint32_t n, const uint32_t *__restrict__ refTri, const uint8_t *__restrict__ refPair, const float4 *__restrict__ boxLo,
+                            const float4 *__restrict__ boxHi, float4 *__restrict__ refLo, float4 *__restrict__ refHi)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n)
+        return;
+    const uint32_t g = refTri[r];
+    float4 lo = boxLo[g], hi = boxHi[g];
+    if (refPair[r])
+    {
+        const float4 l1 = boxLo[g + 1], h1 = boxHi[g + 1];
+        lo = make_float4(fminf(lo.x, l1.x), fminf(lo.y, l1.y), fminf(lo.z, l1.z), 0.0f);
+        hi = make_float4(fmaxf(hi.x, h1.x), fmaxf(hi.y, h1.y), fmaxf(hi.z, h1.z), 0.0f);
+    }
+    refLo[r] = lo;
+    refHi[r] = hi;
+}
+
+// triangle slots of the sorted references (exclusive scan follows): sizes[i] = 1 or 2 for i < nv, sizes[nv] = 0
+__global__ void k_slot_sizes(uint32_t nv, const uint32_t *__restrict__ vals, const uint8_t *__restrict__ refPair, uint32_t *__restrict__ sizes)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= nv)
+        sizes[i] = i < nv ? 1u + (uint32_t)refPair[vals[i]] : 0u;
+}
+
 // ---- triangle pre-splitting (round 4) ------------------------------------------------------------------------------
 // A triangle that is large against the cells of the tree around it -- a floor or wall made of two triangles, a long curtain
 // strip, a diagonal beam -- has ONE box in a tree of single-triangle leaves: every ray that crosses that box pays a node visit
@@ -1454,16 +1560,24 @@ __global__ void k_emit(int n, const uint32_t *__restrict__ vals, const float4 *_
                        const float4 *__restrict__ nodeHi, const Tri *__restrict__ triTmp, BvhNode *__restrict__ nodes,
                        Tri *__restrict__ tris, const DevPair *__restrict__ pairs, const PtxVertex *__restrict__ vertices,
                        const uint32_t *__restrict__ indices, ShadeTri *__restrict__ shadeTris, const uint8_t *__restrict__ decide,
-                       const uint32_t *__restrict__ refTri)
+                       const uint32_t *__restrict__ refTri, const uint32_t *__restrict__ slotOf, const uint8_t *__restrict__ refPair)
 {
     // vals[i] = the leaf reference at sorted position i; refTri (null: the identity) names its triangle -- a triangle that was
-    // split stands in several slots, record and all
+    // split stands in several slots, record and all; slotOf (null: the identity) is where its first triangle goes, and a pair
+    // reference (refPair) puts its second triangle into the next slot
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
     {
-        const Tri t = triTmp[refTri ? refTri[vals[i]] : vals[i]];
-        tris[i] = t;
-        writeShadeTri(t, pairs, vertices, indices, &shadeTris[i]);
+        const uint32_t g = refTri ? refTri[vals[i]] : vals[i], s = slotOf ? slotOf[i] : (uint32_t)i;
+        const Tri t = triTmp[g];
+        tris[s] = t;
+        writeShadeTri(t, pairs, vertices, indices, &shadeTris[s]);
+        if (refPair && refPair[vals[i]])
+        {
+            const Tri t2 = triTmp[g + 1];
+            tris[s + 1] = t2;
+            writeShadeTri(t2, pairs, vertices, indices, &shadeTris[s + 1]);
+        }
     }
     if (i >= n - 1)
         return;
@@ -1619,10 +1733,19 @@ __global__ void k_emit(int n, const uint32_t *__restrict__ vals, const float4 *_
     }
     BvhNode nd;
     nd.a = make_float4(o[0], o[1], o[2], __uint_as_float(ebits[0] | (ebits[1] << 8) | (ebits[2] << 16) | (orderAxis << 24)));
-    // a leaf of a non-opaque geometry says so in its ref: the traversal fetches its any-hit record beside the triangle
+    // a leaf names its first triangle slot; a leaf of a non-opaque geometry says so in its ref (the traversal fetches its any-hit
+    // record beside the triangle), a pair leaf too
     for (int k = 0; k < count; k++)
-        if (c[k].ref < 0 && (__float_as_uint(triTmp[refTri ? refTri[vals[~c[k].ref]] : vals[~c[k].ref]].c.w) & kTriNonOpaque))
-            c[k].ref = ~(int)((uint32_t)~c[k].ref | kLeafNonOpaque);
+        if (c[k].ref < 0)
+        {
+            const uint32_t pos = (uint32_t)~c[k].ref, r = vals[pos];
+            uint32_t bits = slotOf ? slotOf[pos] : pos;
+            if (__float_as_uint(triTmp[refTri ? refTri[r] : r].c.w) & kTriNonOpaque)
+                bits |= kLeafNonOpaque;
+            if (refPair && refPair[r])
+                bits |= kLeafPair;
+            c[k].ref = ~(int)bits;
+        }
     nd.refs = make_int4(c[0].ref, c[1].ref, count > 2 ? c[2].ref : kEmptyRef, count > 3 ? c[3].ref : kEmptyRef);
     nd.q0 = make_uint4(qlo[0], qhi[0], qlo[1], qhi[1]);
     nd.q1 = make_uint4(qlo[2], qhi[2], 0u, 0u);
@@ -1729,16 +1852,24 @@ __global__ void k_place_nodes(uint32_t count, const BvhNode *__restrict__ nodes,
     out[pos[i]] = nd;
 }
 
-// a one-triangle scene has no internal node: give it a root with one leaf child
+// a one-reference scene has no internal node: give it a root with one leaf child (one triangle or a pair)
 __global__ void k_single_leaf_root(const uint32_t *vals, const float4 *boxLo, const float4 *boxHi, const Tri *triTmp, BvhNode *nodes, Tri *tris,
-                                   const DevPair *pairs, const PtxVertex *vertices, const uint32_t *indices, ShadeTri *shadeTris)
+                                   const DevPair *pairs, const PtxVertex *vertices, const uint32_t *indices, ShadeTri *shadeTris,
+                                   const uint32_t *refTri, const uint8_t *refPair)
 {
-    const uint32_t g = vals[0]; // the one triangle of the tree (the others, if any, are inert)
+    const uint32_t r = vals[0]; // the one reference of the tree (the others, if any, are inert)
+    const uint32_t g = refTri ? refTri[r] : r;
+    const bool pair = refPair && refPair[r];
     writeShadeTri(triTmp[g], pairs, vertices, indices, &shadeTris[0]);
     tris[0] = triTmp[g];
+    if (pair)
+    {
+        writeShadeTri(triTmp[g + 1], pairs, vertices, indices, &shadeTris[1]);
+        tris[1] = triTmp[g + 1];
+    }
     BvhNode nd;
     // origin below the box, scale covering it: child 0 spans the whole quantised range
-    const float lo[3] = { boxLo[g].x, boxLo[g].y, boxLo[g].z }, hi[3] = { boxHi[g].x, boxHi[g].y, boxHi[g].z };
+    const float lo[3] = { boxLo[r].x, boxLo[r].y, boxLo[r].z }, hi[3] = { boxHi[r].x, boxHi[r].y, boxHi[r].z };
     uint32_t eb[3];
     for (int a = 0; a < 3; a++)
     {
@@ -1748,7 +1879,8 @@ __global__ void k_single_leaf_root(const uint32_t *vals, const float4 *boxLo, co
         eb[a] = (uint32_t)e;
     }
     nd.a = make_float4(lo[0], lo[1], lo[2], __uint_as_float(eb[0] | (eb[1] << 8) | (eb[2] << 16)));
-    nd.refs = make_int4((__float_as_uint(triTmp[g].c.w) & kTriNonOpaque) ? ~(int)kLeafNonOpaque : ~0, kEmptyRef, kEmptyRef, kEmptyRef);
+    const uint32_t bits = ((__float_as_uint(triTmp[g].c.w) & kTriNonOpaque) ? kLeafNonOpaque : 0u) | (pair ? kLeafPair : 0u);
+    nd.refs = make_int4(~(int)bits, kEmptyRef, kEmptyRef, kEmptyRef);
     nd.q0 = make_uint4(0xffffff00u, 0x000000ffu, 0xffffff00u, 0x000000ffu);
     nd.q1 = make_uint4(0xffffff00u, 0x000000ffu, 0u, 0u);
     nodes[0] = nd;

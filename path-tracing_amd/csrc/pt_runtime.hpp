@@ -100,10 +100,13 @@ struct EnvSwitches
     uint32_t copyGroups = 0;     // PTX_COPY_GROUPS: workgroups of the read-back copy kernel (0: one, or 2 per rank of a tile shard, at most 16)
     bool snapshotMemcpy = false; // PTX_SNAPSHOT_MEMCPY=1: the read-back's device-side snapshot by hipMemcpyAsync (rounds 1-4) instead of a kernel
     bool fenceRefit = false;     // PTX_FENCE_REFIT=1: the round-4 bottom-up kernels (fence and atomic per node) instead of the level lists
+    bool pairLeaves = true;      // PTX_PAIR_LEAVES=0: single-triangle leaves only (pt_bvh_build.hpp, "pair leaves")
     static EnvSwitches read()
     {
         EnvSwitches e;
         e.verbose = getenv("PTX_VERBOSE") != nullptr;
+        if (const char *v = getenv("PTX_PAIR_LEAVES"))
+            e.pairLeaves = std::strcmp(v, "0") != 0;
         if (const char *v = getenv("PTX_COPY_GROUPS"))
             e.copyGroups = (uint32_t)strtoul(v, nullptr, 10);
         e.snapshotMemcpy = getenv("PTX_SNAPSHOT_MEMCPY") != nullptr && std::strcmp(getenv("PTX_SNAPSHOT_MEMCPY"), "0") != 0;
@@ -197,7 +200,12 @@ struct PtxRenderer
         DevBuf<float4> refLo, refHi;
         DevBuf<uint32_t> refTri;
         DevBuf<uint8_t> refInert;
-        uint32_t refCount = 0; // references of the last full build (= triangles unless it split some)
+        // ... or that pairs them (k_pair_*): refTri names a reference's first triangle, refPair says whether the next one is in it
+        // too, slotOf is the first triangle slot of the reference at each sorted position
+        DevBuf<uint8_t> refPair;
+        DevBuf<uint32_t> slotOf;
+        bool pairRefs = false;
+        uint32_t refCount = 0; // references of the last full build (= triangles unless it split or paired some)
         uint32_t treeTris = 0; // triangles in the tree = the first treeTris entries of the sorted order
         DevBuf<uint64_t> keys0, keys1;
         DevBuf<int2> children;
@@ -218,7 +226,7 @@ struct PtxRenderer
             triTmp.release(); boxLo.release(); boxHi.release(); nodeLo.release(); nodeHi.release(); sceneBounds.release();
             vals0.release(); vals1.release(); hist.release(); histSums.release(); flags.release(); inert.release(); keys0.release(); keys1.release();
             children.release(); parentOfNode.release(); parentOfLeaf.release(); rawNodes.release(); oldOf.release(); collapseCost.release(); collapseDecide.release();
-            refLo.release(); refHi.release(); refTri.release(); refInert.release();
+            refLo.release(); refHi.release(); refTri.release(); refInert.release(); refPair.release(); slotOf.release(); pairRefs = false;
             lvDepth0.release(); lvDepth1.release(); lvVals0.release(); lvVals1.release(); lvStartDev.release(); lvAnc0.release(); lvAnc1.release();
             levelOrder = nullptr; levelStart.clear(); levelsValid = false;
             valid = false;
@@ -843,7 +851,7 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s)
         }
     }
     if (tri > kMaxTriangles)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "scene has %llu triangles; limit is 2^30-1", (unsigned long long)tri);
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "scene has %llu triangles; limit is 2^29-1", (unsigned long long)tri);
     pairFirst.push_back(static_cast<uint32_t>(tri));
     {
         uint32_t typesSeen = 0; // bit per material type, unknown types share bit 3
@@ -1379,6 +1387,54 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
             }
         }
     }
+    // ---- or pair leaves (pt_bvh_build.hpp): not with pre-splitting; a refit keeps the pairs and recomputes their union boxes
+    if (!refit)
+    {
+        B.pairRefs = false;
+        if (r->env.pairLeaves && r->tree.splitBudget <= 0.0f && nTri > 1)
+        {
+            DevBuf<uint8_t> link;
+            DevBuf<uint32_t> s0, s1, head, sums;
+            const uint32_t sb = (nTri + 1 + kScan32Block - 1) / kScan32Block, tb = (nTri + 255) / 256;
+            BUILD_TRY(link.alloc(nTri)); BUILD_TRY(s0.alloc(nTri)); BUILD_TRY(s1.alloc(nTri)); BUILD_TRY(head.alloc((size_t)nTri + 1)); BUILD_TRY(sums.alloc(sb));
+            k_pair_links<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, r->pairs.p, r->indices.p, B.boxLo.p, B.boxHi.p, B.inert.p, link.p);
+            k_pair_jump<<<tb, 256, 0, r->stream>>>(nTri, link.p, nullptr, s0.p);
+            for (uint32_t span = 1; span < nTri; span *= 2) // after k jumps a run start up to 2^k positions back is found
+            {
+                k_pair_jump<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, s1.p);
+                s0.swap(s1);
+            }
+            BUILD_TRY(hipMemsetAsync(head.p + nTri, 0, sizeof(uint32_t), r->stream));
+            k_pair_heads<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, head.p);
+            if (sb > 1)
+            {
+                k_scan32_sums<<<sb, 256, 0, r->stream>>>(nTri + 1, head.p, sums.p);
+                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(sb, sums.p);
+                k_scan32_apply<<<sb, 256, 0, r->stream>>>(nTri + 1, head.p, sums.p);
+            }
+            else
+                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(nTri + 1, head.p);
+            uint32_t refs = 0;
+            BUILD_TRY(hipMemcpyAsync(&refs, head.p + nTri, sizeof(refs), hipMemcpyDeviceToHost, r->stream));
+            BUILD_TRY(hipStreamSynchronize(r->stream));
+            if (refs < nTri)
+            {
+                BUILD_TRY(B.refLo.alloc(refs)); BUILD_TRY(B.refHi.alloc(refs)); BUILD_TRY(B.refTri.alloc(refs)); BUILD_TRY(B.refInert.alloc(refs));
+                BUILD_TRY(B.refPair.alloc(refs)); BUILD_TRY(B.slotOf.alloc((size_t)refs + 1));
+                k_pair_write<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, head.p, B.inert.p, B.refTri.p, B.refPair.p, B.refInert.p);
+                BUILD_TRY(hipStreamSynchronize(r->stream)); // (the temporaries go out of scope)
+                n = refs;
+                B.pairRefs = true;
+            }
+        }
+    }
+    if (B.pairRefs)
+    {
+        k_ref_boxes<<<(n + 255) / 256, 256, 0, r->stream>>>(n, B.refTri.p, B.refPair.p, B.boxLo.p, B.boxHi.p, B.refLo.p, B.refHi.p);
+        refLo = B.refLo.p; refHi = B.refHi.p; refInert = B.refInert.p; refTri = B.refTri.p;
+    }
+    const uint8_t *refPair = B.pairRefs ? B.refPair.p : nullptr;
+    const uint32_t slotCap = std::max(n, nTri); // triangle slots: split copies, or every triangle once when references pair them
     if (!refit)
         B.refCount = n;
 
@@ -1388,8 +1444,8 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
     if (!refit)
     {
         BUILD_TRY(r->nodes.alloc(n)); // (as many as the emitted array: the two change places in the depth-first relayout)
-        BUILD_TRY(r->tris.alloc(n));
-        BUILD_TRY(r->shadeTris.alloc(n));
+        BUILD_TRY(r->tris.alloc(slotCap));
+        BUILD_TRY(r->shadeTris.alloc(slotCap));
         BUILD_TRY(B.nodeLo.alloc(n)); BUILD_TRY(B.nodeHi.alloc(n)); BUILD_TRY(B.vals0.alloc(n)); BUILD_TRY(B.vals1.alloc(n));
         BUILD_TRY(B.hist.alloc(histCount)); BUILD_TRY(B.histSums.alloc(histBlocks)); BUILD_TRY(B.flags.alloc(n));
         BUILD_TRY(B.keys0.alloc(n)); BUILD_TRY(B.keys1.alloc(n));
@@ -1437,15 +1493,35 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
         BUILD_TRY(hipMemcpyAsync(&nv, &B.sceneBounds.p[6], sizeof(nv), hipMemcpyDeviceToHost, r->stream));
         BUILD_TRY(hipStreamSynchronize(r->stream));
         B.treeTris = nv;
+        if (B.pairRefs) // the first triangle slot of every sorted reference (kept for refits, whose order is the same)
+        {
+            const uint32_t sb = (nv + 1 + kScan32Block - 1) / kScan32Block;
+            DevBuf<uint32_t> sums;
+            BUILD_TRY(sums.alloc(sb));
+            k_slot_sizes<<<(nv + 1 + 255) / 256, 256, 0, r->stream>>>(nv, vin, B.refPair.p, B.slotOf.p);
+            if (sb > 1)
+            {
+                k_scan32_sums<<<sb, 256, 0, r->stream>>>(nv + 1, B.slotOf.p, sums.p);
+                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(sb, sums.p);
+                k_scan32_apply<<<sb, 256, 0, r->stream>>>(nv + 1, B.slotOf.p, sums.p);
+            }
+            else
+                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(nv + 1, B.slotOf.p);
+            BUILD_TRY(hipStreamSynchronize(r->stream)); // (sums goes out of scope)
+        }
     }
-    r->treeTris = nv;
+    // triangle slots in the tree: the references', plus the second triangle of every pair (pairs are live: all in the tree)
+    const uint32_t pairLeaves = B.pairRefs ? nTri - n : 0u, slots = nv + pairLeaves;
+    r->treeTris = slots;
     r->stats.bvhNodes = nv > 1 ? nv - 1 : (nv ? 1 : 0);
-    r->stats.treeReferences = nv;
+    r->stats.treeReferences = slots;
     r->stats.treeTriangles = nTri - (n - nv); // a zero-area triangle has exactly one reference, and they are the ones left out
+    if (r->env.verbose && !refit && B.pairRefs)
+        std::fprintf(stderr, "[ptx] pair leaves: %u (%u of %u tree triangles paired)\n", pairLeaves, 2 * pairLeaves, slots);
     const uint32_t vblocks = (nv + 255) / 256;
     if (nv == 1)
         k_single_leaf_root<<<1, 1, 0, r->stream>>>(vin, refLo, refHi, B.triTmp.p, r->nodes.p, r->tris.p, r->pairs.p, r->vertices.p,
-                                                   r->indices.p, r->shadeTris.p);
+                                                   r->indices.p, r->shadeTris.p, refTri, refPair);
     else if (nv > 1)
     {
         bool boxesDone = false;
@@ -1584,7 +1660,7 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
         }
         k_emit<<<vblocks, 256, 0, r->stream>>>((int)nv, vin, refLo, refHi, B.children.p, B.nodeLo.p, B.nodeHi.p, B.triTmp.p,
                                               B.rawNodes.p, r->tris.p, r->pairs.p, r->vertices.p, r->indices.p, r->shadeTris.p,
-                                              r->tree.collapse ? B.collapseDecide.p : nullptr, refTri);
+                                              r->tree.collapse ? B.collapseDecide.p : nullptr, refTri, B.pairRefs ? B.slotOf.p : nullptr, refPair);
         // breadth-first relayout into the compact array (k_relayout_level): the host reads the level's end after each launch
         uint32_t *nextFree = B.oldOf.p + n;
         const uint32_t first[1] = { 0u }, one = 1u;
@@ -1626,8 +1702,8 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
     }
     if (r->anyNonOpaque && nv) // the any-hit records of the slots k_emit has just written
     {
-        BUILD_TRY(r->alphaTris.alloc(n));
-        k_alpha_tris<<<vblocks, 256, 0, r->stream>>>(nv, r->tris.p, r->shadeTris.p, makeSceneView(r), r->alphaTexOf.p, r->alphaTex.p, r->alphaTris.p);
+        BUILD_TRY(r->alphaTris.alloc(slotCap));
+        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->tris.p, r->shadeTris.p, makeSceneView(r), r->alphaTexOf.p, r->alphaTex.p, r->alphaTris.p);
     }
     uint32_t revived = 0;
     if (refit)

@@ -37,18 +37,19 @@ dbg.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
 
 
 def stats():
-    out, rounds = np.zeros((2, 68), np.uint32), np.zeros((2, 8), np.uint64)
+    out, rounds = np.zeros((2, 68), np.uint32), np.zeros((2, 10), np.uint64)
     assert dbg(out.ctypes.data, rounds.ctypes.data, 1) == 0
     return out, rounds
 
 
-def show_rounds(rs):
-    rounds, refills, refilled, nsteps, nlanes, leafs, llanes, waves = (float(x) for x in rs)
+def show_rounds(rs, rays):
+    rounds, refills, refilled, nsteps, nlanes, leafs, llanes, waves, leafVisits, triTests = (float(x) for x in rs)
     if not rounds:
         return
     print(f"    wave loop: {rounds / waves:8.1f} rounds per wave-launch; a round runs the refill {100 * refills / rounds:.0f} % of the time "
           f"({refilled / max(refills, 1):.1f} lanes), {nsteps / rounds:.2f} node steps ({nlanes / max(nsteps, 1):.1f} of 64 lanes in each), "
-          f"the leaf phase {100 * leafs / rounds:.0f} % ({llanes / max(leafs, 1):.1f} lanes)")
+          f"the leaf phase {100 * leafs / rounds:.0f} % ({llanes / max(leafs, 1):.1f} lanes); per ray {leafVisits / max(rays, 1):.2f} leaf visits, "
+          f"{triTests / max(rays, 1):.2f} triangle tests")
 
 
 def show(label, row):
@@ -82,6 +83,6 @@ for name in sys.argv[1:] or ["chess_like", "temple_like", "atrium_like", "street
         s, rs = stats()
         print(f" depth {depth}, 8 spp:")
         show("k_trace_closest", s[0])
-        show_rounds(rs[0])
+        show_rounds(rs[0], int(s[0][2]))
         show("k_trace_shadow ", s[1])
-        show_rounds(rs[1])
+        show_rounds(rs[1], int(s[1][2]))
