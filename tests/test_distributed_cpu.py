@@ -12,6 +12,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from util import pack_shard as _pack, unpack_shard as _unpack
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 
@@ -20,34 +22,6 @@ def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
-
-
-def _pack(img, mask_tiles, tile, W, H):
-    """Dense tile-major shard buffer [ownedTile][tile*tile][4] in the slot order of
-    csrc/pt_wavefront.hpp slotPixel(): 8x8 pixel blocks inside a tile."""
-    tiles_x = (W + tile - 1) // tile
-    out = np.zeros((len(mask_tiles), tile * tile, 4), np.float32)
-    bpr = tile // 8
-    o = np.arange(tile * tile)
-    blk, ib = o // 64, o % 64
-    lx, ly = (blk % bpr) * 8 + ib % 8, (blk // bpr) * 8 + ib // 8
-    for k, t in enumerate(mask_tiles):
-        x, y = (t % tiles_x) * tile + lx, (t // tiles_x) * tile + ly
-        ok = (x < W) & (y < H)
-        out[k, ok] = img[y[ok], x[ok]]
-    return out
-
-
-def _unpack(buf, mask_tiles, tile, W, H, img):
-    tiles_x = (W + tile - 1) // tile
-    bpr = tile // 8
-    o = np.arange(tile * tile)
-    blk, ib = o // 64, o % 64
-    lx, ly = (blk % bpr) * 8 + ib % 8, (blk // bpr) * 8 + ib // 8
-    for k, t in enumerate(mask_tiles):
-        x, y = (t % tiles_x) * tile + lx, (t // tiles_x) * tile + ly
-        ok = (x < W) & (y < H)
-        img[y[ok], x[ok]] = buf[k, ok]
 
 
 def _worker(rank, world, port, outdir):
@@ -136,7 +110,7 @@ def test_host_frames_in_shared_memory_are_seen_by_every_rank(tmp_path):
 # ---------------------------------------------------------------------------------------
 # the real N > 1 path: bench.py under torch.distributed.run, two ranks sharing GPU 0
 # ---------------------------------------------------------------------------------------
-def _run_bench_two_ranks(tmp_path, backend, extra=(), launcher=True):
+def _run_bench_two_ranks(tmp_path, backend, extra=(), launcher=True, ranks=2):
     import json
     import subprocess
 
@@ -146,8 +120,8 @@ def _run_bench_two_ranks(tmp_path, backend, extra=(), launcher=True):
         env.pop(k, None)
     cmd = [sys.executable]
     if launcher:  # as the driver starts an N > 1 run
-        cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-    cmd += [os.path.join(REPO, "bench.py"), "--gpus", "2", "--single-device", "--dist-backend", backend, "--full",
+        cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
+    cmd += [os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--single-device", "--dist-backend", backend, "--full",
             "--steps", "2", "--warmup", "1", "--repeats", "1", "--scene", "chess_like", "--detail", "0.05", "--width", "328", "--height", "200",
             "--spp", "4", "--depth", "6", "--cpu-seconds", "1", "--dump-image", str(out), "--dump-frames", str(tmp_path / f"frames_{backend}.npy"), *extra]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -166,17 +140,23 @@ def _single_rank_frame(pkg, W=328, H=200):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("backend", ["gloo", "nccl"])
-def test_bench_two_ranks_gather_the_single_rank_frame(pkg, tmp_path, backend):
+@pytest.mark.parametrize("backend,ranks", [("gloo", 2), ("nccl", 2), ("gloo", 3)], ids=["gloo", "nccl", "gloo-3ranks"])
+def test_bench_two_ranks_gather_the_single_rank_frame(pkg, tmp_path, backend, ranks):
     """bench.py's own step() with two ranks on one GPU -- samples accumulated straight in the gather's message
     (ptx_bind_shard_accumulation), ONE gather per step to the frame's owner, the owner ROTATING over the ranks (step k: rank k % 2),
     one ptx_unpack_shards launch that stores only to the host's frame, host frames in one shared-memory segment: EVERY frame of the
     job's store, whichever rank composed it, must be the single-rank frame bit for bit, and the JSON line must carry the
     strong-scaling metric with the weak one beside it, roofline.frac and the number of ranks the collective saw.
-    The gloo variant starts WITHOUT a launcher: bench.py spawns its own ranks."""
+    The gloo variant starts WITHOUT a launcher: bench.py spawns its own ranks.
+    With THREE ranks the world does not divide the 16 frames in flight: the rotating owner k % 3 against ring slot k % 16 gives
+    lcm = 48 host frames, the shards are unequal (26 / 26 / 25 tiles), and F + warm-up + steps = 16 + 1 + 31 = 48 steps write every
+    one of them once."""
     import json
+    import time
 
-    p, out = _run_bench_two_ranks(tmp_path, backend, launcher=(backend == "nccl"))
+    t0 = time.perf_counter()
+    p, out = _run_bench_two_ranks(tmp_path, backend, launcher=(backend == "nccl"), ranks=ranks, extra=("--steps", "31") if ranks == 3 else ())
+    print(f"bench.py with {ranks} {backend} ranks: {time.perf_counter() - t0:.1f} s wall")
     if p.returncode != 0 and backend == "nccl":
         # RCCL refuses two ranks on ONE device at communicator init ("Duplicate GPU detected", ncclInvalidUsage): that, and only
         # that, is a reason to skip -- any other failure of the RCCL branch is a failure of this test
@@ -188,17 +168,17 @@ def test_bench_two_ranks_gather_the_single_rank_frame(pkg, tmp_path, backend):
     last = p.stdout.splitlines()[-1]  # the LAST stdout line parses on its own, under RCCL's stdout chatter too
     line = json.loads(last)
     assert len(last) < 4096
-    assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["scaling"] == "strong" and line["weak"]["scaling"] == "weak" and line["value"] > 0
+    assert line["n_gpus"] == ranks and line["n_ranks_seen"] == ranks and line["scaling"] == "strong" and line["weak"]["scaling"] == "weak" and line["value"] > 0
     assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["cores"] >= 1  # the N > 1 line carries the CPU leg too
     assert 0 < line["roofline"]["frac"] < 1 and "rank k % N" in line["config"]["parallelism"]
     ref = _single_rank_frame(pkg)  # W, H = 328, 200: ragged, 328 is not a multiple of the 32-pixel tile
     got = np.load(out)
     assert (got.view(np.uint32) == ref.view(np.uint32)).all()
     frames = np.load(tmp_path / f"frames_{backend}.npy")
-    assert frames.shape[0] == 16  # lcm(2 ranks, 16 single-stream frames in flight); frame j composed by rank j % 2
+    assert frames.shape[0] == {2: 16, 3: 48}[ranks]  # lcm(ranks, 16 single-stream frames in flight); frame j composed by rank j % ranks
     assert line["config"]["frames_in_flight"] == 16 and "one stream" in line["config"]["parallelism"]
     for j in range(frames.shape[0]):
-        assert (frames[j].view(np.uint32) == ref.view(np.uint32)).all(), f"frame {j} (owner: rank {j % 2}) differs from the single-rank frame"
+        assert (frames[j].view(np.uint32) == ref.view(np.uint32)).all(), f"frame {j} (owner: rank {j % ranks}) differs from the single-rank frame"
 
 
 @pytest.mark.gpu

@@ -88,6 +88,96 @@ def random_rays(rng, n, lo, hi, tmax=1e4):
     return rays
 
 
+# ---------------------------------------------------------------------------------------
+# the tile-shard message of the gather (include/ptx.h: PtxTileShard, ptx_pack_shard, ptx_unpack_shards)
+# ---------------------------------------------------------------------------------------
+def pack_shard(img, mask_tiles, tile, W, H):
+    """Dense tile-major shard buffer [ownedTile][tile*tile][4] in the slot order of
+    csrc/pt_wavefront.hpp slotPixel(): 8x8 pixel blocks inside a tile."""
+    tiles_x = (W + tile - 1) // tile
+    out = np.zeros((len(mask_tiles), tile * tile, 4), np.float32)
+    bpr = tile // 8
+    o = np.arange(tile * tile)
+    blk, ib = o // 64, o % 64
+    lx, ly = (blk % bpr) * 8 + ib % 8, (blk // bpr) * 8 + ib // 8
+    for k, t in enumerate(mask_tiles):
+        x, y = (t % tiles_x) * tile + lx, (t // tiles_x) * tile + ly
+        ok = (x < W) & (y < H)
+        out[k, ok] = img[y[ok], x[ok]]
+    return out
+
+
+def unpack_shard(buf, mask_tiles, tile, W, H, img):
+    tiles_x = (W + tile - 1) // tile
+    bpr = tile // 8
+    o = np.arange(tile * tile)
+    blk, ib = o // 64, o % 64
+    lx, ly = (blk % bpr) * 8 + ib % 8, (blk // bpr) * 8 + ib // 8
+    for k, t in enumerate(mask_tiles):
+        x, y = (t % tiles_x) * tile + lx, (t // tiles_x) * tile + ly
+        ok = (x < W) & (y < H)
+        img[y[ok], x[ok]] = buf[k, ok]
+
+
+def shard_entries(W, H, rank, world, tile):
+    """The message of one rank, entry by entry, as include/ptx.h words it: the image is cut into tile x tile tiles numbered
+    row-major; the rank owns the tiles with tile % world == rank and its message holds them in increasing order, tile * tile
+    entries each; inside a tile the entries run over 8x8 pixel blocks in row-major order, inside a block over its pixels in
+    row-major order.  Returns int64[ownedTiles * tile * tile]: the row-major pixel index (y * W + x) of every entry, -1 for the
+    entries of a ragged tile that lie outside the image."""
+    assert tile >= 8 and tile % 8 == 0 and 0 <= rank < world
+    tiles_x, tiles_y = -(-W // tile), -(-H // tile)
+    blocks_per_row = tile // 8
+    out = []
+    for t in range(tiles_x * tiles_y):
+        if t % world != rank:
+            continue
+        x0, y0 = (t % tiles_x) * tile, (t // tiles_x) * tile
+        e = np.arange(tile * tile, dtype=np.int64)
+        block, inside = e // 64, e % 64
+        x = x0 + (block % blocks_per_row) * 8 + inside % 8
+        y = y0 + (block // blocks_per_row) * 8 + inside // 8
+        out.append(np.where((x < W) & (y < H), y * W + x, -1))
+    return np.concatenate(out) if out else np.zeros(0, np.int64)
+
+
+def gather_index(W, H, world, tile, stride_entries):
+    """For every pixel (row-major) the entry of the gather's receive buffer it comes from: the pieces of ranks 0 .. world-1 lie
+    `stride_entries` entries apart.  Written per pixel (which tile, whose, the how-manyeth of that rank, which 8x8 block of the
+    tile, which pixel of the block), not by inverting shard_entries.  Returns int64[W * H]."""
+    assert tile >= 8 and tile % 8 == 0
+    tiles_x = -(-W // tile)
+    y, x = np.divmod(np.arange(W * H, dtype=np.int64), W)
+    t = (y // tile) * tiles_x + x // tile
+    rank, nth = t % world, t // world
+    lx, ly = x % tile, y % tile
+    block = (ly // 8) * (tile // 8) + lx // 8
+    return rank * stride_entries + nth * tile * tile + block * 64 + (ly % 8) * 8 + lx % 8
+
+
+# (W, H, world, tile) -> (tiles_x, tiles_y, fewest owned tiles, most, empty ranks, entries outside the image), why the case is here
+SHARD_CASES = {
+    (1920, 1080, 4, 32): (60, 34, 510, 510, 0, 15360),   # BASELINE configs[3]
+    (1920, 1080, 8, 32): (60, 34, 255, 255, 0, 15360),   # the strong-scaling frame: equal tiles, unequal pixels per rank
+    (3840, 2160, 8, 32): (120, 68, 1020, 1020, 0, 61440),  # configs[4], bench.py's default tile
+    (3840, 2160, 8, 16): (240, 135, 4050, 4050, 0, 0),   # configs[4] as test_long_sample_schedules shards it
+    (512, 512, 8, 32): (16, 16, 32, 32, 0, 0),           # configs[0]; tiles_x % world == 0: a rank owns whole columns
+    (200, 120, 3, 32): (7, 4, 9, 10, 0, 4672),           # unequal shards
+    (328, 200, 2, 32): (11, 7, 38, 39, 0, 13248),        # the bench test's shape
+    (328, 200, 5, 8): (41, 25, 205, 205, 0, 0),          # smallest tile: one block per tile row
+    (328, 200, 7, 64): (6, 4, 3, 4, 0, 32704),           # large tile, prime world, 5,120 pixels beside 12,800
+    (257, 33, 5, 24): (11, 2, 4, 5, 0, 4191),            # 3 blocks per tile row
+    (131, 77, 1, 40): (4, 2, 8, 8, 0, 2713),             # 5 blocks per tile row; world 1 through the gather
+    (33, 257, 6, 16): (3, 17, 8, 9, 0, 4575),            # tall image, a rank with 128 pixels
+    (640, 360, 8, 128): (5, 3, 1, 2, 0, 15360),          # one and two owned tiles
+    (96, 54, 8, 32): (3, 2, 0, 1, 2, 960),               # more ranks than tiles
+    (100, 70, 16, 32): (4, 3, 0, 1, 4, 5288),            # world 16
+    (7, 5, 3, 8): (1, 1, 0, 1, 2, 29),                   # image smaller than a tile
+    (1, 1, 2, 8): (1, 1, 0, 1, 1, 63),
+}
+SHARD_SENTINEL = 0x7FC5A5A5  # a quiet NaN with a recognisable payload: what no renderer writes
+
+
 def render_pair(pkg, orc, name, detail, W, H, frames, depth, backend=0, brute=False, lens=0.0, sample_count=1, tile=None):
     """Render `frames` launches with the HIP path and with the oracle; returns both accumulation images
     after checking that segment / shadow-ray / sample / retry counts agree launch by launch."""
