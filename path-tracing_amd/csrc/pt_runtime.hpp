@@ -1,5 +1,5 @@
 // pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle, its device buffers, scene
-// upload, the tree build (kernels: pt_bvh_build.hpp), the bounce schedule of the wavefront backend, read-back, the output
+// upload, the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the bounce schedule of the wavefront backend, read-back, the output
 // stage.  Functions here take a valid handle; include/ptx.h's entry points (ptx_capi.hip) are thin wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
@@ -21,7 +21,7 @@
 // Host side: the renderer object behind the C-ABI
 // =====================================================================================
 
-// Owning device allocation: freed when it goes out of scope, so error returns (HIP_TRY / BUILD_TRY) and ptx_destroy
+// Owning device allocation: freed when it goes out of scope, so error returns (HIP_TRY) and ptx_destroy
 // release everything without a list of names to keep in step.
 template <typename T> struct DevBuf
 {
@@ -30,6 +30,8 @@ template <typename T> struct DevBuf
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { release(); swap(o); return *this; }
     ~DevBuf() { release(); }
     hipError_t alloc(size_t count)
     {
@@ -221,16 +223,6 @@ struct PtxRenderer
         std::vector<uint32_t> levelStart;     // [d] first position of depth d in levelOrder, [maxDepth + 1] = nodes
         bool levelsValid = false;
         bool valid = false;
-        void release()
-        {
-            triTmp.release(); boxLo.release(); boxHi.release(); nodeLo.release(); nodeHi.release(); sceneBounds.release();
-            vals0.release(); vals1.release(); hist.release(); histSums.release(); flags.release(); inert.release(); keys0.release(); keys1.release();
-            children.release(); parentOfNode.release(); parentOfLeaf.release(); rawNodes.release(); oldOf.release(); collapseCost.release(); collapseDecide.release();
-            refLo.release(); refHi.release(); refTri.release(); refInert.release(); refPair.release(); slotOf.release(); pairRefs = false;
-            lvDepth0.release(); lvDepth1.release(); lvVals0.release(); lvVals1.release(); lvStartDev.release(); lvAnc0.release(); lvAnc1.release();
-            levelOrder = nullptr; levelStart.clear(); levelsValid = false;
-            valid = false;
-        }
     } build;
     bool anyNonOpaque = false;  // some instanced geometry lacks the opaque flag: any-hit stages run
     bool mixedMaterialTypes = false; // the instanced meshes use more than one material type (ShaderTypes.incl:143-145): k_shade sorts its queue
@@ -747,7 +739,7 @@ static int shareScene(PtxRenderer *r, PtxRenderer *owner)
     r->alphaTex.release(); r->alphaTexOf.release(); r->alphaQuads.release(); r->alphaTris.release();
     r->animatedVertices.release(); r->skinSource.release(); r->bones.release();
     r->nodes.release(); r->tris.release(); r->shadeTris.release();
-    r->build.release();
+    r->build = PtxRenderer::BuildState();
     r->sceneReady = false;
     r->sceneOwner = owner;
     owner->sceneSharers.push_back(r);
@@ -873,7 +865,7 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s)
     r->staticVertexCount = s->vertexCount;
     r->skinnedCount = static_cast<uint32_t>(skinSource.size());
     r->boneCount = 0;
-    r->build.release();
+    r->build = PtxRenderer::BuildState();
     // bind pose of every skinned copy (OutBindPoseAnimatedVertices); the staging vectors live until the stream
     // synchronisation at the end of this function
     std::vector<PtxVertex> verts;
@@ -1192,702 +1184,7 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s)
     return PTX_OK;
 }
 
-static SceneView makeSceneView(const PtxRenderer *r);
-
-// One 8-bit pass of the LSD radix sort of pt_bvh_build.hpp over `count` (key, value) pairs; hist / histSums sized by the caller.
-static void radixPass(PtxRenderer *r, uint32_t count, const uint64_t *kin, const uint32_t *vin, uint64_t *kout, uint32_t *vout, uint32_t shift,
-                      uint32_t *hist, uint32_t *histSums)
-{
-    const uint32_t numTiles = (count + kSortTile - 1) / kSortTile;
-    const uint32_t histCount = 256 * numTiles, histBlocks = (histCount + kScan32Block - 1) / kScan32Block;
-    k_sort_hist<<<numTiles, 64, 0, r->stream>>>(count, kin, shift, numTiles, hist);
-    if (histBlocks > 1)
-    {
-        k_scan32_sums<<<histBlocks, 256, 0, r->stream>>>(histCount, hist, histSums);
-        k_scan_exclusive<<<1, 1024, 0, r->stream>>>(histBlocks, histSums);
-        k_scan32_apply<<<histBlocks, 256, 0, r->stream>>>(histCount, hist, histSums);
-    }
-    else
-        k_scan_exclusive<<<1, 1024, 0, r->stream>>>(histCount, hist);
-    k_sort_scatter<<<numTiles, 64, 0, r->stream>>>(count, kin, vin, kout, vout, shift, numTiles, hist);
-}
-
-// Level lists of the CURRENT binary topology over nv leaves (B.children / B.parentOfNode): B.levelOrder, B.levelStart.
-// *usable = false: the tree is deeper than kMaxTreeLevels (or is not a tree) and the caller takes the fence-and-atomic kernels.
-// Scratch: B.keys0 / keys1 (the Morton keys are done with), B.hist / histSums.
-static hipError_t treeLevels(PtxRenderer *r, uint32_t nv, bool *usable)
-{
-    PtxRenderer::BuildState &B = r->build;
-    B.levelsValid = false;
-    *usable = false;
-    if (nv < 2)
-        return hipSuccess;
-    const uint32_t nodes = nv - 1, blocks = (nodes + 255) / 256;
-#define LV_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
-    LV_TRY(B.lvDepth0.alloc(nodes)); LV_TRY(B.lvDepth1.alloc(nodes)); LV_TRY(B.lvAnc0.alloc(nodes)); LV_TRY(B.lvAnc1.alloc(nodes));
-    LV_TRY(B.lvVals0.alloc(nodes)); LV_TRY(B.lvVals1.alloc(nodes)); LV_TRY(B.lvStartDev.alloc(kMaxTreeLevels + 2));
-    uint32_t *d0 = B.lvDepth0.p, *d1 = B.lvDepth1.p, *flag = B.lvStartDev.p; // (flag: the first word, before the starts are written)
-    int *a0 = B.lvAnc0.p, *a1 = B.lvAnc1.p;
-    k_depth_init<<<blocks, 256, 0, r->stream>>>((int)nodes, B.parentOfNode.p, d0, a0);
-    bool done = false;
-    for (uint32_t pass = 0; pass < 24 && !done; pass++) // pass k covers paths of 2^(k + 1) links
-    {
-        LV_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), r->stream));
-        k_depth_jump<<<blocks, 256, 0, r->stream>>>((int)nodes, d0, a0, d1, a1, flag);
-        std::swap(d0, d1);
-        std::swap(a0, a1);
-        if (pass >= 4) // (a tree of 64 or more leaves is at least six deep: no point in asking earlier)
-        {
-            uint32_t pending = 0;
-            LV_TRY(hipMemcpyAsync(&pending, flag, sizeof(pending), hipMemcpyDeviceToHost, r->stream));
-            LV_TRY(hipStreamSynchronize(r->stream));
-            done = pending == 0;
-        }
-    }
-    if (!done)
-        return hipSuccess; // a parent chain longer than 2^24: not a tree the level passes can take
-    uint32_t maxDepth = 0;
-    LV_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), r->stream));
-    k_depth_keys<<<blocks, 256, 0, r->stream>>>((int)nodes, d0, B.keys0.p, B.lvVals0.p, flag);
-    LV_TRY(hipMemcpyAsync(&maxDepth, flag, sizeof(maxDepth), hipMemcpyDeviceToHost, r->stream));
-    LV_TRY(hipStreamSynchronize(r->stream));
-    if (maxDepth >= kMaxTreeLevels)
-        return hipSuccess;
-    const uint64_t *sortedKeys = B.keys1.p;
-    radixPass(r, nodes, B.keys0.p, B.lvVals0.p, B.keys1.p, B.lvVals1.p, 0, B.hist.p, B.histSums.p);
-    B.levelOrder = B.lvVals1.p;
-    if (maxDepth > 255)
-    {
-        radixPass(r, nodes, B.keys1.p, B.lvVals1.p, B.keys0.p, B.lvVals0.p, 8, B.hist.p, B.histSums.p);
-        B.levelOrder = B.lvVals0.p;
-        sortedKeys = B.keys0.p;
-    }
-    k_level_starts<<<blocks, 256, 0, r->stream>>>((int)nodes, sortedKeys, B.lvStartDev.p);
-    B.levelStart.assign(maxDepth + 2, 0u);
-    LV_TRY(hipMemcpyAsync(B.levelStart.data(), B.lvStartDev.p, (maxDepth + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    LV_TRY(hipStreamSynchronize(r->stream));
-    B.levelStart[maxDepth + 1] = nodes;
-    for (uint32_t d = 0; d <= maxDepth; d++) // every depth up to the deepest holds a node, in order
-        if (B.levelStart[d] >= B.levelStart[d + 1])
-            return hipSuccess;
-#undef LV_TRY
-    B.levelsValid = true;
-    *usable = true;
-    return hipSuccess;
-}
-
-// Bottom-up boxes of the binary tree over the level lists: one launch per level, deepest first.
-static void refitLevels(PtxRenderer *r, const uint32_t *vin, const float4 *refLo, const float4 *refHi)
-{
-    PtxRenderer::BuildState &B = r->build;
-    for (size_t d = B.levelStart.size() - 1; d-- > 0;)
-    {
-        const uint32_t first = B.levelStart[d], count = B.levelStart[d + 1] - first;
-        k_refit_level<<<(count + 255) / 256, 256, 0, r->stream>>>(first, count, B.levelOrder, vin, refLo, refHi, B.children.p, B.nodeLo.p, B.nodeHi.p);
-    }
-}
-
-// Full build (refit = false) or refit: new triangle records and leaf boxes, then the bottom-up box pass and the
-// 4-wide emit over the KEPT Morton order and binary topology.  keepState leaves the temporaries allocated for
-// later refits; a static scene frees them.
-static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
-{
-    HIP_TRY(r, hipSetDevice(r->device));
-    const uint32_t nTri = r->triCount;
-    if (nTri == 0)
-    {
-        if (!refit)
-        {
-            HIP_TRY(r, r->nodes.alloc(1));
-            HIP_TRY(r, r->tris.alloc(1));
-            HIP_TRY(r, r->shadeTris.alloc(1));
-        }
-        r->accelReady = true;
-        r->treeTris = 0;
-        r->stats.bvhNodes = 0;
-        r->stats.treeTriangles = r->stats.treeReferences = 0;
-        r->stats.lastBuildMs = 0.0;
-        return PTX_OK;
-    }
-    PtxRenderer::BuildState &B = r->build;
-#define BUILD_TRY(expr)                                                                                                    \
-    do                                                                                                                     \
-    {                                                                                                                      \
-        const hipError_t e_ = (expr);                                                                                      \
-        if (e_ != hipSuccess)                                                                                              \
-        {                                                                                                                  \
-            B.release();                                                                                                   \
-            return fail(r, e_ == hipErrorOutOfMemory ? PTX_ERROR_OUT_OF_MEMORY : PTX_ERROR_DEVICE, "%s: %s", #expr,       \
-                        hipGetErrorString(e_));                                                                            \
-        }                                                                                                                  \
-    } while (0)
-    // ---- per triangle: world-space record, padded box, zero-area flag
-    if (!refit)
-    {
-        B.valid = false;
-        // the level lists describe the topology of the LAST build: a full build starts without them (a build whose reinsertion
-        // passes do not run -- PTX_REINSERT=0, a broken pass, the rebuild after a revived triangle -- would otherwise price its
-        // collapse in the order and over the node count of an older tree)
-        B.levelsValid = false;
-        B.levelOrder = nullptr;
-        B.levelStart.clear();
-        BUILD_TRY(B.triTmp.alloc(nTri)); BUILD_TRY(B.boxLo.alloc(nTri)); BUILD_TRY(B.boxHi.alloc(nTri)); BUILD_TRY(B.inert.alloc(nTri));
-        BUILD_TRY(B.sceneBounds.alloc(8));
-    }
-    // [0..5] centroid bounds (ordered floats), [6] references in the tree (k_count_valid), [7] a refit found a revived triangle
-    const uint32_t initBounds[8] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u };
-    BUILD_TRY(hipMemcpyAsync(B.sceneBounds.p, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, r->stream));
-    BUILD_TRY(hipEventRecord(r->evA, r->stream));
-    k_tri_setup<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, r->pairCount, r->pairFirst.p, r->pairs.p, r->vertices.p, r->indices.p, B.triTmp.p,
-                                                          B.boxLo.p, B.boxHi.p, B.sceneBounds.p, B.inert.p, refit ? 1 : 0);
-
-    // ---- leaf references: one per triangle, or the pieces of the triangles worth splitting (static scenes, full builds: a
-    // refit keeps the references of the last full build, and a build that keeps its state for refits does not split)
-    uint32_t n = refit ? B.refCount : nTri;
-    const float4 *refLo = B.boxLo.p, *refHi = B.boxHi.p;
-    const uint8_t *refInert = B.inert.p;
-    const uint32_t *refTri = nullptr; // reference -> triangle (null: the identity)
-    if (!refit && !keepState && r->tree.splitBudget > 0.0f && nTri > 1)
-    {
-        DevBuf<float> priority;
-        DevBuf<uint32_t> count, sums;
-        DevBuf<unsigned long long> sum;
-        const uint32_t sb = (nTri + 1 + kScan32Block - 1) / kScan32Block;
-        BUILD_TRY(priority.alloc(nTri)); BUILD_TRY(count.alloc((size_t)nTri + 1)); BUILD_TRY(sums.alloc(sb)); BUILD_TRY(sum.alloc(1));
-        BUILD_TRY(hipMemsetAsync(sum.p, 0, sizeof(unsigned long long), r->stream));
-        k_split_priority<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p,
-                                                                   r->tree.mortonCubic ? 1 : 0, priority.p, sum.p);
-        unsigned long long total = 0;
-        BUILD_TRY(hipMemcpyAsync(&total, sum.p, sizeof(total), hipMemcpyDeviceToHost, r->stream));
-        BUILD_TRY(hipStreamSynchronize(r->stream));
-        if (total)
-        {
-            const float perPriority = (float)((double)r->tree.splitBudget * nTri / ((double)total / kSplitPriorityScale));
-            BUILD_TRY(hipMemsetAsync(count.p + nTri, 0, sizeof(uint32_t), r->stream));
-            k_split_count<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, priority.p, perPriority, count.p);
-            if (sb > 1)
-            {
-                k_scan32_sums<<<sb, 256, 0, r->stream>>>(nTri + 1, count.p, sums.p);
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(sb, sums.p);
-                k_scan32_apply<<<sb, 256, 0, r->stream>>>(nTri + 1, count.p, sums.p);
-            }
-            else
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(nTri + 1, count.p);
-            uint32_t refs = 0;
-            BUILD_TRY(hipMemcpyAsync(&refs, count.p + nTri, sizeof(refs), hipMemcpyDeviceToHost, r->stream));
-            BUILD_TRY(hipStreamSynchronize(r->stream));
-            if (refs > nTri && refs <= kMaxTriangles)
-            {
-                BUILD_TRY(B.refLo.alloc(refs)); BUILD_TRY(B.refHi.alloc(refs)); BUILD_TRY(B.refTri.alloc(refs)); BUILD_TRY(B.refInert.alloc(refs));
-                k_split_write<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p,
-                                                                        r->tree.mortonCubic ? 1 : 0, count.p, refs, B.refLo.p, B.refHi.p, B.refTri.p, B.refInert.p);
-                BUILD_TRY(hipStreamSynchronize(r->stream)); // (count and priority go out of scope)
-                n = refs;
-                refLo = B.refLo.p; refHi = B.refHi.p; refInert = B.refInert.p; refTri = B.refTri.p;
-            }
-        }
-    }
-    // ---- or pair leaves (pt_bvh_build.hpp): not with pre-splitting; a refit keeps the pairs and recomputes their union boxes
-    if (!refit)
-    {
-        B.pairRefs = false;
-        if (r->env.pairLeaves && r->tree.splitBudget <= 0.0f && nTri > 1)
-        {
-            DevBuf<uint8_t> link;
-            DevBuf<uint32_t> s0, s1, head, sums;
-            const uint32_t sb = (nTri + 1 + kScan32Block - 1) / kScan32Block, tb = (nTri + 255) / 256;
-            BUILD_TRY(link.alloc(nTri)); BUILD_TRY(s0.alloc(nTri)); BUILD_TRY(s1.alloc(nTri)); BUILD_TRY(head.alloc((size_t)nTri + 1)); BUILD_TRY(sums.alloc(sb));
-            k_pair_links<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, r->pairs.p, r->indices.p, B.boxLo.p, B.boxHi.p, B.inert.p, link.p);
-            k_pair_jump<<<tb, 256, 0, r->stream>>>(nTri, link.p, nullptr, s0.p);
-            for (uint32_t span = 1; span < nTri; span *= 2) // after k jumps a run start up to 2^k positions back is found
-            {
-                k_pair_jump<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, s1.p);
-                s0.swap(s1);
-            }
-            BUILD_TRY(hipMemsetAsync(head.p + nTri, 0, sizeof(uint32_t), r->stream));
-            k_pair_heads<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, head.p);
-            if (sb > 1)
-            {
-                k_scan32_sums<<<sb, 256, 0, r->stream>>>(nTri + 1, head.p, sums.p);
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(sb, sums.p);
-                k_scan32_apply<<<sb, 256, 0, r->stream>>>(nTri + 1, head.p, sums.p);
-            }
-            else
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(nTri + 1, head.p);
-            uint32_t refs = 0;
-            BUILD_TRY(hipMemcpyAsync(&refs, head.p + nTri, sizeof(refs), hipMemcpyDeviceToHost, r->stream));
-            BUILD_TRY(hipStreamSynchronize(r->stream));
-            if (refs < nTri)
-            {
-                BUILD_TRY(B.refLo.alloc(refs)); BUILD_TRY(B.refHi.alloc(refs)); BUILD_TRY(B.refTri.alloc(refs)); BUILD_TRY(B.refInert.alloc(refs));
-                BUILD_TRY(B.refPair.alloc(refs)); BUILD_TRY(B.slotOf.alloc((size_t)refs + 1));
-                k_pair_write<<<tb, 256, 0, r->stream>>>(nTri, link.p, s0.p, head.p, B.inert.p, B.refTri.p, B.refPair.p, B.refInert.p);
-                BUILD_TRY(hipStreamSynchronize(r->stream)); // (the temporaries go out of scope)
-                n = refs;
-                B.pairRefs = true;
-            }
-        }
-    }
-    if (B.pairRefs)
-    {
-        k_ref_boxes<<<(n + 255) / 256, 256, 0, r->stream>>>(n, B.refTri.p, B.refPair.p, B.boxLo.p, B.boxHi.p, B.refLo.p, B.refHi.p);
-        refLo = B.refLo.p; refHi = B.refHi.p; refInert = B.refInert.p; refTri = B.refTri.p;
-    }
-    const uint8_t *refPair = B.pairRefs ? B.refPair.p : nullptr;
-    const uint32_t slotCap = std::max(n, nTri); // triangle slots: split copies, or every triangle once when references pair them
-    if (!refit)
-        B.refCount = n;
-
-    // ---- per reference: everything from the Morton sort on
-    const uint32_t numTiles = (n + kSortTile - 1) / kSortTile;
-    const uint32_t histCount = 256 * numTiles, histBlocks = (histCount + kScan32Block - 1) / kScan32Block;
-    if (!refit)
-    {
-        BUILD_TRY(r->nodes.alloc(n)); // (as many as the emitted array: the two change places in the depth-first relayout)
-        BUILD_TRY(r->tris.alloc(slotCap));
-        BUILD_TRY(r->shadeTris.alloc(slotCap));
-        BUILD_TRY(B.nodeLo.alloc(n)); BUILD_TRY(B.nodeHi.alloc(n)); BUILD_TRY(B.vals0.alloc(n)); BUILD_TRY(B.vals1.alloc(n));
-        BUILD_TRY(B.hist.alloc(histCount)); BUILD_TRY(B.histSums.alloc(histBlocks)); BUILD_TRY(B.flags.alloc(n));
-        BUILD_TRY(B.keys0.alloc(n)); BUILD_TRY(B.keys1.alloc(n));
-        BUILD_TRY(B.children.alloc(n)); BUILD_TRY(B.parentOfNode.alloc(n)); BUILD_TRY(B.parentOfLeaf.alloc(n));
-        BUILD_TRY(B.rawNodes.alloc(n)); BUILD_TRY(B.oldOf.alloc((size_t)n + 1)); BUILD_TRY(B.collapseCost.alloc(n)); BUILD_TRY(B.collapseDecide.alloc(n));
-    }
-
-    // PLOC temporaries: two cluster sequences, neighbour indices, scan flags (sized for all n; freed when this returns)
-    DevBuf<int> cl0, cl1;
-    DevBuf<float4> lo0, hi0, lo1, hi1;
-    DevBuf<uint32_t> nn;
-    DevBuf<unsigned long long> flags, sums, total;
-    if (!refit && r->usePloc && n > 1)
-    {
-        BUILD_TRY(cl0.alloc(n)); BUILD_TRY(cl1.alloc(n)); BUILD_TRY(lo0.alloc(n)); BUILD_TRY(hi0.alloc(n)); BUILD_TRY(lo1.alloc(n));
-        BUILD_TRY(hi1.alloc(n)); BUILD_TRY(nn.alloc(n)); BUILD_TRY(flags.alloc(n)); BUILD_TRY(sums.alloc((n + kScanBlock - 1) / kScanBlock));
-        BUILD_TRY(total.alloc(1));
-    }
-    BUILD_TRY(hipMemsetAsync(B.flags.p, 0, (size_t)n * 4, r->stream));
-
-    const uint32_t blocks = (n + 255) / 256;
-    // 8 radix passes ping-pong the buffers an even number of times: the sorted order ends in keys0 / vals0
-    uint64_t *kin = B.keys0.p, *kout = B.keys1.p;
-    uint32_t *vin = B.vals0.p, *vout = B.vals1.p;
-    uint32_t nv = B.treeTris; // triangles in the tree: all but the zero-area ones, which sort to the end
-    if (!refit)
-    {
-        k_morton<<<blocks, 256, 0, r->stream>>>(n, refLo, refHi, B.sceneBounds.p, refInert, B.keys0.p, B.vals0.p, r->tree.mortonCubic ? 1 : 0);
-        for (uint32_t shift = 0; shift < 64; shift += 8) // 63-bit keys + the all-ones sentinel of inert triangles: 8 passes
-        {
-            k_sort_hist<<<numTiles, 64, 0, r->stream>>>(n, kin, shift, numTiles, B.hist.p);
-            if (histBlocks > 1)
-            {
-                k_scan32_sums<<<histBlocks, 256, 0, r->stream>>>(histCount, B.hist.p, B.histSums.p);
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(histBlocks, B.histSums.p);
-                k_scan32_apply<<<histBlocks, 256, 0, r->stream>>>(histCount, B.hist.p, B.histSums.p);
-            }
-            else
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(histCount, B.hist.p);
-            k_sort_scatter<<<numTiles, 64, 0, r->stream>>>(n, kin, vin, kout, vout, shift, numTiles, B.hist.p);
-            std::swap(kin, kout);
-            std::swap(vin, vout);
-        }
-        k_count_valid<<<1, 1, 0, r->stream>>>(n, kin, &B.sceneBounds.p[6]);
-        BUILD_TRY(hipMemcpyAsync(&nv, &B.sceneBounds.p[6], sizeof(nv), hipMemcpyDeviceToHost, r->stream));
-        BUILD_TRY(hipStreamSynchronize(r->stream));
-        B.treeTris = nv;
-        if (B.pairRefs) // the first triangle slot of every sorted reference (kept for refits, whose order is the same)
-        {
-            const uint32_t sb = (nv + 1 + kScan32Block - 1) / kScan32Block;
-            DevBuf<uint32_t> sums;
-            BUILD_TRY(sums.alloc(sb));
-            k_slot_sizes<<<(nv + 1 + 255) / 256, 256, 0, r->stream>>>(nv, vin, B.refPair.p, B.slotOf.p);
-            if (sb > 1)
-            {
-                k_scan32_sums<<<sb, 256, 0, r->stream>>>(nv + 1, B.slotOf.p, sums.p);
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(sb, sums.p);
-                k_scan32_apply<<<sb, 256, 0, r->stream>>>(nv + 1, B.slotOf.p, sums.p);
-            }
-            else
-                k_scan_exclusive<<<1, 1024, 0, r->stream>>>(nv + 1, B.slotOf.p);
-            BUILD_TRY(hipStreamSynchronize(r->stream)); // (sums goes out of scope)
-        }
-    }
-    // triangle slots in the tree: the references', plus the second triangle of every pair (pairs are live: all in the tree)
-    const uint32_t pairLeaves = B.pairRefs ? nTri - n : 0u, slots = nv + pairLeaves;
-    r->treeTris = slots;
-    r->stats.bvhNodes = nv > 1 ? nv - 1 : (nv ? 1 : 0);
-    r->stats.treeReferences = slots;
-    r->stats.treeTriangles = nTri - (n - nv); // a zero-area triangle has exactly one reference, and they are the ones left out
-    if (r->env.verbose && !refit && B.pairRefs)
-        std::fprintf(stderr, "[ptx] pair leaves: %u (%u of %u tree triangles paired)\n", pairLeaves, 2 * pairLeaves, slots);
-    const uint32_t vblocks = (nv + 255) / 256;
-    if (nv == 1)
-        k_single_leaf_root<<<1, 1, 0, r->stream>>>(vin, refLo, refHi, B.triTmp.p, r->nodes.p, r->tris.p, r->pairs.p, r->vertices.p,
-                                                   r->indices.p, r->shadeTris.p, refTri, refPair);
-    else if (nv > 1)
-    {
-        bool boxesDone = false;
-        if (!refit && r->usePloc)
-        {
-            // PLOC over the sorted leaves (temporaries allocated above, outside the timed span)
-            k_ploc_init<<<vblocks, 256, 0, r->stream>>>(nv, vin, refLo, refHi, cl0.p, lo0.p, hi0.p);
-            int *cIn = cl0.p, *cOut = cl1.p;
-            float4 *lIn = lo0.p, *hIn = hi0.p, *lOut = lo1.p, *hOut = hi1.p;
-            uint32_t count = nv;
-            int nextId = (int)nv - 2;
-            uint32_t iterations = 0;
-            while (count > 1)
-            {
-                const uint32_t cb = (count + 255) / 256, sb = (count + kScanBlock - 1) / kScanBlock;
-                k_ploc_nearest<<<cb, 256, 0, r->stream>>>(count, r->tree.plocRadius, r->tree.plocShape, lIn, hIn, nn.p);
-                k_ploc_flags<<<cb, 256, 0, r->stream>>>(count, nn.p, flags.p);
-                k_scan64_sums<<<sb, 256, 0, r->stream>>>(count, flags.p, sums.p);
-                k_scan64_top<<<1, 1024, 0, r->stream>>>(sb, sums.p, total.p);
-                k_scan64_apply<<<sb, 256, 0, r->stream>>>(count, flags.p, sums.p);
-                k_ploc_merge<<<cb, 256, 0, r->stream>>>(count, cIn, lIn, hIn, nn.p, flags.p, nextId, cOut, lOut, hOut, B.children.p, B.parentOfNode.p,
-                                                        B.parentOfLeaf.p, B.nodeLo.p, B.nodeHi.p);
-                unsigned long long t = 0;
-                BUILD_TRY(hipMemcpyAsync(&t, total.p, sizeof(t), hipMemcpyDeviceToHost, r->stream));
-                BUILD_TRY(hipStreamSynchronize(r->stream));
-                const uint32_t kept = (uint32_t)t, merged = (uint32_t)(t >> 32);
-                if (merged == 0 || kept + merged != count)
-                {
-                    B.release();
-                    return fail(r, PTX_ERROR_DEVICE, "ptx_build_accel: PLOC made no progress (%u clusters, %u kept, %u merged)", count, kept, merged);
-                }
-                nextId -= (int)merged;
-                count = kept;
-                std::swap(cIn, cOut);
-                std::swap(lIn, lOut);
-                std::swap(hIn, hOut);
-                iterations++;
-            }
-            if (r->env.verbose)
-                std::fprintf(stderr, "[ptx] PLOC: %u triangles (%u inert left out), %u iterations\n", nv, n - nv, iterations);
-            boxesDone = true;
-        }
-        else if (!refit)
-            k_karras<<<vblocks, 256, 0, r->stream>>>((int)nv, kin, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p);
-        // bottom-up boxes: over the level lists (kept from the last full build for a refit); the fence-and-atomic climb only for a
-        // tree the lists cannot take
-        const bool fenceKernels = r->env.fenceRefit;
-        bool haveLevels = false;
-        if (!boxesDone)
-        {
-            if (refit)
-                haveLevels = B.levelsValid && !fenceKernels;
-            else if (!fenceKernels)
-                BUILD_TRY(treeLevels(r, nv, &haveLevels));
-            if (haveLevels)
-                refitLevels(r, vin, refLo, refHi);
-            else
-                k_refit<<<vblocks, 256, 0, r->stream>>>((int)nv, vin, refLo, refHi, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p,
-                                                   B.nodeLo.p, B.nodeHi.p, B.flags.p);
-        }
-        const uint32_t reinsertPasses = (refit || r->reinsertBroken) ? 0u : r->tree.reinsertPasses;
-        if (reinsertPasses && nv > 3)
-        {
-            // parallel reinsertion over the binary tree (k_reinsert_find / _claim / _apply), boxes recomputed after every pass
-            const uint32_t slots = 2 * nv - 1, sblocks = (slots + 255) / 256;
-            DevBuf<int> target, top;
-            DevBuf<float> gain;
-            DevBuf<unsigned long long> lock;
-            DevBuf<uint32_t> applied;
-            BUILD_TRY(target.alloc(slots)); BUILD_TRY(top.alloc(slots)); BUILD_TRY(gain.alloc(slots)); BUILD_TRY(lock.alloc(slots)); BUILD_TRY(applied.alloc(1));
-            const ReinsertTree rt = { (int)nv, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p, B.nodeLo.p, B.nodeHi.p, vin, refLo, refHi };
-            for (uint32_t pass = 0; pass < reinsertPasses; pass++)
-            {
-                BUILD_TRY(hipMemsetAsync(lock.p, 0, (size_t)slots * sizeof(unsigned long long), r->stream));
-                BUILD_TRY(hipMemsetAsync(applied.p, 0, sizeof(uint32_t), r->stream));
-                k_reinsert_find<<<sblocks, 256, 0, r->stream>>>(rt, 1u, 0u, target.p, gain.p, top.p);
-                k_reinsert_claim<<<sblocks, 256, 0, r->stream>>>(rt, target.p, gain.p, top.p, lock.p);
-                k_reinsert_apply<<<sblocks, 256, 0, r->stream>>>(rt, target.p, gain.p, top.p, lock.p, applied.p);
-                // still a tree?  (a knot would hang k_refit: checked BEFORE the boxes are recomputed)
-                uint32_t moved = 0, check[3] = { 0, 0, 0 };
-                {
-                    DevBuf<uint32_t> counts;
-                    BUILD_TRY(counts.alloc(3));
-                    BUILD_TRY(hipMemsetAsync(counts.p, 0, 3 * sizeof(uint32_t), r->stream));
-                    k_tree_check<<<vblocks, 256, 0, r->stream>>>(rt, counts.p);
-                    BUILD_TRY(hipMemcpyAsync(check, counts.p, sizeof(check), hipMemcpyDeviceToHost, r->stream));
-                    BUILD_TRY(hipMemcpyAsync(&moved, applied.p, sizeof(moved), hipMemcpyDeviceToHost, r->stream));
-                    BUILD_TRY(hipStreamSynchronize(r->stream));
-                }
-                if (r->env.verbose)
-                    std::fprintf(stderr, "[ptx] reinsertion pass %u: %u moves; check: %u bad parent links, %u leaves off the root, longest path %u\n", pass,
-                                 moved, check[0], check[1], check[2]);
-                if (check[0] || check[1])
-                {
-                    // Not a tree any more (never seen since the path locks were completed, but the moves of a pass race by design):
-                    // this handle builds without reinsertion from now on, starting with this tree again.
-                    r->reinsertBroken = true;
-                    fail(r, PTX_OK, "ptx_build_accel: reinsertion pass %u left %u bad parent links, %u leaves off the root: rebuilt without reinsertion",
-                         pass, check[0], check[1]);
-                    if (r->env.verbose)
-                        std::fprintf(stderr, "[ptx] %s\n", r->error.c_str());
-                    BUILD_TRY(hipStreamSynchronize(r->stream));
-                    return buildAccel(r, false, keepState);
-                }
-                haveLevels = false;
-                if (!fenceKernels)
-                    BUILD_TRY(treeLevels(r, nv, &haveLevels)); // the pass changed the topology
-                if (haveLevels)
-                    refitLevels(r, vin, refLo, refHi);
-                else
-                {
-                    BUILD_TRY(hipMemsetAsync(B.flags.p, 0, (size_t)nv * 4, r->stream));
-                    k_refit<<<vblocks, 256, 0, r->stream>>>((int)nv, vin, refLo, refHi, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p, B.nodeLo.p, B.nodeHi.p,
-                                                       B.flags.p);
-                }
-            }
-            BUILD_TRY(hipStreamSynchronize(r->stream)); // (the pass's buffers go out of scope)
-        }
-        if (r->tree.collapse)
-        {
-            if (!refit && !B.levelsValid && !fenceKernels) // (PLOC computes its boxes itself: no pass above has asked for the lists yet)
-                BUILD_TRY(treeLevels(r, nv, &haveLevels));
-            if (B.levelsValid && !fenceKernels)
-                for (size_t d = B.levelStart.size() - 1; d-- > 0;)
-                {
-                    const uint32_t first = B.levelStart[d], count = B.levelStart[d + 1] - first;
-                    k_collapse_cost_level<<<(count + 255) / 256, 256, 0, r->stream>>>(first, count, B.levelOrder, vin, refLo, refHi, B.children.p, B.nodeLo.p,
-                                                                                     B.nodeHi.p, B.collapseCost.p, B.collapseDecide.p);
-                }
-            else
-            {
-                BUILD_TRY(hipMemsetAsync(B.flags.p, 0, (size_t)nv * 4, r->stream)); // (the arrival flags of k_refit: done with)
-                k_collapse_cost<<<vblocks, 256, 0, r->stream>>>((int)nv, vin, refLo, refHi, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p, B.nodeLo.p, B.nodeHi.p,
-                                                           B.flags.p, B.collapseCost.p, B.collapseDecide.p);
-            }
-        }
-        k_emit<<<vblocks, 256, 0, r->stream>>>((int)nv, vin, refLo, refHi, B.children.p, B.nodeLo.p, B.nodeHi.p, B.triTmp.p,
-                                              B.rawNodes.p, r->tris.p, r->pairs.p, r->vertices.p, r->indices.p, r->shadeTris.p,
-                                              r->tree.collapse ? B.collapseDecide.p : nullptr, refTri, B.pairRefs ? B.slotOf.p : nullptr, refPair);
-        // breadth-first relayout into the compact array (k_relayout_level): the host reads the level's end after each launch
-        uint32_t *nextFree = B.oldOf.p + n;
-        const uint32_t first[1] = { 0u }, one = 1u;
-        BUILD_TRY(hipMemcpyAsync(B.oldOf.p, first, sizeof(first), hipMemcpyHostToDevice, r->stream)); // the root stays node 0
-        BUILD_TRY(hipMemcpyAsync(nextFree, &one, sizeof(one), hipMemcpyHostToDevice, r->stream));
-        uint32_t lo = 0, hi = 1, levels = 0;
-        std::vector<uint32_t> levelStart; // of the breadth-first array, plus its end
-        while (lo < hi)
-        {
-            levelStart.push_back(lo);
-            k_relayout_level<<<(hi - lo + 255) / 256, 256, 0, r->stream>>>(lo, hi, B.rawNodes.p, B.oldOf.p, nextFree, r->nodes.p);
-            uint32_t end = 0;
-            BUILD_TRY(hipMemcpyAsync(&end, nextFree, sizeof(end), hipMemcpyDeviceToHost, r->stream));
-            BUILD_TRY(hipStreamSynchronize(r->stream));
-            if (end < hi || end > nv - 1)
-            {
-                B.release();
-                return fail(r, PTX_ERROR_DEVICE, "ptx_build_accel: relayout placed %u nodes of at most %u", end, nv - 1);
-            }
-            lo = hi;
-            hi = end;
-            levels++;
-        }
-        r->stats.bvhNodes = hi;
-        if (r->tree.layout == 1 && hi > 1)
-        {
-            // depth-first order (k_subtree_size / _pos / k_place_nodes); scratch: the build's flag and neighbour arrays are done with
-            levelStart.push_back(hi);
-            uint32_t *size = B.flags.p, *pos = B.vals1.p == vin ? B.vals0.p : B.vals1.p; // (the sorted order sits in the other one)
-            for (uint32_t l = levels; l-- > 0;)
-                k_subtree_size<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->nodes.p, size);
-            for (uint32_t l = 0; l < levels; l++)
-                k_subtree_pos<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->nodes.p, size, pos);
-            k_place_nodes<<<(hi + 255) / 256, 256, 0, r->stream>>>(hi, r->nodes.p, pos, B.rawNodes.p);
-            r->nodes.swap(B.rawNodes); // the emitted nodes are not needed again before the next k_emit, which rewrites them all
-        }
-        if (r->env.verbose)
-            std::fprintf(stderr, "[ptx] relayout: %u of %u emitted nodes are live, %u levels\n", hi, nv - 1, levels);
-    }
-    if (r->anyNonOpaque && nv) // the any-hit records of the slots k_emit has just written
-    {
-        BUILD_TRY(r->alphaTris.alloc(slotCap));
-        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->tris.p, r->shadeTris.p, makeSceneView(r), r->alphaTexOf.p, r->alphaTex.p, r->alphaTris.p);
-    }
-    uint32_t revived = 0;
-    if (refit)
-        BUILD_TRY(hipMemcpyAsync(&revived, &B.sceneBounds.p[7], sizeof(revived), hipMemcpyDeviceToHost, r->stream));
-    BUILD_TRY(hipEventRecord(r->evB, r->stream));
-    BUILD_TRY(hipStreamSynchronize(r->stream));
-    BUILD_TRY(hipGetLastError());
-    if (revived) // a triangle the last full build left out has an area now: it is not in the kept topology
-        return buildAccel(r, false, keepState);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r->evA, r->evB);
-    r->stats.lastBuildMs = ms;
-    if (keepState)
-        B.valid = true;
-    else
-        B.release();
-#undef BUILD_TRY
-    r->accelReady = true;
-    return PTX_OK;
-}
-
-static TraceScene makeTraceScene(const PtxRenderer *r);
-
-// The price of the tree just built on the sampled segments (k_sample_tree_cost): mean visits + tests per ray, the tail, and
-// the figure the candidates are compared by.  The tail term: a persistent traversal launch ends with its longest ray, and in the
-// thin launches of late bounces and of small tile shards that ray IS the launch -- a tree that saves 1 % on the mean and grows
-// its longest walks by a third is not cheaper.
-struct TreeCost
-{
-    double mean = 0.0;   // visits + tests per ray, without the top 0.1 % of the rays (robust against the odd ray that skims a surface)
-    uint32_t p999 = 0;   // 99.9th percentile
-    uint32_t worst = 0;
-    double figure() const { return mean + kTreeTailWeight * (double)p999; }
-    static constexpr double kTreeTailWeight = 0.02; // a p99.9 five times the mean adds 10 % to the figure
-};
-constexpr uint32_t kTreeSampleRays = 65536;
-
-static int sampleTreeCost(PtxRenderer *r, DevBuf<float4> &segments, bool drawSegments, TreeCost *cost)
-{
-    DevBuf<uint32_t> d;
-    HIP_TRY(r, d.alloc(kTreeSampleRays));
-    HIP_TRY(r, segments.alloc(2 * (size_t)kTreeSampleRays));
-    const TraceScene sc = makeTraceScene(r);
-    if (drawSegments)
-        k_sample_segments<<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, kTreeSampleRays, segments.p);
-    if (r->anyNonOpaque)
-        k_sample_tree_cost<true><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
-    else
-        k_sample_tree_cost<false><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
-    std::vector<uint32_t> h(kTreeSampleRays);
-    HIP_TRY(r, hipMemcpyAsync(h.data(), d.p, kTreeSampleRays * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    std::sort(h.begin(), h.end());
-    const uint32_t kept = kTreeSampleRays - kTreeSampleRays / 1000;
-    unsigned long long sum = 0;
-    for (uint32_t k = 0; k < kept; k++)
-        sum += h[k];
-    cost->mean = (double)sum / kept;
-    cost->p999 = h[kept - 1];
-    cost->worst = h.back();
-    return PTX_OK;
-}
-
-static int buildBestTree(PtxRenderer *r)
-{
-    if (r && r->sceneOwner)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_build_accel: this renderer shares another renderer's scene (ptx_share_scene)");
-    if (!r || !r->sceneReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_build_accel: no scene uploaded");
-    quiesceSharers(r);
-    r->sceneEpoch++; // schedules learnt on the old tree's scene are not this one's (ptx_scene_upload without a build in between cannot render)
-    // Which tree?  Build a few candidates, price each on the same sampled surface-to-surface segments, keep the cheapest (its
-    // buffers are swapped aside while the others are built; lastBuildMs is the time of everything).  Parameters given in the
-    // environment, the Karras builder and small scenes skip the comparison; the per-frame rebuilds of an animation use the
-    // parameters chosen here.
-    struct Candidate { uint32_t radius; float shape; bool cubic; };
-    // (round 4, on the cosine-ray sampler, twelve settings tried per stand-in: these seven hold every scene's best or come within
-    // 0.3 % of it -- chess_like (64, 0.25), atrium_like (4, 0.25), street_like (8, 1, cubic), temple_like (16, 0.25); the spread
-    // between best and worst setting of a scene is 5-10 %)
-    static const Candidate kTreeCandidates[] = { { 8u, 0.0f, false }, { 16u, 0.0f, false }, { 16u, 0.25f, false }, { 32u, 1.0f, false }, { 8u, 1.0f, true },
-                                                 { 64u, 0.25f, false }, { 4u, 0.25f, false } };
-    constexpr uint32_t kCandidates = sizeof(kTreeCandidates) / sizeof(kTreeCandidates[0]);
-    if (!r->usePloc || r->env.plocFixed || r->triCount < 4096u)
-    {
-        // ONE tree: it gets the full number of reinsertion passes at once
-        const TreeParams keep = r->tree;
-        r->tree.reinsertPasses = std::max(keep.reinsertPasses, keep.reinsertFinal);
-        const int rc = buildAccel(r, false, false);
-        r->tree = keep;
-        return rc;
-    }
-    DevBuf<BvhNode> bestNodes;
-    DevBuf<Tri> bestTris;
-    DevBuf<ShadeTri> bestShadeTris;
-    DevBuf<AlphaTri> bestAlphaTris;
-    DevBuf<float4> segments;
-    auto swapTree = [&]() { r->nodes.swap(bestNodes); r->tris.swap(bestTris); r->shadeTris.swap(bestShadeTris); r->alphaTris.swap(bestAlphaTris); };
-    TreeCost cost[kCandidates];
-    uint64_t bestNodeCount = 0, bestReferences = 0;
-    uint32_t bestTreeTris = 0; // (leaf slots: with pre-splitting the candidates can differ -- cubic cells move the cut planes)
-    double totalMs = 0.0;
-    uint32_t best = 0, built = 0;
-    const TreeParams given = r->tree; // what the candidates do not vary (the collapse)
-    // While candidates are built the renderer's buffers hold whichever tree was built last and the best one sits in the locals
-    // above: nothing may render (or borrow the scene) until the final swap.  A candidate that fails (out of memory, a device
-    // error) does not take the scene down with it when an earlier one succeeded: that tree, its parameters and its node count
-    // are put back and the build succeeds with it.
-    r->accelReady = false;
-    for (uint32_t k = 0; k < kCandidates; k++)
-    {
-        r->tree = given;
-        r->tree.plocRadius = kTreeCandidates[k].radius;
-        r->tree.plocShape = kTreeCandidates[k].shape;
-        r->tree.mortonCubic = kTreeCandidates[k].cubic;
-        int rc = buildAccel(r, false, false);
-        totalMs += r->stats.lastBuildMs;
-        if (rc != PTX_OK || (rc = sampleTreeCost(r, segments, k == 0, &cost[k])) != PTX_OK)
-        {
-            r->accelReady = false;
-            if (k == 0)
-                return rc; // no tree at all: the error stands (ptx_last_error has the text)
-            if (r->env.verbose)
-                std::fprintf(stderr, "[ptx] tree candidate %u failed (%s): keeping candidate %u\n", k, r->error.c_str(), best);
-            break;
-        }
-        built = k + 1;
-        if (k == 0 || cost[k].figure() < cost[best].figure())
-        {
-            best = k;
-            bestNodeCount = r->stats.bvhNodes;
-            bestReferences = r->stats.treeReferences;
-            bestTreeTris = r->treeTris;
-            swapTree(); // the renderer's buffers now hold the previous best (or nothing): the next candidate is built over them
-        }
-    }
-    // The winner once more, with the full number of reinsertion passes (the candidates had a few: the ranking is the same with 2
-    // as with 64, the cost keeps falling for dozens of passes).  Built over the renderer's buffers -- they hold a loser --, priced
-    // on the same rays, and kept only if it is no worse; if it fails, the candidate stands.
-    TreeCost finalCost;
-    bool haveFinal = false;
-    if (given.reinsertFinal > given.reinsertPasses && built > 0)
-    {
-        r->tree = given;
-        r->tree.plocRadius = kTreeCandidates[best].radius;
-        r->tree.plocShape = kTreeCandidates[best].shape;
-        r->tree.mortonCubic = kTreeCandidates[best].cubic;
-        r->tree.reinsertPasses = given.reinsertFinal;
-        int rc = buildAccel(r, false, false);
-        totalMs += r->stats.lastBuildMs;
-        if (rc == PTX_OK && sampleTreeCost(r, segments, false, &finalCost) == PTX_OK && finalCost.figure() <= cost[best].figure())
-        {
-            haveFinal = true;
-            bestNodeCount = r->stats.bvhNodes;
-            bestReferences = r->stats.treeReferences;
-            bestTreeTris = r->treeTris;
-        }
-        else if (r->env.verbose)
-            std::fprintf(stderr, "[ptx] the fully re-optimised tree was not kept (%s)\n", rc == PTX_OK ? "no cheaper" : r->error.c_str());
-        r->accelReady = false;
-    }
-    if (!haveFinal)
-        swapTree();
-    r->stats.bvhNodes = bestNodeCount;
-    r->stats.treeReferences = bestReferences;
-    r->treeTris = bestTreeTris;
-    r->tree = given;
-    r->tree.plocRadius = kTreeCandidates[best].radius;
-    r->tree.plocShape = kTreeCandidates[best].shape;
-    r->tree.mortonCubic = kTreeCandidates[best].cubic;
-    r->stats.lastBuildMs = totalMs;
-    r->accelReady = true;
-    if (r->env.verbose)
-    {
-        std::fprintf(stderr, "[ptx] tree cost on %u sampled rays, mean (lowest 99.9 %%) / p99.9 / max visits + tests per ray:", kTreeSampleRays);
-        for (uint32_t k = 0; k < built; k++)
-            std::fprintf(stderr, " (radius %u, shape %.2f%s) %.2f / %u / %u%s", kTreeCandidates[k].radius, kTreeCandidates[k].shape,
-                         kTreeCandidates[k].cubic ? ", cubic cells" : "", cost[k].mean, cost[k].p999, cost[k].worst, k == best ? " <- kept" : "");
-        if (haveFinal)
-            std::fprintf(stderr, "; with %u reinsertion passes %.2f / %u / %u", given.reinsertFinal, finalCost.mean, finalCost.p999, finalCost.worst);
-        std::fprintf(stderr, "; collapse %s, %u reinsertion passes per candidate; %.1f ms\n", given.collapse ? "cost-driven" : "greedy", given.reinsertPasses, totalMs);
-    }
-    return PTX_OK;
-}
+#include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
 
 // Renderer.cpp:1750-1754 (+ RecordSkinningCommands :854-890, AccelerationStructure::Update :48-57)
 static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, uint32_t instanceCount, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate)
