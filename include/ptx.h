@@ -406,7 +406,8 @@ PTX_API int ptx_device_count(void);
  * this with the header it was written against before the first call (the Python package and RendererHip do). */
 PTX_API uint32_t ptx_abi_version(void);
 
-/* Renderer::UpdateSceneData (Renderer.cpp:238-439): copy the scene to HBM. */
+/* Renderer::UpdateSceneData (Renderer.cpp:238-439): copy the scene to HBM.  A description that is refused with
+ * PTX_ERROR_INVALID_ARGUMENT, for whatever reason, leaves the handle as it was: its own scene, or the one it borrows. */
 PTX_API int ptx_scene_upload(PtxRenderer *r, const PtxSceneDesc *scene);
 /* AccelerationStructure::Build (AccelerationStructure.cpp:26-46; BLAS :64-247, TLAS
  * :250-301), replaced by a software LBVH over the flattened world-space triangles.

@@ -3,9 +3,6 @@
 // Included by pt_runtime.hpp below the renderer object (PtxRenderer, DevBuf, HIP_TRY, fail); a stage returns a PTX_* code.
 #pragma once
 
-static SceneView makeSceneView(const PtxRenderer *r);
-static TraceScene makeTraceScene(const PtxRenderer *r);
-
 // Exclusive scan in place of `count` 32-bit counts; blockSums holds one word per kScan32Block counts (unused for one block).
 static void scanExclusive32(hipStream_t stream, uint32_t count, uint32_t *data, uint32_t *blockSums)
 {
@@ -139,7 +136,7 @@ static int bottomUpPass(PtxRenderer *r, const RefSet &refs, uint32_t nv, bool pr
 static int triangleRecords(PtxRenderer *r, bool refit)
 {
     PtxRenderer::BuildState &B = r->build;
-    const uint32_t nTri = r->triCount;
+    const uint32_t nTri = r->scene.triCount;
     if (!refit)
     {
         B.valid = false;
@@ -156,7 +153,7 @@ static int triangleRecords(PtxRenderer *r, bool refit)
     const uint32_t initBounds[8] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u };
     HIP_TRY(r, hipMemcpyAsync(B.sceneBounds.p, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, r->stream));
     HIP_TRY(r, hipEventRecord(r->evA, r->stream));
-    k_tri_setup<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, r->pairCount, r->pairFirst.p, r->pairs.p, r->vertices.p, r->indices.p, B.triTmp.p,
+    k_tri_setup<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, r->scene.pairCount, r->scene.pairFirst.p, r->scene.pairs.p, r->scene.vertices.p, r->scene.indices.p, B.triTmp.p,
                                                           B.boxLo.p, B.boxHi.p, B.sceneBounds.p, B.inert.p, refit ? 1 : 0);
     return PTX_OK;
 }
@@ -166,7 +163,7 @@ static int triangleRecords(PtxRenderer *r, bool refit)
 static int splitReferences(PtxRenderer *r, uint32_t *n)
 {
     PtxRenderer::BuildState &B = r->build;
-    const uint32_t nTri = r->triCount, tb = (nTri + 255) / 256;
+    const uint32_t nTri = r->scene.triCount, tb = (nTri + 255) / 256;
     DevBuf<float> priority;
     DevBuf<uint32_t> count, sums;
     DevBuf<unsigned long long> sum;
@@ -200,12 +197,12 @@ static int splitReferences(PtxRenderer *r, uint32_t *n)
 static int pairReferences(PtxRenderer *r, uint32_t *n)
 {
     PtxRenderer::BuildState &B = r->build;
-    const uint32_t nTri = r->triCount, tb = (nTri + 255) / 256;
+    const uint32_t nTri = r->scene.triCount, tb = (nTri + 255) / 256;
     DevBuf<uint8_t> link;
     DevBuf<uint32_t> s0, s1, head, sums;
     HIP_TRY(r, link.alloc(nTri)); HIP_TRY(r, s0.alloc(nTri)); HIP_TRY(r, s1.alloc(nTri)); HIP_TRY(r, head.alloc((size_t)nTri + 1));
     HIP_TRY(r, sums.alloc((nTri + 1 + kScan32Block - 1) / kScan32Block));
-    k_pair_links<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, r->pairs.p, r->indices.p, B.boxLo.p, B.boxHi.p, B.inert.p, link.p);
+    k_pair_links<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, r->scene.pairs.p, r->scene.indices.p, B.boxLo.p, B.boxHi.p, B.inert.p, link.p);
     k_pair_jump<<<tb, 256, 0, r->stream>>>(nTri, link.p, nullptr, s0.p);
     for (uint32_t span = 1; span < nTri; span *= 2) // after k jumps a run start up to 2^k positions back is found
     {
@@ -234,7 +231,7 @@ static int pairReferences(PtxRenderer *r, uint32_t *n)
 static int leafReferences(PtxRenderer *r, bool refit, bool keepState, RefSet *refs)
 {
     PtxRenderer::BuildState &B = r->build;
-    const uint32_t nTri = r->triCount;
+    const uint32_t nTri = r->scene.triCount;
     uint32_t n = refit ? B.refCount : nTri;
     int rc;
     if (!refit)
@@ -455,7 +452,7 @@ static int relayoutNodes(PtxRenderer *r, uint32_t n, uint32_t nv)
 static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver)
 {
     PtxRenderer::BuildState &B = r->build;
-    const uint32_t nTri = r->triCount;
+    const uint32_t nTri = r->scene.triCount;
     int rc;
     RefSet refs;
     PlocScratch ploc;
@@ -474,8 +471,8 @@ static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver
     if (r->env.verbose && !refit && B.pairRefs)
         std::fprintf(stderr, "[ptx] pair leaves: %u (%u of %u tree triangles paired)\n", pairLeaves, 2 * pairLeaves, slots);
     if (nv == 1)
-        k_single_leaf_root<<<1, 1, 0, r->stream>>>(B.vals0.p, refs.lo, refs.hi, B.triTmp.p, r->nodes.p, r->tris.p, r->pairs.p, r->vertices.p,
-                                                   r->indices.p, r->shadeTris.p, refs.tri, refs.pair);
+        k_single_leaf_root<<<1, 1, 0, r->stream>>>(B.vals0.p, refs.lo, refs.hi, B.triTmp.p, r->nodes.p, r->tris.p, r->scene.pairs.p, r->scene.vertices.p,
+                                                   r->scene.indices.p, r->shadeTris.p, refs.tri, refs.pair);
     else if (nv > 1)
     {
         if (refit)
@@ -488,15 +485,15 @@ static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver
         if (r->tree.collapse && (rc = bottomUpPass(r, refs, nv, true, !refit && !B.levelsValid)) != PTX_OK)
             return rc;
         k_emit<<<(nv + 255) / 256, 256, 0, r->stream>>>((int)nv, B.vals0.p, refs.lo, refs.hi, B.children.p, B.nodeLo.p, B.nodeHi.p, B.triTmp.p,
-                                                       B.rawNodes.p, r->tris.p, r->pairs.p, r->vertices.p, r->indices.p, r->shadeTris.p,
+                                                       B.rawNodes.p, r->tris.p, r->scene.pairs.p, r->scene.vertices.p, r->scene.indices.p, r->shadeTris.p,
                                                        r->tree.collapse ? B.collapseDecide.p : nullptr, refs.tri, B.pairRefs ? B.slotOf.p : nullptr, refs.pair);
         if ((rc = relayoutNodes(r, refs.n, nv)) != PTX_OK)
             return rc;
     }
-    if (r->anyNonOpaque && nv) // the any-hit records of the slots k_emit has just written
+    if (r->scene.anyNonOpaque && nv) // the any-hit records of the slots k_emit has just written
     {
         HIP_TRY(r, r->alphaTris.alloc(slotCap));
-        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->tris.p, r->shadeTris.p, makeSceneView(r), r->alphaTexOf.p, r->alphaTex.p, r->alphaTris.p);
+        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->tris.p, r->shadeTris.p, makeSceneView(r), r->scene.alphaTexOf.p, r->scene.alphaTex.p, r->alphaTris.p);
     }
     uint32_t revived = 0;
     if (refit)
@@ -513,7 +510,7 @@ static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver
 static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
 {
     HIP_TRY(r, hipSetDevice(r->device));
-    if (r->triCount == 0)
+    if (r->scene.triCount == 0)
     {
         if (!refit)
         {
@@ -565,7 +562,7 @@ static int sampleTreeCost(PtxRenderer *r, DevBuf<float4> &segments, bool drawSeg
     const TraceScene sc = makeTraceScene(r);
     if (drawSegments)
         k_sample_segments<<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, kTreeSampleRays, segments.p);
-    if (r->anyNonOpaque)
+    if (r->scene.anyNonOpaque)
         k_sample_tree_cost<true><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
     else
         k_sample_tree_cost<false><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
@@ -615,7 +612,7 @@ static int buildBestTree(PtxRenderer *r)
     static const TreeCandidate kTreeCandidates[] = { { 8u, 0.0f, false }, { 16u, 0.0f, false }, { 16u, 0.25f, false }, { 32u, 1.0f, false }, { 8u, 1.0f, true },
                                                      { 64u, 0.25f, false }, { 4u, 0.25f, false } };
     constexpr uint32_t kCandidates = sizeof(kTreeCandidates) / sizeof(kTreeCandidates[0]);
-    if (!r->usePloc || r->env.plocFixed || r->triCount < 4096u)
+    if (!r->usePloc || r->env.plocFixed || r->scene.triCount < 4096u)
     {
         // ONE tree: it gets the full number of reinsertion passes at once
         const TreeParams keep = r->tree;

@@ -1,5 +1,5 @@
 // pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle, its device buffers, scene
-// upload, the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the bounce schedule of the wavefront backend, read-back, the output
+// upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the bounce schedule of the wavefront backend, read-back, the output
 // stage.  Functions here take a valid handle; include/ptx.h's entry points (ptx_capi.hip) are thin wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
@@ -150,17 +150,10 @@ struct EnvSwitches
     }
 };
 
-struct PtxRenderer
+// What ptx_scene_upload produces (pt_scene_host.hpp): HBM copies of the Scene getters, the decoded textures, the any-hit tables,
+// the host's side of the animation.  One member of the handle, so that ptx_share_scene drops a borrower's copy by assignment.
+struct SceneData
 {
-    EnvSwitches env;
-    int device = 0;
-    uint32_t backend = PTX_BACKEND_WAVEFRONT;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    bool counted = false; // in g_liveHandles
-    std::string error;
-
-    // scene (HBM copies of the Scene getters)
     DevBuf<PtxVertex> vertices;
     DevBuf<uint32_t> indices;
     DevBuf<PtxMetallicRoughnessMaterial> mr;
@@ -168,20 +161,14 @@ struct PtxRenderer
     DevBuf<PtxPhongMaterial> phong;
     DevBuf<DevPair> pairs;
     DevBuf<uint32_t> pairFirst;
-    DevBuf<PtxLightsUbo> lights;
-    DevBuf<DevTexture> textures;
-    DevBuf<uint32_t> texels8; // upload time: the pools of the image formats, in which mip chains are built; released after
-    DevBuf<float4> texelsF;
-    DevBuf<float> srgbLut;
     DevBuf<DevTexture> renderTextures; // what the render kernels sample: every texel decoded to four floats, one pool
     DevBuf<float4> renderTexels;
     // what the any-hit stages read (scenes with non-opaque geometry; pt_bvh.hpp, hitAlpha)
     DevBuf<AlphaTex> alphaTex;     // per colour texture
     DevBuf<uint32_t> alphaTexOf;   // scene texture -> entry of alphaTex
     DevBuf<float4> alphaQuads;     // 2 x 2 alpha footprints of their base levels
-    DevBuf<AlphaTri> alphaTris;    // per triangle slot, written behind k_emit
     uint32_t textureCount = 0;
-    uint32_t skyKind = PTX_SKYBOX_CLEAR_COLOR; // its images follow the scene textures in `textures`
+    uint32_t skyKind = PTX_SKYBOX_CLEAR_COLOR; // its images follow the scene textures in `renderTextures`
     bool samplerNeeded = false; // some uploaded texture is not a 1x1 white placeholder
     // animation (row N3)
     std::vector<DevPair> hostPairs;            // to recompose pair transforms when instances move
@@ -192,6 +179,25 @@ struct PtxRenderer
     DevBuf<PtxAnimatedVertex> animatedVertices;
     DevBuf<uint32_t> skinSource;
     DevBuf<PtxTransform> bones;
+    bool anyNonOpaque = false;  // some instanced geometry lacks the opaque flag: any-hit stages run
+    bool mixedMaterialTypes = false; // the instanced meshes use more than one material type (ShaderTypes.incl:143-145): k_shade sorts its queue
+    bool mixedTextured = false;      // ... or materials with and without scene textures: the sampler runs for waves of textured hits only
+    uint32_t pairCount = 0, triCount = 0, dxNormalTextures = 0;
+};
+
+struct PtxRenderer
+{
+    EnvSwitches env;
+    int device = 0;
+    uint32_t backend = PTX_BACKEND_WAVEFRONT;
+    hipStream_t stream = nullptr;
+    bool ownStream = false;
+    bool counted = false; // in g_liveHandles
+    std::string error;
+
+    SceneData scene;
+    DevBuf<PtxLightsUbo> lights;
+    DevBuf<AlphaTri> alphaTris;    // what the any-hit stages read per triangle slot, written behind k_emit
     struct BuildState // what a refit reuses from the last full build: sorted order and the binary topology
     {
         DevBuf<Tri> triTmp;
@@ -224,9 +230,6 @@ struct PtxRenderer
         bool levelsValid = false;
         bool valid = false;
     } build;
-    bool anyNonOpaque = false;  // some instanced geometry lacks the opaque flag: any-hit stages run
-    bool mixedMaterialTypes = false; // the instanced meshes use more than one material type (ShaderTypes.incl:143-145): k_shade sorts its queue
-    bool mixedTextured = false;      // ... or materials with and without scene textures: the sampler runs for waves of textured hits only
     bool usePloc = true;        // PLOC topology instead of Karras (PTX_BUILDER=lbvh switches back)
     TreeParams tree;            // of the tree in use; the per-frame rebuilds of an animation build with them again
     bool reinsertBroken = false; // a reinsertion pass once left something that was not a tree (k_tree_check): off for this handle
@@ -234,8 +237,7 @@ struct PtxRenderer
     DevBuf<float4> decal;
     DevBuf<float> decalT;
     size_t decalCapacity = 0;
-    uint32_t pairCount = 0, triCount = 0, dxNormalTextures = 0;
-    uint32_t treeTris = 0; // triCount minus the zero-area triangles, which are not in the tree
+    uint32_t treeTris = 0; // scene.triCount minus the zero-area triangles, which are not in the tree
     bool sceneReady = false, accelReady = false;
     // ptx_share_scene: this renderer renders the scene and tree of `sceneOwner` instead of holding copies (frames in flight
     // share one scene, as the reference's per-frame resources do); the owner knows who borrows from it
@@ -625,12 +627,9 @@ static void destroyRenderer(PtxRenderer *r)
     if (r->stream)
         (void)hipStreamSynchronize(r->stream);
     detachSharedScene(r);
-    for (PtxRenderer *sh : r->sceneSharers) // borrowers of this scene: wait for their frames, then they have no scene
+    quiesceSharers(r);
+    for (PtxRenderer *sh : r->sceneSharers) // borrowers of this scene: their frames have ended, and now they have no scene
     {
-        if (sh->stream)
-            (void)hipStreamSynchronize(sh->stream);
-        if (sh->auxStream)
-            (void)hipStreamSynchronize(sh->auxStream);
         sh->sceneOwner = nullptr;
         sh->accelReady = false;
     }
@@ -655,534 +654,38 @@ static void destroyRenderer(PtxRenderer *r)
     delete r;
 }
 
-
-// Does the material's branch of material.glsl:62-142 fetch a scene texture (an index at or past PTX_SCENE_TEXTURE_OFFSET inside
-// the uploaded table) through any of its five slots?  The five indices sit at the same offsets in the three 96-byte structs.
-static bool materialSamplesSceneTexture(const PtxSceneDesc *s, uint32_t materialId)
+// Kernel variant of the uploaded scene: 0 = opaque geometry with the fixed 1x1 textures only, 1 = ray
+// differentials + software sampler, 2 = 1 + the any-hit stages (alpha test, decals).
+static int kernelMode(const PtxRenderer *r)
 {
-    const uint32_t type = materialId & 0xffu, index = materialId >> 8;
-    const uint32_t *idx = nullptr;
-    if (type == PTX_MATERIAL_TYPE_METALLIC_ROUGHNESS && index < s->metallicRoughnessMaterialCount)
-        idx = &s->metallicRoughnessMaterials[index].EmissiveIdx;
-    else if (type == PTX_MATERIAL_TYPE_SPECULAR_GLOSSINESS && index < s->specularGlossinessMaterialCount)
-        idx = &s->specularGlossinessMaterials[index].EmissiveIdx;
-    else if (type == PTX_MATERIAL_TYPE_PHONG && index < s->phongMaterialCount)
-        idx = &s->phongMaterials[index].EmissiveIdx;
-    if (!idx)
-        return false;
-    for (int k = 0; k < 5; k++)
-        if (idx[k] >= PTX_SCENE_TEXTURE_OFFSET && idx[k] - PTX_SCENE_TEXTURE_OFFSET < s->textureCount)
-            return true;
-    return false;
+    const PtxRenderer *s = sceneOf(r);
+    return s->scene.anyNonOpaque ? 2 : (s->scene.samplerNeeded ? 1 : 0);
 }
 
-// world = A_instance * A_mesh * x (sampling.glsl:7)
-static void composeTransform(const float *Ai, const float *Am, float *M)
+static SceneView makeSceneView(const PtxRenderer *r)
 {
-    for (int r = 0; r < 3; r++)
-    {
-        for (int c = 0; c < 3; c++)
-            M[r * 4 + c] = (Ai[r * 4 + 0] * Am[0 * 4 + c] + Ai[r * 4 + 1] * Am[1 * 4 + c]) + Ai[r * 4 + 2] * Am[2 * 4 + c];
-        M[r * 4 + 3] = ((Ai[r * 4 + 0] * Am[0 * 4 + 3] + Ai[r * 4 + 1] * Am[1 * 4 + 3]) + Ai[r * 4 + 2] * Am[2 * 4 + 3]) + Ai[r * 4 + 3];
-    }
+    const PtxRenderer *s = sceneOf(r);
+    SceneView sv;
+    sv.shadeTris = s->shadeTris.p;
+    sv.vertices = s->scene.vertices.p; sv.indices = s->scene.indices.p; sv.mr = s->scene.mr.p; sv.sg = s->scene.sg.p; sv.phong = s->scene.phong.p;
+    sv.pairs = s->scene.pairs.p; sv.dxNormalTextures = s->scene.dxNormalTextures;
+    sv.lights = r->lights.p; // the lights come with every launch: each frame in flight has its own
+    sv.tex.textures = s->scene.renderTextures.p; sv.tex.textureCount = s->scene.textureCount; sv.tex.texels8 = nullptr; sv.tex.texelsF = s->scene.renderTexels.p;
+    sv.tex.srgbLut = nullptr;
+    sv.skyKind = s->scene.skyKind;
+    return sv;
 }
 
-// inverse of the 3x3 linear part by cofactors * (1/det), columns out
-static void inverseLinear(const float *M, float *Rinv)
+static TraceScene makeTraceScene(const PtxRenderer *r)
 {
-    const float m00 = M[0], m01 = M[4], m02 = M[8]; // column 0 of the math matrix
-    const float m10 = M[1], m11 = M[5], m12 = M[9];
-    const float m20 = M[2], m21 = M[6], m22 = M[10];
-    const float det = (m00 * (m11 * m22 - m21 * m12) - m10 * (m01 * m22 - m21 * m02)) + m20 * (m01 * m12 - m11 * m02);
-    const float id = 1.0f / det;
-    Rinv[0] = (m11 * m22 - m21 * m12) * id;
-    Rinv[3] = -(m10 * m22 - m20 * m12) * id;
-    Rinv[6] = (m10 * m21 - m20 * m11) * id;
-    Rinv[1] = -(m01 * m22 - m21 * m02) * id;
-    Rinv[4] = (m00 * m22 - m20 * m02) * id;
-    Rinv[7] = -(m00 * m21 - m20 * m01) * id;
-    Rinv[2] = (m01 * m12 - m11 * m02) * id;
-    Rinv[5] = -(m00 * m12 - m10 * m02) * id;
-    Rinv[8] = (m00 * m11 - m10 * m01) * id;
+    const PtxRenderer *s = sceneOf(r);
+    TraceScene sc;
+    sc.nodes = s->nodes.p; sc.tris = s->tris.p; sc.triCount = s->treeTris;
+    sc.alphaTris = s->alphaTris.p; sc.alphaQuads = s->scene.alphaQuads.p;
+    return sc;
 }
 
-template <typename T> static int upload(PtxRenderer *r, DevBuf<T> &buf, const T *src, size_t count)
-{
-    HIP_TRY(r, buf.alloc(count));
-    if (count)
-        HIP_TRY(r, hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, r->stream));
-    return PTX_OK;
-}
-
-static int shareScene(PtxRenderer *r, PtxRenderer *owner)
-{
-    if (!r || !owner || r == owner)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: need two different renderers");
-    if (owner->sceneOwner || !r->sceneSharers.empty())
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: the owner must hold its own scene, and a renderer others share from cannot borrow");
-    if (owner->device != r->device)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: renderers on different devices (%d, %d)", r->device, owner->device);
-    if (!owner->sceneReady || !owner->accelReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_share_scene: the owner needs ptx_scene_upload and ptx_build_accel first");
-    HIP_TRY(r, hipSetDevice(r->device));
-    // the owner's uploads and build are enqueued on ITS stream: finished before any stream of the borrower reads them;
-    // the borrower's own frames in flight end before its scene goes away
-    HIP_TRY(r, hipStreamSynchronize(owner->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    if (r->auxStream)
-        HIP_TRY(r, hipStreamSynchronize(r->auxStream));
-    detachSharedScene(r);
-    // its own copies are not needed any more
-    r->vertices.release(); r->indices.release(); r->mr.release(); r->sg.release(); r->phong.release(); r->pairs.release();
-    r->pairFirst.release(); r->textures.release(); r->texels8.release(); r->texelsF.release(); r->srgbLut.release();
-    r->renderTextures.release(); r->renderTexels.release();
-    r->alphaTex.release(); r->alphaTexOf.release(); r->alphaQuads.release(); r->alphaTris.release();
-    r->animatedVertices.release(); r->skinSource.release(); r->bones.release();
-    r->nodes.release(); r->tris.release(); r->shadeTris.release();
-    r->build = PtxRenderer::BuildState();
-    r->sceneReady = false;
-    r->sceneOwner = owner;
-    owner->sceneSharers.push_back(r);
-    r->accelReady = true;
-    r->hintSlots = 0u; // whatever this handle had learnt, it had learnt on another scene
-    r->stats.triangles = owner->stats.triangles;
-    r->stats.bvhNodes = owner->stats.bvhNodes;
-    r->stats.treeTriangles = owner->stats.treeTriangles;
-    r->stats.treeReferences = owner->stats.treeReferences;
-    return PTX_OK;
-}
-
-static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s)
-{
-    if (!r || !s)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_scene_upload: null argument");
-    HIP_TRY(r, hipSetDevice(r->device));
-
-    // validate indices the kernels will dereference (the reference trusts its importer); a description that is refused
-    // here leaves the handle as it was -- its own scene, or the one it borrows
-    for (uint32_t i = 0; i < s->instanceCount; i++)
-        if (s->instances[i].ModelIndex >= s->modelCount)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "instance %u: model index out of range", i);
-    for (uint32_t m = 0; m < s->modelCount; m++)
-        if ((uint64_t)s->models[m].MeshOffset + s->models[m].MeshCount > s->meshCount)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "model %u: mesh range out of bounds", m);
-    for (uint32_t k = 0; k < s->meshCount; k++)
-    {
-        const PtxMeshRecord &rec = s->meshes[k];
-        if (rec.GeometryIndex >= s->geometryCount || rec.TransformIndex >= s->transformCount)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "mesh %u: geometry/transform index out of range", k);
-        const uint32_t type = rec.MaterialId & 0xffu, index = rec.MaterialId >> 8;
-        const uint32_t limit = type == PTX_MATERIAL_TYPE_METALLIC_ROUGHNESS    ? s->metallicRoughnessMaterialCount
-                               : type == PTX_MATERIAL_TYPE_SPECULAR_GLOSSINESS ? s->specularGlossinessMaterialCount
-                               : type == PTX_MATERIAL_TYPE_PHONG               ? s->phongMaterialCount
-                                                                               : 0xffffffffu;
-        if (type <= PTX_MATERIAL_TYPE_PHONG && index >= limit)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "mesh %u: material index out of range", k);
-    }
-    for (uint32_t g = 0; g < s->geometryCount; g++)
-    {
-        const PtxGeometry &geo = s->geometries[g];
-        // an animated geometry addresses the animated vertex / index arrays (Renderer.cpp:280-312)
-        const uint64_t vLimit = geo.IsAnimated ? (s->animatedVertices ? s->animatedVertexCount : 0) : s->vertexCount;
-        const uint64_t iLimit = geo.IsAnimated ? (s->animatedIndices ? s->animatedIndexCount : 0) : s->indexCount;
-        const uint32_t *idx = geo.IsAnimated ? s->animatedIndices : s->indices;
-        if ((uint64_t)geo.VertexOffset + geo.VertexLength > vLimit || (uint64_t)geo.IndexOffset + geo.IndexLength > iLimit)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "geometry %u: vertex/index range out of bounds", g);
-        for (uint32_t k = 0; k < geo.IndexLength; k++)
-            if (idx[geo.IndexOffset + k] >= geo.VertexLength)
-                return fail(r, PTX_ERROR_INVALID_ARGUMENT, "geometry %u: index %u beyond its vertex range", g, k);
-    }
-
-    // from here on the old scene is gone, whatever happens
-    detachSharedScene(r); // a renderer that was borrowing a scene gets its own again
-    quiesceSharers(r);
-    r->sceneReady = r->accelReady = false;
-    r->sceneEpoch++;
-
-    // (instance, mesh) pairs in instance-then-mesh order; global triangle id = running prim count
-    // Device vertex buffer = scene vertices, then one skinned copy per instanced animated mesh in pair order
-    // (OutAnimatedVertexBuffer, Renderer.cpp:296-303); device index buffer = scene indices, then the animated indices.
-    std::vector<DevPair> pairs;
-    std::vector<uint32_t> pairFirst;
-    std::vector<uint32_t> skinSource; // output vertex -> animated vertex (AnimatedVertexMapBuffer)
-    r->pairInstance.clear();
-    r->pairMeshTransform.clear();
-    uint64_t tri = 0;
-    bool anyNonOpaque = false;
-    for (uint32_t i = 0; i < s->instanceCount; i++)
-    {
-        const PtxModelInstance &inst = s->instances[i];
-        const PtxModel &model = s->models[inst.ModelIndex];
-        for (uint32_t k = 0; k < model.MeshCount; k++)
-        {
-            const PtxMeshRecord &rec = s->meshes[model.MeshOffset + k];
-            const PtxGeometry &geo = s->geometries[rec.GeometryIndex];
-            DevPair pr;
-            composeTransform(inst.Transform.m, s->transforms[rec.TransformIndex].m, pr.M);
-            inverseLinear(pr.M, pr.Rinv);
-            pr.vertexOffset = geo.VertexOffset;
-            pr.indexOffset = geo.IndexOffset;
-            if (geo.IsAnimated)
-            {
-                if (s->vertexCount + skinSource.size() + geo.VertexLength > 0xffffffffull || s->indexCount + s->animatedIndexCount > 0xffffffffull)
-                    return fail(r, PTX_ERROR_INVALID_ARGUMENT, "animated meshes exceed the 32-bit vertex / index space");
-                pr.vertexOffset = static_cast<uint32_t>(s->vertexCount + skinSource.size());
-                pr.indexOffset = static_cast<uint32_t>(s->indexCount + geo.IndexOffset);
-                for (uint32_t v = 0; v < geo.VertexLength; v++)
-                    skinSource.push_back(geo.VertexOffset + v);
-            }
-            r->pairInstance.push_back(i);
-            r->pairMeshTransform.push_back(s->transforms[rec.TransformIndex]);
-            pr.materialId = rec.MaterialId;
-            pr.flags = (geo.IsOpaque ? 0u : kPairNonOpaque) | (materialSamplesSceneTexture(s, rec.MaterialId) ? kPairTextured : 0u);
-            if (pr.flags & kPairNonOpaque)
-                anyNonOpaque = true;
-            pairs.push_back(pr);
-            pairFirst.push_back(static_cast<uint32_t>(tri));
-            tri += geo.IndexLength / 3;
-        }
-    }
-    if (tri > kMaxTriangles)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "scene has %llu triangles; limit is 2^29-1", (unsigned long long)tri);
-    pairFirst.push_back(static_cast<uint32_t>(tri));
-    {
-        uint32_t typesSeen = 0; // bit per material type, unknown types share bit 3
-        for (const DevPair &pr : pairs)
-            typesSeen |= 1u << ((pr.materialId & 0xffu) <= PTX_MATERIAL_TYPE_PHONG ? (pr.materialId & 0xffu) : 3u);
-        r->mixedMaterialTypes = (typesSeen & (typesSeen - 1u)) != 0u;
-        bool textured = false, plain = false;
-        for (const DevPair &pr : pairs)
-            ((pr.flags & kPairTextured) ? textured : plain) = true;
-        r->mixedTextured = textured && plain;
-    }
-    r->pairCount = static_cast<uint32_t>(pairs.size());
-    r->triCount = static_cast<uint32_t>(tri);
-    r->dxNormalTextures = s->dxNormalTextures;
-
-    int rc;
-    r->hostPairs = pairs;
-    r->instanceCount = s->instanceCount;
-    r->staticVertexCount = s->vertexCount;
-    r->skinnedCount = static_cast<uint32_t>(skinSource.size());
-    r->boneCount = 0;
-    r->build = PtxRenderer::BuildState();
-    // bind pose of every skinned copy (OutBindPoseAnimatedVertices); the staging vectors live until the stream
-    // synchronisation at the end of this function
-    std::vector<PtxVertex> verts;
-    std::vector<uint32_t> inds;
-    {
-        verts.assign(s->vertices, s->vertices + s->vertexCount);
-        verts.reserve(verts.size() + skinSource.size());
-        for (uint32_t src : skinSource)
-        {
-            const PtxAnimatedVertex &a = s->animatedVertices[src];
-            PtxVertex v;
-            std::memset(&v, 0, sizeof(v));
-            std::memcpy(v.Position, a.Position, 12); std::memcpy(v.TexCoords, a.TexCoords, 8); std::memcpy(v.Normal, a.Normal, 12);
-            std::memcpy(v.Tangent, a.Tangent, 12); std::memcpy(v.Bitangent, a.Bitangent, 12);
-            verts.push_back(v);
-        }
-        inds.assign(s->indices, s->indices + s->indexCount);
-        if (s->animatedIndices)
-            inds.insert(inds.end(), s->animatedIndices, s->animatedIndices + s->animatedIndexCount);
-        if ((rc = upload(r, r->vertices, verts.data(), verts.size())) != PTX_OK) return rc;
-        if ((rc = upload(r, r->indices, inds.data(), inds.size())) != PTX_OK) return rc;
-        if ((rc = upload(r, r->animatedVertices, s->animatedVertices, skinSource.empty() ? 0 : s->animatedVertexCount)) != PTX_OK) return rc;
-        if ((rc = upload(r, r->skinSource, skinSource.data(), skinSource.size())) != PTX_OK) return rc;
-    }
-    if ((rc = upload(r, r->mr, s->metallicRoughnessMaterials, s->metallicRoughnessMaterialCount)) != PTX_OK) return rc;
-    if ((rc = upload(r, r->sg, s->specularGlossinessMaterials, s->specularGlossinessMaterialCount)) != PTX_OK) return rc;
-    if ((rc = upload(r, r->phong, s->phongMaterials, s->phongMaterialCount)) != PTX_OK) return rc;
-    if ((rc = upload(r, r->pairs, pairs.data(), pairs.size())) != PTX_OK) return rc;
-    if ((rc = upload(r, r->pairFirst, pairFirst.data(), pairFirst.size())) != PTX_OK) return rc;
-    // textures (row N1): level 0 to the pools, then the mip chain level by level on the device
-    {
-        HIP_TRY(r, r->srgbLut.alloc(256));
-        k_build_srgb_lut<<<1, 256, 0, r->stream>>>(r->srgbLut.p);
-        r->textureCount = s->textures ? s->textureCount : 0;
-        // the skybox images follow the scene textures in the table, one level each (TextureUploader.cpp:203-262)
-        r->skyKind = s->skybox ? s->skyboxKind : (uint32_t)PTX_SKYBOX_CLEAR_COLOR;
-        if (r->skyKind > PTX_SKYBOX_CUBE)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "unknown skybox kind %u", r->skyKind);
-        const uint32_t skyCount = r->skyKind == PTX_SKYBOX_2D ? 1u : r->skyKind == PTX_SKYBOX_CUBE ? 6u : 0u;
-        const uint32_t total = r->textureCount + skyCount;
-        auto descOf = [&](uint32_t i) -> const PtxTextureDesc & { return i < r->textureCount ? s->textures[i] : s->skybox[i - r->textureCount]; };
-        if (r->skyKind == PTX_SKYBOX_CUBE)
-            for (uint32_t f = 0; f < 6; f++)
-                if (s->skybox[f].width != s->skybox[0].width || s->skybox[f].height != s->skybox[0].width || s->skybox[f].format != s->skybox[0].format)
-                    return fail(r, PTX_ERROR_INVALID_ARGUMENT, "cube skybox: the six faces must be equal squares of one format");
-        // TextureUploader::DetermineMaxTextureSizes (TextureUploader.cpp:551-569): the largest square extent whose full chain
-        // fits the per-texture share of the budget (Config.h:63-64,162-163: min(80 % of the device memory, 1 GiB)), per format;
-        // forceFullTextureSize keeps MaxTextureDataSize = 4096 (TextureUploader.h:74).  Block-compressed files arrive decoded
-        // to RGBA8 and are budgeted as that.
-        uint32_t maxExtent[3] = { 4096u, 4096u, 4096u };
-        if (!s->forceFullTextureSize && r->textureCount && s->textureMemoryBudget != ~0ull)
-        {
-            uint64_t budget = s->textureMemoryBudget;
-            if (!budget)
-            {
-                size_t freeB = 0, totalB = 0;
-                HIP_TRY(r, hipMemGetInfo(&freeB, &totalB));
-                budget = (uint64_t)totalB / 100u * 80u;
-                if (budget > (1024ull << 20))
-                    budget = 1024ull << 20;
-            }
-            const uint64_t perTexture = budget / r->textureCount;
-            for (uint32_t f = 0; f <= PTX_TEXTURE_RGBA32F; f++)
-                while (maxExtent[f] > 1u)
-                {
-                    uint64_t texels = 0;
-                    for (uint32_t e = maxExtent[f]; e; e >>= 1)
-                        texels += (uint64_t)e * e;
-                    if (texels * (f == PTX_TEXTURE_RGBA32F ? 16u : 4u) <= perTexture)
-                        break;
-                    maxExtent[f] >>= 1;
-                }
-        }
-        auto fullLevels = [](uint32_t w, uint32_t h) {
-            uint32_t m = w > h ? w : h, levels = 1;
-            while (m > 1) { m >>= 1; levels++; } // floor(log2(max)) + 1, Image.cpp:14-17
-            return levels > 16u ? 16u : levels;
-        };
-        auto dim = [](uint32_t v, uint32_t l) { return v >> l ? v >> l : 1u; };
-        // per texture: what lands in the table, and how its level 0 is produced
-        struct Placement
-        {
-            uint32_t srcW, srcH;  // the file's level 0
-            uint32_t fileLevels;  // levels in the caller's data
-            uint32_t firstFile;   // file level that becomes level 0 when the file's own chain is used
-            bool useFileChain;    // every level comes from the file (TextureUploader.cpp:440,492-501)
-            uint32_t halvings;    // blits from the file's level 0 down towards the budgeted extent (:479-490)
-            int temp;             // table entry of the scratch chain, or -1
-        };
-        std::vector<Placement> place(total);
-        std::vector<DevTexture> table(total);
-        size_t n8 = 0, nf = 0, scratch8 = 0, scratchF = 0;
-        uint32_t scaled = 0;
-        for (uint32_t i = 0; i < total; i++)
-        {
-            const PtxTextureDesc &d = descOf(i);
-            DevTexture &t = table[i];
-            Placement &pl = place[i];
-            if (d.format > PTX_TEXTURE_RGBA32F)
-                return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture %u: unknown format %u", i, d.format);
-            pl.srcW = d.width ? d.width : 1;
-            pl.srcH = d.height ? d.height : 1;
-            pl.fileLevels = d.levels ? d.levels : 1u;
-            pl.firstFile = 0;
-            pl.useFileChain = false;
-            pl.halvings = 0;
-            pl.temp = -1;
-            t.width = pl.srcW;
-            t.height = pl.srcH;
-            t.format = d.format;
-            if (i < r->textureCount)
-            {
-                // TextureUploader::UploadTexture (:409-415): integer scale that brings both sides under the limit
-                const uint32_t mx = maxExtent[d.format];
-                const uint32_t scale = std::max((pl.srcW + mx - 1) / mx, (pl.srcH + mx - 1) / mx);
-                t.width = std::max(pl.srcW / scale, 1u);
-                t.height = std::max(pl.srcH / scale, 1u);
-                t.levels = fullLevels(t.width, t.height);
-                if (pl.fileLevels > fullLevels(pl.srcW, pl.srcH))
-                    return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture %u: %u levels for a %u x %u image", i, pl.fileLevels, pl.srcW, pl.srcH);
-                if (scale == 1)
-                    pl.useFileChain = pl.fileLevels == t.levels && t.levels > 1;
-                else
-                {
-                    // a file with its own chain: the levels from the budgeted extent down are taken as they are (:492-501)
-                    const uint32_t skip = pl.fileLevels > t.levels ? pl.fileLevels - t.levels : 0u;
-                    if (skip && dim(pl.srcW, skip) == t.width && dim(pl.srcH, skip) == t.height)
-                    {
-                        pl.useFileChain = true;
-                        pl.firstFile = skip;
-                    }
-                    else
-                    {
-                        while (dim(pl.srcW, pl.halvings + 1) >= t.width && dim(pl.srcH, pl.halvings + 1) >= t.height &&
-                               (dim(pl.srcW, pl.halvings) > t.width || dim(pl.srcH, pl.halvings) > t.height))
-                            pl.halvings++;
-                        pl.temp = (int)(total + scaled++);
-                        size_t need = 0;
-                        for (uint32_t l = 0; l <= pl.halvings; l++)
-                            need += (size_t)dim(pl.srcW, l) * dim(pl.srcH, l);
-                        size_t &sc = d.format == PTX_TEXTURE_RGBA32F ? scratchF : scratch8;
-                        sc = std::max(sc, need);
-                    }
-                }
-            }
-            else
-                t.levels = 1;
-            size_t &cursor = t.format == PTX_TEXTURE_RGBA32F ? nf : n8;
-            for (uint32_t l = 0; l < t.levels; l++)
-            {
-                t.levelOffset[l] = (uint32_t)cursor;
-                cursor += (size_t)dim(t.width, l) * dim(t.height, l);
-            }
-        }
-        // scratch chains of the textures that are scaled down: one region per pool behind the textures, used by one
-        // texture after the other (stream order); their table entries follow the real ones
-        table.resize(total + scaled);
-        for (uint32_t i = 0; i < total; i++)
-            if (place[i].temp >= 0)
-            {
-                DevTexture &t = table[(size_t)place[i].temp];
-                t.width = place[i].srcW;
-                t.height = place[i].srcH;
-                t.format = table[i].format;
-                t.levels = place[i].halvings + 1;
-                size_t cursor = t.format == PTX_TEXTURE_RGBA32F ? nf : n8;
-                for (uint32_t l = 0; l < t.levels; l++)
-                {
-                    t.levelOffset[l] = (uint32_t)cursor;
-                    cursor += (size_t)dim(t.width, l) * dim(t.height, l);
-                }
-            }
-        if (n8 + scratch8 > 0xffffffffull || nf + scratchF > 0xffffffffull)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture pool exceeds 2^32 texels");
-        HIP_TRY(r, r->textures.alloc(total + scaled));
-        HIP_TRY(r, r->texels8.alloc(n8 + scratch8));
-        HIP_TRY(r, r->texelsF.alloc(nf + scratchF));
-        if (n8)
-            HIP_TRY(r, hipMemsetAsync(r->texels8.p, 0, n8 * 4, r->stream)); // a texture without data reads as zeros
-        if (nf)
-            HIP_TRY(r, hipMemsetAsync(r->texelsF.p, 0, nf * 16, r->stream));
-        // A 1x1 opaque-white 8-bit texture decodes to exactly (1,1,1,1) in both formats, which is what the
-        // kernels without the sampler return for any index >= 9: only other content needs the TEX variants.
-        r->samplerNeeded = false;
-        r->anyNonOpaque = anyNonOpaque;
-        for (uint32_t i = 0; i < r->textureCount; i++)
-        {
-            const PtxTextureDesc &d = s->textures[i];
-            const bool whitePlaceholder = table[i].width == 1 && table[i].height == 1 && d.format != PTX_TEXTURE_RGBA32F && d.data &&
-                                          *static_cast<const uint32_t *>(d.data) == 0xffffffffu && place[i].srcW == 1 && place[i].srcH == 1;
-            if (!whitePlaceholder)
-                r->samplerNeeded = true;
-        }
-        if (!table.empty())
-            HIP_TRY(r, hipMemcpyAsync(r->textures.p, table.data(), table.size() * sizeof(DevTexture), hipMemcpyHostToDevice, r->stream));
-        TextureView tv;
-        tv.textures = r->textures.p; tv.textureCount = r->textureCount; tv.texels8 = r->texels8.p; tv.texelsF = r->texelsF.p;
-        tv.srgbLut = r->srgbLut.p;
-        for (uint32_t i = 0; i < total; i++)
-        {
-            const PtxTextureDesc &d = descOf(i);
-            const DevTexture &t = table[i];
-            const Placement &pl = place[i];
-            const bool isFloat = t.format == PTX_TEXTURE_RGBA32F;
-            const size_t texel = isFloat ? 16 : 4;
-            auto poolAt = [&](uint32_t offset) -> void * { return isFloat ? (void *)(r->texelsF.p + offset) : (void *)(r->texels8.p + offset); };
-            auto blit = [&](uint32_t src, uint32_t srcLevel, uint32_t dst, uint32_t dstLevel) {
-                const uint32_t dw = dim(table[dst].width, dstLevel), dh = dim(table[dst].height, dstLevel);
-                k_blit_level<<<(dw * dh + 255) / 256, 256, 0, r->stream>>>(tv, src, srcLevel, dst, dstLevel, r->texels8.p, r->texelsF.p);
-            };
-            if (d.data && pl.useFileChain)
-            {
-                // the file's own levels, from the one that has the budgeted extent
-                const uint8_t *p = static_cast<const uint8_t *>(d.data);
-                for (uint32_t l = 0; l < pl.firstFile; l++)
-                    p += (size_t)dim(pl.srcW, l) * dim(pl.srcH, l) * texel;
-                for (uint32_t l = 0; l < t.levels; l++)
-                {
-                    const size_t nl = (size_t)dim(t.width, l) * dim(t.height, l);
-                    HIP_TRY(r, hipMemcpyAsync(poolAt(t.levelOffset[l]), p, nl * texel, hipMemcpyHostToDevice, r->stream));
-                    p += nl * texel;
-                }
-                continue;
-            }
-            if (d.data && pl.temp >= 0)
-            {
-                // scaled down: the file's level 0 into the scratch chain, halved by linear blits, then into level 0
-                const DevTexture &tt = table[(size_t)pl.temp];
-                HIP_TRY(r, hipMemcpyAsync(poolAt(tt.levelOffset[0]), d.data, (size_t)pl.srcW * pl.srcH * texel, hipMemcpyHostToDevice, r->stream));
-                for (uint32_t l = 1; l <= pl.halvings; l++)
-                    blit((uint32_t)pl.temp, l - 1, (uint32_t)pl.temp, l);
-                if (dim(pl.srcW, pl.halvings) == t.width && dim(pl.srcH, pl.halvings) == t.height)
-                    HIP_TRY(r, hipMemcpyAsync(poolAt(t.levelOffset[0]), poolAt(tt.levelOffset[pl.halvings]), (size_t)t.width * t.height * texel,
-                                              hipMemcpyDeviceToDevice, r->stream));
-                else
-                    blit((uint32_t)pl.temp, pl.halvings, i, 0);
-            }
-            else if (d.data)
-                HIP_TRY(r, hipMemcpyAsync(poolAt(t.levelOffset[0]), d.data, (size_t)t.width * t.height * texel, hipMemcpyHostToDevice, r->stream));
-            for (uint32_t l = 1; l < t.levels; l++)
-                blit(i, l - 1, i, l);
-        }
-        // The pool the render kernels sample (pt_device.hpp, fetchTexel): every level of every texture decoded to four floats,
-        // the RGBA32F pool first, the 8-bit textures behind it; `renderTextures` is the table with offsets into that pool.
-        if ((uint64_t)nf + n8 > 0xffffffffull)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture pool exceeds 2^32 texels");
-        HIP_TRY(r, r->renderTexels.alloc(nf + n8));
-        HIP_TRY(r, r->renderTextures.alloc(total));
-        if (nf)
-            HIP_TRY(r, hipMemcpyAsync(r->renderTexels.p, r->texelsF.p, nf * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
-        std::vector<DevTexture> renderTable(table.begin(), table.begin() + total);
-        for (uint32_t i = 0; i < total; i++)
-        {
-            DevTexture &t = renderTable[i];
-            if (t.format == PTX_TEXTURE_RGBA32F)
-                continue;
-            size_t count = 0;
-            for (uint32_t l = 0; l < t.levels; l++)
-                count += (size_t)dim(t.width, l) * dim(t.height, l);
-            const uint32_t first = t.levelOffset[0];
-            k_decode_texels<<<(uint32_t)((count + 255) / 256), 256, 0, r->stream>>>(r->texels8.p, r->srgbLut.p, first, (uint32_t)count, t.format,
-                                                                                  r->renderTexels.p + nf + first);
-            for (uint32_t l = 0; l < t.levels; l++)
-                t.levelOffset[l] += (uint32_t)nf;
-        }
-        if (total)
-            HIP_TRY(r, hipMemcpyAsync(r->renderTextures.p, renderTable.data(), total * sizeof(DevTexture), hipMemcpyHostToDevice, r->stream));
-        // any-hit data: the alpha footprints of every texture some material names as its colour texture
-        std::vector<AlphaTex> alphaTex;
-        std::vector<uint32_t> alphaTexOf(r->textureCount ? r->textureCount : 1u, kNoAlphaTex);
-        if (anyNonOpaque)
-        {
-            size_t quads = 0;
-            bool tooLarge = false; // the extent of an alpha texture rides in 15 + 15 bits of the triangle record
-            auto mark = [&](uint32_t colorIdx) {
-                if (colorIdx < PTX_SCENE_TEXTURE_OFFSET || colorIdx - PTX_SCENE_TEXTURE_OFFSET >= r->textureCount)
-                    return;
-                const uint32_t ti = colorIdx - PTX_SCENE_TEXTURE_OFFSET;
-                if (alphaTexOf[ti] != kNoAlphaTex)
-                    return;
-                if (renderTable[ti].width > 32768u || renderTable[ti].height > 32768u)
-                {
-                    tooLarge = true;
-                    return;
-                }
-                alphaTexOf[ti] = (uint32_t)alphaTex.size();
-                alphaTex.push_back({ renderTable[ti].width, renderTable[ti].height, (uint32_t)quads, 0u });
-                quads += (size_t)renderTable[ti].width * renderTable[ti].height;
-            };
-            for (uint32_t i = 0; i < s->metallicRoughnessMaterialCount; i++) mark(s->metallicRoughnessMaterials[i].ColorIdx);
-            for (uint32_t i = 0; i < s->specularGlossinessMaterialCount; i++) mark(s->specularGlossinessMaterials[i].ColorIdx);
-            for (uint32_t i = 0; i < s->phongMaterialCount; i++) mark(s->phongMaterials[i].ColorIdx);
-            if (tooLarge)
-                return fail(r, PTX_ERROR_INVALID_ARGUMENT, "a colour texture of a non-opaque geometry is larger than 32768 texels across");
-            if (quads >= 0xffffffffull)
-                return fail(r, PTX_ERROR_INVALID_ARGUMENT, "alpha footprints exceed 2^32 texels");
-            HIP_TRY(r, r->alphaQuads.alloc(quads));
-            for (uint32_t ti = 0; ti < r->textureCount; ti++)
-                if (alphaTexOf[ti] != kNoAlphaTex)
-                {
-                    const AlphaTex &at = alphaTex[alphaTexOf[ti]];
-                    k_alpha_quads<<<(at.width * at.height + 255) / 256, 256, 0, r->stream>>>(at.width, at.height, r->renderTexels.p + renderTable[ti].levelOffset[0],
-                                                                                            r->alphaQuads.p + at.offset);
-                }
-        }
-        if ((rc = upload(r, r->alphaTex, alphaTex.data(), alphaTex.size())) != PTX_OK) return rc;
-        if ((rc = upload(r, r->alphaTexOf, alphaTexOf.data(), alphaTexOf.size())) != PTX_OK) return rc;
-        HIP_TRY(r, hipStreamSynchronize(r->stream)); // `table` and the caller's texel arrays may go away
-        HIP_TRY(r, hipGetLastError());
-        // the pools of the upload formats have done their work (mip chains, scaling)
-        r->texels8.release(); r->texelsF.release(); r->srgbLut.release(); r->textures.release();
-    }
-    HIP_TRY(r, hipStreamSynchronize(r->stream)); // the host vectors above go out of scope
-    r->sceneReady = true;
-    r->stats.triangles = tri;
-    return PTX_OK;
-}
+#include "pt_scene_host.hpp" // ptx_share_scene and ptx_scene_upload: shareScene, sceneUpload and its stages
 
 #include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
 
@@ -1196,67 +699,36 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
     if (!r->sceneReady)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_update_animation: no scene uploaded");
     quiesceSharers(r);
-    if (instanceTransforms && instanceCount != r->instanceCount)
+    if (instanceTransforms && instanceCount != r->scene.instanceCount)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_update_animation: %u instance transforms for a scene of %u instances", instanceCount,
-                    r->instanceCount);
+                    r->scene.instanceCount);
     HIP_TRY(r, hipSetDevice(r->device));
     if (instanceTransforms)
     {
-        for (size_t p = 0; p < r->hostPairs.size(); p++)
+        for (size_t p = 0; p < r->scene.hostPairs.size(); p++)
         {
-            DevPair &pr = r->hostPairs[p];
-            composeTransform(instanceTransforms[r->pairInstance[p]].m, r->pairMeshTransform[p].m, pr.M);
+            DevPair &pr = r->scene.hostPairs[p];
+            composeTransform(instanceTransforms[r->scene.pairInstance[p]].m, r->scene.pairMeshTransform[p].m, pr.M);
             inverseLinear(pr.M, pr.Rinv);
         }
-        if (!r->hostPairs.empty())
-            HIP_TRY(r, hipMemcpyAsync(r->pairs.p, r->hostPairs.data(), r->hostPairs.size() * sizeof(DevPair), hipMemcpyHostToDevice, r->stream));
+        if (!r->scene.hostPairs.empty())
+            HIP_TRY(r, hipMemcpyAsync(r->scene.pairs.p, r->scene.hostPairs.data(), r->scene.hostPairs.size() * sizeof(DevPair), hipMemcpyHostToDevice, r->stream));
     }
-    if (boneTransforms && r->skinnedCount)
+    if (boneTransforms && r->scene.skinnedCount)
     {
-        if (boneCount > r->bones.n)
-            HIP_TRY(r, r->bones.alloc(boneCount));
-        r->boneCount = boneCount;
+        if (boneCount > r->scene.bones.n)
+            HIP_TRY(r, r->scene.bones.alloc(boneCount));
+        r->scene.boneCount = boneCount;
         if (boneCount)
-            HIP_TRY(r, hipMemcpyAsync(r->bones.p, boneTransforms, (size_t)boneCount * sizeof(PtxTransform), hipMemcpyHostToDevice, r->stream));
-        k_skin<<<(r->skinnedCount + 255) / 256, 256, 0, r->stream>>>(r->animatedVertices.p, r->skinSource.p, r->skinnedCount, r->bones.p, boneCount,
-                                                                  r->vertices.p + r->staticVertexCount);
+            HIP_TRY(r, hipMemcpyAsync(r->scene.bones.p, boneTransforms, (size_t)boneCount * sizeof(PtxTransform), hipMemcpyHostToDevice, r->stream));
+        k_skin<<<(r->scene.skinnedCount + 255) / 256, 256, 0, r->stream>>>(r->scene.animatedVertices.p, r->scene.skinSource.p, r->scene.skinnedCount, r->scene.bones.p, boneCount,
+                                                                  r->scene.vertices.p + r->scene.staticVertexCount);
     }
     HIP_TRY(r, hipStreamSynchronize(r->stream)); // the caller's arrays may go away
     const bool refit = accelUpdate == PTX_ACCEL_REFIT && r->build.valid && r->accelReady;
     return buildAccel(r, refit, true);
 }
 
-
-// Kernel variant of the uploaded scene: 0 = opaque geometry with the fixed 1x1 textures only, 1 = ray
-// differentials + software sampler, 2 = 1 + the any-hit stages (alpha test, decals).
-static int kernelMode(const PtxRenderer *r)
-{
-    const PtxRenderer *s = sceneOf(r);
-    return s->anyNonOpaque ? 2 : (s->samplerNeeded ? 1 : 0);
-}
-
-static SceneView makeSceneView(const PtxRenderer *r)
-{
-    const PtxRenderer *s = sceneOf(r);
-    SceneView sv;
-    sv.shadeTris = s->shadeTris.p;
-    sv.vertices = s->vertices.p; sv.indices = s->indices.p; sv.mr = s->mr.p; sv.sg = s->sg.p; sv.phong = s->phong.p;
-    sv.pairs = s->pairs.p; sv.dxNormalTextures = s->dxNormalTextures;
-    sv.lights = r->lights.p; // the lights come with every launch: each frame in flight has its own
-    sv.tex.textures = s->renderTextures.p; sv.tex.textureCount = s->textureCount; sv.tex.texels8 = nullptr; sv.tex.texelsF = s->renderTexels.p;
-    sv.tex.srgbLut = nullptr;
-    sv.skyKind = s->skyKind;
-    return sv;
-}
-
-static TraceScene makeTraceScene(const PtxRenderer *r)
-{
-    const PtxRenderer *s = sceneOf(r);
-    TraceScene sc;
-    sc.nodes = s->nodes.p; sc.tris = s->tris.p; sc.triCount = s->treeTris;
-    sc.alphaTris = s->alphaTris.p; sc.alphaQuads = s->alphaQuads.p;
-    return sc;
-}
 
 static int ensureSlots(PtxRenderer *r, size_t slots)
 {
@@ -1645,7 +1117,7 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         if (rcr != PTX_OK)
             return rcr;
     }
-    pl.sortShade = (sceneOf(r)->mixedMaterialTypes || sceneOf(r)->mixedTextured) ? 1u : 0u;
+    pl.sortShade = (sceneOf(r)->scene.mixedMaterialTypes || sceneOf(r)->scene.mixedTextured) ? 1u : 0u;
     if (r->env.shadeSort >= 0)
         pl.sortShade = (uint32_t)r->env.shadeSort;
     // measured with 16 hardware queues (chess_like, ms per step at 25 / 50 / 75 / 100 / 200 / 400 K live paths): whole frame 8.04 / 7.82 /
@@ -2036,7 +1508,7 @@ static int testTexture(PtxRenderer *r, const float *in, float *out, uint32_t n, 
     HIP_TRY(r, r->testOut.alloc((size_t)n * 4));
     HIP_TRY(r, hipMemcpyAsync(r->testIn.p, in, (size_t)n * 28, hipMemcpyHostToDevice, r->stream));
     TextureView tv;
-    tv.textures = r->renderTextures.p; tv.textureCount = r->textureCount; tv.texels8 = nullptr; tv.texelsF = r->renderTexels.p;
+    tv.textures = r->scene.renderTextures.p; tv.textureCount = r->scene.textureCount; tv.texels8 = nullptr; tv.texelsF = r->scene.renderTexels.p;
     tv.srgbLut = nullptr;
     k_test_texture<<<(n + 63) / 64, 64, 0, r->stream>>>(tv, r->testIn.p, r->testOut.p, n, implicitLod);
     HIP_TRY(r, hipMemcpyAsync(out, r->testOut.p, (size_t)n * 16, hipMemcpyDeviceToHost, r->stream));
@@ -2069,7 +1541,7 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
         (void)hipEventRecord(r->evT0, r->stream);
         (void)hipMemsetAsync(&r->counters.p[C_CHUNK], 0, sizeof(uint32_t), r->stream);
         (void)hipMemsetAsync(dOverflow.p, 0, sizeof(uint32_t), r->stream);
-        if (sceneOf(r)->anyNonOpaque)
+        if (sceneOf(r)->scene.anyNonOpaque)
             k_trace_rays<true><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p,
                                                                      dOverflow.p);
         else
