@@ -409,6 +409,38 @@ PTX_API uint32_t ptx_abi_version(void);
 /* Renderer::UpdateSceneData (Renderer.cpp:238-439): copy the scene to HBM.  A description that is refused with
  * PTX_ERROR_INVALID_ARGUMENT, for whatever reason, leaves the handle as it was: its own scene, or the one it borrows. */
 PTX_API int ptx_scene_upload(PtxRenderer *r, const PtxSceneDesc *scene);
+/* The same upload without waiting for the textures (Renderer.cpp:419-438: every scene texture is first mapped to a stand-in, then
+ * TextureUploader::UploadTextures fills them in).  A scene texture with data == NULL is PENDING instead of reading as zeros: its
+ * width / height / format / levels are binding -- the plan places it exactly as if the texels were there, budget rule included --
+ * and until it is committed it samples as the fixed 1 x 1 texture standIn[i], one of the nine indices below
+ * PTX_SCENE_TEXTURE_OFFSET (the caller passes what Renderer.cpp:426-428 computes: the placeholder for Color, the type's default
+ * otherwise); standIn == NULL: the placeholder for all.  Textures that carry data are uploaded at once, and so are the skybox
+ * images (UploadSkyboxBlocking, Renderer.cpp:408-411).  A scene with a pending texture renders with the sampling kernels from
+ * the start; that never changes afterwards.  Refusals (a stand-in index above 8 among them) leave the handle as it was. */
+PTX_API int ptx_scene_upload_streamed(PtxRenderer *r, const PtxSceneDesc *scene, const uint32_t *standIn);
+/* TextureUploader's submit step for one texture (TextureUploader.cpp:312-360).  `index` is the scene texture's index (0-based,
+ * not the shader index); `desc` repeats the width / height / format / levels declared at upload and carries `data`.  The texels
+ * are copied into page-locked staging of the library before the call returns; the copy to the device, the scaled-down path,
+ * the mip chain, the decode into the pool the render kernels sample and, for a colour texture of non-opaque geometry, its alpha
+ * footprints are enqueued on an upload stream of their own (created by the first call; it takes a hardware queue,
+ * INTEGRATION.md).  The call does not wait for frames in flight and changes nothing a frame sees; it waits only when both
+ * staging slots still hold an upload in flight (the reference's free-buffer semaphore).  PTX_ERROR_INVALID_ARGUMENT: index out
+ * of range, a descriptor that differs from the declared one, NULL data, a texture that is not pending, a scene that was not
+ * uploaded by ptx_scene_upload_streamed, a handle that borrows its scene (uploads are the owner's calls).  Replacing a resident
+ * texture is not supported. */
+PTX_API int ptx_texture_upload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *desc);
+/* Renderer::UpdateTexture (Renderer.cpp:441-471) for every texture uploaded since the last commit: from the ptx_render* /
+ * ptx_trace_rays / ptx_test_texture calls that follow, on this handle and on its borrowers, these textures sample as a blocking
+ * ptx_scene_upload of the same description would have made them; nothing enqueued earlier changes.  Which of the two a frame
+ * sees is fixed by the order of the calls, never by timing.  The render stream waits for the upload stream on the device (an
+ * event); the host waits only for the borrowers' frames in flight, as ptx_build_accel does.  With a tree built, the any-hit
+ * records of its triangles are rewritten (an alpha texture's extent and footprints are part of them); before ptx_build_accel the
+ * commit only switches the tables and the build picks them up.  *committed (may be NULL): textures switched by this call; nothing
+ * to commit is PTX_OK with 0.  The accumulation is not reset: as in the reference, that is the caller's decision. */
+PTX_API int ptx_textures_commit(PtxRenderer *r, uint32_t *committed);
+/* Counts over the scene's textures (of the owner's scene on a borrower): resident = uploaded with the scene or committed,
+ * pending = everything else.  After a plain ptx_scene_upload every texture is resident. */
+PTX_API int ptx_texture_residency(PtxRenderer *r, uint32_t *resident, uint32_t *pending);
 /* AccelerationStructure::Build (AccelerationStructure.cpp:26-46; BLAS :64-247, TLAS
  * :250-301), replaced by a software LBVH over the flattened world-space triangles.
  * The reference asks its driver for ePreferFastTrace (AccelerationStructure.cpp:319-324); this build spends time the same way:

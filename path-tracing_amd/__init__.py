@@ -60,6 +60,7 @@ PTX_SYMBOLS = [
     "ptx_shard_bytes", "ptx_pack_shard", "ptx_unpack_shard", "ptx_unpack_shard_host", "ptx_unpack_shards", "ptx_bind_shard_accumulation", "ptx_get_stats", "ptx_bind_accumulation",
     "ptx_trace_rays", "ptx_test_input_stride", "ptx_test_output_stride", "ptx_test_eval", "ptx_test_texture",
     "ptx_postprocess", "ptx_read_output", "ptx_write_accumulation", "ptx_update_animation",
+    "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -93,6 +94,14 @@ class SceneDesc(C.Structure):
         ("animatedIndices", C.c_void_p), ("animatedIndexCount", C.c_uint64),
         ("textureMemoryBudget", C.c_uint64),
     ]
+
+
+class TextureDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("levels", C.c_uint32), ("data", C.c_void_p)]
+
+
+TEXTURE_RGBA8_UNORM, TEXTURE_RGBA8_SRGB, TEXTURE_RGBA32F = 0, 1, 2
+PLACEHOLDER_TEXTURE_INDEX = 8  # PTX_PLACEHOLDER_TEXTURE_INDEX
 
 
 class RaygenUniformData(C.Structure):
@@ -309,6 +318,10 @@ def load_hip() -> C.CDLL:
         lib.ptx_test_output_stride.argtypes = [C.c_uint32]
         lib.ptx_test_eval.argtypes = [P, C.c_uint32, P, P, C.c_uint32]
         lib.ptx_test_texture.argtypes = [P, P, P, C.c_uint32, C.c_int]
+        lib.ptx_scene_upload_streamed.argtypes = [P, C.POINTER(SceneDesc), P]
+        lib.ptx_texture_upload.argtypes = [P, C.c_uint32, C.POINTER(TextureDesc)]
+        lib.ptx_textures_commit.argtypes = [P, C.POINTER(C.c_uint32)]
+        lib.ptx_texture_residency.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _hip = lib
     return _hip
 
@@ -428,6 +441,42 @@ class Renderer:
         d = scene.desc if isinstance(scene, Scene) else scene
         self._check(self.lib.ptx_scene_upload(self.handle, C.byref(d)))
         self._check(self.lib.ptx_build_accel(self.handle))
+
+    def upload_streamed(self, scene: Scene | SceneDesc, stand_in=None, build: bool = True):
+        """ptx_scene_upload_streamed (+ ptx_build_accel): the scene textures whose `data` is NULL are pending and sample as the
+        fixed 1 x 1 texture stand_in[i] (an index below 9; None: the placeholder for all) until upload_texture and
+        commit_textures bring them in."""
+        d = scene.desc if isinstance(scene, Scene) else scene
+        si = None if stand_in is None else np.ascontiguousarray(stand_in, np.uint32)
+        if si is not None and si.size != d.textureCount:
+            raise PtxError(f"stand_in has {si.size} entries for {d.textureCount} textures")
+        self._check(self.lib.ptx_scene_upload_streamed(self.handle, C.byref(d), si.ctypes.data if si is not None and si.size else None))
+        if build:
+            self._check(self.lib.ptx_build_accel(self.handle))
+
+    def upload_texture(self, index: int, desc, fmt: int | None = None, levels: int = 1):
+        """ptx_texture_upload: `desc` is a TextureDesc, or an H x W x 4 array (uint8 with `fmt` UNORM / sRGB, float32 for RGBA32F)
+        holding level 0.  The texels are staged before the call returns."""
+        if not isinstance(desc, TextureDesc):
+            a = np.ascontiguousarray(desc)
+            if a.ndim != 3 or a.shape[2] != 4 or a.dtype not in (np.uint8, np.float32):
+                raise PtxError("upload_texture: need an H x W x 4 array of uint8 or float32")
+            if fmt is None:
+                fmt = TEXTURE_RGBA32F if a.dtype == np.float32 else TEXTURE_RGBA8_SRGB
+            desc = TextureDesc(a.shape[1], a.shape[0], fmt, levels, a.ctypes.data)
+        self._check(self.lib.ptx_texture_upload(self.handle, index, C.byref(desc)))
+
+    def commit_textures(self) -> int:
+        """ptx_textures_commit: the textures uploaded so far are what the frames enqueued from now on sample; returns their count."""
+        n = C.c_uint32()
+        self._check(self.lib.ptx_textures_commit(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def texture_residency(self):
+        """ptx_texture_residency: (resident, pending) over the scene's textures."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.ptx_texture_residency(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def share_scene(self, owner: "Renderer"):
         """Render `owner`'s scene and tree instead of holding copies (ptx_share_scene): frames in flight share one scene."""

@@ -36,10 +36,8 @@ __global__ void k_blit_level(TextureView tv, uint32_t src, uint32_t srcLevel, ui
     const size_t idx = (size_t)td.levelOffset[dstLevel] + (size_t)j * dw + i;
     if (td.format == PTX_TEXTURE_RGBA32F)
         texelsF[idx] = make_float4(c.x, c.y, c.z, c.w);
-    else if (td.format == PTX_TEXTURE_RGBA8_SRGB)
-        texels8[idx] = quantize8(linearToSrgb(c.x)) | quantize8(linearToSrgb(c.y)) << 8 | quantize8(linearToSrgb(c.z)) << 16 | quantize8(c.w) << 24;
     else
-        texels8[idx] = quantize8(c.x) | quantize8(c.y) << 8 | quantize8(c.z) << 16 | quantize8(c.w) << 24;
+        texels8[idx] = encodeTexel8(td.format, c);
 }
 
 // All levels of one 8-bit texture (a contiguous run of its pool) into the decoded pool the render kernels sample.
@@ -61,6 +59,152 @@ __global__ void k_decode_texels(const uint32_t *__restrict__ texels8, const floa
     }
     r.w = (float)(p >> 24) / 255.0f;
     decoded[k] = r;
+}
+
+// ---- streamed textures (ptx_texture_upload): the mip chain of ONE texture, several levels per launch, in LDS ------------------
+// A workgroup takes a kStreamTile x kStreamTile tile (half that for RGBA32F) of level `srcLevel` from the ENCODED copy in the
+// upload's scratch pool, writes it decoded into the pool the render kernels sample, and produces the next `steps` levels of the
+// tile inside LDS: each one re-encoded to the image format as k_blit_level stores it, and written decoded.  The host asks for a
+// step only while every extent of the level above is even or 1: then destination texel (i, j) reads source texels 2i, 2i + 1 x
+// 2j, 2j + 1 (or 0, 0 along an extent of 1), which lie in the same tile, and a tile needs nothing of its neighbours.  Every
+// texel comes out of k_blit_level's own expressions with its operands -- x, ax, the clamps, lerp4(.., ax), lerp4(top, bot, ay),
+// the encode --; only where the four source texels are read from differs.  The level a launch ends on also goes to the scratch
+// pool encoded (encOut): the next launch, or the general blit path from the first odd extent on, continues from it.
+constexpr uint32_t kStreamTile = 64, kStreamSteps = 6, kStreamBlock = 256;
+struct StreamChainArgs
+{
+    uint32_t srcOffset;     // scratch pool: first texel of the source level
+    uint32_t sw, sh;        // its extent
+    uint32_t format, steps; // steps <= log2(tile)
+    uint32_t writeSource;   // the source level itself is still to be decoded (the first launch of a chain)
+    uint32_t encOut;        // scratch pool: first texel of level `steps` below the source, 0xffffffff: not wanted
+    uint32_t decoded[kStreamSteps + 1]; // decoded pool: first texel of the source level and of each level below it
+};
+
+template <bool FLOAT>
+__global__ __launch_bounds__(kStreamBlock) void k_stream_chain(StreamChainArgs a, void *pool, const float *__restrict__ srgbLut,
+                                                              float4 *__restrict__ decodedPool)
+{
+    constexpr uint32_t T = FLOAT ? kStreamTile / 2 : kStreamTile;
+    // level k of the tile sits in bufA (k even) or bufB (k odd) with row stride T >> k, in the image format: 16 + 4 + 1 KB
+    __shared__ float4 bufA[kStreamTile * kStreamTile / 4];
+    __shared__ float4 bufB[kStreamTile * kStreamTile / 16];
+    __shared__ float lut[256];
+    const uint32_t tid = threadIdx.x;
+    if (!FLOAT && tid < 256)
+        lut[tid] = srgbLut[tid];
+    const uint32_t tilesX = (a.sw + T - 1) / T;
+    const uint32_t ox = (blockIdx.x % tilesX) * T, oy = (blockIdx.x / tilesX) * T;
+    if (oy >= a.sh)
+        return;
+    uint32_t W = a.sw, H = a.sh; // the level in LDS: its extent, and which part of it this tile holds
+    uint32_t vw = W - ox < T ? W - ox : T, vh = H - oy < T ? H - oy : T;
+    __syncthreads();
+    for (uint32_t e = tid; e < vw * vh; e += kStreamBlock)
+    {
+        const uint32_t lx = e % vw, ly = e / vw;
+        const size_t g = (size_t)(oy + ly) * W + (ox + lx);
+        float4 d;
+        if (FLOAT)
+        {
+            d = static_cast<const float4 *>(pool)[a.srcOffset + g];
+            bufA[ly * T + lx] = d;
+        }
+        else
+        {
+            const uint32_t p = static_cast<const uint32_t *>(pool)[a.srcOffset + g];
+            reinterpret_cast<uint32_t *>(bufA)[ly * T + lx] = p;
+            const f4 c = decodeTexel8(lut, a.format, p);
+            d = make_float4(c.x, c.y, c.z, c.w);
+        }
+        if (a.writeSource)
+            decodedPool[a.decoded[0] + g] = d;
+    }
+    for (uint32_t k = 0; k < a.steps; k++)
+    {
+        __syncthreads();
+        const float4 *src = (k & 1u) ? bufB : bufA;
+        float4 *dst = (k & 1u) ? bufA : bufB;
+        const uint32_t stride = T >> k, dstride = T >> (k + 1);
+        const uint32_t sox = ox >> k, soy = oy >> k, dox = ox >> (k + 1), doy = oy >> (k + 1);
+        const uint32_t dW = levelDim(W, 1), dH = levelDim(H, 1);
+        const uint32_t dvw = dox >= dW ? 0u : (dW - dox < dstride ? dW - dox : dstride), dvh = doy >= dH ? 0u : (dH - doy < dstride ? dH - doy : dstride);
+        const bool last = k + 1 == a.steps;
+        for (uint32_t e = tid; e < dvw * dvh; e += kStreamBlock)
+        {
+            const uint32_t li = e % dvw, lj = e / dvw, i = dox + li, j = doy + lj;
+            // k_blit_level, source level (W, H) -> (dW, dH)
+            const float x = ((float)i + 0.5f) * ((float)W / (float)dW) - 0.5f, y = ((float)j + 0.5f) * ((float)H / (float)dH) - 0.5f;
+            const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y), ax = x - x0, ay = y - y0;
+            const float cx0 = clamp_(x0, 0.0f, (float)(W - 1)), cx1 = clamp_(x0 + 1.0f, 0.0f, (float)(W - 1));
+            const float cy0 = clamp_(y0, 0.0f, (float)(H - 1)), cy1 = clamp_(y0 + 1.0f, 0.0f, (float)(H - 1));
+            // the same four texels, from the tile; the bounds hold by the evenness rule and are clamped for safety all the same
+            const uint32_t mx = vw - 1, my = vh - 1;
+            uint32_t sx0 = (uint32_t)cx0 - sox, sx1 = (uint32_t)cx1 - sox, sy0 = (uint32_t)cy0 - soy, sy1 = (uint32_t)cy1 - soy;
+            sx0 = sx0 > mx ? mx : sx0; sx1 = sx1 > mx ? mx : sx1; sy0 = sy0 > my ? my : sy0; sy1 = sy1 > my ? my : sy1;
+            f4 t00, t10, t01, t11;
+            if (FLOAT)
+            {
+                const float4 v00 = src[sy0 * stride + sx0], v10 = src[sy0 * stride + sx1], v01 = src[sy1 * stride + sx0], v11 = src[sy1 * stride + sx1];
+                t00.x = v00.x; t00.y = v00.y; t00.z = v00.z; t00.w = v00.w; t10.x = v10.x; t10.y = v10.y; t10.z = v10.z; t10.w = v10.w;
+                t01.x = v01.x; t01.y = v01.y; t01.z = v01.z; t01.w = v01.w; t11.x = v11.x; t11.y = v11.y; t11.z = v11.z; t11.w = v11.w;
+            }
+            else
+            {
+                const uint32_t *s8 = reinterpret_cast<const uint32_t *>(src);
+                t00 = decodeTexel8(lut, a.format, s8[sy0 * stride + sx0]); t10 = decodeTexel8(lut, a.format, s8[sy0 * stride + sx1]);
+                t01 = decodeTexel8(lut, a.format, s8[sy1 * stride + sx0]); t11 = decodeTexel8(lut, a.format, s8[sy1 * stride + sx1]);
+            }
+            const f4 top = lerp4(t00, t10, ax);
+            const f4 bot = lerp4(t01, t11, ax);
+            const f4 c = lerp4(top, bot, ay);
+            const size_t g = (size_t)j * dW + i;
+            if (FLOAT)
+            {
+                const float4 v = make_float4(c.x, c.y, c.z, c.w);
+                dst[lj * dstride + li] = v;
+                decodedPool[a.decoded[k + 1] + g] = v;
+                if (last && a.encOut != 0xffffffffu)
+                    static_cast<float4 *>(pool)[a.encOut + g] = v;
+            }
+            else
+            {
+                const uint32_t p = encodeTexel8(a.format, c);
+                reinterpret_cast<uint32_t *>(dst)[lj * dstride + li] = p;
+                const f4 d = decodeTexel8(lut, a.format, p);
+                decodedPool[a.decoded[k + 1] + g] = make_float4(d.x, d.y, d.z, d.w);
+                if (last && a.encOut != 0xffffffffu)
+                    static_cast<uint32_t *>(pool)[a.encOut + g] = p;
+            }
+        }
+        W = dW; H = dH; vw = dvw; vh = dvh;
+    }
+}
+
+// The nine fixed 1 x 1 texels (sampleTexture(idx), ShaderRendererTypes.incl:49-56) as texels of the decoded pool and as alpha
+// quads: what a pending texture's table entries point at until ptx_textures_commit.
+__global__ void k_stream_stand_ins(float4 *__restrict__ texels, float4 *__restrict__ quads)
+{
+    const uint32_t k = threadIdx.x;
+    if (k >= PTX_SCENE_TEXTURE_OFFSET)
+        return;
+    const f4 c = sampleTexture(k);
+    texels[k] = make_float4(c.x, c.y, c.z, c.w);
+    if (quads)
+        quads[k] = make_float4(c.w, c.w, c.w, c.w); // k_alpha_quads of a 1 x 1 level
+}
+
+// ptx_textures_commit: the table entries of the textures in `list` take their final values.
+__global__ void k_commit_textures(const uint32_t *__restrict__ list, uint32_t n, const DevTexture *__restrict__ finalTextures, DevTexture *__restrict__ textures,
+                                  const uint32_t *__restrict__ alphaTexOf, const AlphaTex *__restrict__ finalAlphaTex, AlphaTex *__restrict__ alphaTex)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const uint32_t ti = list[k];
+    textures[ti] = finalTextures[ti];
+    if (alphaTexOf && alphaTexOf[ti] != kNoAlphaTex)
+        alphaTex[alphaTexOf[ti]] = finalAlphaTex[alphaTexOf[ti]];
 }
 
 __global__ void k_test_texture(TextureView tv, const float *__restrict__ in, float *__restrict__ out, uint32_t n, int implicitLod)

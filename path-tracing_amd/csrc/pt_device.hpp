@@ -949,22 +949,14 @@ PT_DEV uint32_t quantize8(float x)
     return (uint32_t)__builtin_floorf(x * 255.0f + 0.5f);
 }
 
-// Upload-time form of a texel (k_blit_level builds mip chains in the image's own format, Image.cpp:264-300): decode from
-// the pool of the texture's format.
-PT_DEV f4 fetchTexelEncoded(const TextureView &tv, const DevTexture &t, uint32_t level, uint32_t x, uint32_t y)
+// An 8-bit texel of the image format decoded to four floats: the sRGB table (256 entries, byte -> linear) for the colour
+// channels of an sRGB image, c / 255 otherwise.
+PT_DEV f4 decodeTexel8(const float *srgbLut, uint32_t format, uint32_t p)
 {
-    const size_t idx = (size_t)t.levelOffset[level] + (size_t)y * levelDim(t.width, level) + x;
     f4 r;
-    if (t.format == PTX_TEXTURE_RGBA32F)
+    if (format == PTX_TEXTURE_RGBA8_SRGB)
     {
-        const float4 v = tv.texelsF[idx];
-        r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
-        return r;
-    }
-    const uint32_t p = tv.texels8[idx];
-    if (t.format == PTX_TEXTURE_RGBA8_SRGB)
-    {
-        r.x = tv.srgbLut[p & 255u]; r.y = tv.srgbLut[(p >> 8) & 255u]; r.z = tv.srgbLut[(p >> 16) & 255u];
+        r.x = srgbLut[p & 255u]; r.y = srgbLut[(p >> 8) & 255u]; r.z = srgbLut[(p >> 16) & 255u];
     }
     else
     {
@@ -972,6 +964,28 @@ PT_DEV f4 fetchTexelEncoded(const TextureView &tv, const DevTexture &t, uint32_t
     }
     r.w = (float)(p >> 24) / 255.0f;
     return r;
+}
+// ... and a filtered value back into it, as a blit stores it
+PT_DEV uint32_t encodeTexel8(uint32_t format, f4 c)
+{
+    if (format == PTX_TEXTURE_RGBA8_SRGB)
+        return quantize8(linearToSrgb(c.x)) | quantize8(linearToSrgb(c.y)) << 8 | quantize8(linearToSrgb(c.z)) << 16 | quantize8(c.w) << 24;
+    return quantize8(c.x) | quantize8(c.y) << 8 | quantize8(c.z) << 16 | quantize8(c.w) << 24;
+}
+
+// Upload-time form of a texel (k_blit_level builds mip chains in the image's own format, Image.cpp:264-300): decode from
+// the pool of the texture's format.
+PT_DEV f4 fetchTexelEncoded(const TextureView &tv, const DevTexture &t, uint32_t level, uint32_t x, uint32_t y)
+{
+    const size_t idx = (size_t)t.levelOffset[level] + (size_t)y * levelDim(t.width, level) + x;
+    if (t.format == PTX_TEXTURE_RGBA32F)
+    {
+        const float4 v = tv.texelsF[idx];
+        f4 r;
+        r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
+        return r;
+    }
+    return decodeTexel8(tv.srgbLut, t.format, tv.texels8[idx]);
 }
 
 // Render-time form: every level of every texture sits DECODED (four floats per texel, the values fetchTexelEncoded returns)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -103,10 +104,12 @@ struct EnvSwitches
     bool snapshotMemcpy = false; // PTX_SNAPSHOT_MEMCPY=1: the read-back's device-side snapshot by hipMemcpyAsync (rounds 1-4) instead of a kernel
     bool fenceRefit = false;     // PTX_FENCE_REFIT=1: the round-4 bottom-up kernels (fence and atomic per node) instead of the level lists
     bool pairLeaves = true;      // PTX_PAIR_LEAVES=0: single-triangle leaves only (pt_bvh_build.hpp, "pair leaves")
+    bool streamLevelwise = false; // PTX_STREAM_LEVELWISE=1: ptx_texture_upload builds every chain level by level (k_blit_level) instead of k_stream_chain
     static EnvSwitches read()
     {
         EnvSwitches e;
         e.verbose = getenv("PTX_VERBOSE") != nullptr;
+        e.streamLevelwise = getenv("PTX_STREAM_LEVELWISE") != nullptr && std::strcmp(getenv("PTX_STREAM_LEVELWISE"), "0") != 0;
         if (const char *v = getenv("PTX_PAIR_LEAVES"))
             e.pairLeaves = std::strcmp(v, "0") != 0;
         if (const char *v = getenv("PTX_COPY_GROUPS"))
@@ -183,6 +186,9 @@ struct SceneData
     bool mixedMaterialTypes = false; // the instanced meshes use more than one material type (ShaderTypes.incl:143-145): k_shade sorts its queue
     bool mixedTextured = false;      // ... or materials with and without scene textures: the sampler runs for waves of textured hits only
     uint32_t pairCount = 0, triCount = 0, dxNormalTextures = 0;
+    // ptx_scene_upload_streamed: the plan, the texture states and the upload stream (pt_scene_host.hpp); null after a plain upload.
+    // The last member: it goes first, and its destructor waits for the uploads that still write into the buffers above.
+    std::shared_ptr<struct TextureStreaming> streaming;
 };
 
 struct PtxRenderer
@@ -1029,6 +1035,8 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         if (rcPrev != PTX_OK)
             return rcPrev;
     }
+    if (const int rcCommit = waitForCommits(r))
+        return rcCommit;
 
     const LaunchParams p = makeParams(r, uniform, firstFrame, frames);
     if ((uint64_t)p.slotsPerFrame * frames > 0x7fffffffull)
@@ -1533,6 +1541,8 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
     HIP_TRY(r, dHits.alloc(n));
     HIP_TRY(r, dIds.alloc(n));
     HIP_TRY(r, dOverflow.alloc(1));
+    if (const int rcCommit = waitForCommits(r))
+        return rcCommit;
     TraceScene sc;
     sc = makeTraceScene(r);
     hipError_t e = hipMemcpyAsync(dRays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice, r->stream);

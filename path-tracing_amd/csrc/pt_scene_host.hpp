@@ -1,4 +1,4 @@
-// pt_scene_host.hpp -- host side of the scene: ptx_share_scene and ptx_scene_upload.  An upload is a checked plan, then named
+// pt_scene_host.hpp -- host side of the scene: ptx_share_scene, ptx_scene_upload and the streamed textures.  An upload is a checked plan, then named
 // stages: validateSceneDesc, flattenScene and planTextures read the description only and hold every PTX_ERROR_INVALID_ARGUMENT
 // refusal, so a refused description leaves the handle as it was; uploadGeometry, uploadTextures and alphaFootprints then write
 // r->scene in place.  Included by pt_runtime.hpp below the renderer object (PtxRenderer, SceneData, DevBuf, HIP_TRY, fail) and
@@ -81,7 +81,8 @@ static int shareScene(PtxRenderer *r, PtxRenderer *owner)
     if (r->auxStream)
         HIP_TRY(r, hipStreamSynchronize(r->auxStream));
     detachSharedScene(r);
-    // its own copies are not needed any more
+    // its own copies are not needed any more (uploads still streaming into them end first)
+    r->scene.streaming.reset();
     r->scene = SceneData();
     r->nodes.release(); r->tris.release(); r->shadeTris.release(); r->alphaTris.release();
     r->build = PtxRenderer::BuildState();
@@ -419,7 +420,8 @@ static int uploadGeometry(PtxRenderer *r, const PtxSceneDesc *s, FlatScene &flat
 // Stage 5 (row N1): every texture into the pools of the upload formats -- the file's own chain, or its level 0 (scaled through the
 // scratch chain where the plan says so) and the mip chain below it level by level on the device --, then decoded into the pool the
 // render kernels sample.  The upload-format pools are this stage's own: freed when it returns, whichever way (hipFree waits).
-static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePlan &plan)
+// extraTexels: room behind the decoded pool (the stand-in texels of a streamed upload).
+static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePlan &plan, size_t extraTexels = 0)
 {
     SceneData &sc = r->scene;
     DevBuf<DevTexture> textures; // upload time only: the table, the pools of the image formats in which mip chains are built,
@@ -480,7 +482,7 @@ static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePl
     }
     // The pool the render kernels sample (pt_device.hpp, fetchTexel): every level of every texture decoded to four floats,
     // the RGBA32F pool first, the 8-bit textures behind it; `renderTextures` is the table with offsets into that pool.
-    HIP_TRY(r, sc.renderTexels.alloc(plan.nf + plan.n8));
+    HIP_TRY(r, sc.renderTexels.alloc(plan.nf + plan.n8 + extraTexels));
     HIP_TRY(r, sc.renderTextures.alloc(plan.total));
     if (plan.nf)
         HIP_TRY(r, hipMemcpyAsync(sc.renderTexels.p, texelsF.p, plan.nf * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
@@ -502,14 +504,16 @@ static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePl
 }
 
 // Stage 6: what the any-hit stages read of the textures.
-static int alphaFootprints(PtxRenderer *r, const TexturePlan &plan)
+// pending / extraQuads (a streamed upload): the textures whose texels are still to come get their quads from
+// ptx_texture_upload, and the stand-in quads sit behind the scene's.
+static int alphaFootprints(PtxRenderer *r, const TexturePlan &plan, const std::vector<uint8_t> *pending = nullptr, size_t extraQuads = 0)
 {
     SceneData &sc = r->scene;
     int rc;
     if (sc.anyNonOpaque)
-        HIP_TRY(r, sc.alphaQuads.alloc(plan.alphaQuads));
+        HIP_TRY(r, sc.alphaQuads.alloc(plan.alphaQuads + extraQuads));
     for (uint32_t ti = 0; ti < plan.textureCount; ti++)
-        if (plan.alphaTexOf[ti] != kNoAlphaTex)
+        if (plan.alphaTexOf[ti] != kNoAlphaTex && !(pending && (*pending)[ti]))
         {
             const AlphaTex &at = plan.alphaTex[plan.alphaTexOf[ti]];
             k_alpha_quads<<<(at.width * at.height + 255) / 256, 256, 0, r->stream>>>(at.width, at.height, sc.renderTexels.p + plan.renderTable[ti].levelOffset[0],
@@ -519,34 +523,407 @@ static int alphaFootprints(PtxRenderer *r, const TexturePlan &plan)
     return upload(r, sc.alphaTexOf, plan.alphaTexOf.data(), plan.alphaTexOf.size());
 }
 
-static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s)
+// ---- streamed textures: ptx_scene_upload_streamed, ptx_texture_upload, ptx_textures_commit, ptx_texture_residency ----------------
+// A texture of a streamed upload is PENDING (no texels yet: its table entries name the 1 x 1 stand-in), UPLOADED (its pool
+// region is being filled on the upload stream; the tables still name the stand-in) or RESIDENT (committed, or it came with
+// its data).  Nothing a frame reads changes outside ptx_textures_commit.
+enum : uint8_t { kTexResident = 0, kTexPending = 1, kTexUploaded = 2 };
+constexpr uint32_t kStreamRing = 2; // staging slots: a ptx_texture_upload waits only when both still hold an upload in flight
+
+struct TextureStreaming
 {
+    int device = 0;
+    TexturePlan plan;
+    std::vector<PtxTextureDesc> declared; // width / height / format / levels as ptx_scene_upload_streamed saw them
+    std::vector<uint8_t> state;           // [textureCount] kTex*
+    uint32_t pendingCount = 0, uploadedCount = 0;
+    uint32_t standInTexel = 0, standInQuad = 0; // first of the nine stand-ins in renderTexels / alphaQuads
+    std::vector<DevTexture> liveTable;    // what the device tables hold for the pending textures at upload
+    std::vector<AlphaTex> liveAlphaTex;
+    DevBuf<DevTexture> finalTextures;     // the plan's entries, for k_commit_textures
+    DevBuf<AlphaTex> finalAlphaTex;
+    DevBuf<float> srgbLut;
+    hipStream_t stream = nullptr;         // the upload stream, created by the first ptx_texture_upload
+    hipEvent_t evUploaded = nullptr, evCommitted = nullptr;
+    uint32_t *commitList = nullptr;       // pinned, [textureCount]: every texture is committed once, so entries are never reused
+    uint32_t commitCursor = 0;
+    uint64_t commits = 0;                 // commits that switched something: borrowers' streams wait for evCommitted
+    struct Slot
+    {
+        void *host = nullptr;             // pinned: the slot's one-texture table (two entries), then the caller's texels
+        size_t hostBytes = 0;
+        DevBuf<uint8_t> pool;             // device: the one-texture pool of the image format (chain, then the scratch chain)
+        DevBuf<DevTexture> table;
+        hipEvent_t done = nullptr;
+        bool busy = false;
+    } ring[kStreamRing];
+    uint32_t nextSlot = 0;
+    ~TextureStreaming()
+    {
+        (void)hipSetDevice(device);
+        if (stream)
+        {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+        for (Slot &sl : ring)
+        {
+            if (sl.host) (void)hipHostFree(sl.host);
+            if (sl.done) (void)hipEventDestroy(sl.done);
+        }
+        if (commitList) (void)hipHostFree(commitList);
+        if (evUploaded) (void)hipEventDestroy(evUploaded);
+        if (evCommitted) (void)hipEventDestroy(evCommitted);
+    }
+};
+
+// Frames, rays and lookups enqueued after a commit see it: on the owner by stream order (the commit is enqueued on its render
+// stream), on a borrower by this wait.
+static int waitForCommits(PtxRenderer *r)
+{
+    if (!r->sceneOwner)
+        return PTX_OK;
+    const TextureStreaming *st = r->sceneOwner->scene.streaming.get();
+    if (st && st->commits)
+        HIP_TRY(r, hipStreamWaitEvent(r->stream, st->evCommitted, 0));
+    return PTX_OK;
+}
+
+// The streamed half of an upload, behind uploadTextures and alphaFootprints: stand-ins, the tables of the pending textures.
+static int beginStreaming(PtxRenderer *r, const PtxSceneDesc *s, std::shared_ptr<TextureStreaming> st, const uint32_t *standIn)
+{
+    SceneData &sc = r->scene;
+    const TexturePlan &plan = st->plan;
+    int rc;
+    st->device = r->device;
+    st->standInTexel = (uint32_t)(plan.nf + plan.n8);
+    st->standInQuad = (uint32_t)plan.alphaQuads;
+    HIP_TRY(r, st->srgbLut.alloc(256));
+    k_build_srgb_lut<<<1, 256, 0, r->stream>>>(st->srgbLut.p);
+    k_stream_stand_ins<<<1, 64, 0, r->stream>>>(sc.renderTexels.p + st->standInTexel, sc.anyNonOpaque ? sc.alphaQuads.p + st->standInQuad : nullptr);
+    st->liveTable = plan.renderTable;
+    st->liveAlphaTex = plan.alphaTex;
+    for (uint32_t i = 0; i < plan.textureCount; i++)
+    {
+        st->declared[i] = s->textures[i];
+        st->declared[i].data = nullptr;
+        if (st->state[i] != kTexPending)
+            continue;
+        const uint32_t k = standIn ? standIn[i] : (uint32_t)PTX_PLACEHOLDER_TEXTURE_INDEX;
+        st->liveTable[i] = { 1u, 1u, 1u, plan.renderTable[i].format, { st->standInTexel + k } };
+        if (plan.alphaTexOf[i] != kNoAlphaTex)
+            st->liveAlphaTex[plan.alphaTexOf[i]] = { 1u, 1u, st->standInQuad + k, 0u };
+    }
+    if (plan.total)
+        HIP_TRY(r, hipMemcpyAsync(sc.renderTextures.p, st->liveTable.data(), plan.total * sizeof(DevTexture), hipMemcpyHostToDevice, r->stream));
+    if (!st->liveAlphaTex.empty())
+        HIP_TRY(r, hipMemcpyAsync(sc.alphaTex.p, st->liveAlphaTex.data(), st->liveAlphaTex.size() * sizeof(AlphaTex), hipMemcpyHostToDevice, r->stream));
+    if ((rc = upload(r, st->finalTextures, plan.renderTable.data(), plan.total)) != PTX_OK) return rc;
+    if ((rc = upload(r, st->finalAlphaTex, plan.alphaTex.data(), plan.alphaTex.size())) != PTX_OK) return rc;
+    HIP_TRY(r, hipHostMalloc(reinterpret_cast<void **>(&st->commitList), (plan.textureCount ? plan.textureCount : 1u) * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(r, hipEventCreateWithFlags(&st->evUploaded, hipEventDisableTiming));
+    HIP_TRY(r, hipEventCreateWithFlags(&st->evCommitted, hipEventDisableTiming));
+    sc.streaming = st;
+    return PTX_OK;
+}
+
+static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s, bool streamed = false, const uint32_t *standIn = nullptr)
+{
+    const char *who = streamed ? "ptx_scene_upload_streamed" : "ptx_scene_upload";
     if (!r || !s)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_scene_upload: null argument");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
     HIP_TRY(r, hipSetDevice(r->device));
     // The plan: host only.  A description that is refused here leaves the handle as it was -- its own scene, or the one it
     // borrows -- and nothing below refuses one.
     int rc;
     FlatScene flat;
-    TexturePlan plan;
+    std::shared_ptr<TextureStreaming> st;
+    TexturePlan localPlan;
+    if (streamed)
+        st = std::make_shared<TextureStreaming>();
+    TexturePlan &plan = streamed ? st->plan : localPlan;
     size_t freeB = 0, totalB = 0;
     if ((rc = validateSceneDesc(r, s)) != PTX_OK) return rc;
     if ((rc = flattenScene(r, s, flat)) != PTX_OK) return rc;
     if (!s->forceFullTextureSize && s->textures && s->textureCount && !s->textureMemoryBudget) // the one case planTextures reads it in
         HIP_TRY(r, hipMemGetInfo(&freeB, &totalB));
     if ((rc = planTextures(r, s, totalB, flat.anyNonOpaque, plan)) != PTX_OK) return rc;
+    if (streamed)
+    {
+        st->state.assign(plan.textureCount, kTexResident);
+        st->declared.resize(plan.textureCount);
+        for (uint32_t i = 0; i < plan.textureCount; i++)
+        {
+            if (standIn && standIn[i] >= PTX_SCENE_TEXTURE_OFFSET)
+                return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: stand-in %u of texture %u is not one of the nine fixed textures", who, standIn[i], i);
+            if (!s->textures[i].data)
+            {
+                st->state[i] = kTexPending;
+                st->pendingCount++;
+            }
+        }
+        if ((uint64_t)plan.nf + plan.n8 + PTX_SCENE_TEXTURE_OFFSET > 0xffffffffull || (uint64_t)plan.alphaQuads + PTX_SCENE_TEXTURE_OFFSET >= 0xffffffffull)
+            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture pool exceeds 2^32 texels", who);
+    }
 
     // from here on the old scene is gone, whatever happens
     detachSharedScene(r); // a renderer that was borrowing a scene gets its own again
     quiesceSharers(r);
+    r->scene.streaming.reset(); // (waits for the uploads that still write into the old pools)
     r->sceneReady = r->accelReady = false;
     r->sceneEpoch++;
     r->build = PtxRenderer::BuildState();
     if ((rc = uploadGeometry(r, s, flat)) != PTX_OK) return rc;
-    if ((rc = uploadTextures(r, s, plan)) != PTX_OK) return rc;
-    if ((rc = alphaFootprints(r, plan)) != PTX_OK) return rc;
+    if ((rc = uploadTextures(r, s, plan, streamed ? PTX_SCENE_TEXTURE_OFFSET : 0)) != PTX_OK) return rc;
+    if ((rc = alphaFootprints(r, plan, streamed ? &st->state : nullptr, streamed ? PTX_SCENE_TEXTURE_OFFSET : 0)) != PTX_OK) return rc;
+    if (streamed && (rc = beginStreaming(r, s, st, standIn)) != PTX_OK) return rc;
     HIP_TRY(r, hipStreamSynchronize(r->stream)); // `flat`, `plan` and the caller's arrays may go away
+    if (streamed)
+        HIP_TRY(r, hipGetLastError());
     r->sceneReady = true;
     r->stats.triangles = flat.triangles;
+    return PTX_OK;
+}
+
+static int streamingOf(PtxRenderer *r, const char *who, TextureStreaming **out)
+{
+    if (!r)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    if (r->sceneOwner)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: this renderer shares another renderer's scene (ptx_share_scene); uploads are the owner's calls", who);
+    if (!r->sceneReady)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no scene uploaded", who);
+    if (!r->scene.streaming)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the scene was not uploaded by ptx_scene_upload_streamed", who);
+    *out = r->scene.streaming.get();
+    return PTX_OK;
+}
+
+// The chain of texture `i` below its level 0, which sits encoded at the head of the slot's pool: k_stream_chain while every
+// extent of the level above is even or 1, k_blit_level from there on; everything decoded into the texture's region of
+// renderTexels.  levelwise: k_blit_level for every level (PTX_STREAM_LEVELWISE, and what the blocking upload does).
+static int streamChain(PtxRenderer *r, TextureStreaming *st, TextureStreaming::Slot &sl, uint32_t i, const TextureView &tv, bool levelwise)
+{
+    const DevTexture &t = st->plan.table[i], &rt = st->plan.renderTable[i];
+    const bool isFloat = t.format == PTX_TEXTURE_RGBA32F;
+    const uint32_t logTile = isFloat ? kStreamSteps - 1 : kStreamSteps, tile = 1u << logTile;
+    float4 *decoded = r->scene.renderTexels.p;
+    auto even = [&](uint32_t l) {
+        const uint32_t w = mipDim(t.width, l), h = mipDim(t.height, l);
+        return l + 1 < t.levels && (w % 2 == 0 || w == 1) && (h % 2 == 0 || h == 1);
+    };
+    uint32_t cur = 0;       // the coarsest level the pool holds encoded
+    uint32_t firstToDecode = 0; // levels below this one are in renderTexels already
+    while (!levelwise && even(cur))
+    {
+        StreamChainArgs a = {};
+        while (a.steps < logTile && even(cur + a.steps))
+            a.steps++;
+        a.srcOffset = (uint32_t)chainTexels(t.width, t.height, cur);
+        a.sw = mipDim(t.width, cur); a.sh = mipDim(t.height, cur);
+        a.format = t.format;
+        a.writeSource = cur == 0 ? 1u : 0u;
+        a.encOut = cur + a.steps + 1 < t.levels ? (uint32_t)chainTexels(t.width, t.height, cur + a.steps) : 0xffffffffu;
+        for (uint32_t k = 0; k <= a.steps; k++)
+            a.decoded[k] = rt.levelOffset[cur + k];
+        const uint32_t grid = ((a.sw + tile - 1) / tile) * ((a.sh + tile - 1) / tile);
+        if (isFloat)
+            k_stream_chain<true><<<grid, kStreamBlock, 0, st->stream>>>(a, sl.pool.p, st->srgbLut.p, decoded);
+        else
+            k_stream_chain<false><<<grid, kStreamBlock, 0, st->stream>>>(a, sl.pool.p, st->srgbLut.p, decoded);
+        cur += a.steps;
+        firstToDecode = cur + 1;
+    }
+    for (uint32_t l = cur + 1; l < t.levels; l++)
+    {
+        const uint32_t dw = mipDim(t.width, l), dh = mipDim(t.height, l);
+        k_blit_level<<<(dw * dh + 255) / 256, 256, 0, st->stream>>>(tv, 0u, l - 1, 0u, l, reinterpret_cast<uint32_t *>(sl.pool.p), reinterpret_cast<float4 *>(sl.pool.p));
+    }
+    if (firstToDecode < t.levels)
+    {
+        const size_t first = chainTexels(t.width, t.height, firstToDecode), count = chainTexels(t.width, t.height, t.levels) - first;
+        if (isFloat)
+            HIP_TRY(r, hipMemcpyAsync(decoded + rt.levelOffset[firstToDecode], reinterpret_cast<float4 *>(sl.pool.p) + first, count * sizeof(float4),
+                                      hipMemcpyDeviceToDevice, st->stream));
+        else
+            k_decode_texels<<<(uint32_t)((count + 255) / 256), 256, 0, st->stream>>>(reinterpret_cast<uint32_t *>(sl.pool.p), st->srgbLut.p, (uint32_t)first, (uint32_t)count,
+                                                                                    t.format, decoded + rt.levelOffset[firstToDecode]);
+    }
+    return PTX_OK;
+}
+
+// TextureUploader's submit thread for one texture (TextureUploader.cpp:312-360): the caller's texels into a staging slot, the
+// device work on the upload stream.  Nothing a frame reads is touched.
+static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d)
+{
+    const char *who = "ptx_texture_upload";
+    TextureStreaming *st = nullptr;
+    int rc;
+    if ((rc = streamingOf(r, who, &st)) != PTX_OK) return rc;
+    const TexturePlan &plan = st->plan;
+    if (!d || index >= plan.textureCount)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture index %u out of range (%u textures)", who, index, plan.textureCount);
+    const PtxTextureDesc &decl = st->declared[index];
+    auto one = [](uint32_t v) { return v ? v : 1u; };
+    if (one(d->width) != one(decl.width) || one(d->height) != one(decl.height) || d->format != decl.format || one(d->levels) != one(decl.levels))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u was declared %u x %u, format %u, %u level(s)", who, index, decl.width, decl.height, decl.format,
+                    decl.levels);
+    if (!d->data)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u: null data", who, index);
+    if (st->state[index] != kTexPending)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u is not pending (already uploaded or resident)", who, index);
+    HIP_TRY(r, hipSetDevice(r->device));
+    if (!st->stream)
+        HIP_TRY(r, hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
+
+    const DevTexture &t = plan.table[index];
+    const Placement &pl = plan.place[index];
+    const bool isFloat = t.format == PTX_TEXTURE_RGBA32F;
+    const size_t texel = isFloat ? 16 : 4;
+    // the slot's one-texture pool: the chain at its head, the scratch chain of a scaled texture behind it
+    DevTexture tab[2];
+    tab[0] = t;
+    size_t poolTexels = placeLevels(tab[0], 0);
+    tab[1] = tab[0];
+    if (pl.temp >= 0)
+    {
+        tab[1] = plan.table[(size_t)pl.temp];
+        poolTexels = placeLevels(tab[1], poolTexels);
+    }
+    const uint8_t *src = static_cast<const uint8_t *>(d->data) + (pl.useFileChain ? chainTexels(pl.srcW, pl.srcH, pl.firstFile) * texel : 0);
+    const size_t srcBytes = (pl.useFileChain ? chainTexels(t.width, t.height, t.levels) : (size_t)pl.srcW * pl.srcH) * texel;
+    const size_t header = 256; // the table, and the texels 16-byte aligned behind it
+
+    // a free slot: the reference's free-buffer semaphore
+    TextureStreaming::Slot &sl = st->ring[st->nextSlot];
+    if (!sl.done)
+        HIP_TRY(r, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (sl.busy)
+    {
+        HIP_TRY(r, hipEventSynchronize(sl.done));
+        sl.busy = false;
+    }
+    if (sl.hostBytes < header + srcBytes)
+    {
+        if (sl.host)
+            (void)hipHostFree(sl.host);
+        sl.host = nullptr;
+        sl.hostBytes = 0;
+        HIP_TRY(r, hipHostMalloc(&sl.host, header + srcBytes, hipHostMallocDefault));
+        sl.hostBytes = header + srcBytes;
+    }
+    HIP_TRY(r, sl.pool.alloc(poolTexels * texel));
+    HIP_TRY(r, sl.table.alloc(2));
+    st->nextSlot = (st->nextSlot + 1) % kStreamRing;
+    std::memcpy(sl.host, tab, sizeof(tab));
+    std::memcpy(static_cast<uint8_t *>(sl.host) + header, src, srcBytes);
+    const uint8_t *staged = static_cast<const uint8_t *>(sl.host) + header;
+
+    hipStream_t S = st->stream;
+    float4 *decoded = r->scene.renderTexels.p;
+    const DevTexture &rt = plan.renderTable[index];
+    HIP_TRY(r, hipMemcpyAsync(sl.table.p, sl.host, sizeof(tab), hipMemcpyHostToDevice, S));
+    const TextureView tv = { sl.table.p, 2u, reinterpret_cast<const uint32_t *>(sl.pool.p), reinterpret_cast<const float4 *>(sl.pool.p), st->srgbLut.p };
+    auto poolAt = [&](uint32_t offset) -> void * { return sl.pool.p + (size_t)offset * texel; };
+    auto blit = [&](uint32_t s0, uint32_t srcLevel, uint32_t d0, uint32_t dstLevel) {
+        const uint32_t dw = mipDim(tab[d0].width, dstLevel), dh = mipDim(tab[d0].height, dstLevel);
+        k_blit_level<<<(dw * dh + 255) / 256, 256, 0, S>>>(tv, s0, srcLevel, d0, dstLevel, reinterpret_cast<uint32_t *>(sl.pool.p), reinterpret_cast<float4 *>(sl.pool.p));
+    };
+    if (pl.useFileChain)
+    {
+        // the file's own levels from the one that has the budgeted extent: one copy, then decoded as they are
+        const size_t count = chainTexels(t.width, t.height, t.levels);
+        HIP_TRY(r, hipMemcpyAsync(sl.pool.p, staged, srcBytes, hipMemcpyHostToDevice, S));
+        if (isFloat)
+            HIP_TRY(r, hipMemcpyAsync(decoded + rt.levelOffset[0], sl.pool.p, srcBytes, hipMemcpyDeviceToDevice, S));
+        else
+            k_decode_texels<<<(uint32_t)((count + 255) / 256), 256, 0, S>>>(reinterpret_cast<uint32_t *>(sl.pool.p), st->srgbLut.p, 0u, (uint32_t)count, t.format,
+                                                                           decoded + rt.levelOffset[0]);
+    }
+    else
+    {
+        if (pl.temp >= 0)
+        {
+            // scaled down: the file's level 0 into the scratch chain, halved by linear blits, then into level 0 (uploadTextures)
+            HIP_TRY(r, hipMemcpyAsync(poolAt(tab[1].levelOffset[0]), staged, srcBytes, hipMemcpyHostToDevice, S));
+            for (uint32_t l = 1; l <= pl.halvings; l++)
+                blit(1, l - 1, 1, l);
+            if (mipDim(pl.srcW, pl.halvings) == t.width && mipDim(pl.srcH, pl.halvings) == t.height)
+                HIP_TRY(r, hipMemcpyAsync(poolAt(0), poolAt(tab[1].levelOffset[pl.halvings]), (size_t)t.width * t.height * texel, hipMemcpyDeviceToDevice, S));
+            else
+                blit(1, pl.halvings, 0, 0);
+        }
+        else
+            HIP_TRY(r, hipMemcpyAsync(poolAt(0), staged, srcBytes, hipMemcpyHostToDevice, S));
+        if ((rc = streamChain(r, st, sl, index, tv, r->env.streamLevelwise)) != PTX_OK) return rc;
+    }
+    if (plan.alphaTexOf[index] != kNoAlphaTex)
+    {
+        const AlphaTex &at = plan.alphaTex[plan.alphaTexOf[index]];
+        k_alpha_quads<<<(at.width * at.height + 255) / 256, 256, 0, S>>>(at.width, at.height, decoded + rt.levelOffset[0], r->scene.alphaQuads.p + at.offset);
+    }
+    HIP_TRY(r, hipEventRecord(sl.done, S));
+    HIP_TRY(r, hipGetLastError());
+    sl.busy = true;
+    st->state[index] = kTexUploaded;
+    st->pendingCount--;
+    st->uploadedCount++;
+    return PTX_OK;
+}
+
+// Renderer::UpdateTexture (Renderer.cpp:441-471) for every texture uploaded so far: between frames, on the render stream.
+static int texturesCommit(PtxRenderer *r, uint32_t *committed)
+{
+    const char *who = "ptx_textures_commit";
+    TextureStreaming *st = nullptr;
+    int rc;
+    if (committed)
+        *committed = 0;
+    if ((rc = streamingOf(r, who, &st)) != PTX_OK) return rc;
+    if (!st->uploadedCount)
+        return PTX_OK;
+    HIP_TRY(r, hipSetDevice(r->device));
+    SceneData &sc = r->scene;
+    const uint32_t first = st->commitCursor;
+    bool alpha = false;
+    for (uint32_t i = 0; i < st->plan.textureCount; i++)
+        if (st->state[i] == kTexUploaded)
+        {
+            st->commitList[st->commitCursor++] = i;
+            st->state[i] = kTexResident;
+            alpha |= st->plan.alphaTexOf[i] != kNoAlphaTex;
+        }
+    const uint32_t n = st->commitCursor - first;
+    st->uploadedCount = 0;
+    // the uploads, then the switch: the render stream waits for the upload stream on the device, the host does not
+    HIP_TRY(r, hipEventRecord(st->evUploaded, st->stream));
+    HIP_TRY(r, hipStreamWaitEvent(r->stream, st->evUploaded, 0));
+    quiesceSharers(r); // the borrowers' frames in flight still read the tables
+    k_commit_textures<<<(n + 63) / 64, 64, 0, r->stream>>>(st->commitList + first, n, st->finalTextures.p, sc.renderTextures.p,
+                                                          sc.anyNonOpaque ? sc.alphaTexOf.p : nullptr, st->finalAlphaTex.p, sc.alphaTex.p);
+    if (alpha && sc.anyNonOpaque && r->accelReady && r->treeTris) // the any-hit records carry the texture's extent and first quad
+        k_alpha_tris<<<(r->treeTris + 255) / 256, 256, 0, r->stream>>>(r->treeTris, r->tris.p, r->shadeTris.p, makeSceneView(r), sc.alphaTexOf.p, sc.alphaTex.p, r->alphaTris.p);
+    HIP_TRY(r, hipEventRecord(st->evCommitted, r->stream));
+    HIP_TRY(r, hipGetLastError());
+    st->commits++;
+    if (committed)
+        *committed = n;
+    return PTX_OK;
+}
+
+static int textureResidency(PtxRenderer *r, uint32_t *resident, uint32_t *pending)
+{
+    if (!r)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    const PtxRenderer *s = sceneOf(r);
+    if (!s->sceneReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_texture_residency: no scene uploaded");
+    const TextureStreaming *st = s->scene.streaming.get();
+    uint32_t notResident = 0;
+    if (st)
+        for (uint8_t v : st->state)
+            notResident += v != kTexResident;
+    if (resident) *resident = s->scene.textureCount - notResident;
+    if (pending) *pending = notResident;
     return PTX_OK;
 }

@@ -53,6 +53,26 @@ int ptx_scene_upload(PtxRenderer *r, const PtxSceneDesc *s)
     return sceneUpload(r, s);
 }
 
+int ptx_scene_upload_streamed(PtxRenderer *r, const PtxSceneDesc *s, const uint32_t *standIn)
+{
+    return sceneUpload(r, s, true, standIn);
+}
+
+int ptx_texture_upload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *desc)
+{
+    return textureUpload(r, index, desc);
+}
+
+int ptx_textures_commit(PtxRenderer *r, uint32_t *committed)
+{
+    return texturesCommit(r, committed);
+}
+
+int ptx_texture_residency(PtxRenderer *r, uint32_t *resident, uint32_t *pending)
+{
+    return textureResidency(r, resident, pending);
+}
+
 int ptx_build_accel(PtxRenderer *r)
 {
     return buildBestTree(r);
