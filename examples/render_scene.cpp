@@ -7,6 +7,7 @@
 //   g++ -std=c++20 -O2 examples/render_scene.cpp path-tracing_amd/host/{Scene,Camera,ExampleScenes,OutputSaver,TextureImporter,JpegDecoder,SceneImporter,SceneDescription,FbxReader,ObjReader,RendererHip}.cpp \
 //       -Ipath-tracing_amd/host -Lpath-tracing_amd -lptx_hip -Wl,-rpath,'$ORIGIN/../path-tracing_amd' -o examples/render_scene
 //   examples/render_scene default 640 360 16 4 out.png
+//   examples/render_scene default 640 360 1 4 normals.png --debug-mode 2    (the debug view instead: PTX_DEBUG_MODE_*)
 #include <cmath>
 #include <cstdio>
 #include <filesystem>
@@ -20,6 +21,16 @@ using namespace PathTracing;
 
 int main(int argc, char **argv)
 {
+    int debugMode = -1; // --debug-mode N anywhere on the line: one frame of the debug view instead of the path tracer
+    for (int i = 1; i + 1 < argc; i++)
+        if (std::string(argv[i]) == "--debug-mode")
+        {
+            debugMode = std::atoi(argv[i + 1]);
+            for (int k = i; k + 2 < argc; k++)
+                argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     const std::string name = argc > 1 ? argv[1] : "default";
     const uint32_t width = argc > 2 ? std::atoi(argv[2]) : 640, height = argc > 3 ? std::atoi(argv[3]) : 360;
     const uint32_t spp = argc > 4 ? std::atoi(argv[4]) : 16, bounces = argc > 5 ? std::atoi(argv[5]) : 4;
@@ -36,7 +47,9 @@ int main(int argc, char **argv)
         RendererHip::PathTracingSettings settings;
         settings.BounceCount = bounces;
         RendererHip::SetSettings(settings);
-        for (uint32_t i = 0; i < spp; i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)
+        if (debugMode >= 0)
+            RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
+        for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)
             RendererHip::Render();
         const std::vector<float> acc = RendererHip::ReadAccumulationImage();
         const float inv = 1.0f / static_cast<float>(RendererHip::GetTotalSamples());

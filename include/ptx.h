@@ -658,6 +658,57 @@ typedef enum PtxTestFunction {
  * (texture index as uint bits, u, v, dudx, dvdx, dudy, dvdy); out: rgba. */
 PTX_API int ptx_test_texture(PtxRenderer *r, const float *in, float *out, uint32_t n, int implicitLod);
 
+/* ------------------------------------------------------------------------- */
+/* Debug view (row D16): the debug ray-tracing pipeline, Shaders/Debug and   */
+/* Renderer::SetDebugRaytracingPipeline (Renderer.cpp:579-610, 769-772)      */
+/* ------------------------------------------------------------------------- */
+
+/* DebugShaderTypes.incl:18-26 (s_RenderMode) */
+enum {
+    PTX_DEBUG_MODE_COLOR = 0,          /* rasteriser-style direct light with shadow rays, debugClosestHit.rchit:204-243 */
+    PTX_DEBUG_MODE_WORLD_POSITION = 1,
+    PTX_DEBUG_MODE_NORMAL = 2,         /* the shading normal, normal map applied */
+    PTX_DEBUG_MODE_TEXTURE_COORDS = 3,
+    PTX_DEBUG_MODE_MIPS = 4,           /* 0.1 * computeLod(derivatives) + 1 */
+    PTX_DEBUG_MODE_GEOMETRY = 5,       /* getRandomColor(gl_GeometryIndexEXT): the mesh's index inside its model */
+    PTX_DEBUG_MODE_PRIMITIVE = 6,      /* getRandomColor(gl_PrimitiveID) */
+    PTX_DEBUG_MODE_INSTANCE = 7        /* getRandomColor(gl_InstanceID): the index of the PtxModelInstance */
+};
+/* DebugShaderTypes.incl:28-31 (s_RaygenFlags) */
+enum {
+    PTX_DEBUG_RAYGEN_FORCE_OPAQUE = 1u,    /* gl_RayFlagsOpaqueEXT on the primary ray: no any-hit stage, no decal */
+    PTX_DEBUG_RAYGEN_CULL_BACK_FACES = 2u  /* gl_RayFlagsCullBackFacingTrianglesEXT on the primary ray; facing is decided in the
+                                            * space of the model's acceleration structure: a mirrored instance keeps its winding */
+};
+/* DebugShaderTypes.incl:33-39 (s_HitGroupFlags).  HitGroupFlagsDxNormalTextures is not the caller's: it follows
+ * PtxSceneDesc.dxNormalTextures of the uploaded scene, as Renderer.cpp:699-708 sets it. */
+enum {
+    PTX_DEBUG_HIT_DISABLE_COLOR_TEXTURE = 1u,  /* the colour slot reads PTX_DEFAULT_COLOR_TEXTURE_INDEX (material.glsl:69-70) */
+    PTX_DEBUG_HIT_DISABLE_NORMAL_TEXTURE = 2u, /* the normal slot reads PTX_DEFAULT_NORMAL_TEXTURE_INDEX */
+    PTX_DEBUG_HIT_DISABLE_MIP_MAPS = 4u,       /* derivatives = vec4(0) */
+    PTX_DEBUG_HIT_DISABLE_SHADOWS = 8u         /* every light is added without its shadow ray */
+};
+typedef struct PtxDebugViewDesc {
+    uint32_t renderMode;    /* PTX_DEBUG_MODE_* */
+    uint32_t raygenFlags;   /* PTX_DEBUG_RAYGEN_* */
+    uint32_t hitGroupFlags; /* PTX_DEBUG_HIT_* */
+    uint32_t reserved;      /* 0 */
+} PtxDebugViewDesc;
+
+/* RecordPathTracingCommands with the debug pipeline bound (debugRaygen.rgen:22-40): one primary ray through the centre of every
+ * owned pixel of the current tile shard, no RNG and no lens (LensRadius, FocalDistance, BounceCount, SampleCount and TotalSamples
+ * of the uniform are ignored), and the result is STORED, not added: image[pixel] = payload.Color, alpha included; no other pixel
+ * is touched.  Asynchronous on the render stream, like ptx_render; works on a borrower of a shared scene and on a scene with
+ * pending streamed textures (they sample their stand-ins).  PTX_ERROR_INVALID_ARGUMENT: a mode above 7, unknown flag bits,
+ * reserved != 0, LightCount above PTX_MAX_LIGHT_COUNT; PTX_ERROR_NOT_READY: no scene, tree or image, or a shard accumulation buffer
+ * is bound.  ptx_get_stats afterwards: pathSamples = owned pixels, segments = primary rays, shadowRays = occlusion queries
+ * (1 + LightCount per hit pixel, 0 with shadows disabled), retries = 0, lastRenderMs; the other timing fields 0. */
+PTX_API int ptx_render_debug(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, const PtxDebugViewDesc *view);
+/* Function-level entry for the two pieces of arithmetic only this stage has.  which = 0: DDDcomputeLightContribution
+ * (debugClosestHit.rchit:71-141), in: lightDir lightColor attenuation V N color roughness metalness (18 floats), out: rgb;
+ * which = 1: getRandomColor (:143-162), in: x (u32 bits), out: rgb. */
+PTX_API int ptx_test_debug_eval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

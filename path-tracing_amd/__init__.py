@@ -61,6 +61,7 @@ PTX_SYMBOLS = [
     "ptx_trace_rays", "ptx_test_input_stride", "ptx_test_output_stride", "ptx_test_eval", "ptx_test_texture",
     "ptx_postprocess", "ptx_read_output", "ptx_write_accumulation", "ptx_update_animation",
     "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency",
+    "ptx_render_debug", "ptx_test_debug_eval",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -132,6 +133,17 @@ class LightsUbo(C.Structure):
 class PostProcessingUniformData(C.Structure):
     _fields_ = [("TotalSamples", C.c_uint32), ("Exposure", C.c_float), ("BloomThreshold", C.c_float), ("BloomIntensity", C.c_float)]
 
+
+class DebugViewDesc(C.Structure):
+    _fields_ = [("renderMode", C.c_uint32), ("raygenFlags", C.c_uint32), ("hitGroupFlags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# PTX_DEBUG_MODE_* / PTX_DEBUG_RAYGEN_* / PTX_DEBUG_HIT_* of include/ptx.h
+(DEBUG_MODE_COLOR, DEBUG_MODE_WORLD_POSITION, DEBUG_MODE_NORMAL, DEBUG_MODE_TEXTURE_COORDS, DEBUG_MODE_MIPS, DEBUG_MODE_GEOMETRY,
+ DEBUG_MODE_PRIMITIVE, DEBUG_MODE_INSTANCE) = range(8)
+DEBUG_RAYGEN_FORCE_OPAQUE, DEBUG_RAYGEN_CULL_BACK_FACES = 1, 2
+DEBUG_HIT_DISABLE_COLOR_TEXTURE, DEBUG_HIT_DISABLE_NORMAL_TEXTURE, DEBUG_HIT_DISABLE_MIP_MAPS, DEBUG_HIT_DISABLE_SHADOWS = 1, 2, 4, 8
+DEBUG_EVAL_LIGHT_CONTRIBUTION, DEBUG_EVAL_RANDOM_COLOR = 0, 1  # `which` of ptx_test_debug_eval
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -322,6 +334,8 @@ def load_hip() -> C.CDLL:
         lib.ptx_texture_upload.argtypes = [P, C.c_uint32, C.POINTER(TextureDesc)]
         lib.ptx_textures_commit.argtypes = [P, C.POINTER(C.c_uint32)]
         lib.ptx_texture_residency.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.ptx_render_debug.argtypes = [P, C.POINTER(RaygenUniformData), C.POINTER(LightsUbo), C.POINTER(DebugViewDesc)]
+        lib.ptx_test_debug_eval.argtypes = [P, C.c_uint32, P, P, C.c_uint32]
         _hip = lib
     return _hip
 
@@ -499,6 +513,11 @@ class Renderer:
     def render(self, uniform: RaygenUniformData, lights: LightsUbo):
         self._check(self.lib.ptx_render(self.handle, C.byref(uniform), C.byref(lights)))
 
+    def render_debug(self, uniform: RaygenUniformData, lights: LightsUbo, mode: int, raygen_flags: int = 0, hit_flags: int = 0):
+        """ptx_render_debug: one frame of the debug view (DEBUG_MODE_*, DEBUG_RAYGEN_*, DEBUG_HIT_*) STORED into the owned pixels."""
+        view = DebugViewDesc(mode, raygen_flags, hit_flags, 0)
+        self._check(self.lib.ptx_render_debug(self.handle, C.byref(uniform), C.byref(lights), C.byref(view)))
+
     def render_frames(self, uniform: RaygenUniformData, lights: LightsUbo, first_frame: int, frames: int):
         self._check(self.lib.ptx_render_frames(self.handle, C.byref(uniform), C.byref(lights), first_frame, frames))
 
@@ -593,6 +612,13 @@ class Renderer:
         inputs = np.ascontiguousarray(inputs).view(np.uint32).reshape(-1, nin)
         out = np.zeros((inputs.shape[0], nout), np.uint32)
         self._check(self.lib.ptx_test_eval(self.handle, fn, inputs.ctypes.data, out.ctypes.data, inputs.shape[0]))
+        return out
+
+    def test_debug_eval(self, which: int, inputs: np.ndarray) -> np.ndarray:
+        """ptx_test_debug_eval: DEBUG_EVAL_LIGHT_CONTRIBUTION (rows of 18 floats) or DEBUG_EVAL_RANDOM_COLOR (uint32 ids) -> rgb bits."""
+        inputs = np.ascontiguousarray(inputs).view(np.uint32).reshape(-1, 18 if which == DEBUG_EVAL_LIGHT_CONTRIBUTION else 1)
+        out = np.zeros((inputs.shape[0], 3), np.uint32)
+        self._check(self.lib.ptx_test_debug_eval(self.handle, which, inputs.ctypes.data, out.ctypes.data, inputs.shape[0]))
         return out
 
 

@@ -406,9 +406,24 @@ PT_DEV f3 fastInverse(f3 d) { return F3(__builtin_amdgcn_rcpf(d.x), __builtin_am
 // smaller (pair, prim), i.e. the smaller global triangle id -- independent of tree shape.
 // STATS: counts node visits and triangle tests (two for a pair leaf), and with stackDepth the deepest stack position the walk
 // reached (entries held at once, counted on past the capacity of the stack: a walk that overflowed reports more than it can hold).
-template <bool ANY_HIT, bool STATS = false, bool ALPHA = false>
+// CULL_BACK (gl_RayFlagsCullBackFacingTrianglesEXT, the debug view's primary ray): a back-facing triangle is no candidate at all -- it
+// neither shortens the ray nor reaches the any-hit stage.  Facing is decided in the space of the model's acceleration structure
+// (no flip-facing flag, AccelerationStructure.cpp:273): back-facing iff dot(cross(p1 - p0, p2 - p0), d) > 0 there.  On the world-space
+// edges of a Tri that is the same sign test times the sign of the determinant of the instance's linear part
+// (cross(A a, A b) . A d = det A * cross(a, b) . d), which pairIds carries per (instance, mesh) pair (kDebugPairMirrored).
+struct DebugPair
+{
+    uint32_t instance; // gl_InstanceID: index of the PtxModelInstance
+    uint32_t geometry; // gl_GeometryIndexEXT: record index - Model.MeshOffset (AccelerationStructure.cpp:270-274)
+    uint32_t flags;    // kDebugPairMirrored
+};
+static_assert(sizeof(DebugPair) == 12, "DebugPair is 12 B");
+constexpr uint32_t kDebugPairMirrored = 1u; // the instance's linear part has a negative determinant
+
+template <bool ANY_HIT, bool STATS = false, bool ALPHA = false, bool CULL_BACK = false>
 PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, Stack &st, Hit &best, uint32_t *nodeVisits = nullptr,
-                     uint32_t *triTests = nullptr, Decal *decalOut = nullptr, uint32_t *stackDepth = nullptr)
+                     uint32_t *triTests = nullptr, Decal *decalOut = nullptr, uint32_t *stackDepth = nullptr,
+                     const DebugPair *pairIds = nullptr)
 {
     Decal decal = noDecal();
     if (ALPHA && decalOut)
@@ -473,6 +488,8 @@ PT_DEV bool traceRay(const TraceScene &sc, f3 o, f3 d, float tmin, float tmax, S
                 const float4 ta = tp->a, tb = tp->b, tc = tp->c;
                 float t, u, v;
                 if (intersectTri(F3(ta.x, ta.y, ta.z), F3(ta.w, tb.x, tb.y), F3(tb.z, tb.w, tc.x), o, d, tmin, tmax, t, u, v) &&
+                    (!CULL_BACK || !((dot(cross(F3(ta.w, tb.x, tb.y), F3(tb.z, tb.w, tc.x)), d) > 0.0f) !=
+                                     ((pairIds[__float_as_uint(tc.y)].flags & kDebugPairMirrored) != 0u))) &&
                     (!ALPHA || !(__float_as_uint(tc.w) & kTriNonOpaque) ||
                      anyHitKeeps<ANY_HIT>(sc, __float_as_uint(tc.y), __float_as_uint(tc.z), leafSlot, __float_as_uint(tc.w), t, u, v, decal)))
                 {

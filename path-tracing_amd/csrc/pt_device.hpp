@@ -1440,14 +1440,18 @@ PT_DEV f4 sampleCube(const TextureView &tv, const DevTexture *faces, f3 r)
     return sampleFaceSeamless(tv, faces, face, u, v);
 }
 
+// texture(skybox2D, texCoords).xyz of miss.rmiss:18-29 / debugMiss.rmiss:20-29: the equirectangular lookup itself
+PT_DEV f3 skybox2DLookup(const SceneView &sv, f3 rayDir)
+{
+    const f2 uv = missSkyboxTexCoords(rayDir);
+    return rgb(sampleLevel(sv.tex, sv.tex.textures[sv.tex.textureCount], 0, uv.x, uv.y));
+}
+
 // payload.Emissive of miss.rmiss:16-39 (Pdf = -1 is the caller's path termination)
 PT_DEV f3 missEmissive(const SceneView &sv, f3 rayDir)
 {
     if (sv.skyKind == PTX_SKYBOX_2D)
-    {
-        const f2 uv = missSkyboxTexCoords(rayDir);
-        return hdrToLdr(rgb(sampleLevel(sv.tex, sv.tex.textures[sv.tex.textureCount], 0, uv.x, uv.y)));
-    }
+        return hdrToLdr(skybox2DLookup(sv, rayDir));
     if (sv.skyKind == PTX_SKYBOX_CUBE)
         return rgb(sampleCube(sv.tex, sv.tex.textures + sv.tex.textureCount, rayDir));
     return F3(0.08f, 0.09f, 0.1f);
@@ -1528,8 +1532,11 @@ PT_DEV MaterialSample unknownMaterial()
     return ret;
 }
 
+// defaultColorTexture / defaultNormalTexture: HitGroupFlagsDisableColorTexture / ...NormalTexture of the debug pipeline -- the slot
+// reads the default texture's index instead of the material's (material.glsl:69-70, :93-94, :122-123)
 template <bool TEX>
-PT_DEV MaterialSample sampleMaterial(const SceneView &sv, uint32_t materialId, f2 texCoords, f4 derivatives, bool isHitFromInside) // :144-171
+PT_DEV MaterialSample sampleMaterial(const SceneView &sv, uint32_t materialId, f2 texCoords, f4 derivatives, bool isHitFromInside,
+                                     bool defaultColorTexture = false, bool defaultNormalTexture = false) // :144-171
 {
     const uint32_t materialType = materialId & 0xffu;
     const uint32_t materialIndex = materialId >> 8;
@@ -1555,6 +1562,10 @@ PT_DEV MaterialSample sampleMaterial(const SceneView &sv, uint32_t materialId, f
         {
             i0 = ph->EmissiveIdx; i1 = ph->ColorIdx; i2 = ph->NormalIdx; i3 = ph->SpecularIdx; i4 = ph->ShininessIdx;
         }
+        if (defaultColorTexture)
+            i1 = PTX_DEFAULT_COLOR_TEXTURE_INDEX;
+        if (defaultNormalTexture)
+            i2 = PTX_DEFAULT_NORMAL_TEXTURE_INDEX;
         MaterialTexels t;
         if (TEX)
         {

@@ -16,6 +16,7 @@
 
 #include "pt_aux_kernels.hpp"
 #include "pt_bvh_build.hpp"
+#include "pt_debug_view.hpp"
 #include "pt_post.hpp"
 
 // =====================================================================================
@@ -164,6 +165,7 @@ struct SceneData
     DevBuf<PtxPhongMaterial> phong;
     DevBuf<DevPair> pairs;
     DevBuf<uint32_t> pairFirst;
+    DevBuf<DebugPair> debugPairs; // per pair: instance, geometry index inside the model, mirrored (the debug view's ids and face culling)
     DevBuf<DevTexture> renderTextures; // what the render kernels sample: every texel decoded to four floats, one pool
     DevBuf<float4> renderTexels;
     // what the any-hit stages read (scenes with non-opaque geometry; pt_bvh.hpp, hitAlpha)
@@ -177,6 +179,7 @@ struct SceneData
     std::vector<DevPair> hostPairs;            // to recompose pair transforms when instances move
     std::vector<uint32_t> pairInstance;        // pair -> instance
     std::vector<PtxTransform> pairMeshTransform; // pair -> baked mesh transform
+    std::vector<DebugPair> hostDebugPairs;     // to refresh the mirrored flags when instances move
     uint32_t instanceCount = 0, skinnedCount = 0, boneCount = 0;
     uint64_t staticVertexCount = 0;
     DevBuf<PtxAnimatedVertex> animatedVertices;
@@ -309,6 +312,7 @@ struct PtxRenderer
     uint32_t pendingBounces = 0, pendingTailBelow = 0, pendingSlots = 0;
     uint64_t pendingEpoch = 0;
     uint32_t pendingDeadSlots = 0; // slots of ragged edge tiles outside the image: in the first queue, not rays
+    bool pendingDebugView = false; // the launch to collect is a ptx_render_debug: its counters are the kernel's own, no bounce schedule
     bool pendingVerbose = false;
     std::vector<uint32_t> hintActive; // queue length per bounce of the last canonical launch: sizes the grids of the next one
     uint32_t hintSlots = 0, hintBounces = 0;
@@ -691,6 +695,14 @@ static TraceScene makeTraceScene(const PtxRenderer *r)
     return sc;
 }
 
+// Does the linear part of a mat3x4 have a negative determinant (an instance that mirrors its model)?
+static bool transformMirrors(const float *m)
+{
+    const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
+                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
+    return det < 0.0;
+}
+
 #include "pt_scene_host.hpp" // ptx_share_scene and ptx_scene_upload: shareScene, sceneUpload and its stages
 
 #include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
@@ -716,9 +728,13 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
             DevPair &pr = r->scene.hostPairs[p];
             composeTransform(instanceTransforms[r->scene.pairInstance[p]].m, r->scene.pairMeshTransform[p].m, pr.M);
             inverseLinear(pr.M, pr.Rinv);
+            r->scene.hostDebugPairs[p].flags = transformMirrors(instanceTransforms[r->scene.pairInstance[p]].m) ? kDebugPairMirrored : 0u;
         }
         if (!r->scene.hostPairs.empty())
+        {
             HIP_TRY(r, hipMemcpyAsync(r->scene.pairs.p, r->scene.hostPairs.data(), r->scene.hostPairs.size() * sizeof(DevPair), hipMemcpyHostToDevice, r->stream));
+            HIP_TRY(r, hipMemcpyAsync(r->scene.debugPairs.p, r->scene.hostDebugPairs.data(), r->scene.hostDebugPairs.size() * sizeof(DebugPair), hipMemcpyHostToDevice, r->stream));
+        }
     }
     if (boneTransforms && r->scene.skinnedCount)
     {
@@ -966,6 +982,14 @@ static int collectRender(PtxRenderer *r)
         return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
     if (h[C_OVERFLOW + 1])
         return fail(r, PTX_ERROR_DEVICE, "ptx_render: %u paths never produced a finite sample in %u attempts", h[C_OVERFLOW + 1], kMaxSampleRetries);
+    if (r->pendingDebugView)
+    {
+        r->pendingDebugView = false;
+        r->stats.segments = h[C_SEGMENTS];
+        r->stats.shadowRays = h[C_HITS];
+        r->stats.pathSamples = h[C_SAMPLES];
+        return PTX_OK;
+    }
     unsigned long long waveSegments = 0;
     std::memcpy(&waveSegments, &h[C_WAVE_SEGMENTS], sizeof(waveSegments));
     waveSegments -= r->pendingDeadSlots; // k_prologue counted the whole first queue
@@ -1206,6 +1230,95 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
     r->pendingEpoch = sceneOf(r)->sceneEpoch;
     r->pendingDeadSlots = p.numSlots - p.ownedPixels * frames;
     r->pendingVerbose = r->env.verbose;
+    return PTX_OK;
+}
+
+// ptx_render_debug: RecordPathTracingCommands with the debug pipeline bound (pt_debug_view.hpp).  One launch, enqueued like
+// a wavefront launch: the counter block comes back with collectRender.
+static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, const PtxDebugViewDesc *view)
+{
+    if (!r || !uniform || !lights || !view)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: null argument");
+    if (view->renderMode > PTX_DEBUG_MODE_INSTANCE || (view->raygenFlags & ~(PTX_DEBUG_RAYGEN_FORCE_OPAQUE | PTX_DEBUG_RAYGEN_CULL_BACK_FACES)) != 0u ||
+        (view->hitGroupFlags & ~(PTX_DEBUG_HIT_DISABLE_COLOR_TEXTURE | PTX_DEBUG_HIT_DISABLE_NORMAL_TEXTURE | PTX_DEBUG_HIT_DISABLE_MIP_MAPS | PTX_DEBUG_HIT_DISABLE_SHADOWS)) != 0u ||
+        view->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: render mode %u, raygen flags 0x%x, hit group flags 0x%x, reserved %u", view->renderMode,
+                    view->raygenFlags, view->hitGroupFlags, view->reserved);
+    if (!sceneUsable(r) || !imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_render_debug: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
+    if (r->boundShard)
+        return frameIsElsewhere(r, "ptx_render_debug");
+    if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: LightCount %u exceeds MaxLightCount", lights->LightCount);
+    HIP_TRY(r, hipSetDevice(r->device));
+    {
+        const int rcPrev = collectRender(r); // statistics / errors of the previous launch; the counter block is reused below
+        if (rcPrev != PTX_OK)
+            return rcPrev;
+    }
+    if (const int rcCommit = waitForCommits(r))
+        return rcCommit;
+
+    const LaunchParams p = makeParams(r, uniform, 0, 1);
+    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, r->lights.p);
+    HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
+    r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = 0;
+    r->stats.traceLaunches = 0;
+    r->stats.tracedRays = 0;
+    r->stats.lastTraceMs = 0.0;
+    r->stats.lastShadeMs = r->stats.lastShadowMs = r->stats.lastTailMs = 0.0;
+    HIP_TRY(r, hipEventRecord(r->evA, r->stream));
+    if (p.slotsPerFrame)
+    {
+        const SceneView sv = makeSceneView(r);
+        const TraceScene sc = makeTraceScene(r);
+        const DebugPair *pairIds = sceneOf(r)->scene.debugPairs.p;
+        DebugView dv;
+        dv.renderMode = view->renderMode; dv.raygenFlags = view->raygenFlags; dv.hitGroupFlags = view->hitGroupFlags;
+        // at most kMaxPersistentThreads threads: the global part of the traversal stack is sized for that many
+        const dim3 grid(gridFor(p.slotsPerFrame, kBlock, kMaxPersistentThreads / kBlock));
+        const int mode = kernelMode(r);
+        const bool cull = (view->raygenFlags & PTX_DEBUG_RAYGEN_CULL_BACK_FACES) != 0u;
+#define PT_LAUNCH_DEBUG_VIEW(M)                                                                                            \
+    do                                                                                                                     \
+    {                                                                                                                      \
+        if (cull)                                                                                                          \
+            k_debug_view<M, true><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->counters.p, r->spill.p);  \
+        else                                                                                                               \
+            k_debug_view<M, false><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->counters.p, r->spill.p); \
+    } while (0)
+        if (mode == 2)
+            PT_LAUNCH_DEBUG_VIEW(2);
+        else if (mode == 1)
+            PT_LAUNCH_DEBUG_VIEW(1);
+        else
+            PT_LAUNCH_DEBUG_VIEW(0);
+#undef PT_LAUNCH_DEBUG_VIEW
+    }
+    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+    HIP_TRY(r, hipGetLastError());
+    r->statsPending = true;
+    r->pendingDebugView = true;
+    r->outputReady = false;
+    return PTX_OK;
+}
+
+static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
+{
+    if (!r || which > 1u || !in || !out)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_test_debug_eval: bad argument");
+    if (!n)
+        return PTX_OK;
+    HIP_TRY(r, hipSetDevice(r->device));
+    const size_t ni = (size_t)n * (which == 0u ? 18u : 1u), no = (size_t)n * 3u;
+    HIP_TRY(r, r->testIn.alloc(ni));
+    HIP_TRY(r, r->testOut.alloc(no));
+    HIP_TRY(r, hipMemcpyAsync(r->testIn.p, in, ni * 4, hipMemcpyHostToDevice, r->stream));
+    k_test_debug_eval<<<(n + 63) / 64, 64, 0, r->stream>>>(which, r->testIn.p, r->testOut.p, n);
+    HIP_TRY(r, hipMemcpyAsync(out, r->testOut.p, no * 4, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
     return PTX_OK;
 }
 

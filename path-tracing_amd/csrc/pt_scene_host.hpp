@@ -143,6 +143,7 @@ struct FlatScene
 {
     std::vector<DevPair> pairs;
     std::vector<uint32_t> pairFirst, pairInstance;
+    std::vector<DebugPair> debugPairs; // the ids and the winding the debug view shows per pair (pt_debug_view.hpp)
     std::vector<uint32_t> skinSource; // output vertex -> animated vertex (AnimatedVertexMapBuffer)
     std::vector<PtxTransform> pairMeshTransform;
     uint64_t triangles = 0;
@@ -178,6 +179,9 @@ static int flattenScene(PtxRenderer *r, const PtxSceneDesc *s, FlatScene &flat)
                     flat.skinSource.push_back(geo.VertexOffset + v);
             }
             flat.pairInstance.push_back(i);
+            // gl_InstanceID / gl_GeometryIndexEXT of the pair, and whether the instance mirrors: the TLAS instance carries
+            // inst.Transform alone (AccelerationStructure.cpp:271), the mesh transform is baked into the BLAS
+            flat.debugPairs.push_back(DebugPair{ i, k, transformMirrors(inst.Transform.m) ? kDebugPairMirrored : 0u });
             flat.pairMeshTransform.push_back(s->transforms[rec.TransformIndex]);
             pr.materialId = rec.MaterialId;
             pr.flags = (geo.IsOpaque ? 0u : kPairNonOpaque) | (materialSamplesSceneTexture(s, rec.MaterialId) ? kPairTextured : 0u);
@@ -389,6 +393,7 @@ static int uploadGeometry(PtxRenderer *r, const PtxSceneDesc *s, FlatScene &flat
     sc.pairCount = static_cast<uint32_t>(flat.pairs.size()); sc.triCount = static_cast<uint32_t>(flat.triangles);
     sc.anyNonOpaque = flat.anyNonOpaque; sc.mixedMaterialTypes = flat.mixedMaterialTypes; sc.mixedTextured = flat.mixedTextured;
     sc.hostPairs = flat.pairs; sc.pairInstance = std::move(flat.pairInstance); sc.pairMeshTransform = std::move(flat.pairMeshTransform);
+    sc.hostDebugPairs = flat.debugPairs;
     sc.instanceCount = s->instanceCount; sc.staticVertexCount = s->vertexCount; sc.dxNormalTextures = s->dxNormalTextures;
     sc.skinnedCount = static_cast<uint32_t>(flat.skinSource.size()); sc.boneCount = 0;
     // bind pose of every skinned copy (OutBindPoseAnimatedVertices)
@@ -414,6 +419,7 @@ static int uploadGeometry(PtxRenderer *r, const PtxSceneDesc *s, FlatScene &flat
     if ((rc = upload(r, sc.sg, s->specularGlossinessMaterials, s->specularGlossinessMaterialCount)) != PTX_OK) return rc;
     if ((rc = upload(r, sc.phong, s->phongMaterials, s->phongMaterialCount)) != PTX_OK) return rc;
     if ((rc = upload(r, sc.pairs, flat.pairs.data(), flat.pairs.size())) != PTX_OK) return rc;
+    if ((rc = upload(r, sc.debugPairs, flat.debugPairs.data(), flat.debugPairs.size())) != PTX_OK) return rc;
     return upload(r, sc.pairFirst, flat.pairFirst.data(), flat.pairFirst.size());
 }
 

@@ -138,6 +138,16 @@ int ptx_render_frames(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
     return renderImpl(r, &u, lights, firstFrame, frames);
 }
 
+int ptx_render_debug(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, const PtxDebugViewDesc *view)
+{
+    return renderDebug(r, uniform, lights, view);
+}
+
+int ptx_test_debug_eval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
+{
+    return testDebugEval(r, which, in, out, n);
+}
+
 int ptx_synchronize(PtxRenderer *r)
 {
     if (!r)

@@ -11,6 +11,8 @@ RendererHip::PathTracingSettings s_PathTracingSettings;
 uint32_t s_SamplesPerFrame = 1;
 uint32_t s_TotalSamples = 0;
 uint32_t s_Width = 0, s_Height = 0;
+bool s_DebugPipeline = false; // s_ActiveRaytracingPipeline == the debug pipeline (Renderer.cpp:579-610)
+PtxDebugViewDesc s_DebugView = { PTX_DEBUG_MODE_COLOR, 0u, 0u, 0u };
 }
 
 void RendererHip::Check(int status)
@@ -100,12 +102,34 @@ void RendererHip::Render()
     rgenData.TotalSamples = s_TotalSamples;
     s_TotalSamples += s_SamplesPerFrame;
     const PtxLightsUbo lights = s_Scene->GetLightsUbo();
+    if (s_DebugPipeline) // the debug raygen stores its one sample: nothing accumulates
+    {
+        s_TotalSamples = 0;
+        Check(ptx_render_debug(s_Renderer, &rgenData, &lights, &s_DebugView));
+        return;
+    }
     Check(ptx_render(s_Renderer, &rgenData, &lights));
 }
 
+// Renderer.cpp:579-610 / :769-772
+void RendererHip::SetDebugRaytracingPipeline(uint32_t renderMode, uint32_t raygenFlags, uint32_t hitGroupFlags)
+{
+    s_DebugPipeline = true;
+    s_DebugView = { renderMode, raygenFlags, hitGroupFlags, 0u };
+}
+
+void RendererHip::SetPathTracingPipeline()
+{
+    if (!s_DebugPipeline)
+        return;
+    s_DebugPipeline = false;
+    ResetAccumulationImage(); // the image holds a debug frame, not a running sum
+}
+
+// Renderer.cpp:1697-1711: a debug frame is post-processed as one sample
 uint32_t RendererHip::GetTotalSamples()
 {
-    return s_TotalSamples;
+    return s_DebugPipeline ? 1u : s_TotalSamples;
 }
 
 static RendererHip::PostProcessSettings s_PostProcessSettings;

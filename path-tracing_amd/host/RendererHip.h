@@ -38,6 +38,11 @@ public:
     // Renderer::Render (Renderer.cpp:1659-1809): uniform fill + one path-tracing launch.
     static void Render();
     static void ResetAccumulationImage();
+    // Renderer::SetDebugRaytracingPipeline (Renderer.cpp:579-610, :769-772): from now on Render() draws the debug view
+    // (ptx_render_debug: PTX_DEBUG_MODE_*, PTX_DEBUG_RAYGEN_*, PTX_DEBUG_HIT_*), GetTotalSamples() is 1 and SaveOutput
+    // post-processes the frame as one sample (Renderer.cpp:1697-1711).  SetPathTracingPipeline switches back and resets the accumulation.
+    static void SetDebugRaytracingPipeline(uint32_t renderMode, uint32_t raygenFlags = 0, uint32_t hitGroupFlags = 0);
+    static void SetPathTracingPipeline();
 
     // Renderer::PostProcessSettings (Renderer.h:68-75) / RenderSettings::Output
     struct PostProcessSettings
