@@ -1,6 +1,7 @@
 // pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle, its device buffers, scene
-// upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the bounce schedule of the wavefront backend, read-back, the output
-// stage.  Functions here take a valid handle; include/ptx.h's entry points (ptx_capi.hip) are thin wrappers around them.
+// upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the render launches with the bounce schedule
+// of the wavefront backend (pt_render_host.hpp), read-back, the output stage.  Functions here take a valid handle; include/ptx.h's
+// entry points (ptx_capi.hip) are thin wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
@@ -194,6 +195,55 @@ struct SceneData
     std::shared_ptr<struct TextureStreaming> streaming;
 };
 
+// Per-slot state of the paths in flight (the Wavefront of pt_wavefront.hpp, owned), grown by ensureSlots (pt_render_host.hpp).
+struct PathState
+{
+    DevBuf<float4> rayO, rayD, thr, rad, hit, shO, shD, shC, slotRad;
+    DevBuf<uint4> meta;
+    DevBuf<uint32_t> hitPair, queue0, queue1, shadowQueue, restartQueue;
+    DevBuf<uint8_t> shadowResult;
+    DevBuf<float4> diffs; // three planes of ray differentials, only for scenes with textures (kernel mode >= 1)
+    DevBuf<float4> decal; DevBuf<float> decalT; // nearest ignored any-hit candidate and its distance, only for non-opaque geometry (mode 2)
+    Wavefront view(int mode, uint32_t *counters, uint32_t *spill) const
+    {
+        Wavefront wf;
+        wf.rayO = rayO.p; wf.rayD = rayD.p; wf.thr = thr.p; wf.rad = rad.p;
+        wf.meta = meta.p; wf.hit = hit.p; wf.hitPair = hitPair.p;
+        wf.shO = shO.p; wf.shD = shD.p; wf.shC = shC.p; wf.slotRad = slotRad.p;
+        wf.queue[0] = queue0.p; wf.queue[1] = queue1.p; wf.shadowQueue = shadowQueue.p; wf.shadowResult = shadowResult.p;
+        wf.restartQueue = restartQueue.p;
+        for (int k = 0; k < 3; k++)
+            wf.diff[k] = mode >= 1 ? diffs.p + (size_t)k * (diffs.n / 3) : nullptr; // the three planes lie one stride apart
+        wf.decal = mode == 2 ? decal.p : nullptr;
+        wf.decalT = mode == 2 ? decalT.p : nullptr;
+        wf.counters = counters;
+        wf.spill = spill;
+        return wf;
+    }
+};
+
+// What the last launch left for ptx_get_stats / the next launch to pick up once the device is done (collectRender).
+struct PendingLaunch
+{
+    enum Kind { kNone, kWavefront, kDebugView } kind = kNone; // kDebugView: a ptx_render_debug, whose counters are the kernel's own
+    uint32_t bounces = 0, tailBelow = 0, slots = 0; // slots: 0 for a launch that is not canonical, it teaches no hint
+    uint32_t deadSlots = 0; // slots of ragged edge tiles outside the image: in the first queue, not rays
+    uint64_t epoch = 0;     // sceneEpoch of the scene it rendered
+    bool verbose = false;
+};
+
+// The bounce schedule learnt from the last canonical launch: sizes the grids of the next one of the same shape on the same scene.
+struct BounceStep { uint32_t bounce, est; int tail; }; // one bounce of a hinted round (hintedSchedule, enqueueBounce)
+struct ScheduleHint
+{
+    std::vector<uint32_t> active; // queue length per bounce
+    std::vector<BounceStep> steps; // the round laid out for the launch that uses the hint
+    uint32_t slots = 0, bounces = 0;
+    uint64_t epoch = 0; // sceneEpoch of the scene the hint was learnt on
+    bool matches(uint32_t s, uint32_t b, uint64_t e) const { return slots == s && bounces == b && epoch == e && !active.empty(); }
+    void forget() { slots = 0u; } // (no launch has 0 slots: the next one is driven from the host and learns again)
+};
+
 struct PtxRenderer
 {
     EnvSwitches env;
@@ -243,9 +293,6 @@ struct PtxRenderer
     TreeParams tree;            // of the tree in use; the per-frame rebuilds of an animation build with them again
     bool reinsertBroken = false; // a reinsertion pass once left something that was not a tree (k_tree_check): off for this handle
     uint32_t residentClosest[2] = { 0, 0 }, residentShadow[2] = { 0, 0 }; // blocks the chip holds at once, per [ALPHA] variant
-    DevBuf<float4> decal;
-    DevBuf<float> decalT;
-    size_t decalCapacity = 0;
     uint32_t treeTris = 0; // scene.triCount minus the zero-area triangles, which are not in the tree
     bool sceneReady = false, accelReady = false;
     // ptx_share_scene: this renderer renders the scene and tree of `sceneOwner` instead of holding copies (frames in flight
@@ -281,13 +328,8 @@ struct PtxRenderer
     bool copyInFlight = false;
 
     // wavefront state
-    size_t slotCapacity = 0;
-    DevBuf<float4> rayO, rayD, thr, rad, hit, shO, shD, shC, slotRad;
-    DevBuf<float4> diffs; // 3 x slotCapacity ray differentials, only for scenes with textures
-    size_t diffCapacity = 0;
-    DevBuf<uint4> meta;
-    DevBuf<uint32_t> hitPair, queue0, queue1, shadowQueue, restartQueue, counters, spill;
-    DevBuf<uint8_t> shadowResult;
+    PathState paths;
+    DevBuf<uint32_t> counters, spill; // the counter block (enum Counter) and the traversal-stack overflow region of the main stream
     uint32_t *hostCounters = nullptr; // pinned
 
     DevBuf<float> testIn, testOut;
@@ -295,7 +337,7 @@ struct PtxRenderer
 
     hipEvent_t evA = nullptr, evB = nullptr, evT0 = nullptr, evT1 = nullptr; // render / build span; ptx_trace_rays kernel span
 
-    // bounce schedule of the wavefront backend (renderImpl): closest + shade on `stream`, shadow + tail on `auxStream`
+    // bounce schedule of the wavefront backend (pt_render_host.hpp): closest + shade on `stream`, shadow + tail on `auxStream`
     hipStream_t auxStream = nullptr;
     bool auxIsMain = false; // single-stream handle: auxStream is `stream` itself
     bool singleStream = false; // PtxDeviceDesc.flags & PTX_DEVICE_SINGLE_STREAM
@@ -307,16 +349,8 @@ struct PtxRenderer
         hipEvent_t x0 = nullptr, x1 = nullptr, x2 = nullptr; // auxStream: before shadow, after shadow, after tail
     };
     std::vector<BounceEvents> bounceEvents; // [min(BounceCount, kMaxTimedBounces)], reused cyclically beyond
-    // what the last launch left for ptx_get_stats / the next launch to pick up once the device is done
-    bool statsPending = false;
-    uint32_t pendingBounces = 0, pendingTailBelow = 0, pendingSlots = 0;
-    uint64_t pendingEpoch = 0;
-    uint32_t pendingDeadSlots = 0; // slots of ragged edge tiles outside the image: in the first queue, not rays
-    bool pendingDebugView = false; // the launch to collect is a ptx_render_debug: its counters are the kernel's own, no bounce schedule
-    bool pendingVerbose = false;
-    std::vector<uint32_t> hintActive; // queue length per bounce of the last canonical launch: sizes the grids of the next one
-    uint32_t hintSlots = 0, hintBounces = 0;
-    uint64_t hintEpoch = 0;  // sceneEpoch of the scene the hint was learnt on
+    PendingLaunch pending;
+    ScheduleHint hint;
     uint64_t sceneEpoch = 1; // bumped by every upload and full build of THIS handle's scene (a refit keeps it: the poses of
                              // an animation differ little from frame to frame)
     PtxStats stats = {};
@@ -751,558 +785,7 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
     return buildAccel(r, refit, true);
 }
 
-
-static int ensureSlots(PtxRenderer *r, size_t slots)
-{
-    if (kernelMode(r) >= 1 && r->diffCapacity < std::max(slots, r->slotCapacity))
-    {
-        HIP_TRY(r, r->diffs.alloc(3 * std::max(slots, r->slotCapacity)));
-        r->diffCapacity = std::max(slots, r->slotCapacity);
-    }
-    if (kernelMode(r) == 2 && r->decalCapacity < std::max(slots, r->slotCapacity))
-    {
-        HIP_TRY(r, r->decal.alloc(std::max(slots, r->slotCapacity)));
-        HIP_TRY(r, r->decalT.alloc(std::max(slots, r->slotCapacity)));
-        r->decalCapacity = std::max(slots, r->slotCapacity);
-    }
-    if (slots <= r->slotCapacity)
-        return PTX_OK;
-    HIP_TRY(r, r->slotRad.alloc(slots));
-    HIP_TRY(r, r->rayO.alloc(slots)); HIP_TRY(r, r->rayD.alloc(slots)); HIP_TRY(r, r->thr.alloc(slots)); HIP_TRY(r, r->rad.alloc(slots));
-    HIP_TRY(r, r->hit.alloc(slots)); HIP_TRY(r, r->shO.alloc(slots)); HIP_TRY(r, r->shD.alloc(slots)); HIP_TRY(r, r->shC.alloc(slots));
-    HIP_TRY(r, r->meta.alloc(slots)); HIP_TRY(r, r->hitPair.alloc(slots));
-    HIP_TRY(r, r->queue0.alloc(slots)); HIP_TRY(r, r->queue1.alloc(slots)); HIP_TRY(r, r->shadowQueue.alloc(slots)); HIP_TRY(r, r->shadowResult.alloc(slots));
-    HIP_TRY(r, r->restartQueue.alloc(slots));
-    r->slotCapacity = slots;
-    return PTX_OK;
-}
-
-__global__ void k_upload_lights(PtxLightsUbo lights, PtxLightsUbo *dst) // 3,120 bytes as a kernel argument: no staging buffer to keep alive
-{
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&lights);
-    uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-    for (uint32_t i = threadIdx.x; i < sizeof(PtxLightsUbo) / 4; i += blockDim.x)
-        d[i] = src[i];
-}
-
-static int ensureRenderResources(PtxRenderer *r, uint32_t bounces)
-{
-    if (!r->auxStream)
-    {
-    {
-        // PTX_DEVICE_SINGLE_STREAM (or PTX_SINGLE_STREAM=1 in the environment): the shadow and tail kernels ride on the main stream
-        // too -- no overlap inside a frame, one hardware queue per frame in flight instead of two (twice the frames on the same
-        // queues; what a rank's thin tile shard of an N-GPU job wants, include/ptx.h)
-        if (r->env.singleStream || r->singleStream)
-        {
-            r->auxStream = r->stream;
-            r->auxIsMain = true;
-        }
-        else
-            HIP_TRY(r, createStreamOn(&r->auxStream, r->auxXcds, r->device));
-    }
-        HIP_TRY(r, r->spillAux.alloc((size_t)kGlobalSpill * kMaxPersistentThreads));
-    }
-    const size_t want = bounces < (uint32_t)kMaxTimedBounces ? bounces : (uint32_t)kMaxTimedBounces;
-    while (r->bounceEvents.size() < want)
-    {
-        PtxRenderer::BounceEvents e;
-        for (hipEvent_t *ev : { &e.t0, &e.t1, &e.t2, &e.x0, &e.x1, &e.x2 })
-            HIP_TRY(r, hipEventCreate(ev));
-        r->bounceEvents.push_back(e);
-    }
-    return PTX_OK;
-}
-
-// What the kernels of one launch share.
-struct RenderPlan
-{
-    LaunchParams p;
-    SceneView sv;
-    TraceScene sc;
-    int mode;           // kernelMode()
-    uint32_t bounces;   // BounceCount
-    uint32_t tailBelow; // queues of at most this many paths are finished by k_tail
-    uint32_t sortShade; // material-sorted shade queue (scenes that mix material types; PTX_SHADE_SORT=0 / 1 overrides)
-    Wavefront wf, wfAux;
-};
-
-// One BOUNCE of the wavefront over queue `qin` (length in the counter block, at most `est`), enqueued without waiting
-// for the device: every kernel reads its queue length from the counter block (BounceCtl).
-//
-//   stream     P(b)  closest(b)  [wait aux(b-1)]  shade(b)                      P(b+1) closest(b+1) ...
-//   auxStream                                     [wait shade(b)] shadow(b) [tail(b)]
-//
-// shadow(b) only adds into rad[slot], which shade(b + 1) reads -- not closest(b + 1) -- so it runs beside the next
-// traversal; k_tail, where the schedule has one, follows it in stream order (the NEE adds it continues from have
-// landed): the last shadow query before the tail needs no event of its own.
-// tail: 0 = none, 1 = k_tail takes the queue shade(b) filled if it holds at most pl.tailBelow paths, 2 = takes it whatever
-// its length (nothing is enqueued behind this bounce).
-static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, uint32_t skipBelow, int tail)
-{
-    const bool textured = pl.mode >= 1, alpha = pl.mode == 2;
-    hipStream_t S = r->stream, X = r->auxStream;
-    PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
-    const BounceCtl ctl = { b, skipBelow };
-    const int qout = qin ^ 1;
-    k_prologue<<<1, 1, 0, S>>>(pl.wf, qin, ctl);
-    HIP_TRY(r, hipEventRecord(ev.t0, S));
-    if (alpha)
-        k_trace_closest<true><<<traceGridFor(est, r->residentClosest[1]), kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
-    else
-        k_trace_closest<false><<<traceGridFor(est, r->residentClosest[0]), kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
-    HIP_TRY(r, hipEventRecord(ev.t1, S));
-    if (b > 1) // shade reads rad[slot]: the previous bounce's shadow adds must have landed
-        HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
-    const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
-    if (textured && pl.sortShade)
-        k_shade_sorted<true><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
-    else if (textured)
-        k_shade<true><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
-    else if (pl.sortShade)
-        k_shade_sorted<false><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
-    else
-        k_shade<false><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
-    HIP_TRY(r, hipEventRecord(ev.t2, S));
-    HIP_TRY(r, hipStreamWaitEvent(X, ev.t2, 0));
-    HIP_TRY(r, hipEventRecord(ev.x0, X));
-    if (alpha)
-        k_trace_shadow<true><<<traceGridFor(est, r->residentShadow[1]), kBlock, 0, X>>>(pl.p, pl.sc, pl.wfAux, qout, (int)(b & 1u));
-    else
-        k_trace_shadow<false><<<traceGridFor(est, r->residentShadow[0]), kBlock, 0, X>>>(pl.p, pl.sc, pl.wfAux, qout, (int)(b & 1u));
-    k_apply_shadow<<<gridFor(est, kBlock, 4096u), kBlock, 0, X>>>(pl.p, pl.wfAux, (int)(b & 1u));
-    HIP_TRY(r, hipEventRecord(ev.x1, X));
-    if (tail)
-    {
-        // grid-stride loop; the spill region holds kMaxPersistentThreads.  A hinted schedule (tail == 2) hands the tail
-        // whatever is left, and the hint is last frame's: a view that keeps four times the paths alive still finds a thread
-        // per path (blocks beyond the queue return at once), anything beyond that strides.
-        const uint32_t room = tail == 2 ? 4u * pl.tailBelow : pl.tailBelow;
-        const uint32_t most = est < room ? est : room;
-        const BounceCtl tctl = { b, tail == 2 ? 0xffffffffu : pl.tailBelow };
-        const dim3 grid(gridFor(most, kBlock, kMaxPersistentThreads / kBlock));
-        if (pl.mode == 2)
-            k_tail<2><<<grid, kBlock, 0, X>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qout, tctl);
-        else if (pl.mode == 1)
-            k_tail<1><<<grid, kBlock, 0, X>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qout, tctl);
-        else
-            k_tail<0><<<grid, kBlock, 0, X>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qout, tctl);
-    }
-    HIP_TRY(r, hipEventRecord(ev.x2, X));
-    return PTX_OK;
-}
-
-// One ROUND: the slots listed in queue 0 (ACTIVE0 set by the caller, at most `upperBound`) start at bounce 0 of a sample
-// and are advanced BounceCount times, or until the queue is short enough for k_tail to finish them in one launch.
-//
-// With a hint (queue lengths of the previous canonical launch of this shape) the whole round is enqueued at once: the
-// bounces that ran as wavefront kernels last time, then k_tail for whatever is left -- results do not depend on who
-// finishes a path, only the time does, and collectRender drops a hint that turned out wrong.  No kernel is launched just
-// to find its queue empty, and the host does not wait for the device.
-// Without one (first launch of a shape, rounds of a multi-sample launch) the round is driven bounce by bounce: the host
-// reads the counter block after every shade kernel and decides -- which is also how the hint is learned.
-static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBound, const uint32_t *hint)
-{
-    hipStream_t S = r->stream;
-    uint32_t last = 0;
-    int qin = 0;
-    if (hint)
-    {
-        last = pl.bounces;
-        if (pl.tailBelow)
-            for (uint32_t b = 1; b < pl.bounces && b < (uint32_t)kMaxTimedBounces; b++)
-                if (hint[b + 1] <= pl.tailBelow) // k_tail took the queue of bounce b (or nothing was left of it)
-                {
-                    last = b;
-                    break;
-                }
-        for (uint32_t b = 1; b <= last; b++)
-        {
-            uint32_t est = upperBound; // exact for the first bounce; later ones shrink
-            if (b > 1 && b <= (uint32_t)kMaxTimedBounces)
-            {
-                const uint64_t e = (uint64_t)hint[b] + hint[b] / 4 + 4096;
-                est = e < upperBound ? (uint32_t)e : upperBound;
-            }
-            const int rcb = enqueueBounce(r, pl, b, qin, est, 0u, (b == last && last < pl.bounces) ? 2 : 0);
-            if (rcb != PTX_OK)
-                return rcb;
-            qin ^= 1;
-        }
-    }
-    else
-    {
-        uint32_t est = upperBound;
-        for (uint32_t b = 1; b <= pl.bounces; b++)
-        {
-            const int rcb = enqueueBounce(r, pl, b, qin, est, 0u, 0);
-            if (rcb != PTX_OK)
-                return rcb;
-            last = b;
-            qin ^= 1;
-            HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, S));
-            HIP_TRY(r, hipStreamSynchronize(S));
-            if (r->hostCounters[C_OVERFLOW])
-                return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
-            est = r->hostCounters[qin ? C_ACTIVE1 : C_ACTIVE0];
-            if (est == 0u)
-                break;
-            if (b < pl.bounces && est <= pl.tailBelow)
-            {
-                // the queue is short: k_tail finishes it, behind the shadow kernel of this bounce on its stream
-                PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
-                const BounceCtl tctl = { b, 0xffffffffu };
-                const dim3 grid(gridFor(est, kBlock, kMaxPersistentThreads / kBlock));
-                if (pl.mode == 2)
-                    k_tail<2><<<grid, kBlock, 0, r->auxStream>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qin, tctl);
-                else if (pl.mode == 1)
-                    k_tail<1><<<grid, kBlock, 0, r->auxStream>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qin, tctl);
-                else
-                    k_tail<0><<<grid, kBlock, 0, r->auxStream>>>(pl.p, pl.sv, pl.sc, pl.wfAux, qin, tctl);
-                HIP_TRY(r, hipEventRecord(ev.x2, r->auxStream)); // re-recorded behind the tail: what the stream waits for below
-                break;
-            }
-        }
-    }
-    if (last)
-        HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(last - 1) % r->bounceEvents.size()].x2, 0));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-// Statistics and errors of the last wavefront launch, once the device is done with it (blocks until then).
-static int collectRender(PtxRenderer *r)
-{
-    if (!r->statsPending)
-        return PTX_OK;
-    r->statsPending = false;
-    HIP_TRY(r, hipEventSynchronize(r->evB));
-    const uint32_t *h = r->hostCounters;
-    if (h[C_OVERFLOW])
-        return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
-    if (h[C_OVERFLOW + 1])
-        return fail(r, PTX_ERROR_DEVICE, "ptx_render: %u paths never produced a finite sample in %u attempts", h[C_OVERFLOW + 1], kMaxSampleRetries);
-    if (r->pendingDebugView)
-    {
-        r->pendingDebugView = false;
-        r->stats.segments = h[C_SEGMENTS];
-        r->stats.shadowRays = h[C_HITS];
-        r->stats.pathSamples = h[C_SAMPLES];
-        return PTX_OK;
-    }
-    unsigned long long waveSegments = 0;
-    std::memcpy(&waveSegments, &h[C_WAVE_SEGMENTS], sizeof(waveSegments));
-    waveSegments -= r->pendingDeadSlots; // k_prologue counted the whole first queue
-    r->stats.segments = waveSegments + h[C_SEGMENTS];
-    r->stats.tracedRays = waveSegments;
-    r->stats.shadowRays = h[C_HITS];
-    r->stats.pathSamples = h[C_SAMPLES];
-    r->stats.retries = h[C_RETRIES];
-    // kernel times of the bounces that ran (the others returned at once), from the events around every launch
-    const uint32_t timed = r->pendingBounces < (uint32_t)kMaxTimedBounces ? r->pendingBounces : (uint32_t)kMaxTimedBounces;
-    const uint32_t tailPaths = h[C_TAIL_PATHS], tailBounce = h[C_TAIL_PATHS + 1]; // k_tail took the queue shade(tailBounce) filled
-    for (uint32_t b = 1; b <= timed; b++)
-    {
-        const PtxRenderer::BounceEvents &ev = r->bounceEvents[b - 1];
-        const uint32_t active = h[C_BOUNCE_ACTIVE + b];
-        const bool ran = active != 0u && !(tailPaths && b > tailBounce);
-        if (!ran)
-            continue;
-        float closestMs = 0.0f, shadeMs = 0.0f, shadowMs = 0.0f, tailMs = 0.0f;
-        (void)hipEventElapsedTime(&closestMs, ev.t0, ev.t1);
-        (void)hipEventElapsedTime(&shadeMs, ev.t1, ev.t2);
-        (void)hipEventElapsedTime(&shadowMs, ev.x0, ev.x1);
-        r->stats.lastTraceMs += closestMs;
-        r->stats.lastShadeMs += shadeMs;
-        r->stats.lastShadowMs += shadowMs;
-        r->stats.traceLaunches += 2;
-        if (tailPaths && tailBounce == b)
-        {
-            (void)hipEventElapsedTime(&tailMs, ev.x1, ev.x2);
-            r->stats.lastTailMs += tailMs;
-        }
-        if (r->pendingVerbose)
-        {
-            fprintf(stderr, "[ptx] bounce %u: %u rays closest %.3f ms (%.2f Grays/s) | shade (incl. wait for the previous shadow kernel) %.3f ms | shadow %.3f ms\n",
-                    b, active, closestMs, active / closestMs / 1e6, shadeMs, shadowMs);
-            if (tailMs > 0.0f)
-                fprintf(stderr, "[ptx] tail: %u paths, %u segments, %.3f ms\n", tailPaths, h[C_SEGMENTS], tailMs);
-        }
-    }
-    if (r->pendingVerbose && h[C_RETRIES])
-        fprintf(stderr, "[ptx] %u NaN / Inf sample restarts\n", h[C_RETRIES]);
-    // grid / schedule hints for the next launch of this shape.  The queue k_tail took over is part of them (a truncated
-    // schedule has no prologue behind its last bounce to record it); a tail that had to take more than its threshold
-    // means the hints were off: forget them, the next launch runs the full schedule and learns again.
-    r->hintActive.assign(h + C_BOUNCE_ACTIVE, h + C_BOUNCE_ACTIVE + kMaxTimedBounces + 1);
-    if (tailPaths && tailBounce + 1 <= (uint32_t)kMaxTimedBounces)
-        r->hintActive[tailBounce + 1] = tailPaths;
-    r->hintSlots = tailPaths > r->pendingTailBelow ? 0u : r->pendingSlots;
-    r->hintBounces = r->pendingBounces;
-    r->hintEpoch = r->pendingEpoch;
-    return PTX_OK;
-}
-
-static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, uint32_t firstFrame, uint32_t frames)
-{
-    if (!r || !uniform || !lights)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: null argument");
-    if (!sceneUsable(r) || !imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_render: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
-    if (uniform->SampleCount == 0 || uniform->SampleCount > 0xffffu || uniform->BounceCount > 0xffffu || frames == 0)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: SampleCount must be in [1, 65535], BounceCount <= 65535");
-    if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: LightCount %u exceeds MaxLightCount", lights->LightCount);
-    HIP_TRY(r, hipSetDevice(r->device));
-    {
-        const int rcPrev = collectRender(r); // statistics / errors of the previous launch; the counter block is reused below
-        if (rcPrev != PTX_OK)
-            return rcPrev;
-    }
-    if (const int rcCommit = waitForCommits(r))
-        return rcCommit;
-
-    const LaunchParams p = makeParams(r, uniform, firstFrame, frames);
-    if ((uint64_t)p.slotsPerFrame * frames > 0x7fffffffull)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: too many path slots in one batch");
-    const int rc = ensureSlots(r, p.numSlots);
-    if (rc != PTX_OK)
-        return rc;
-
-    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, r->lights.p);
-    HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
-
-    RenderPlan pl;
-    pl.p = p;
-    pl.sv = makeSceneView(r);
-    pl.mode = kernelMode(r);
-    pl.sc = makeTraceScene(r);
-    pl.bounces = uniform->BounceCount;
-    const SceneView &sv = pl.sv;
-    const TraceScene &sc = pl.sc;
-    const int mode = pl.mode;
-
-    r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = 0;
-    r->stats.traceLaunches = 0;
-    r->stats.tracedRays = 0;
-    r->stats.lastTraceMs = 0.0;
-    r->stats.lastShadeMs = r->stats.lastShadowMs = r->stats.lastTailMs = 0.0;
-    HIP_TRY(r, hipEventRecord(r->evA, r->stream));
-
-    if (p.numSlots == 0)
-    {
-        HIP_TRY(r, hipEventRecord(r->evB, r->stream));
-        return PTX_OK;
-    }
-
-    if (uniform->BounceCount == 0 && r->backend != PTX_BACKEND_MEGAKERNEL)
-    {
-        // raygen.rgen:62: the bounce loop never runs, every sample ends with radiance 0 -- nothing is generated, traced or
-        // shaded (the wavefront kernels test the bounce limit only AFTER a bounce); the image still gets its alpha
-        HIP_TRY(r, hipMemsetAsync(r->slotRad.p, 0, (size_t)p.numSlots * sizeof(float4), r->stream));
-        k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->slotRad.p, accumTarget(r), nullptr, r->boundShard ? 1u : 0u);
-        HIP_TRY(r, hipEventRecord(r->evB, r->stream));
-        HIP_TRY(r, hipGetLastError());
-        r->stats.pathSamples = (uint64_t)p.ownedPixels * frames * uniform->SampleCount;
-        return PTX_OK;
-    }
-
-    if (r->backend == PTX_BACKEND_MEGAKERNEL)
-    {
-        const dim3 grid((p.numSlots + kBlock - 1) / kBlock);
-        if (mode == 2)
-            k_megakernel<2><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, r->slotRad.p, r->counters.p);
-        else if (mode == 1)
-            k_megakernel<1><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, r->slotRad.p, r->counters.p);
-        else
-            k_megakernel<0><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, r->slotRad.p, r->counters.p);
-        k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->slotRad.p, accumTarget(r), nullptr, r->boundShard ? 1u : 0u);
-        HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-        HIP_TRY(r, hipEventRecord(r->evB, r->stream));
-        HIP_TRY(r, hipStreamSynchronize(r->stream));
-        HIP_TRY(r, hipGetLastError());
-        if (r->hostCounters[C_OVERFLOW])
-            return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow in the megakernel (depth > %d)", kLdsStackMega);
-        if (r->hostCounters[C_OVERFLOW + 1])
-            return fail(r, PTX_ERROR_DEVICE, "ptx_render: %u paths never produced a finite sample in %u attempts", r->hostCounters[C_OVERFLOW + 1],
-                        kMaxSampleRetries);
-        r->stats.segments = r->hostCounters[C_SEGMENTS];
-        r->stats.shadowRays = r->hostCounters[C_HITS];
-        r->stats.pathSamples = r->hostCounters[C_SAMPLES];
-        r->stats.retries = r->hostCounters[C_RETRIES];
-        return PTX_OK;
-    }
-
-    // ---- wavefront.  The whole launch is enqueued without waiting for the device (enqueueRound): the kernels take their
-    // queue lengths from the counter block, k_tail decides for itself when to take a queue over, and the rare NaN / Inf
-    // restarts of a canonical launch are finished on the device too (k_finish_restarts).  The host reads ONE counter
-    // block per launch, after the fact (collectRender: statistics, errors, grid hints).  A step of the benchmark used
-    // to carry 26 host round trips (0.33 ms of idle GPU per 10 ms step, 6 % of a 1/8 tile shard's step).
-    //
-    // Measured and dropped along the way: sub-batches of one call as interleaved state machines
-    // (PTX_BATCHES: 1 -> 1204, 2 -> 1017, 3 -> 1006, 4 -> 733 Msamples/s -- they pass through their throughput- and
-    // latency-bound phases in lockstep), staggered sub-batches (the tail kernel starves beside full-size kernels), ONE
-    // traversal launch per bounce carrying closest(b + 1) and shadow(b) (11.4 vs 11.1 ms), a one-entry software pipeline
-    // in k_shade (3.50 vs 3.44 ms).
-    {
-        const int rcr = ensureRenderResources(r, pl.bounces);
-        if (rcr != PTX_OK)
-            return rcr;
-    }
-    pl.sortShade = (sceneOf(r)->scene.mixedMaterialTypes || sceneOf(r)->scene.mixedTextured) ? 1u : 0u;
-    if (r->env.shadeSort >= 0)
-        pl.sortShade = (uint32_t)r->env.shadeSort;
-    // measured with 16 hardware queues (chess_like, ms per step at 25 / 50 / 75 / 100 / 200 / 400 K live paths): whole frame 8.04 / 7.82 /
-    // 7.85 / 7.80 / 8.14 / 8.13, a rank's tile shard of 8: 1.44 / 1.44 / 1.39 / 1.39 / 1.54 / 1.55, of 4: 2.29 / 2.24 / 2.24 / 2.33 / 2.34 /
-    // 2.77, of 2: 3.93 / 3.89 / 3.91 / 3.98 / 4.06 / 4.41; the other scenes are flat from 50 K to 200 K
-    pl.tailBelow = 75000;
-    if (r->env.tailThreshold >= 0)
-        pl.tailBelow = (uint32_t)r->env.tailThreshold;
-    Wavefront &wf = pl.wf;
-    wf.rayO = r->rayO.p; wf.rayD = r->rayD.p; wf.thr = r->thr.p; wf.rad = r->rad.p;
-    wf.meta = r->meta.p; wf.hit = r->hit.p; wf.hitPair = r->hitPair.p;
-    wf.shO = r->shO.p; wf.shD = r->shD.p; wf.shC = r->shC.p; wf.slotRad = r->slotRad.p;
-    wf.queue[0] = r->queue0.p; wf.queue[1] = r->queue1.p; wf.shadowQueue = r->shadowQueue.p; wf.shadowResult = r->shadowResult.p;
-    wf.restartQueue = r->restartQueue.p;
-    for (int k = 0; k < 3; k++)
-        wf.diff[k] = mode >= 1 ? r->diffs.p + (size_t)k * r->diffCapacity : nullptr;
-    wf.decal = mode == 2 ? r->decal.p : nullptr;
-    wf.decalT = mode == 2 ? r->decalT.p : nullptr;
-    wf.counters = r->counters.p;
-    wf.spill = r->spill.p;
-    pl.wfAux = wf;
-    pl.wfAux.spill = r->spillAux.p;
-
-    const bool canonical = uniform->SampleCount == 1;
-    // the learnt schedule belongs to (shape of the launch, scene it was learnt on); a camera or light change inside one scene
-    // keeps it -- a hint that is off costs time, never results, and the tail's grid leaves room for that (enqueueBounce)
-    const uint32_t *hint = (canonical && r->hintSlots == p.numSlots && r->hintBounces == pl.bounces && r->hintEpoch == sceneOf(r)->sceneEpoch && !r->hintActive.empty())
-                               ? r->hintActive.data() : nullptr;
-    k_generate<<<gridFor(p.numSlots), kBlock, 0, r->stream>>>(p, wf);
-    HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)p.numSlots, 1, r->stream));
-    int rcq = enqueueRound(r, pl, p.numSlots, hint);
-    if (rcq != PTX_OK)
-        return rcq;
-    if (canonical)
-    {
-        const dim3 grid(64);
-        if (mode == 2)
-            k_finish_restarts<2><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, wf);
-        else if (mode == 1)
-            k_finish_restarts<1><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, wf);
-        else
-            k_finish_restarts<0><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, wf);
-    }
-    else
-    {
-        // multi-sample launch: every slot comes back through the restart queue once per extra sample (and per NaN / Inf
-        // restart, raygen.rgen:99-112), one round each; a path that never yields a finite sample would go round for ever
-        // (it hangs the GPU in the reference): give up instead
-        const uint64_t maxRounds = (uint64_t)uniform->SampleCount * 64 + 64;
-        for (uint64_t round = 1;; round++)
-        {
-            HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-            HIP_TRY(r, hipStreamSynchronize(r->stream));
-            if (r->hostCounters[C_OVERFLOW])
-                return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
-            const uint32_t restarts = r->hostCounters[C_RESTART];
-            if (!restarts)
-                break;
-            if (round > maxRounds)
-                return fail(r, PTX_ERROR_DEVICE, "ptx_render: %u paths still active after %llu rounds", restarts, (unsigned long long)maxRounds);
-            k_restart<<<gridFor(restarts), kBlock, 0, r->stream>>>(p, wf, restarts); // next primary ray of every re-queued slot
-            HIP_TRY(r, hipMemcpyAsync(wf.queue[0], wf.restartQueue, (size_t)restarts * sizeof(uint32_t), hipMemcpyDeviceToDevice, r->stream));
-            HIP_TRY(r, hipMemsetAsync(&r->counters.p[C_RESTART], 0, sizeof(uint32_t), r->stream));
-            HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)restarts, 1, r->stream));
-            rcq = enqueueRound(r, pl, restarts, nullptr);
-            if (rcq != PTX_OK)
-                return rcq;
-        }
-    }
-    k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->slotRad.p, accumTarget(r), nullptr, r->boundShard ? 1u : 0u);
-    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
-    HIP_TRY(r, hipGetLastError());
-    r->statsPending = true;
-    r->pendingBounces = pl.bounces;
-    r->pendingTailBelow = pl.tailBelow;
-    r->pendingSlots = canonical ? p.numSlots : 0u;
-    r->pendingEpoch = sceneOf(r)->sceneEpoch;
-    r->pendingDeadSlots = p.numSlots - p.ownedPixels * frames;
-    r->pendingVerbose = r->env.verbose;
-    return PTX_OK;
-}
-
-// ptx_render_debug: RecordPathTracingCommands with the debug pipeline bound (pt_debug_view.hpp).  One launch, enqueued like
-// a wavefront launch: the counter block comes back with collectRender.
-static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, const PtxDebugViewDesc *view)
-{
-    if (!r || !uniform || !lights || !view)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: null argument");
-    if (view->renderMode > PTX_DEBUG_MODE_INSTANCE || (view->raygenFlags & ~(PTX_DEBUG_RAYGEN_FORCE_OPAQUE | PTX_DEBUG_RAYGEN_CULL_BACK_FACES)) != 0u ||
-        (view->hitGroupFlags & ~(PTX_DEBUG_HIT_DISABLE_COLOR_TEXTURE | PTX_DEBUG_HIT_DISABLE_NORMAL_TEXTURE | PTX_DEBUG_HIT_DISABLE_MIP_MAPS | PTX_DEBUG_HIT_DISABLE_SHADOWS)) != 0u ||
-        view->reserved != 0u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: render mode %u, raygen flags 0x%x, hit group flags 0x%x, reserved %u", view->renderMode,
-                    view->raygenFlags, view->hitGroupFlags, view->reserved);
-    if (!sceneUsable(r) || !imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_render_debug: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_render_debug");
-    if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: LightCount %u exceeds MaxLightCount", lights->LightCount);
-    HIP_TRY(r, hipSetDevice(r->device));
-    {
-        const int rcPrev = collectRender(r); // statistics / errors of the previous launch; the counter block is reused below
-        if (rcPrev != PTX_OK)
-            return rcPrev;
-    }
-    if (const int rcCommit = waitForCommits(r))
-        return rcCommit;
-
-    const LaunchParams p = makeParams(r, uniform, 0, 1);
-    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, r->lights.p);
-    HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
-    r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = 0;
-    r->stats.traceLaunches = 0;
-    r->stats.tracedRays = 0;
-    r->stats.lastTraceMs = 0.0;
-    r->stats.lastShadeMs = r->stats.lastShadowMs = r->stats.lastTailMs = 0.0;
-    HIP_TRY(r, hipEventRecord(r->evA, r->stream));
-    if (p.slotsPerFrame)
-    {
-        const SceneView sv = makeSceneView(r);
-        const TraceScene sc = makeTraceScene(r);
-        const DebugPair *pairIds = sceneOf(r)->scene.debugPairs.p;
-        DebugView dv;
-        dv.renderMode = view->renderMode; dv.raygenFlags = view->raygenFlags; dv.hitGroupFlags = view->hitGroupFlags;
-        // at most kMaxPersistentThreads threads: the global part of the traversal stack is sized for that many
-        const dim3 grid(gridFor(p.slotsPerFrame, kBlock, kMaxPersistentThreads / kBlock));
-        const int mode = kernelMode(r);
-        const bool cull = (view->raygenFlags & PTX_DEBUG_RAYGEN_CULL_BACK_FACES) != 0u;
-#define PT_LAUNCH_DEBUG_VIEW(M)                                                                                            \
-    do                                                                                                                     \
-    {                                                                                                                      \
-        if (cull)                                                                                                          \
-            k_debug_view<M, true><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->counters.p, r->spill.p);  \
-        else                                                                                                               \
-            k_debug_view<M, false><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->counters.p, r->spill.p); \
-    } while (0)
-        if (mode == 2)
-            PT_LAUNCH_DEBUG_VIEW(2);
-        else if (mode == 1)
-            PT_LAUNCH_DEBUG_VIEW(1);
-        else
-            PT_LAUNCH_DEBUG_VIEW(0);
-#undef PT_LAUNCH_DEBUG_VIEW
-    }
-    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
-    HIP_TRY(r, hipGetLastError());
-    r->statsPending = true;
-    r->pendingDebugView = true;
-    r->outputReady = false;
-    return PTX_OK;
-}
+#include "pt_render_host.hpp" // ptx_render, ptx_render_debug: renderImpl and its stages, collectRender, renderDebug
 
 static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
 {
@@ -1664,12 +1147,9 @@ static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, 
         (void)hipEventRecord(r->evT0, r->stream);
         (void)hipMemsetAsync(&r->counters.p[C_CHUNK], 0, sizeof(uint32_t), r->stream);
         (void)hipMemsetAsync(dOverflow.p, 0, sizeof(uint32_t), r->stream);
-        if (sceneOf(r)->scene.anyNonOpaque)
-            k_trace_rays<true><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p,
-                                                                     dOverflow.p);
-        else
-            k_trace_rays<false><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p,
-                                                                      dOverflow.p);
+        withFlag(sceneOf(r)->scene.anyNonOpaque, [&](auto ALPHA) {
+            k_trace_rays<decltype(ALPHA)::value><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p, dOverflow.p);
+        });
         (void)hipEventRecord(r->evT1, r->stream);
         e = hipMemcpyAsync(hits, dHits.p, (size_t)n * 16, hipMemcpyDeviceToHost, r->stream);
     }

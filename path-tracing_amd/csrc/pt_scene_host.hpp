@@ -90,7 +90,7 @@ static int shareScene(PtxRenderer *r, PtxRenderer *owner)
     r->sceneOwner = owner;
     owner->sceneSharers.push_back(r);
     r->accelReady = true;
-    r->hintSlots = 0u; // whatever this handle had learnt, it had learnt on another scene
+    r->hint.forget(); // whatever this handle had learnt, it had learnt on another scene
     r->stats.triangles = owner->stats.triangles;
     r->stats.bvhNodes = owner->stats.bvhNodes;
     r->stats.treeTriangles = owner->stats.treeTriangles;

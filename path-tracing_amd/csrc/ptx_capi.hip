@@ -1,6 +1,7 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
-// Renderer member it replaces in include/ptx.h; the implementations are in pt_runtime.hpp (host side) and pt_wavefront.hpp /
-// pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp (device side).  No exceptions cross this boundary: status codes + ptx_last_error.
+// Renderer member it replaces in include/ptx.h; the implementations are in pt_runtime.hpp and the host files it includes
+// (pt_scene_host.hpp, pt_bvh_host.hpp, pt_render_host.hpp) and pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp
+// (device side).  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
 extern "C" {
@@ -38,7 +39,7 @@ int ptx_set_backend(PtxRenderer *r, uint32_t backend)
     if (!r || backend > PTX_BACKEND_MEGAKERNEL)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_set_backend: bad backend %u", backend);
     if (r->backend != backend)
-        r->hintSlots = 0u; // the learnt bounce schedule is the wavefront backend's
+        r->hint.forget(); // the learnt bounce schedule is the wavefront backend's
     r->backend = backend;
     return PTX_OK;
 }

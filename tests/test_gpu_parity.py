@@ -742,6 +742,65 @@ def test_single_stream_handles_render_the_same_image(pkg, orc):
         two.close()
 
 
+def test_stale_schedule_hint_costs_time_not_results(pkg, orc, monkeypatch):
+    """A hint that turns out too optimistic: the hinted schedule hands k_tail whatever the last wavefront bounce left, the tail's
+    grid has room for four times its threshold and strides over the rest, and collecting the launch drops the hint -- time is
+    lost, never results.  One handle, four launches: view B (the camera turned away from all geometry: nothing survives bounce
+    1) is driven from the host and teaches "tail after bounce 1"; view A (the scene's own) then runs on that hint, which is
+    wrong for it; A again, driven from the host because the hint was dropped; A once more on the hint just learnt, which fits.
+    Every launch gives the oracle's image bits and counts for its view.  The preconditions come from the oracle alone, so the
+    test cannot pass vacuously: chess_like at detail 0.05, 96x54, 2 frames, depth 6 keeps (16974 - 10368) / 5 = 1321 paths alive
+    per later bounce on the CPU (1264 - 1321 at details 0.02 - 0.4), hence the threshold of 256 (4 x 256 = 1024 < 1321)."""
+    import torch  # noqa: F401
+
+    threshold = 256
+    monkeypatch.setenv("PTX_TAIL_THRESHOLD", str(threshold))
+    scene = pkg.Scene("chess_like", 0.05)
+    lights = scene.lights
+    W, H, frames, depth = 96, 54, 2, 6
+
+    def uniform(view, frame=0):
+        u = scene.uniform(W, H, bounces=depth, total_samples=frame)
+        if view == "B":  # half a turn about the camera's up axis: its right and backward axes (columns 0 and 2) change sign
+            for k in (0, 1, 2, 8, 9, 10):
+                u.ViewInverse[k] = -u.ViewInverse[k]
+        return u
+
+    osc = orc.OracleScene(scene.desc)
+    want = {}
+    for view in "AB":
+        ref = np.zeros((H, W, 4), np.float32)
+        counts = np.zeros(4, np.int64)
+        for f in range(frames):
+            _, ost = osc.render(uniform(view, f), lights, W, H, accum=ref)
+            counts += (ost.segments, ost.shadowRays, ost.pathSamples, ost.retries)
+        want[view] = (ref, tuple(int(c) for c in counts))
+    seg_b, _, samples_b, _ = want["B"][1]
+    seg_a, _, samples_a, _ = want["A"][1]
+    assert seg_b == samples_b, "view B: nothing may survive bounce 1"
+    assert (seg_a - samples_a) / (depth - 1) > 4 * threshold, "view A must exceed the tail's fourfold room at bounce 2"
+
+    r = pkg.Renderer()
+    try:
+        r.upload(scene)
+        r.resize(W, H)
+        kernels = []  # traversal launches that found work: two per bounce that ran as wavefront kernels
+        for launch, view in enumerate("BAAA"):
+            r.reset()
+            r.render_frames(uniform(view), lights, 0, frames)
+            st = r.stats()
+            img = r.readback()
+            ref, counts = want[view]
+            assert (st.segments, st.shadowRays, st.pathSamples, st.retries) == counts, f"launch {launch} (view {view})"
+            assert (img.view(np.uint32) == ref.view(np.uint32)).all(), f"launch {launch} (view {view})"
+            kernels.append(st.traceLaunches)
+    finally:
+        r.close()
+    # which schedule each launch ran: B and the wrongly hinted A stop after bounce 1; the host-driven A goes on at least to bounce 2
+    # (more than 256 paths are alive there, by the precondition above), and the rightly hinted A repeats it
+    assert kernels[0] == kernels[1] == 2 and kernels[2] >= 4 and kernels[3] == kernels[2], kernels
+
+
 @pytest.mark.gpu
 def test_second_full_build_on_a_handle_does_not_reuse_the_level_lists_of_the_first(pkg, orc, monkeypatch):
     """A handle keeps its build state between ptx_build_accel calls.  With no reinsertion pass (PTX_REINSERT=0) nothing recomputes
