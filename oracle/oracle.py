@@ -64,6 +64,8 @@ def load() -> C.CDLL:
         lib.pto_scene_destroy.argtypes = [P]
         lib.pto_scene_triangle_count.restype = C.c_uint64
         lib.pto_scene_triangle_count.argtypes = [P]
+        lib.pto_scene_skinned_vertices.restype = C.c_uint64
+        lib.pto_scene_skinned_vertices.argtypes = [P, P, C.c_uint64]
         lib.pto_render.argtypes = [P, P, P] + [C.c_uint32] * 6 + [P, P, C.c_int, C.c_int, P]
         lib.pto_trace_closest.argtypes = [P, P, C.c_uint32, P, C.c_int]
         lib.pto_trace_any.argtypes = [P, P, C.c_uint32, P, C.c_int]
@@ -103,6 +105,14 @@ class OracleScene:
     @property
     def triangle_count(self) -> int:
         return int(self.lib.pto_scene_triangle_count(self.handle))
+
+    def skinned_vertices(self) -> np.ndarray:
+        """The skinned vertex block, rows of 14 floats (position, uv, normal, tangent, bitangent): one copy per instanced
+        animated mesh in pair order."""
+        n = int(self.lib.pto_scene_skinned_vertices(self.handle, None, 0))
+        out = np.zeros((n, 14), np.float32)
+        self.lib.pto_scene_skinned_vertices(self.handle, out.ctypes.data, n)
+        return out
 
     def render(self, uniform, lights, width, height, accum=None, region=None, shard=None, threads=0,
                brute_force=False):

@@ -727,6 +727,7 @@ struct PtoScene
     struct OTexture *textures;
     uint32_t textureCount;
     PtxVertex *skinned; /* skinning.comp output: one copy per instanced animated mesh, in pair order */
+    uint64_t skinnedCount;
     uint32_t skyKind; /* PTX_SKYBOX_*; its 1 / 6 images sit at textures[textureCount ...] */
     uint32_t *texels8; /* RGBA8 pool, all levels of all 8-bit textures */
     float *texelsF;    /* RGBA32F pool */
@@ -863,6 +864,7 @@ PtoScene *pto_scene_create_posed(const PtxSceneDesc *desc, const PtxTransform *i
         }
     }
     s->skinned = (PtxVertex *)calloc(skinnedCount ? skinnedCount : 1, sizeof(PtxVertex));
+    s->skinnedCount = skinnedCount;
     size_t skinnedCursor = 0;
     s->v0 = (float *)malloc((triCount ? triCount : 1) * 12);
     s->e1 = (float *)malloc((triCount ? triCount : 1) * 12);
@@ -966,6 +968,13 @@ void pto_scene_destroy(PtoScene *s)
 }
 
 uint64_t pto_scene_triangle_count(const PtoScene *s) { return s->triCount; }
+
+uint64_t pto_scene_skinned_vertices(const PtoScene *s, PtxVertex *out, uint64_t capacity)
+{
+    if (out)
+        memcpy(out, s->skinned, (size_t)(capacity < s->skinnedCount ? capacity : s->skinnedCount) * sizeof(PtxVertex));
+    return s->skinnedCount;
+}
 
 /* ======================================================================== */
 /* Ray / triangle (Moeller-Trumbore on v0,e1,e2) and the two queries        */

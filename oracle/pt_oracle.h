@@ -78,6 +78,9 @@ PTX_API PtoScene *pto_scene_create_posed(const PtxSceneDesc *desc, const PtxTran
                                          uint32_t boneCount, int buildBvh);
 PTX_API void pto_scene_destroy(PtoScene *s);
 PTX_API uint64_t pto_scene_triangle_count(const PtoScene *s);
+/* The skinned vertex block (OutAnimatedVertexBuffer): one copy per instanced animated mesh, in pair order, as authored when the
+ * scene was created without bones.  Copies up to `capacity` vertices to `out` (may be NULL) and returns the block's length. */
+PTX_API uint64_t pto_scene_skinned_vertices(const PtoScene *s, PtxVertex *out, uint64_t capacity);
 
 /* One launch of raygen.rgen over pixels [x0,x1) x [y0,y1) of a W x H image; adds into
  * accum (W*H*4 floats, alpha set to 1).  tileShard may be NULL (whole region). */

@@ -96,12 +96,17 @@ def light_contribution(light_dir, light_color, attenuation, V, N, color, roughne
 
 # ---- the scene as the reference reads it ------------------------------------------------------------------------
 class RefScene:
-    """The per-pair tables of a PtxSceneDesc and its oracle."""
+    """The per-pair tables of a PtxSceneDesc and its oracle; with `instance_transforms` (n x 12) / `bones` (m x 12), of the
+    scene posed that way (ptx_update_animation)."""
 
-    def __init__(self, orc, desc):
+    def __init__(self, orc, desc, instance_transforms=None, bones=None):
         self.orc, self.desc = orc, desc
-        self.osc = orc.OracleScene(desc, build_bvh=True)
+        self.osc = orc.OracleScene(desc, build_bvh=True, instance_transforms=instance_transforms, bones=bones)
         a = util.desc_arrays(desc)
+        if instance_transforms is not None:
+            a["instances"] = a["instances"].copy()
+            a["instances"]["Transform"] = np.asarray(instance_transforms, np.float32).reshape(-1, 12)
+        a["animated_indices"] = util._view(desc.animatedIndices, desc.animatedIndexCount, np.dtype("u4"))
         self.a = a
         self.first = util.pair_first(desc)
         rows = []
@@ -111,6 +116,10 @@ class RefScene:
                 rec = a["meshes"][m["MeshOffset"] + k]
                 rows.append((i, k, int(rec["GeometryIndex"]), int(rec["MaterialId"]), int(rec["TransformIndex"])))
         self.pair = np.array(rows, np.int64).reshape(-1, 5)  # instance, geometry index inside the model, geometry, material id, transform
+        # first vertex of every pair's copy in the skinned vertex block: one copy per instanced animated mesh, in pair order
+        g = a["geometries"][self.pair[:, 2]]
+        length = np.where(g["IsAnimated"] != 0, g["VertexLength"], 0).astype(np.int64)
+        self.skinned_first = np.cumsum(length) - length
         f4 = np.dtype("f4")
         self.materials = [util._view(desc.metallicRoughnessMaterials, desc.metallicRoughnessMaterialCount * 24, f4).reshape(-1, 24),
                           util._view(desc.specularGlossinessMaterials, desc.specularGlossinessMaterialCount * 24, f4).reshape(-1, 24),
@@ -180,7 +189,8 @@ def _decals(rs, o, d, hit_t, hit_sel):
     has, rgba = np.zeros(n, bool), np.zeros((n, 4), np.float32)
     if not len(nonopaque):
         return has, rgba
-    T = util.world_triangles(rs.desc)
+    assert not geo["IsAnimated"][rs.pair[nonopaque, 2]].any(), "decals over animated geometry are not restated"
+    T = util.world_triangles(rs.desc, rs.a["instances"]["Transform"])
     ids = np.concatenate([np.arange(rs.first[p], rs.first[p + 1]) for p in nonopaque])
     pair_of = np.concatenate([np.full(rs.first[p + 1] - rs.first[p], p) for p in nonopaque])
     Tn = T[ids]
@@ -213,8 +223,9 @@ def _decals(rs, o, d, hit_t, hit_sel):
     return has, rgba
 
 
-def render(rs, uniform, lights, W, H, mode, hit_flags=0, dtype=np.float32):
-    """One debug frame of the whole image.  Returns a dict: image (H, W, 4) in `dtype`; hit (H, W) bool; occluded
+def render(rs, uniform, lights, W, H, mode, hit_flags=0, dtype=np.float32, posed=None):
+    """One debug frame of the whole image.  `posed`: the skinned vertex block in `dtype` (tests/skin_ref.py posed_vertices), what
+    hits on animated geometry read their vertices from.  Returns a dict: image (H, W, 4) in `dtype`; hit (H, W) bool; occluded
     (1 + LightCount, H, W) bool, the reference's own occlusion masks (Color mode with shadows); segments / shadow_rays, the counts
     ptx_get_stats reports; t, tri of the primary hits."""
     orc, osc, desc = rs.orc, rs.osc, rs.desc
@@ -260,9 +271,13 @@ def render(rs, uniform, lights, W, H, mode, hit_flags=0, dtype=np.float32):
     u, v = hits["u"][h].astype(dtype), hits["v"][h].astype(dtype)
     b = np.stack([dtype(1) - u - v, u, v], axis=1)
     g = rs.a["geometries"][rs.pair[p, 2]]
-    assert not g["IsAnimated"].any(), "the reference reads static geometry only"
-    vi = rs.a["indices"][(g["IndexOffset"].astype(np.int64) + 3 * prim)[:, None] + np.arange(3)] + g["VertexOffset"].astype(np.int64)[:, None]
-    vtx = rs.a["vertices"][vi].astype(dtype)  # (n, 3, 14): position, uv, normal, tangent, bitangent
+    anim = g["IsAnimated"] != 0
+    corner = (g["IndexOffset"].astype(np.int64) + 3 * prim)[:, None] + np.arange(3)
+    vtx = np.zeros((len(h), 3, 14), dtype)  # position, uv, normal, tangent, bitangent
+    vtx[~anim] = rs.a["vertices"][rs.a["indices"][corner[~anim]] + g["VertexOffset"].astype(np.int64)[~anim, None]].astype(dtype)
+    if anim.any():
+        assert posed is not None and posed.dtype == np.dtype(dtype), "hits on animated geometry need the posed vertex block"
+        vtx[anim] = posed[rs.a["animated_indices"][corner[anim]] + rs.skinned_first[p[anim], None]]
     M = rs.pair_matrix(dtype)[p]
     A, tr = M[:, :, 0:3], M[:, :, 3]
     Ainv_t = np.linalg.inv(A.astype(np.float64)).astype(dtype).transpose(0, 2, 1)  # the normal transform: inverse transpose

@@ -396,11 +396,12 @@ def global_ids(desc, ids):
     return np.where(miss, 0xFFFFFFFF, first[np.where(miss, 0, pair)] + prim).astype(np.uint32)
 
 
-def check_trace_against_bruteforce(r, orc, desc, rays, min_hits, instance_transforms=None, label=""):
+def check_trace_against_bruteforce(r, orc, desc, rays, min_hits, instance_transforms=None, label="", bones=None):
     """Closest-hit and occlusion queries of renderer `r` (its tree over `desc`) against the oracle's brute force: the same
     global triangle per ray, t / u / v bit for bit on hits, the same occlusion flag -- and at least `min_hits` hits, so that a
-    scene every ray misses cannot pass.  Returns the brute-force closest hits."""
-    osc = orc.OracleScene(desc, build_bvh=False, instance_transforms=instance_transforms)
+    scene every ray misses cannot pass.  `bones` (m x 12): the oracle skins its animated meshes with them (None: the bind pose).
+    Returns the brute-force closest hits."""
+    osc = orc.OracleScene(desc, build_bvh=False, instance_transforms=instance_transforms, bones=bones)
     want = osc.trace_closest(rays, brute_force=True)
     occ_want = osc.trace_any(rays, brute_force=True)
     osc.close()
