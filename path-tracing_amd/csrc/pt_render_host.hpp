@@ -40,12 +40,20 @@ static int ensureSlots(PtxRenderer *r, size_t slots)
     return PTX_OK;
 }
 
-__global__ void k_upload_lights(PtxLightsUbo lights, PtxLightsUbo *dst) // 3,120 bytes as a kernel argument: no staging buffer to keep alive
+// 3,120 + 204 bytes as kernel arguments: no staging buffer to keep alive.  The launch parameters go with the lights: the first
+// bounce's traversal kernel reads them through `dstParams` (FirstClosestIO).  Every frame in flight has its own renderer and
+// writes its copy once per launch on its main stream, ahead of the only kernel that reads it: stream order is all it needs.
+__global__ void k_upload_lights(PtxLightsUbo lights, LaunchParams params, PtxLightsUbo *dst, LaunchParams *dstParams)
 {
+    static_assert(sizeof(PtxLightsUbo) % 4 == 0 && sizeof(LaunchParams) % 4 == 0, "copied word by word");
     const uint32_t *src = reinterpret_cast<const uint32_t *>(&lights);
     uint32_t *d = reinterpret_cast<uint32_t *>(dst);
     for (uint32_t i = threadIdx.x; i < sizeof(PtxLightsUbo) / 4; i += blockDim.x)
         d[i] = src[i];
+    const uint32_t *srcP = reinterpret_cast<const uint32_t *>(&params);
+    uint32_t *dP = reinterpret_cast<uint32_t *>(dstParams);
+    for (uint32_t i = threadIdx.x; i < sizeof(LaunchParams) / 4; i += blockDim.x)
+        dP[i] = srcP[i];
 }
 
 static int ensureRenderResources(PtxRenderer *r, uint32_t bounces)
@@ -126,12 +134,20 @@ static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t
 //   stream     P(b)  closest(b)  [wait aux(b-1)]  shade(b)                      P(b+1) closest(b+1) ...
 //   auxStream                                     [wait shade(b)] shadow(b) [tail(b)]
 //
+// `fresh`: b is bounce 1 of the round renderWavefront starts, whose queue is every slot of the launch.  closest(1) and shade(1)
+// are then the <FirstBounce, ..> variants, which compute the primary ray of a slot from the launch parameters -- no k_generate in front:
+//
+//   stream     upload(lights, params)  P(1)  closest<FirstBounce>(1)  shade<FirstBounce>(1)  P(2) closest(2) ...
+//
+// (PTX_FIRST_BOUNCE=0: k_generate, then the general kernels over the identity queue it wrote.)  The rounds k_restart starts
+// (runSampleRounds) are never fresh: their queue is the restart queue and their rays carry the RNG state on.
+//
 // shadow(b) only adds into rad[slot], which shade(b + 1) reads -- not closest(b + 1) -- so it runs beside the next
 // traversal; k_tail, where the schedule has one, follows it in stream order (the NEE adds it continues from have
 // landed): the last shadow query before the tail needs no event of its own.
 // tail: 0 = none, 1 = k_tail takes the queue shade(b) filled if it holds at most pl.tailBelow paths, 2 = takes it whatever
 // its length (nothing is enqueued behind this bounce).
-static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, int tail)
+static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, int tail, bool fresh)
 {
     hipStream_t S = r->stream, X = r->auxStream;
     PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
@@ -140,17 +156,26 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
     k_prologue<<<1, 1, 0, S>>>(pl.wf, qin, ctl);
     HIP_TRY(r, hipEventRecord(ev.t0, S));
     withFlag(pl.mode == 2, [&](auto ALPHA) {
-        k_trace_closest<decltype(ALPHA)::value><<<traceGridFor(est, r->residentClosest[decltype(ALPHA)::value]), kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
+        const dim3 grid(traceGridFor(est, r->residentClosest[decltype(ALPHA)::value])); // (the FIRST variants hold the same occupancy)
+        if (fresh)
+            k_trace_closest<FirstBounce, decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, r->launchParams.p, pl.p.numSlots);
+        else
+            k_trace_closest<decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
     });
     HIP_TRY(r, hipEventRecord(ev.t1, S));
     if (b > 1) // shade reads rad[slot]: the previous bounce's shadow adds must have landed
         HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
     const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
     withFlag(pl.mode >= 1, [&](auto TEXTURED) {
-        if (pl.sortShade)
-            k_shade_sorted<decltype(TEXTURED)::value><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+        constexpr bool TEX = decltype(TEXTURED)::value;
+        if (pl.sortShade && fresh)
+            k_shade_sorted<FirstBounce, TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+        else if (pl.sortShade)
+            k_shade_sorted<TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+        else if (fresh)
+            k_shade<FirstBounce, TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
         else
-            k_shade<decltype(TEXTURED)::value><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
+            k_shade<TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
     });
     HIP_TRY(r, hipEventRecord(ev.t2, S));
     HIP_TRY(r, hipStreamWaitEvent(X, ev.t2, 0));
@@ -199,7 +224,7 @@ static void hintedSchedule(const uint32_t *hint, uint32_t bounces, uint32_t tail
 // to find its queue empty, and the host does not wait for the device.
 // Without one (first launch of a shape, rounds of a multi-sample launch) the round is driven bounce by bounce: the host
 // reads the counter block after every shade kernel and decides -- which is also how the hint is learned.
-static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBound, const uint32_t *hint)
+static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBound, const uint32_t *hint, bool fresh)
 {
     uint32_t last = 0; // the last bounce enqueued
     int qin = 0;
@@ -208,7 +233,7 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
         hintedSchedule(hint, pl.bounces, pl.tailBelow, upperBound, r->hint.steps);
         for (const BounceStep &s : r->hint.steps)
         {
-            if (const int rc = enqueueBounce(r, pl, s.bounce, qin, s.est, s.tail))
+            if (const int rc = enqueueBounce(r, pl, s.bounce, qin, s.est, s.tail, fresh && s.bounce == 1u))
                 return rc;
             last = s.bounce;
             qin ^= 1;
@@ -219,7 +244,7 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
         uint32_t est = upperBound;
         for (uint32_t b = 1; b <= pl.bounces; b++)
         {
-            if (const int rc = enqueueBounce(r, pl, b, qin, est, 0))
+            if (const int rc = enqueueBounce(r, pl, b, qin, est, 0, fresh && b == 1u))
                 return rc;
             last = b;
             qin ^= 1;
@@ -315,7 +340,7 @@ static int collectRender(PtxRenderer *r)
 
 // What ptx_render and ptx_render_debug open with: the previous launch is collected (the counter block is reused below), texture
 // commits land, the per-slot buffers hold `slots` paths (0: none needed), the stream gets the lights, zeroed counters and evA.
-static int beginLaunch(PtxRenderer *r, const PtxLightsUbo *lights, uint64_t slots)
+static int beginLaunch(PtxRenderer *r, const PtxLightsUbo *lights, const LaunchParams &p, uint64_t slots)
 {
     HIP_TRY(r, hipSetDevice(r->device));
     if (const int rc = collectRender(r))
@@ -326,7 +351,7 @@ static int beginLaunch(PtxRenderer *r, const PtxLightsUbo *lights, uint64_t slot
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: too many path slots in one batch");
     if (const int rc = slots ? ensureSlots(r, (size_t)slots) : PTX_OK)
         return rc;
-    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, r->lights.p);
+    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, p, r->lights.p, r->launchParams.p);
     HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
     r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = r->stats.tracedRays = 0;
     r->stats.traceLaunches = 0;
@@ -403,7 +428,7 @@ static int runSampleRounds(PtxRenderer *r, const RenderPlan &pl, uint32_t sample
         HIP_TRY(r, hipMemcpyAsync(pl.wf.queue[0], pl.wf.restartQueue, (size_t)restarts * sizeof(uint32_t), hipMemcpyDeviceToDevice, r->stream));
         HIP_TRY(r, hipMemsetAsync(&r->counters.p[C_RESTART], 0, sizeof(uint32_t), r->stream));
         HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)restarts, 1, r->stream));
-        if (const int rc = enqueueRound(r, pl, restarts, nullptr))
+        if (const int rc = enqueueRound(r, pl, restarts, nullptr, false))
             return rc;
     }
 }
@@ -436,9 +461,12 @@ static int renderWavefront(PtxRenderer *r, RenderPlan &pl, uint32_t sampleCount)
     // the learnt schedule belongs to (shape of the launch, scene it was learnt on); a camera or light change inside one scene
     // keeps it -- a hint that is off costs time, never results, and the tail's grid leaves room for that (enqueueBounce)
     const uint32_t *hint = canonical && r->hint.matches(p.numSlots, pl.bounces, epoch) ? r->hint.active.data() : nullptr;
-    k_generate<<<gridFor(p.numSlots), kBlock, 0, r->stream>>>(p, pl.wf);
+    // the primary rays: computed by the first bounce's kernels, or handed over through memory by k_generate (PTX_FIRST_BOUNCE=0)
+    const bool fresh = r->env.firstBounce;
+    if (!fresh)
+        k_generate<<<gridFor(p.numSlots), kBlock, 0, r->stream>>>(p, pl.wf);
     HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)p.numSlots, 1, r->stream));
-    if (const int rc = enqueueRound(r, pl, p.numSlots, hint))
+    if (const int rc = enqueueRound(r, pl, p.numSlots, hint, fresh))
         return rc;
     if (canonical)
         finishCanonical(r, pl);
@@ -461,7 +489,7 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: LightCount %u exceeds MaxLightCount", lights->LightCount);
     RenderPlan pl;
     pl.p = makeParams(r, uniform, firstFrame, frames);
-    if (const int rc = beginLaunch(r, lights, (uint64_t)pl.p.slotsPerFrame * frames))
+    if (const int rc = beginLaunch(r, lights, pl.p, (uint64_t)pl.p.slotsPerFrame * frames))
         return rc;
     if (pl.p.numSlots == 0)
     {
@@ -495,7 +523,7 @@ static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, cons
     if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: LightCount %u exceeds MaxLightCount", lights->LightCount);
     const LaunchParams p = makeParams(r, uniform, 0, 1);
-    if (const int rc = beginLaunch(r, lights, 0))
+    if (const int rc = beginLaunch(r, lights, p, 0))
         return rc;
     if (p.slotsPerFrame)
     {

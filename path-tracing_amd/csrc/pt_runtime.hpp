@@ -106,6 +106,8 @@ struct EnvSwitches
     bool snapshotMemcpy = false; // PTX_SNAPSHOT_MEMCPY=1: the read-back's device-side snapshot by hipMemcpyAsync (rounds 1-4) instead of a kernel
     bool fenceRefit = false;     // PTX_FENCE_REFIT=1: the round-4 bottom-up kernels (fence and atomic per node) instead of the level lists
     bool pairLeaves = true;      // PTX_PAIR_LEAVES=0: single-triangle leaves only (pt_bvh_build.hpp, "pair leaves")
+    bool firstBounce = true;     // PTX_FIRST_BOUNCE=0: k_generate hands the primary rays over through memory (rounds 1-6) instead of the first
+                                 // bounce's kernels computing them (pt_wavefront.hpp, FirstClosestIO)
     bool streamLevelwise = false; // PTX_STREAM_LEVELWISE=1: ptx_texture_upload builds every chain level by level (k_blit_level) instead of k_stream_chain
     static EnvSwitches read()
     {
@@ -114,6 +116,8 @@ struct EnvSwitches
         e.streamLevelwise = getenv("PTX_STREAM_LEVELWISE") != nullptr && std::strcmp(getenv("PTX_STREAM_LEVELWISE"), "0") != 0;
         if (const char *v = getenv("PTX_PAIR_LEAVES"))
             e.pairLeaves = std::strcmp(v, "0") != 0;
+        if (const char *v = getenv("PTX_FIRST_BOUNCE"))
+            e.firstBounce = std::strcmp(v, "0") != 0;
         if (const char *v = getenv("PTX_COPY_GROUPS"))
             e.copyGroups = (uint32_t)strtoul(v, nullptr, 10);
         e.snapshotMemcpy = getenv("PTX_SNAPSHOT_MEMCPY") != nullptr && std::strcmp(getenv("PTX_SNAPSHOT_MEMCPY"), "0") != 0;
@@ -256,6 +260,7 @@ struct PtxRenderer
 
     SceneData scene;
     DevBuf<PtxLightsUbo> lights;
+    DevBuf<LaunchParams> launchParams; // device copy of the current launch's parameters, written with the lights (k_upload_lights)
     DevBuf<AlphaTri> alphaTris;    // what the any-hit stages read per triangle slot, written behind k_emit
     struct BuildState // what a refit reuses from the last full build: sorted order and the binary topology
     {
@@ -639,7 +644,7 @@ static int createRenderer(const PtxDeviceDesc *desc, PtxRenderer **out)
     (void)hipEventCreate(&r->evT0);
     (void)hipEventCreate(&r->evT1);
     (void)hipHostMalloc(reinterpret_cast<void **>(&r->hostCounters), C_COUNT * sizeof(uint32_t), hipHostMallocDefault);
-    if (r->counters.alloc(C_COUNT) != hipSuccess || r->lights.alloc(1) != hipSuccess || !r->hostCounters ||
+    if (r->counters.alloc(C_COUNT) != hipSuccess || r->lights.alloc(1) != hipSuccess || r->launchParams.alloc(1) != hipSuccess || !r->hostCounters ||
         r->spill.alloc((size_t)kGlobalSpill * kMaxPersistentThreads) != hipSuccess)
     {
         destroyRenderer(r);

@@ -8,7 +8,8 @@
 // is 1, i.e. the path is an iterative loop in raygen: that loop is cut here at the two
 // traceRayEXT calls into a queue-per-stage WAVEFRONT:
 //
-//   k_generate        raygen.rgen:38-60   RNG seed, primary ray
+//   k_generate        raygen.rgen:38-60   RNG seed, primary ray -- only under PTX_FIRST_BOUNCE=0: by default the first bounce's
+//                                         k_trace_closest<FirstBounce, ..> and k_shade<FirstBounce, ..> compute it themselves
 //   k_trace_closest   raygen.rgen:68      closest-hit query over the active queue
 //   k_shade           closestHit.rchit / miss.rmiss + raygen.rgen:71-96 bookkeeping
 //   k_trace_shadow    raygen.rgen:22-34   occlusion query: one answer per shadow-queue entry
@@ -314,6 +315,7 @@ PT_DEV void blockAddCounter(uint32_t *__restrict__ counter, uint32_t v)
 constexpr uint32_t kShadeItems = PT_SHADE_ITEMS; // queue entries per thread per block-wide append in k_shade
 constexpr uint32_t kDeadPair = 0xfffffffeu; // hitPair of a slot outside the image (ragged edge tiles)
 
+// The schedule of rounds 1-6 (PTX_FIRST_BOUNCE=0; the default computes all this in the first bounce's kernels, FirstClosestIO).
 // No queue atomics here: queue 0 is the identity over all slots (the host sets its count);
 // slots of edge tiles that fall outside the image are flagged dead through rayD.w < 0.
 __global__ void __launch_bounds__(kBlock) k_generate(LaunchParams p, Wavefront wf)
@@ -429,6 +431,51 @@ PT_DEV void traceClosestBody(const TraceScene &sc, const Wavefront &wf, int qin,
     if (st.overflow)
         atomicAdd(&wf.counters[C_OVERFLOW], 1u);
 }
+
+// The first bounce of a launch.  The primary ray of a slot is a pure function of (slot, launch parameters): this IO computes it
+// where k_generate used to write 52 bytes per slot (queue entry, rayO, rayD, meta) for the first k_trace_closest and k_shade to
+// read back -- a fifth of a chess_like step's bytes, a full-machine streaming launch per frame and one dependent load at the
+// head of every primary ray's chain.  The queue is the identity over all slots (kHasQueue = false: the item is the slot).
+// The parameters are read through a pointer (the renderer's device copy, k_upload_lights): passed by value the camera matrices
+// stay live in SGPRs across the whole persistent loop and both variants spill (10 / 12 VGPRs, 36 / 44 B of scratch per lane);
+// behind the pointer the stores of the loop keep the scalar loads inside load() and the kernels hold the general variants'
+// occupancy.  The first k_shade recomputes the same ray (shadeBody<.., FIRST>, k_shade<FirstBounce, ..>): nothing of it goes through memory.
+struct FirstClosestIO : ClosestIO
+{
+    static constexpr bool kHasQueue = false;
+    const LaunchParams *gp;
+    PT_DEV bool load(uint32_t item, f3 &o, f3 &d, float &tmin, float &tmax)
+    {
+        const LaunchParams &p = *gp;
+        slot = item;
+        uint32_t f, s;
+        slotFrame(p, slot, f, s);
+        const uint32_t pixel = slotPixel(p, s);
+        if (pixel == 0xffffffffu) // outside the image (ragged edge tiles): dead for the whole launch, k_accumulate skips it
+        {
+            wf.hitPair[slot] = kDeadPair;
+            wf.slotRad[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            return false;
+        }
+        uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, p.firstFrame + f); // raygen.rgen:38
+        DiffRays diff;
+        startSample<false>(p, pixel, rng, o, d, diff); // the differentials are the first k_shade's
+        tmin = 0.00001f;
+        tmax = 10000.0f;
+        if (wf.decalT)
+            wf.decalT[slot] = -1.0f;
+        return true;
+    }
+};
+template <bool ALPHA>
+PT_DEV void traceFirstBody(const TraceScene &sc, const Wavefront &wf, const LaunchParams *gp, uint32_t numSlots)
+{
+    PT_DECLARE_STACK(st, kLdsStack, wf.spill)
+    FirstClosestIO io = { { wf, nullptr, 0u }, gp };
+    persistentTrace<false, ALPHA>(sc, io, numSlots, &wf.counters[C_CHUNK], st);
+    if (st.overflow)
+        atomicAdd(&wf.counters[C_OVERFLOW], 1u);
+}
 template <bool ALPHA>
 __global__ void __launch_bounds__(kBlock) k_trace_closest(TraceScene sc, Wavefront wf, int qin, BounceCtl ctl);
 template <>
@@ -440,6 +487,22 @@ template <>
 __global__ void __launch_bounds__(kBlock) PT_ALPHA_CLOSEST_ATTR k_trace_closest<true>(TraceScene sc, Wavefront wf, int qin, BounceCtl ctl)
 {
     traceClosestBody<true>(sc, wf, qin, ctl);
+}
+// k_trace_closest<FirstBounce, ALPHA>: bounce 1 of the round renderWavefront starts, over all `numSlots` slots with the parameters
+// at `gp`.  A second template of the same name: the tools that group kernels by their base name see one k_trace_closest (and one
+// k_shade, below), and the general variants keep their names and their code.
+struct FirstBounce {};
+template <typename WHICH, bool ALPHA>
+__global__ void __launch_bounds__(kBlock) k_trace_closest(TraceScene sc, Wavefront wf, const LaunchParams *gp, uint32_t numSlots);
+template <>
+__global__ void __launch_bounds__(kBlock) PT_FULL_OCCUPANCY k_trace_closest<FirstBounce, false>(TraceScene sc, Wavefront wf, const LaunchParams *gp, uint32_t numSlots)
+{
+    traceFirstBody<false>(sc, wf, gp, numSlots);
+}
+template <>
+__global__ void __launch_bounds__(kBlock) PT_ALPHA_CLOSEST_ATTR k_trace_closest<FirstBounce, true>(TraceScene sc, Wavefront wf, const LaunchParams *gp, uint32_t numSlots)
+{
+    traceFirstBody<true>(sc, wf, gp, numSlots);
 }
 
 // raygen.rgen:99-112 + sample loop control for a slot whose path has ended.
@@ -490,11 +553,18 @@ PT_DEV void pushRestarts(const Wavefront &wf, bool restart, uint32_t slot)
 
 // SORT: the material-sorted shade queue (below), chosen on the host for scenes that mix material types.  The plain kernels
 // carry neither its code nor its LDS: a kernel argument that switched it kept the sort's state live across the item loop.
-template <bool TEX, bool SORT>
+// FIRST: bounce 1 of the round renderWavefront starts.  The queue is the identity over all slots and is not read (the sorted
+// variant sorts positions); pixel, frame, RNG state, primary ray and differentials of a slot are recomputed from the launch
+// parameters with k_generate's calls in k_generate's order instead of being read from meta / rayO / rayD / diff (FirstClosestIO).
+template <bool TEX, bool SORT, bool FIRST>
 PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefront &wf, int qin, const BounceCtl &ctl);
 template <bool TEX>
 __global__ void __launch_bounds__(kBlock) k_shade(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
+template <typename WHICH, bool TEX> // k_shade<FirstBounce, TEX>
+__global__ void __launch_bounds__(kBlock) k_shade(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
 template <bool TEX>
+__global__ void __launch_bounds__(kBlock) k_shade_sorted(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
+template <typename WHICH, bool TEX>
 __global__ void __launch_bounds__(kBlock) k_shade_sorted(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl);
 // Three waves per SIMD (168 VGPRs): no VGPR spilled, no scratch; 4,703 static VALU instructions with the BSDF terms computed
 // once and the sort in its own kernel (6,162 before, 169 SGPRs spilled into VGPR lanes then, 82 now).  Four waves (128 VGPRs)
@@ -506,12 +576,22 @@ __global__ void __launch_bounds__(kBlock) k_shade_sorted(LaunchParams p, SceneVi
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade<false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<false, false>(p, sv, wf, qin, ctl);
+    shadeBody<false, false, false>(p, sv, wf, qin, ctl);
+}
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade<FirstBounce, false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<false, false, true>(p, sv, wf, qin, ctl);
 }
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade_sorted<false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<false, true>(p, sv, wf, qin, ctl);
+    shadeBody<false, true, false>(p, sv, wf, qin, ctl);
+}
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade_sorted<FirstBounce, false>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<false, true, true>(p, sv, wf, qin, ctl);
 }
 // the textured variant: 221 VGPRs = two waves per SIMD (round 1: a few registers past 256, i.e. ONE wave, held at two for four
 // spilled registers).  Three waves (168 VGPRs, 54 spilled, 164 B scratch) measure flat: atrium_like 725 / 730 -> 723 / 724.
@@ -521,14 +601,24 @@ __global__ void __launch_bounds__(kBlock) PT_SHADE_ATTR k_shade_sorted<false>(La
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade<true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<true, false>(p, sv, wf, qin, ctl);
+    shadeBody<true, false, false>(p, sv, wf, qin, ctl);
+}
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade<FirstBounce, true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<true, false, true>(p, sv, wf, qin, ctl);
 }
 template <>
 __global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade_sorted<true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
 {
-    shadeBody<true, true>(p, sv, wf, qin, ctl);
+    shadeBody<true, true, false>(p, sv, wf, qin, ctl);
 }
-template <bool TEX, bool SORT>
+template <>
+__global__ void __launch_bounds__(kBlock) PT_SHADE_TEX_ATTR k_shade_sorted<FirstBounce, true>(LaunchParams p, SceneView sv, Wavefront wf, int qin, BounceCtl ctl)
+{
+    shadeBody<true, true, true>(p, sv, wf, qin, ctl);
+}
+template <bool TEX, bool SORT, bool FIRST>
 PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefront &wf, int qin, const BounceCtl &ctl)
 {
     __shared__ uint32_t s_cnt[2], s_base[2];
@@ -576,7 +666,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
             uint32_t sl = kPadSlot, key = kKeys - 1u;
             if (i < count)
             {
-                sl = wf.queue[qin][i];
+                sl = FIRST ? i : wf.queue[qin][i];
                 const uint32_t pr = wf.hitPair[sl];
                 if (pr == 0xffffffffu)
                     key = 0u;
@@ -634,7 +724,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
         if (i < count)
         {
             // entries past the block's share of the queue were sorted last, with the dead slots
-            slot = SORT ? s_sorted[item * blockDim.x + threadIdx.x] : wf.queue[qin][i];
+            slot = SORT ? s_sorted[item * blockDim.x + threadIdx.x] : FIRST ? i : wf.queue[qin][i];
             if (slot != kPadSlot)
                 pair = wf.hitPair[slot];
             else
@@ -642,7 +732,23 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
         }
         if (pair != kDeadPair)
         {
-            uint4 meta = wf.meta[slot];
+            uint4 meta;
+            float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d4 = o4; // FIRST: rayO.w = MaxRoughness = 0, raygen.rgen:60
+            DiffRays diff;
+            if (FIRST)
+            {
+                uint32_t f, s;
+                slotFrame(p, slot, f, s);
+                const uint32_t pixel = slotPixel(p, s), frame = p.firstFrame + f;
+                uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
+                f3 o, d;
+                startSample<TEX>(p, pixel, rng, o, d, diff);
+                o4 = make_float4(o.x, o.y, o.z, 0.0f);
+                d4 = make_float4(d.x, d.y, d.z, 0.0f);
+                meta = make_uint4(rng, pixel, 0u, frame); // k_tail, k_apply_shadow, k_restart and k_finish_restarts read it
+            }
+            else
+                meta = wf.meta[slot];
             const float4 hit = wf.hit[slot];
             // first bounce of a sample: throughput = 1 (raygen.rgen:52); and of the first sample: radiance = 0 (:42)
             float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -655,16 +761,20 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
             if (pair == 0xffffffffu)
             {
                 // miss.rmiss:16-39: sky colour / skybox lookup, Pdf = -1 -> raygen.rgen:71-75
-                const float4 d4 = wf.rayD[slot];
+                if (!FIRST)
+                    d4 = wf.rayD[slot];
                 radiance = radiance + throughput * missEmissive(sv, F3(d4.x, d4.y, d4.z));
                 restart = finishSample(p, wf, slot, meta, radiance, nSamples, nRetries);
             }
             else
             {
-                const float4 o4 = wf.rayO[slot], d4 = wf.rayD[slot];
+                if (!FIRST)
+                {
+                    o4 = wf.rayO[slot];
+                    d4 = wf.rayD[slot];
+                }
                 HitOut out;
-                DiffRays diff;
-                if (TEX)
+                if (TEX && !FIRST)
                     diff = loadDiff(wf, slot);
                 Decal decal = noDecal();
                 if (TEX && wf.decalT)

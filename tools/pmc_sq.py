@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel sums of SQ counters from rocprofv3 --pmc passes (counter_collection.csv), per launch.
 Usage: pmc_sq.py [--json out.json --scene NAME --shape KEY --stats-alone kernel_stats_one_in_flight.csv] <dir> [<dir> ...]
-Each dir = one pass; counters of all passes are merged by kernel name (template variants kept apart).  The text summary goes to
+Each dir = one pass; counters of all passes are merged by kernel name (template variants kept apart, except that the first-bounce
+variant k_shade<FirstBounce, false> counts as a launch of k_shade<false>, and so on; where k_generate did not run -- the first bounce
+computes the primary rays -- its entry holds only the launch count, one per k_accumulate launch).  The text summary goes to
 stdout; --json also writes {kernel: {counter: value per launch, "launches": n}, "scene", "shape", "source_digest"}, which
 bench.py reads for roofline.shade (VALU wave-instructions per launch of k_shade against the chip's issue rate).  --stats-alone: the
 rocprofv3 --kernel-trace --stats summary of the same command with ONE frame in flight; every kernel's average duration there goes
@@ -34,7 +36,7 @@ def main():
     for d in args:
         for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(f)):
-                k = r["Kernel_Name"].split("(")[0]
+                k = r["Kernel_Name"].split("(")[0].replace("FirstBounce, ", "")
                 c = agg[k][r["Counter_Name"]]
                 c[0] += 1
                 c[1] += float(r["Counter_Value"])
@@ -49,10 +51,12 @@ def main():
             entry[name] = v / n
             entry["launches"] = n
         doc[k.replace("void ", "")] = entry
+    if "k_generate" not in doc and "k_accumulate" in doc:
+        doc["k_generate"] = {"launches": doc["k_accumulate"]["launches"]}
     if opts["--stats-alone"] and os.path.exists(opts["--stats-alone"]):
         for r in csv.DictReader(open(opts["--stats-alone"])):
             k = r["Name"].split("(")[0].replace("void ", "")
-            if k in doc:
+            if k in doc and "FirstBounce" not in k:  # (the first-bounce variants have rows of their own in the summary: not folded)
                 doc[k]["rocprof_ms_alone"] = float(r["AverageNs"]) * 1e-6
                 doc[k]["rocprof_calls_alone"] = int(r["Calls"])
     if opts["--json"]:

@@ -21,6 +21,10 @@ So the factor is per kernel (FETCH_FACTOR below):
   1   k_shade, as a LOWER bound: divergent 272-byte shading records and texels (factor 1) beside coalesced path state (factor 2);
       `hbm_bytes_per_launch_upper` carries the factor-2 figure of every kernel (what rounds 1-4 reported)
 hbm_bytes = (factor * FETCH_SIZE + WRITE_SIZE) * 1024.
+The first-bounce variants (k_trace_closest<FirstBounce, ..>, k_shade<FirstBounce, ..>) fold into the base kernel's entry like every
+template variant.  On the schedule without k_generate (the default; PTX_FIRST_BOUNCE=0 brings it back) the document still carries a
+k_generate entry -- zero bytes, one launch per k_accumulate launch, i.e. per step: bench.py --full takes the frame count of a traffic
+document from it.
 """
 import collections
 import csv
@@ -73,6 +77,9 @@ def main():
         kk = k.replace("ptd::", "")
         out[k] = {"launches": n, "fetch_size_kib_per_launch": f_kib, "write_size_kib_per_launch": w_kib, "fetch_factor": fetch_factor(kk),
                   "hbm_bytes_per_launch": (fetch_factor(kk) * f_kib + w_kib) * 1024.0, "hbm_bytes_per_launch_upper": (2.0 * f_kib + w_kib) * 1024.0}
+    if "k_generate" not in out and "k_accumulate" in out:  # no k_generate in the trace: the first bounce computes the primary rays
+        out["k_generate"] = {"launches": out["k_accumulate"]["launches"], "fetch_size_kib_per_launch": 0.0, "write_size_kib_per_launch": 0.0,
+                             "fetch_factor": fetch_factor("k_generate"), "hbm_bytes_per_launch": 0.0, "hbm_bytes_per_launch_upper": 0.0}
     ranked = sorted(out.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"] * kv[1]["launches"])
     out["calibration"] = "profiles/r05_fetch_size_calibration.txt: FETCH_SIZE / known bytes = 0.500 coalesced float4 stream, 1.000 one 64-B record per lane"
     out["source_digest"] = source_digest()
