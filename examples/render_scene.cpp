@@ -8,10 +8,13 @@
 //       -Ipath-tracing_amd/host -Lpath-tracing_amd -lptx_hip -Wl,-rpath,'$ORIGIN/../path-tracing_amd' -o examples/render_scene
 //   examples/render_scene default 640 360 16 4 out.png
 //   examples/render_scene default 640 360 1 4 normals.png --debug-mode 2    (the debug view instead: PTX_DEBUG_MODE_*)
+//   examples/render_scene default 640 360 16 4 screen.png --present 1280x720          (the screen path: the frame as an SDR window of that size shows it)
+//   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
 #include <cmath>
 #include <cstdio>
 #include <filesystem>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 
 #include "ExampleScenes.h"
@@ -26,6 +29,30 @@ int main(int argc, char **argv)
         if (std::string(argv[i]) == "--debug-mode")
         {
             debugMode = std::atoi(argv[i + 1]);
+            for (int k = i; k + 2 < argc; k++)
+                argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
+    uint32_t presentWidth = 0, presentHeight = 0; // --present WxH [--hdr10]: the file holds what a window of that extent shows
+    bool hdr10 = false;
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--hdr10")
+        {
+            hdr10 = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
+    for (int i = 1; i + 1 < argc; i++)
+        if (std::string(argv[i]) == "--present")
+        {
+            if (std::sscanf(argv[i + 1], "%ux%u", &presentWidth, &presentHeight) != 2 || !presentWidth || !presentHeight)
+            {
+                std::fprintf(stderr, "error: --present takes WxH\n");
+                return 1;
+            }
             for (int k = i; k + 2 < argc; k++)
                 argv[k] = argv[k + 2];
             argc -= 2;
@@ -60,7 +87,34 @@ int main(int argc, char **argv)
         // post-process chain + OutputSaver: the format follows the file extension like UserInterface.cpp:1060-1074
         const std::string ext = std::filesystem::path(out).extension().string();
         const OutputFormat format = ext == ".hdr" ? OutputFormat::Hdr : ext == ".tga" ? OutputFormat::Tga : OutputFormat::Png;
-        RendererHip::SaveOutput({ out, { width, height }, 0, format });
+        if (presentWidth)
+        {
+            // no ImGui here: the UI image is a title bar, opaque on the left and absent on the right
+            std::vector<uint8_t> ui(static_cast<size_t>(presentWidth) * presentHeight * 4, 0);
+            for (uint32_t y = 0; y < (presentHeight < 16 ? presentHeight : 16u); y++)
+                for (uint32_t x = 0; x < presentWidth / 2; x++)
+                {
+                    uint8_t *t = &ui[(static_cast<size_t>(y) * presentWidth + x) * 4];
+                    t[0] = 40; t[1] = 44; t[2] = 52; t[3] = 255;
+                }
+            RendererHip::UpdateHdr(hdr10);
+            RendererHip::Present(presentWidth, presentHeight, ui.data());
+            const std::vector<std::byte> screen = RendererHip::ReadPresent();
+            if (hdr10)
+            {
+                FILE *f = std::fopen(out, "wb");
+                if (!f || std::fwrite(screen.data(), 1, screen.size(), f) != screen.size())
+                    throw error(std::string("cannot write ") + out);
+                std::fclose(f);
+                uint32_t word = 0;
+                std::memcpy(&word, &screen[(static_cast<size_t>(presentHeight / 2) * presentWidth + presentWidth / 2) * 4], 4);
+                std::printf("HDR10 centre pixel: R %u G %u B %u (10-bit ST 2084 codes, BT.2020)\n", word & 1023u, (word >> 10) & 1023u, (word >> 20) & 1023u);
+            }
+            else if (!OutputSaver::WriteImage({ out, { presentWidth, presentHeight }, 0, OutputFormat::Png }, screen))
+                throw error(std::string("cannot write ") + out);
+        }
+        else
+            RendererHip::SaveOutput({ out, { width, height }, 0, format });
         std::printf("scene %s %ux%u %u spp depth %u: mean radiance %.9g -> %s\n", name.c_str(), width, height, spp, bounces,
                     sum / (3.0 * width * height), out);
         RendererHip::Shutdown();

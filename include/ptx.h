@@ -709,6 +709,53 @@ PTX_API int ptx_render_debug(PtxRenderer *r, const PtxRaygenUniformData *uniform
  * which = 1: getRandomColor (:143-162), in: x (u32 bits), out: rgb. */
 PTX_API int ptx_test_debug_eval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n);
 
+/* ------------------------------------------------------------------------- */
+/* Screen path (row D15): what turns the post-processed frame into the image   */
+/* the window shows -- the final blit of Renderer::RecordPostProcessCommands   */
+/* (Renderer.cpp:1075-1085), RecordUICommands (:1089-1203: toneMapping.comp    */
+/* and uiComposition.comp on the screen image, blit to the swapchain image),   */
+/* Renderer::UpdateHdr / Swapchain::IsHdr (Swapchain.cpp:317-340)              */
+/* ------------------------------------------------------------------------- */
+
+/* the swapchain's format */
+enum { PTX_PRESENT_R8G8B8A8_SRGB = 0, PTX_PRESENT_B8G8R8A8_SRGB = 1,
+       PTX_PRESENT_A2B10G10R10_UNORM = 2,   /* HDR10 */
+       PTX_PRESENT_R16G16B16A16_SFLOAT = 3  /* the screen image itself, 4 x binary16 per pixel */ };
+enum { PTX_PRESENT_UI_ON_DEVICE = 1u };     /* PtxPresentDesc.ui is device memory and is read in place */
+typedef struct PtxPresentDesc {
+    uint32_t width, height;     /* screen extent, 1 .. 16384 each */
+    uint32_t format;            /* PTX_PRESENT_* */
+    uint32_t toneMappingMode;   /* PtxToneMappingMode; HDR = the surface is HDR10 */
+    const void *ui;             /* RGBA8 UNORM, width*height*4 bytes, row-major; NULL = alpha 0 everywhere */
+    uint32_t flags;             /* PTX_PRESENT_* flag bits */
+    uint32_t reserved;          /* 0 */
+} PtxPresentDesc;
+
+/* One frame of the screen path, on the images the last ptx_postprocess left behind (whatever tone-mapping mode that call was
+ * given; its uniform supplies BloomIntensity).  Per screen pixel: the composed colour (composition.comp, not tone-mapped) is
+ * scaled from the render extent to the screen extent by a linear blit with clamp to edge -- the Vulkan specification's filter, not
+ * a bit-match of a GPU's; an axis whose two extents are equal is not filtered, so a frame shown at its own size is the same bits
+ * as ptx_read_output's -- then tone-mapped (toneMapping.comp), then uiComposition.comp:49-63: where the UI's alpha is non-zero,
+ * srgb_to_linear(ui.rgb) * 0.99 + colour * 0.01; in HDR mode linear_to_hdr10(colour, 203) (BT.709 -> BT.2020, ST 2084); alpha 1.
+ * Every store of the reference into its rgba16f screen image is a rounding to binary16 here.  The result is stored in `format`:
+ * the sRGB formats encode as ptx_read_output(PTX_OUTPUT_RGBA8_SRGB) does, bytes R G B A or B G R A; A2B10G10R10 packs
+ * floor(clamp(c, 0, 1) * 1023 + 0.5) as R | G << 10 | B << 20 | 3 << 30; R16G16B16A16 is the four binary16 bit patterns.
+ * The UI image is the caller's (ImGui stays outside) and is not scaled.  Asynchronous on the render stream: a host `ui` is copied on
+ * that stream into a buffer the renderer keeps and must stay unchanged until the stream has passed the call (ptx_synchronize,
+ * ptx_read_present).  Neither the accumulation image nor ptx_read_output's image is touched.
+ * PTX_ERROR_NOT_READY: no ptx_postprocess since the last ptx_resize, or a shard accumulation buffer is bound.
+ * PTX_ERROR_INVALID_ARGUMENT: a zero or too large extent, an unknown format, mode or flag bit, reserved != 0, an 8-bit sRGB format
+ * with the HDR mode or A2B10G10R10 with the SDR mode (the reference never pairs either).  A refused call leaves the previous
+ * present image intact; ptx_resize keeps it too. */
+PTX_API int ptx_present(PtxRenderer *r, const PtxPresentDesc *desc);
+/* The image of the last ptx_present, row-major, top row first: width*height*4 bytes, *8 for R16G16B16A16.  Synchronous, like
+ * ptx_read_output.  PTX_ERROR_INVALID_ARGUMENT: a buffer of another size, or nothing presented yet. */
+PTX_API int ptx_read_present(PtxRenderer *r, void *host, size_t bytes);
+/* ... or its device address and size, for a host that shares the buffer with its window system (NULL / 0 before any present;
+ * a present with a larger image may move it). */
+PTX_API void *ptx_device_present_ptr(PtxRenderer *r);
+PTX_API size_t ptx_present_bytes(const PtxRenderer *r);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

@@ -62,6 +62,7 @@ PTX_SYMBOLS = [
     "ptx_postprocess", "ptx_read_output", "ptx_write_accumulation", "ptx_update_animation",
     "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency",
     "ptx_render_debug", "ptx_test_debug_eval",
+    "ptx_present", "ptx_read_present", "ptx_device_present_ptr", "ptx_present_bytes",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -144,6 +145,17 @@ class DebugViewDesc(C.Structure):
 DEBUG_RAYGEN_FORCE_OPAQUE, DEBUG_RAYGEN_CULL_BACK_FACES = 1, 2
 DEBUG_HIT_DISABLE_COLOR_TEXTURE, DEBUG_HIT_DISABLE_NORMAL_TEXTURE, DEBUG_HIT_DISABLE_MIP_MAPS, DEBUG_HIT_DISABLE_SHADOWS = 1, 2, 4, 8
 DEBUG_EVAL_LIGHT_CONTRIBUTION, DEBUG_EVAL_RANDOM_COLOR = 0, 1  # `which` of ptx_test_debug_eval
+
+
+
+class PresentDesc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32), ("toneMappingMode", C.c_uint32),
+                ("ui", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# PTX_PRESENT_* of include/ptx.h: the swapchain's format, and the flag bit
+PRESENT_R8G8B8A8_SRGB, PRESENT_B8G8R8A8_SRGB, PRESENT_A2B10G10R10_UNORM, PRESENT_R16G16B16A16_SFLOAT = range(4)
+PRESENT_UI_ON_DEVICE = 1
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -336,6 +348,12 @@ def load_hip() -> C.CDLL:
         lib.ptx_texture_residency.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.ptx_render_debug.argtypes = [P, C.POINTER(RaygenUniformData), C.POINTER(LightsUbo), C.POINTER(DebugViewDesc)]
         lib.ptx_test_debug_eval.argtypes = [P, C.c_uint32, P, P, C.c_uint32]
+        lib.ptx_present.argtypes = [P, C.POINTER(PresentDesc)]
+        lib.ptx_read_present.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_present_ptr.argtypes = [P]
+        lib.ptx_device_present_ptr.restype = P
+        lib.ptx_present_bytes.argtypes = [P]
+        lib.ptx_present_bytes.restype = C.c_size_t
         _hip = lib
     return _hip
 
@@ -557,6 +575,48 @@ class Renderer:
         out = np.empty((self.height, self.width, 4), dtype=np.float32 if fmt == OUTPUT_RGBA32F else np.uint8)
         self._check(self.lib.ptx_read_output(self.handle, fmt, out.ctypes.data, out.nbytes))
         return out
+
+    def present(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None):
+        """ptx_present: the last postprocess()' frame at the screen extent width x height in the swapchain format `fmt`, under
+        the UI image `ui`: None, an H x W x 4 uint8 array (RGBA8 UNORM), or a torch tensor of that shape on the renderer's device,
+        which is read in place."""
+        flags, ptr = 0, None
+        if ui is not None and hasattr(ui, "data_ptr"):
+            if not ui.is_cuda:
+                ui = ui.numpy()
+            else:
+                import torch
+                if ui.dtype != torch.uint8 or tuple(ui.shape) != (height, width, 4) or not ui.is_contiguous():
+                    raise ValueError("ui must be a contiguous height x width x 4 uint8 tensor")
+                flags, ptr = PRESENT_UI_ON_DEVICE, ui.data_ptr()
+        if ui is not None and not flags:
+            ui = np.ascontiguousarray(ui, dtype=np.uint8)
+            if ui.shape != (height, width, 4):
+                raise ValueError("ui must be height x width x 4 uint8")
+            ptr = ui.ctypes.data
+        self._present_ui = ui  # the copy is asynchronous: keep the image alive
+        d = PresentDesc(width, height, fmt, tone_mapping, ptr, flags, 0)
+        self._check(self.lib.ptx_present(self.handle, C.byref(d)))
+        self._present = (width, height, fmt)
+
+    def read_present(self) -> np.ndarray:
+        """The image of the last present(): H x W x 4 uint8 (bytes in the format's order), H x W uint32 for A2B10G10R10,
+        H x W x 4 float16 for R16G16B16A16."""
+        if not getattr(self, "_present", None):
+            raise PtxError("status 1: ptx_read_present: nothing presented yet (call ptx_present)")
+        w, h, fmt = self._present
+        if fmt == PRESENT_A2B10G10R10_UNORM:
+            out = np.empty((h, w), np.uint32)
+        else:
+            out = np.empty((h, w, 4), np.float16 if fmt == PRESENT_R16G16B16A16_SFLOAT else np.uint8)
+        self._check(self.lib.ptx_read_present(self.handle, out.ctypes.data, out.nbytes))
+        return out
+
+    def present_ptr(self) -> int:
+        return int(self.lib.ptx_device_present_ptr(self.handle) or 0)
+
+    def present_bytes(self) -> int:
+        return int(self.lib.ptx_present_bytes(self.handle))
 
     def stats(self) -> Stats:
         s = Stats()

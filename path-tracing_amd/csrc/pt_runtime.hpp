@@ -19,6 +19,7 @@
 #include "pt_bvh_build.hpp"
 #include "pt_debug_view.hpp"
 #include "pt_post.hpp"
+#include "pt_present.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -319,6 +320,11 @@ struct PtxRenderer
     DevBuf<float4> outLinear;        // tone-mapped image (OutputSaver's m_LinearImage)
     DevBuf<uint32_t> outSrgb8;
     bool outputReady = false;
+    // screen path (row D15): the swapchain image of the last ptx_present and the caller's UI image
+    PtxPostProcessingUniformData postUniform = {}; // of the last ptx_postprocess (composition.comp's BloomIntensity)
+    DevBuf<uint32_t> presentImage, presentUi;
+    uint32_t presentWidth = 0, presentHeight = 0, presentFormat = 0;
+    size_t presentBytes = 0; // 0: nothing presented yet
     float4 *boundImage = nullptr; // external accumulation buffer, if bound
     float4 *boundShard = nullptr; // ... or the dense tile-major shard buffer the samples are accumulated in (ptx_bind_shard_accumulation)
     size_t boundShardBytes = 0;
@@ -1037,6 +1043,7 @@ static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *unifo
         k_bloom_upsample<<<gridFor((size_t)L[i - 1].w * L[i - 1].h), kBlock, 0, r->stream>>>(L[i], L[i - 1]);
     k_compose_tonemap<<<gridFor(n), kBlock, 0, r->stream>>>(r->postRgb.p, L[0].rgb, n, *uniform, toneMappingMode, r->outLinear.p);
     HIP_TRY(r, hipGetLastError());
+    r->postUniform = *uniform;
     r->outputReady = true;
     return PTX_OK;
 }
@@ -1061,6 +1068,79 @@ static int readOutput(PtxRenderer *r, uint32_t outputFormat, void *host, size_t 
         k_encode_srgb8<<<gridFor(n), kBlock, 0, r->stream>>>(r->outLinear.p, n, r->outSrgb8.p);
         HIP_TRY(r, hipMemcpyAsync(host, r->outSrgb8.p, bytes, hipMemcpyDeviceToHost, r->stream));
     }
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+// The screen path: RecordPostProcessCommands' final blit + RecordUICommands (Renderer.cpp:1075-1203) in one launch of k_present
+static int present(PtxRenderer *r, const PtxPresentDesc *d)
+{
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: null argument");
+    if (!d->width || !d->height || d->width > 16384u || d->height > 16384u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: bad screen extent %ux%u (1 .. 16384 each)", d->width, d->height);
+    if (d->format > PTX_PRESENT_R16G16B16A16_SFLOAT || d->toneMappingMode > PTX_TONE_MAPPING_HDR || (d->flags & ~(uint32_t)PTX_PRESENT_UI_ON_DEVICE) || d->reserved)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: unknown format %u, mode %u or flags 0x%x, or reserved != 0", d->format, d->toneMappingMode, d->flags);
+    const bool hdr = d->toneMappingMode == PTX_TONE_MAPPING_HDR;
+    if ((hdr && d->format <= PTX_PRESENT_B8G8R8A8_SRGB) || (!hdr && d->format == PTX_PRESENT_A2B10G10R10_UNORM))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)");
+    if (!r->outputReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_present: call ptx_postprocess first");
+    if (r->boundShard)
+        return frameIsElsewhere(r, "ptx_present");
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t n = d->width * d->height;
+    const size_t words = (size_t)n * (d->format == PTX_PRESENT_R16G16B16A16_SFLOAT ? 2 : 1);
+    if (words > r->presentImage.n || !r->presentImage.p) // a failed allocation keeps the previous image
+    {
+        DevBuf<uint32_t> grown;
+        HIP_TRY(r, grown.alloc(words));
+        r->presentImage.swap(grown);
+    }
+    PresentArgs a;
+    a.post = r->postRgb.p;
+    a.bloom0 = r->bloomRgb.p; // level 0 of the chain
+    a.ui = static_cast<const uint32_t *>(d->ui);
+    a.out = r->presentImage.p;
+    a.u = r->postUniform;
+    a.W = r->width; a.H = r->height; a.SW = d->width; a.SH = d->height;
+    if (d->ui && !(d->flags & PTX_PRESENT_UI_ON_DEVICE))
+    {
+        HIP_TRY(r, r->presentUi.alloc(n));
+        HIP_TRY(r, hipMemcpyAsync(r->presentUi.p, d->ui, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
+        a.ui = r->presentUi.p;
+    }
+    const uint32_t grid = (n + kPresentBlock - 1) / kPresentBlock;
+    switch (d->format)
+    {
+    case PTX_PRESENT_R8G8B8A8_SRGB: k_present<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+    case PTX_PRESENT_B8G8R8A8_SRGB: k_present<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+    case PTX_PRESENT_A2B10G10R10_UNORM: k_present<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+    default:
+        if (hdr)
+            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a);
+        else
+            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a);
+    }
+    HIP_TRY(r, hipGetLastError());
+    r->presentWidth = d->width;
+    r->presentHeight = d->height;
+    r->presentFormat = d->format;
+    r->presentBytes = words * 4;
+    return PTX_OK;
+}
+
+static int readPresent(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: null argument");
+    if (!r->presentBytes)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: nothing presented yet (call ptx_present)");
+    if (bytes != r->presentBytes)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: buffer must be %zu bytes", r->presentBytes);
+    HIP_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipMemcpyAsync(host, r->presentImage.p, bytes, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;

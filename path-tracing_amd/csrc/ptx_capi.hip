@@ -257,6 +257,26 @@ int ptx_read_output(PtxRenderer *r, uint32_t outputFormat, void *host, size_t by
     return readOutput(r, outputFormat, host, bytes);
 }
 
+int ptx_present(PtxRenderer *r, const PtxPresentDesc *desc)
+{
+    return present(r, desc);
+}
+
+int ptx_read_present(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readPresent(r, host, bytes);
+}
+
+void *ptx_device_present_ptr(PtxRenderer *r)
+{
+    return r && r->presentBytes ? r->presentImage.p : nullptr;
+}
+
+size_t ptx_present_bytes(const PtxRenderer *r)
+{
+    return r ? r->presentBytes : 0;
+}
+
 int ptx_write_accumulation(PtxRenderer *r, const float *rgba, size_t bytes)
 {
     if (!r || !rgba || !imagePtr(r) || bytes != (size_t)r->width * r->height * sizeof(float4))

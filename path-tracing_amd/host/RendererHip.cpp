@@ -153,6 +153,31 @@ void RendererHip::SaveOutput(const OutputInfo &info)
         throw error("SaveOutput: cannot write " + info.Path.string());
 }
 
+static bool s_SurfaceIsHdr = false; // Swapchain::IsHdr()
+
+void RendererHip::UpdateHdr(bool isHdr)
+{
+    s_SurfaceIsHdr = isHdr;
+}
+
+// Renderer.cpp:928-1203 after the path-tracing pass
+void RendererHip::Present(uint32_t width, uint32_t height, const uint8_t *ui)
+{
+    const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
+                                             s_PostProcessSettings.BloomIntensity };
+    const uint32_t mode = s_SurfaceIsHdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR; // Renderer.cpp:737-742
+    Check(ptx_postprocess(s_Renderer, &u, mode));
+    const PtxPresentDesc desc = { width, height, s_SurfaceIsHdr ? (uint32_t)PTX_PRESENT_A2B10G10R10_UNORM : (uint32_t)PTX_PRESENT_R8G8B8A8_SRGB, mode, ui, 0u, 0u };
+    Check(ptx_present(s_Renderer, &desc));
+}
+
+std::vector<std::byte> RendererHip::ReadPresent()
+{
+    std::vector<std::byte> bytes(ptx_present_bytes(s_Renderer));
+    Check(ptx_read_present(s_Renderer, bytes.data(), bytes.size()));
+    return bytes;
+}
+
 std::vector<float> RendererHip::ReadAccumulationImage()
 {
     std::vector<float> image(static_cast<size_t>(s_Width) * s_Height * 4);

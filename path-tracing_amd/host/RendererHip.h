@@ -2,8 +2,9 @@
 // (Path-Tracing/Renderer/Renderer.h:42-85) on top of the C-ABI in include/ptx.h, so
 // host code written against the static Renderer class keeps its call sequence:
 //   Init -> UpdateSceneData -> OnResize -> [SetSettings] -> Render ... -> Shutdown.
-// The path-tracing pass and the output stage (post-processing chain + OutputSaver, row N4) are
-// implemented; UI and presentation stay with the reference's Vulkan renderer (out of scope).
+// The path-tracing pass, the output stage (post-processing chain + OutputSaver, row N4) and the screen path (row D15:
+// scaling blit, tone mapping, UI composition, HDR10 encode, store in the swapchain's format) are implemented; the UI image
+// itself (ImGui), the window and the swapchain stay with the host.
 #pragma once
 
 #include <memory>
@@ -55,6 +56,17 @@ public:
     static void SetPostProcessSettings(const PostProcessSettings &settings);
     // RecordPostProcessCommands + RecordSaveOutputCommands on the current running sum, then OutputSaver::WriteImage
     static void SaveOutput(const OutputInfo &info);
+
+    // Renderer::UpdateHdr (the swapchain was recreated, Application.cpp:281-286): Swapchain::IsHdr() of the surface Present draws
+    // to.  true: the HDR tone-mapping mode and A2B10G10R10_UNORM (HDR10, Swapchain.cpp:317-340); false: SDR and R8G8B8A8_SRGB.
+    static void UpdateHdr(bool isHdr);
+    // The rest of a frame after the path-tracing pass (RecordPostProcessCommands with its final blit + RecordUICommands,
+    // Renderer.cpp:928-1203): post-processes the current running sum with the PostProcessSettings and presents it at the
+    // swapchain's extent under the UI image (RGBA8 UNORM, width * height * 4 bytes, nullptr: none).  Asynchronous: `ui` must
+    // stay unchanged until ReadPresent or the next read-back.
+    static void Present(uint32_t width, uint32_t height, const uint8_t *ui = nullptr);
+    // the presented image: width * height * 4 bytes, R G B A per pixel or one packed A2B10G10R10 word
+    static std::vector<std::byte> ReadPresent();
 
     static uint32_t GetTotalSamples();
     static std::vector<float> ReadAccumulationImage(); // RGBA32F running sum
