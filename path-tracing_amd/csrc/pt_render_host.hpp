@@ -33,8 +33,8 @@ static int ensureSlots(PtxRenderer *r, size_t slots)
     }
     HIP_TRY(r, ps.slotRad.alloc(want));
     HIP_TRY(r, ps.rayO.alloc(want)); HIP_TRY(r, ps.rayD.alloc(want)); HIP_TRY(r, ps.thr.alloc(want)); HIP_TRY(r, ps.rad.alloc(want));
-    HIP_TRY(r, ps.hit.alloc(want)); HIP_TRY(r, ps.shO.alloc(want)); HIP_TRY(r, ps.shD.alloc(want)); HIP_TRY(r, ps.shC.alloc(want));
-    HIP_TRY(r, ps.meta.alloc(want)); HIP_TRY(r, ps.hitPair.alloc(want));
+    HIP_TRY(r, ps.hit.alloc(want)); HIP_TRY(r, ps.shD.alloc(want)); HIP_TRY(r, ps.shC.alloc(want));
+    HIP_TRY(r, ps.hitPair.alloc(want));
     HIP_TRY(r, ps.queue0.alloc(want)); HIP_TRY(r, ps.queue1.alloc(want)); HIP_TRY(r, ps.shadowQueue.alloc(want)); HIP_TRY(r, ps.shadowResult.alloc(want));
     HIP_TRY(r, ps.restartQueue.alloc(want));
     return PTX_OK;
@@ -145,6 +145,8 @@ static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t
 // shadow(b) only adds into rad[slot], which shade(b + 1) reads -- not closest(b + 1) -- so it runs beside the next
 // traversal; k_tail, where the schedule has one, follows it in stream order (the NEE adds it continues from have
 // landed): the last shadow query before the tail needs no event of its own.
+// shadow(b) also READS rayO[slot]: the shadow ray leaves the point the continuation ray leaves, and the record holds it once.
+// closest(b + 1) beside it only reads it too; shade(b + 1) overwrites it, so its wait for aux(b) protects rayO as well as rad.
 // tail: 0 = none, 1 = k_tail takes the queue shade(b) filled if it holds at most pl.tailBelow paths, 2 = takes it whatever
 // its length (nothing is enqueued behind this bounce).
 static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, int tail, bool fresh)
@@ -163,7 +165,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
             k_trace_closest<decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
     });
     HIP_TRY(r, hipEventRecord(ev.t1, S));
-    if (b > 1) // shade reads rad[slot]: the previous bounce's shadow adds must have landed
+    if (b > 1) // shade reads rad[slot] and overwrites rayO[slot]: the previous bounce's shadow adds must have landed, its rays been read
         HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
     const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
     withFlag(pl.mode >= 1, [&](auto TEXTURED) {

@@ -203,8 +203,7 @@ struct SceneData
 // Per-slot state of the paths in flight (the Wavefront of pt_wavefront.hpp, owned), grown by ensureSlots (pt_render_host.hpp).
 struct PathState
 {
-    DevBuf<float4> rayO, rayD, thr, rad, hit, shO, shD, shC, slotRad;
-    DevBuf<uint4> meta;
+    DevBuf<float4> rayO, rayD, thr, rad, hit, shD, shC, slotRad;
     DevBuf<uint32_t> hitPair, queue0, queue1, shadowQueue, restartQueue;
     DevBuf<uint8_t> shadowResult;
     DevBuf<float4> diffs; // three planes of ray differentials, only for scenes with textures (kernel mode >= 1)
@@ -213,8 +212,8 @@ struct PathState
     {
         Wavefront wf;
         wf.rayO = rayO.p; wf.rayD = rayD.p; wf.thr = thr.p; wf.rad = rad.p;
-        wf.meta = meta.p; wf.hit = hit.p; wf.hitPair = hitPair.p;
-        wf.shO = shO.p; wf.shD = shD.p; wf.shC = shC.p; wf.slotRad = slotRad.p;
+        wf.hit = hit.p; wf.hitPair = hitPair.p;
+        wf.shD = shD.p; wf.shC = shC.p; wf.slotRad = slotRad.p;
         wf.queue[0] = queue0.p; wf.queue[1] = queue1.p; wf.shadowQueue = shadowQueue.p; wf.shadowResult = shadowResult.p;
         wf.restartQueue = restartQueue.p;
         for (int k = 0; k < 3; k++)

@@ -17,7 +17,9 @@
 //   k_accumulate      raygen.rgen:115-117  image += radiance, in frame order
 //
 // Every path slot is (frame, pixel); its state lives in SoA arrays in HBM; queues hold
-// slot indices and are compacted by wave-aggregated atomics.  A bring-up MEGAKERNEL
+// slot indices and are compacted by wave-aggregated atomics.  The state is 16-byte records only, each written by one kernel
+// and read once by the next (struct Wavefront): the RNG state and the bounce / sample counters ride in their spare .w words,
+// the shadow ray shares its origin with the continuation ray, pixel and frame are recomputed from the slot.  A bring-up MEGAKERNEL
 // (one thread per slot running the loop 1:1) shares all device functions and is kept as
 // the in-tree A/B reference of the wavefront.
 //
@@ -71,16 +73,18 @@ template <typename T> struct Stream // wf.rayO[slot] reads and writes as before;
 
 struct Wavefront // device pointers of the per-slot state (SoA)
 {
-    Stream<float4> rayO;   // origin.xyz, w = MaxRoughness (payload.MaxRoughness)
-    Stream<float4> rayD;   // direction.xyz
-    Stream<float4> thr;    // throughput.rgb
+    // The two words of a path that are no float -- the RNG state and bounce | smpl << 16 -- ride as bit patterns in the .w of
+    // records that travel anyway (there is no record of their own); pixel and frame are functions of the slot (slotFrame,
+    // slotPixel) and are stored nowhere.
+    Stream<float4> rayO;   // origin.xyz = origin of the shadow ray of the bounce before; w = MaxRoughness (payload.MaxRoughness),
+                           // or, for a path that ended with its shadow query pending, the RNG state (k_apply_shadow's restarts)
+    Stream<float4> rayD;   // direction.xyz, w = bounce | smpl << 16, or kDeadWord (k_generate: slot outside the image)
+    Stream<float4> thr;    // throughput.rgb, w = RNG state
     Stream<float4> rad;    // radiance.rgb accumulated over the samples of this launch
-    Stream<uint4> meta;    // x = rngState, y = pixel (y*W+x) or 0xffffffff, z = bounce | smpl<<16, w = frame
     Stream<float4> hit;    // t, u, v, triangle slot in leaf order (bits)
     Stream<uint32_t> hitPair;
-    Stream<float4> shO;    // shadow origin.xyz, w = tmax (LightDistance)
-    Stream<float4> shD;    // shadow direction.xyz, w = 1 if the path ends after this bounce
-    Stream<float4> shC;    // NEE contribution throughput * DirectLight / DirectLightPdf
+    Stream<float4> shD;    // shadow direction.xyz, w = tmax (LightDistance), sign bit set if the path ends after this bounce
+    Stream<float4> shC;    // NEE contribution throughput * DirectLight / DirectLightPdf, w = bounce | smpl << 16
     Stream<float4> slotRad; // final radiance of the slot (consumed by k_accumulate)
     Stream<float4> decal;   // nearest ignored any-hit candidate: (triangle slot, u, v, pair) -- k_shade fetches its colour and alpha
     Stream<float> decalT;   // (payload.LightDirection / LightDistance) if the hit lies behind it; null unless the scene has non-opaque
@@ -314,10 +318,24 @@ PT_DEV void blockAddCounter(uint32_t *__restrict__ counter, uint32_t v)
 #endif
 constexpr uint32_t kShadeItems = PT_SHADE_ITEMS; // queue entries per thread per block-wide append in k_shade
 constexpr uint32_t kDeadPair = 0xfffffffeu; // hitPair of a slot outside the image (ragged edge tiles)
+// rayD.w of such a slot under PTX_FIRST_BOUNCE=0: the one pattern bounce | smpl << 16 never takes.  A stored smpl is below
+// SampleCount, and renderImpl (pt_render_host.hpp) refuses SampleCount > 0xffff, so the upper half of a live word is at most
+// 0xfffe.  The sign bit alone would not do -- smpl >= 0x8000 sets it in a live word -- so ClosestIO::load compares the whole
+// pattern; as floats the words are denormals and NaNs, and no float comparison is made on them anywhere.
+constexpr uint32_t kDeadWord = 0xffffffffu;
+
+// pixel (or 0xffffffff) of a slot: what k_generate and the first bounce's kernels start a slot from, and what the kernels
+// that start a LATER sample of it (k_restart, k_tail, k_finish_restarts) recompute instead of reading it from the slot state
+PT_DEV uint32_t pixelOfSlot(const LaunchParams &p, uint32_t slot)
+{
+    uint32_t f, s;
+    slotFrame(p, slot, f, s);
+    return slotPixel(p, s);
+}
 
 // The schedule of rounds 1-6 (PTX_FIRST_BOUNCE=0; the default computes all this in the first bounce's kernels, FirstClosestIO).
 // No queue atomics here: queue 0 is the identity over all slots (the host sets its count);
-// slots of edge tiles that fall outside the image are flagged dead through rayD.w < 0.
+// slots of edge tiles that fall outside the image are flagged dead through rayD.w = kDeadWord.
 __global__ void __launch_bounds__(kBlock) k_generate(LaunchParams p, Wavefront wf)
 {
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < p.numSlots; slot += gridDim.x * blockDim.x)
@@ -326,25 +344,23 @@ __global__ void __launch_bounds__(kBlock) k_generate(LaunchParams p, Wavefront w
         slotFrame(p, slot, f, s);
         const uint32_t pixel = slotPixel(p, s);
         const uint32_t frame = p.firstFrame + f;
-        uint4 meta = make_uint4(0u, pixel, 0u, frame);
         wf.queue[0][slot] = slot;
         if (pixel != 0xffffffffu)
         {
             uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
             f3 o, d;
             startSlotSample(p, wf, slot, pixel, rng, o, d);
-            meta.x = rng;
             wf.rayO[slot] = make_float4(o.x, o.y, o.z, 0.0f); // MaxRoughness = 0, raygen.rgen:60
-            wf.rayD[slot] = make_float4(d.x, d.y, d.z, 0.0f);
-            // thr[slot] = 1 and rad[slot] = 0 are implied by meta.z == 0 (first bounce of the first sample): 32 bytes per
-            // slot neither written here nor read by the first k_shade
+            wf.rayD[slot] = make_float4(d.x, d.y, d.z, 0.0f); // bounce | smpl << 16 = 0
+            wf.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(rng)); // raygen.rgen:52
+            // rad[slot] = 0 is implied by rayD.w == 0 (first bounce of the first sample): neither written here nor read by
+            // the first k_shade
         }
         else
         {
-            wf.rayD[slot] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+            wf.rayD[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kDeadWord));
             wf.slotRad[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
-        wf.meta[slot] = meta;
     }
 }
 
@@ -362,7 +378,7 @@ struct ClosestIO
     PT_DEV bool load(uint32_t item, f3 &o, f3 &d, float &tmin, float &tmax)
     {
         const float4 d4 = wf.rayD[slot];
-        if (d4.w < 0.0f)
+        if (__float_as_uint(d4.w) == kDeadWord)
         {
             wf.hitPair[slot] = kDeadPair;
             return false;
@@ -433,7 +449,7 @@ PT_DEV void traceClosestBody(const TraceScene &sc, const Wavefront &wf, int qin,
 }
 
 // The first bounce of a launch.  The primary ray of a slot is a pure function of (slot, launch parameters): this IO computes it
-// where k_generate used to write 52 bytes per slot (queue entry, rayO, rayD, meta) for the first k_trace_closest and k_shade to
+// where k_generate used to write 52 bytes per slot (queue entry, rayO, rayD, RNG state and counters) for the first k_trace_closest and k_shade to
 // read back -- a fifth of a chess_like step's bytes, a full-machine streaming launch per frame and one dependent load at the
 // head of every primary ray's chain.  The queue is the identity over all slots (kHasQueue = false: the item is the slot).
 // The parameters are read through a pointer (the renderer's device copy, k_upload_lights): passed by value the camera matrices
@@ -511,10 +527,12 @@ __global__ void __launch_bounds__(kBlock) PT_ALPHA_CLOSEST_ATTR k_trace_closest<
 // The ray is NOT constructed here: the camera matrices, the lens and the differential code would sit in the register
 // and instruction-cache budget of the shading and traversal kernels for a path the canonical schedule
 // (SampleCount = 1) takes only after a NaN.
-PT_DEV bool finishSample(const LaunchParams &p, const Wavefront &wf, uint32_t slot, uint4 &meta, f3 &radiance,
+// `state` = bounce | smpl << 16 of the path that ended; where true is returned it becomes that of the next sample, and the
+// caller hands it on with the RNG state (storeRestart).
+PT_DEV bool finishSample(const LaunchParams &p, const Wavefront &wf, uint32_t slot, uint32_t &state, f3 &radiance,
                          uint32_t &nSamples, uint32_t &nRetries)
 {
-    uint32_t smpl = meta.z >> 16;
+    uint32_t smpl = state >> 16;
     nSamples++;
     if (badRadiance(radiance))
     {
@@ -526,12 +544,25 @@ PT_DEV bool finishSample(const LaunchParams &p, const Wavefront &wf, uint32_t sl
         smpl = smpl + 1;
     if (smpl < p.u.SampleCount)
     {
-        meta.z = smpl << 16; // bounce = 0
+        state = smpl << 16; // bounce = 0
         wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
         return true;
     }
     wf.slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
     return false;
+}
+
+// What a slot in the restart queue hands to k_restart / k_finish_restarts beside rad[slot]: the RNG state, carried on, and
+// smpl << 16 of its next sample, as single words where a live path has them (thr.w, rayD.w).  Rare in a canonical launch (a NaN).
+PT_DEV void storeRestart(const Wavefront &wf, uint32_t slot, uint32_t rng, uint32_t state)
+{
+    wf.thr.p[slot].w = __uint_as_float(rng);
+    wf.rayD.p[slot].w = __uint_as_float(state);
+}
+PT_DEV void loadRestart(const Wavefront &wf, uint32_t slot, uint32_t &rng, uint32_t &state)
+{
+    rng = __float_as_uint(wf.thr.p[slot].w);
+    state = __float_as_uint(wf.rayD.p[slot].w);
 }
 
 // Appends the slots of the calling lanes (restart == true) to the restart queue with one atomic per wave.  May be
@@ -555,7 +586,7 @@ PT_DEV void pushRestarts(const Wavefront &wf, bool restart, uint32_t slot)
 // carry neither its code nor its LDS: a kernel argument that switched it kept the sort's state live across the item loop.
 // FIRST: bounce 1 of the round renderWavefront starts.  The queue is the identity over all slots and is not read (the sorted
 // variant sorts positions); pixel, frame, RNG state, primary ray and differentials of a slot are recomputed from the launch
-// parameters with k_generate's calls in k_generate's order instead of being read from meta / rayO / rayD / diff (FirstClosestIO).
+// parameters with k_generate's calls in k_generate's order instead of being read from rayO / rayD / thr / diff (FirstClosestIO).
 template <bool TEX, bool SORT, bool FIRST>
 PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefront &wf, int qin, const BounceCtl &ctl);
 template <bool TEX>
@@ -646,7 +677,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
       // by side) 1,313 -> 1,536 Msamples/s, k_shade 8.06 -> 6.29 ms; scenes of ONE material type pay for the sort and get
       // nothing back (temple_like 614 -> 600, chess_like +-0.5 %), hence the two kernels (k_shade_sorted for mixed scenes).
       __shared__ uint32_t s_sorted[SORT ? kBlock * kShadeItems : 1];
-      constexpr uint32_t kPadSlot = 0xffffffffu; // never a slot: 184 B of state per slot bound the count far below
+      constexpr uint32_t kPadSlot = 0xffffffffu; // never a slot: 152 B of state per slot bound the count far below
       if (SORT)
       {
         constexpr uint32_t kKeys = 9, kWaves = kBlock / 64;
@@ -732,47 +763,47 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
         }
         if (pair != kDeadPair)
         {
-            uint4 meta;
+            uint32_t rng, state; // state = bounce | smpl << 16
             float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d4 = o4; // FIRST: rayO.w = MaxRoughness = 0, raygen.rgen:60
+            // first bounce of a sample: throughput = 1 (raygen.rgen:52); and of the first sample: radiance = 0 (:42)
+            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
             DiffRays diff;
             if (FIRST)
             {
                 uint32_t f, s;
                 slotFrame(p, slot, f, s);
                 const uint32_t pixel = slotPixel(p, s), frame = p.firstFrame + f;
-                uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
+                rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
                 f3 o, d;
                 startSample<TEX>(p, pixel, rng, o, d, diff);
                 o4 = make_float4(o.x, o.y, o.z, 0.0f);
                 d4 = make_float4(d.x, d.y, d.z, 0.0f);
-                meta = make_uint4(rng, pixel, 0u, frame); // k_tail, k_apply_shadow, k_restart and k_finish_restarts read it
+                state = 0u;
             }
             else
-                meta = wf.meta[slot];
-            const float4 hit = wf.hit[slot];
-            // first bounce of a sample: throughput = 1 (raygen.rgen:52); and of the first sample: radiance = 0 (:42)
-            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-            if (meta.z != 0u)
-                r4 = wf.rad[slot];
-            if ((meta.z & 0xffffu) != 0u)
+            {
+                // both records are read whole on every segment anyway; at bounce 0 (a round k_restart started, k_generate's
+                // schedule) thr.xyz holds the 1 that used to be implied: its .w is the only copy of the RNG state
+                d4 = wf.rayD[slot];
                 t4 = wf.thr[slot];
+                state = __float_as_uint(d4.w);
+                rng = __float_as_uint(t4.w);
+            }
+            const float4 hit = wf.hit[slot];
+            if (state != 0u)
+                r4 = wf.rad[slot];
             f3 radiance = F3(r4.x, r4.y, r4.z), throughput = F3(t4.x, t4.y, t4.z);
 
             if (pair == 0xffffffffu)
             {
                 // miss.rmiss:16-39: sky colour / skybox lookup, Pdf = -1 -> raygen.rgen:71-75
-                if (!FIRST)
-                    d4 = wf.rayD[slot];
                 radiance = radiance + throughput * missEmissive(sv, F3(d4.x, d4.y, d4.z));
-                restart = finishSample(p, wf, slot, meta, radiance, nSamples, nRetries);
+                restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
             }
             else
             {
                 if (!FIRST)
-                {
                     o4 = wf.rayO[slot];
-                    d4 = wf.rayD[slot];
-                }
                 HitOut out;
                 if (TEX && !FIRST)
                     diff = loadDiff(wf, slot);
@@ -789,7 +820,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
                         decal.pair = __float_as_uint(dq.w);
                     }
                 }
-                closestHit<TEX>(sv, F3(d4.x, d4.y, d4.z), hit.x, hit.y, hit.z, pair, __float_as_uint(hit.w), o4.w, meta.x, out, diff, decal);
+                closestHit<TEX>(sv, F3(d4.x, d4.y, d4.z), hit.x, hit.y, hit.z, pair, __float_as_uint(hit.w), o4.w, rng, out, diff, decal);
                 nHits++;
 
                 radiance = radiance + throughput * out.Emissive; // raygen.rgen:77
@@ -808,10 +839,10 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
 
                 bool finished = false;
                 const float prob = fmin_(maxComponent(throughput), 1.0f); // :86
-                uint32_t bounce = meta.z & 0xffffu;
+                uint32_t bounce = state & 0xffffu;
                 if (prob < 0.001f)
                     finished = true;
-                else if (prob < rnd(meta.x)) // :90
+                else if (prob < rnd(rng)) // :90
                     finished = true;
                 else
                 {
@@ -820,32 +851,38 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
                     if (bounce >= p.u.BounceCount)
                         finished = true;
                 }
-                meta.z = (meta.z & 0xffff0000u) | bounce;
+                state = (state & 0xffff0000u) | bounce;
 
                 if (pushShadow)
                 {
+                    // the shadow ray leaves out.Position, which is rayO.xyz below (ShadowIO::load); its record carries what
+                    // k_apply_shadow needs to finish a path that ends here: `state` beside the contribution, the finished flag
+                    // as the sign bit of the light distance (a length or 100000: never negative; set on the bit pattern)
                     const f3 sd = -normalize(out.LightDirection); // raygen.rgen:24
-                    wf.shO[slot] = make_float4(out.Position.x, out.Position.y, out.Position.z, out.LightDistance);
-                    wf.shD[slot] = make_float4(sd.x, sd.y, sd.z, finished ? 1.0f : 0.0f);
-                    wf.shC[slot] = make_float4(contribution.x, contribution.y, contribution.z, 0.0f);
+                    const uint32_t tmax = (__float_as_uint(out.LightDistance) & 0x7fffffffu) | (finished ? 0x80000000u : 0u);
+                    wf.shD[slot] = make_float4(sd.x, sd.y, sd.z, __uint_as_float(tmax));
+                    wf.shC[slot] = make_float4(contribution.x, contribution.y, contribution.z, __uint_as_float(state));
                 }
                 if (finished && !pushShadow)
-                    restart = finishSample(p, wf, slot, meta, radiance, nSamples, nRetries);
+                    restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
                 else
                 {
                     wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+                    // a path that ends with its shadow query pending has no use for MaxRoughness: its rayO.w keeps the RNG state
+                    // for the restart k_apply_shadow may find it due (next sample of a multi-sample launch, NaN)
+                    wf.rayO[slot] = make_float4(out.Position.x, out.Position.y, out.Position.z, finished ? __uint_as_float(rng) : out.MaxRoughness);
                     if (!finished)
                     {
-                        wf.rayO[slot] = make_float4(out.Position.x, out.Position.y, out.Position.z, out.MaxRoughness);
-                        wf.rayD[slot] = make_float4(out.Direction.x, out.Direction.y, out.Direction.z, 0.0f);
-                        wf.thr[slot] = make_float4(throughput.x, throughput.y, throughput.z, 0.0f);
+                        wf.rayD[slot] = make_float4(out.Direction.x, out.Direction.y, out.Direction.z, __uint_as_float(state));
+                        wf.thr[slot] = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(rng));
                         if (TEX)
                             storeDiff(wf, slot, diff);
                         pushNext = true; // a pending shadow query only adds to rad[slot] before the next bounce
                     }
                 }
             }
-            wf.meta[slot] = meta;
+            if (restart) // the sample ended in this kernel and the slot has another one due
+                storeRestart(wf, slot, rng, state);
         }
         pushRestarts(wf, restart, slot);
         // queue appends with ONE global atomic per block and queue: same-address atomics
@@ -901,18 +938,20 @@ struct ShadowIO
     static constexpr bool kNeedsPrim = false;
     static constexpr bool kHasQueue = true;
     const Wavefront &wf;
-    float finished;
+    float finished; // shD.w of the ray in flight: the sign bit says that its path ends after this bounce
     uint32_t staged;
     PT_DEV uint32_t queueEntry(uint32_t item) const { return wf.shadowQueue[item]; }
     PT_DEV void setEntry(uint32_t s) { staged = s; }
     PT_DEV bool load(uint32_t item, f3 &o, f3 &d, float &tmin, float &tmax)
     {
         const uint32_t slot = staged;
-        const float4 o4 = wf.shO[slot], d4 = wf.shD[slot];
+        // the origin is the hit point k_shade left in rayO.xyz (of the continuation ray, or of a path that ended there);
+        // shD.w = the light distance, its sign bit the finished flag
+        const float4 o4 = wf.rayO[slot], d4 = wf.shD[slot];
         o = F3(o4.x, o4.y, o4.z);
         d = F3(d4.x, d4.y, d4.z);
         tmin = 0.00001f; // raygen.rgen:26-31: tmin = 1e-5, tmax = LightDistance, terminate on first hit
-        tmax = o4.w;
+        tmax = __uint_as_float(__float_as_uint(d4.w) & 0x7fffffffu);
         finished = d4.w;
         return true;
     }
@@ -922,7 +961,7 @@ struct ShadowIO
     // The traversal only records the answer.  What follows from it -- the NEE add into rad[slot], finishing the sample of a
     // path that ended on this bounce -- is k_apply_shadow's: inside the traversal loop those dependent loads and stores
     // sat in the retire phase of nearly every round for a handful of lanes (shadow rounds took 1.8x a closest round).
-    PT_DEV void store(uint32_t item, const Hit &, bool occluded, bool) { wf.shadowResult[item] = (uint8_t)((occluded ? 0u : 1u) | (finished != 0.0f ? 2u : 0u)); }
+    PT_DEV void store(uint32_t item, const Hit &, bool occluded, bool) { wf.shadowResult[item] = (uint8_t)((occluded ? 0u : 1u) | (__float_as_uint(finished) >> 31 ? 2u : 0u)); }
 };
 
 template <bool ALPHA>
@@ -958,20 +997,22 @@ __global__ void __launch_bounds__(kBlock) k_apply_shadow(LaunchParams p, Wavefro
             if (result)
             {
                 float4 r4 = wf.rad[slot];
+                // the record is read for its contribution or for its bounce | smpl << 16: an occluded light on a path that
+                // ended is the one case that reads it for the word alone
+                const float4 c = wf.shC[slot];
                 if (result & 1u)
                 {
-                    const float4 c = wf.shC[slot];
                     r4.x = r4.x + c.x;
                     r4.y = r4.y + c.y;
                     r4.z = r4.z + c.z;
                 }
                 if (result & 2u)
                 {
-                    uint4 meta = wf.meta[slot];
+                    uint32_t state = __float_as_uint(c.w);
                     f3 radiance = F3(r4.x, r4.y, r4.z);
-                    restart = finishSample(p, wf, slot, meta, radiance, nSamples, nRetries);
-                    if (restart)
-                        wf.meta.p[slot].z = meta.z;
+                    restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
+                    if (restart) // k_shade left the RNG state of a path that ended in rayO.w
+                        storeRestart(wf, slot, __float_as_uint(wf.rayO.p[slot].w), state);
                 }
                 else
                     wf.rad[slot] = r4; // the slot is already in the next queue (k_shade)
@@ -1002,12 +1043,13 @@ __global__ void __launch_bounds__(kBlock) k_restart(LaunchParams p, Wavefront wf
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x)
     {
         const uint32_t slot = wf.restartQueue[i];
-        uint4 meta = wf.meta[slot];
+        uint32_t rng, state;
+        loadRestart(wf, slot, rng, state);
         f3 o, d;
-        startSlotSample(p, wf, slot, meta.y, meta.x, o, d);
+        startSlotSample(p, wf, slot, pixelOfSlot(p, slot), rng, o, d);
         wf.rayO[slot] = make_float4(o.x, o.y, o.z, 0.0f);
-        wf.rayD[slot] = make_float4(d.x, d.y, d.z, 0.0f);
-        wf.meta[slot] = meta; // bounce 0: thr[slot] = 1 is implied
+        wf.rayD[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(state)); // smpl << 16: bounce 0
+        wf.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(rng)); // raygen.rgen:52
     }
 }
 
@@ -1250,26 +1292,25 @@ PT_DEV void tailBody(const LaunchParams &p, const SceneView &sv, const TraceScen
         if (i < count)
         {
             const uint32_t slot = wf.queue[qin][i];
-            const uint4 meta = wf.meta[slot];
-            const float4 o4 = wf.rayO[slot], d4 = wf.rayD[slot];
-            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f); // see k_shade
-            if (meta.z != 0u)
+            const float4 o4 = wf.rayO[slot], d4 = wf.rayD[slot], t4 = wf.thr[slot];
+            const uint32_t state = __float_as_uint(d4.w); // bounce | smpl << 16 and, in thr.w, the RNG state: see k_shade
+            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (state != 0u)
                 r4 = wf.rad[slot];
-            if ((meta.z & 0xffffu) != 0u)
-                t4 = wf.thr[slot];
-            uint32_t rng = meta.x;
+            uint32_t rng = __float_as_uint(t4.w);
             DiffRays diff;
             if (MODE >= 1)
                 diff = loadDiff(wf, slot);
             else
                 diff.rxOrigin = diff.rxDirection = diff.ryOrigin = diff.ryDirection = F3s(0.0f);
-            int smpl = (int)(meta.z >> 16);
-            const f3 radiance = runPath<MODE, true>(p, sv, sc, st, meta.y, rng, F3(r4.x, r4.y, r4.z), F3(t4.x, t4.y, t4.z), F3(o4.x, o4.y, o4.z),
-                                                   F3(d4.x, d4.y, d4.z), diff, o4.w, meta.z & 0xffffu, smpl, false, pc);
+            int smpl = (int)(state >> 16);
+            // (ONE_SAMPLE starts no sample: the pixel is not needed)
+            const f3 radiance = runPath<MODE, true>(p, sv, sc, st, 0u, rng, F3(r4.x, r4.y, r4.z), F3(t4.x, t4.y, t4.z), F3(o4.x, o4.y, o4.z),
+                                                   F3(d4.x, d4.y, d4.z), diff, o4.w, state & 0xffffu, smpl, false, pc);
             if (smpl < (int)p.u.SampleCount)
             {
                 wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
-                wf.meta[slot] = make_uint4(rng, meta.y, (uint32_t)smpl << 16, meta.w);
+                storeRestart(wf, slot, rng, (uint32_t)smpl << 16);
                 restart = true;
                 restartSlot = slot;
             }
@@ -1303,14 +1344,14 @@ __global__ void __launch_bounds__(kBlock) PT_TAIL_TEX_ATTR k_finish_restarts(Lau
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x)
     {
         const uint32_t slot = wf.restartQueue[i];
-        const uint4 meta = wf.meta[slot];
+        uint32_t rng, state;
+        loadRestart(wf, slot, rng, state);
         const float4 r4 = wf.rad[slot];
-        uint32_t rng = meta.x;
         DiffRays diff;
         diff.rxOrigin = diff.rxDirection = diff.ryOrigin = diff.ryDirection = F3s(0.0f);
-        int smpl = (int)(meta.z >> 16);
-        const f3 radiance = runPath<MODE>(p, sv, sc, st, meta.y, rng, F3(r4.x, r4.y, r4.z), F3s(1.0f), F3s(0.0f), F3s(0.0f), diff, 0.0f, 0u, smpl,
-                                          true, pc);
+        int smpl = (int)(state >> 16);
+        const f3 radiance = runPath<MODE>(p, sv, sc, st, pixelOfSlot(p, slot), rng, F3(r4.x, r4.y, r4.z), F3s(1.0f), F3s(0.0f), F3s(0.0f), diff, 0.0f, 0u,
+                                          smpl, true, pc);
         wf.slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
     }
     if (st.overflow)
