@@ -10,6 +10,7 @@
 //   examples/render_scene default 640 360 1 4 normals.png --debug-mode 2    (the debug view instead: PTX_DEBUG_MODE_*)
 //   examples/render_scene default 640 360 16 4 screen.png --present 1280x720          (the screen path: the frame as an SDR window of that size shows it)
 //   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
+//   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
 #include <cmath>
 #include <cstdio>
 #include <filesystem>
@@ -58,6 +59,21 @@ int main(int argc, char **argv)
             argc -= 2;
             break;
         }
+    RendererHip::DenoiserSettings denoiser; // --denoise [iterations]: the filter between the path-tracing pass and the output stage
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--denoise")
+        {
+            denoiser.Enabled = true;
+            // the iteration count is optional: one digit 1 .. 6 right behind the switch
+            const bool counted = i + 1 < argc && std::strlen(argv[i + 1]) == 1 && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '6';
+            if (counted)
+                denoiser.Iterations = static_cast<uint32_t>(argv[i + 1][0] - '0');
+            const int drop = counted ? 2 : 1;
+            for (int k = i; k + drop < argc; k++)
+                argv[k] = argv[k + drop];
+            argc -= drop;
+            break;
+        }
     const std::string name = argc > 1 ? argv[1] : "default";
     const uint32_t width = argc > 2 ? std::atoi(argv[2]) : 640, height = argc > 3 ? std::atoi(argv[3]) : 360;
     const uint32_t spp = argc > 4 ? std::atoi(argv[4]) : 16, bounces = argc > 5 ? std::atoi(argv[5]) : 4;
@@ -74,6 +90,7 @@ int main(int argc, char **argv)
         RendererHip::PathTracingSettings settings;
         settings.BounceCount = bounces;
         RendererHip::SetSettings(settings);
+        RendererHip::SetSettings(denoiser);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

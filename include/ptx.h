@@ -756,6 +756,68 @@ PTX_API int ptx_read_present(PtxRenderer *r, void *host, size_t bytes);
 PTX_API void *ptx_device_present_ptr(PtxRenderer *r);
 PTX_API size_t ptx_present_bytes(const PtxRenderer *r);
 
+/* ------------------------------------------------------------------------- */
+/* Denoiser (docs/NEXT_ROWS.md section 13).  The reference has none: it relies */
+/* on accumulation.  This is the stated exception of DESIGN.md section 9, the  */
+/* piece that makes a frame of 1 - 8 samples per pixel presentable.            */
+/* ------------------------------------------------------------------------- */
+
+enum {
+    PTX_GUIDE_NORMAL = 0,   /* hit: the value of PTX_DEBUG_MODE_NORMAL, w = 1;                        miss: (0, 0, 0, 0) */
+    PTX_GUIDE_POSITION = 1, /* hit: the value of PTX_DEBUG_MODE_WORLD_POSITION, w = the hit distance; miss: (0, 0, 0, 0) */
+    PTX_GUIDE_ALBEDO = 2,   /* hit: material.Color after the decal mix, w = 1;                        miss: (1, 1, 1, 1) */
+    PTX_GUIDE_COUNT = 3
+};
+
+/* The guide pass: one primary ray through the centre of every owned pixel of the current tile shard -- ptx_render_debug's ray
+ * (no RNG, no lens, no culling, no flags; tmin 1e-5, tmax 1e4; the any-hit stage with its decal) -- and the first hit's shading
+ * normal, world position + hit distance and base colour STORED into three RGBA32F images of the render extent that the renderer
+ * keeps.  Asynchronous on the render stream; works on a borrower and on a scene with pending streamed textures (they sample
+ * their stand-ins).  The accumulation image is not touched.  PTX_ERROR_NOT_READY: no scene, tree or image, or a shard
+ * accumulation buffer is bound.  A traversal-stack overflow fails the stream, as in ptx_render.  ptx_get_stats afterwards:
+ * pathSamples = owned pixels, segments = primary rays, shadowRays = retries = 0.  ptx_resize drops the guides. */
+PTX_API int ptx_render_guides(PtxRenderer *r, const PtxRaygenUniformData *uniform);
+/* One guide image, device -> host, width*height*16 bytes.  Synchronous, like ptx_read_output.  PTX_ERROR_INVALID_ARGUMENT: an
+ * unknown guide or a buffer of another size; PTX_ERROR_NOT_READY: no ptx_render_guides since the last ptx_resize. */
+PTX_API int ptx_read_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes);
+/* ... or its device address (width*height*16 bytes; NULL without guides). */
+PTX_API void *ptx_device_guide_ptr(PtxRenderer *r, uint32_t which);
+
+typedef struct PtxDenoiseDesc {
+    uint32_t totalSamples;  /* samples in the accumulation image: the filter works on the mean, sum / totalSamples */
+    uint32_t iterations;    /* 1 .. 6: iteration i (from 0) spreads its 5 x 5 taps 2^i pixels apart */
+    float sigmaColor;       /* >= 0; 0: no colour term.  Halved with every iteration */
+    float sigmaNormal;      /* > 0 */
+    float sigmaPosition;    /* > 0, relative to the centre pixel's hit distance */
+    uint32_t flags;         /* 0 */
+    uint32_t reserved;      /* 0 */
+} PtxDenoiseDesc;
+
+/* The edge-avoiding a-trous filter.  Input: the accumulation image S and the three guides; output: a renderer-owned RGBA32F
+ * image D of the MEAN, alpha 1; neither input is written.  With h = (1/16, 1/4, 3/8, 1/4, 1/16), m(p) = S(p).rgb / totalSamples
+ * and a_p = max(albedo_p, 0.01) per channel, a pixel p is VALID when it was hit, m(p), n_p and t_p are finite and t_p > 0.
+ * c_0(p) = m(p) / a_p on valid pixels and m(p) elsewhere; for i = 0 .. iterations-1 and s = 2^i, on a valid p
+ *     c_{i+1}(p) = sum_q w_q c_i(q) / sum_q w_q       over q = p + s (dx, dy), dx, dy in -2 .. 2,
+ * the centre with w = h[2] h[2] by rule, any other tap only if q is inside the image and valid, c_i(q) is finite and e >= 0, with
+ *     w = h[dx+2] h[dy+2] exp(-e),
+ *     e = |c_i(p) - c_i(q)|^2 / (sigmaColor 2^-i)^2 + |n_p - n_q|^2 / sigmaNormal^2 + (dot(n_p, x_q - x_p) / (sigmaPosition t_p))^2
+ * (the colour term only with sigmaColor > 0); on any other p, c_{i+1}(p) = c_i(p).  D(p).rgb = c_N(p) a_p on valid pixels and
+ * m(p) elsewhere: a NaN or Inf pixel keeps its class and still gets postprocess.comp's marker.  float32 throughout.  One launch
+ * per iteration, asynchronous on the render stream.
+ * PTX_ERROR_INVALID_ARGUMENT: iterations outside 1 .. 6, totalSamples 0, a sigma that is negative or not finite, sigmaNormal or
+ * sigmaPosition 0, unknown flags, reserved != 0.  PTX_ERROR_NOT_READY: no image, no ptx_render_guides since the last ptx_resize, a
+ * shard accumulation buffer is bound, or a tile shard with worldSize > 1 (the taps cross tiles; denoising a gathered frame is
+ * out of scope).  A refused call leaves the previous D intact; ptx_resize drops it. */
+PTX_API int ptx_denoise(PtxRenderer *r, const PtxDenoiseDesc *desc);
+/* D, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_NOT_READY: no ptx_denoise since the last ptx_resize. */
+PTX_API int ptx_read_denoised(PtxRenderer *r, void *host, size_t bytes);
+/* ... or its device address (NULL without one; the next ptx_denoise may move it). */
+PTX_API void *ptx_device_denoised_ptr(PtxRenderer *r);
+/* ptx_postprocess's chain with D as the source and TotalSamples taken as 1 (the uniform's own value is ignored): the same
+ * kernels on another pointer.  ptx_read_output and ptx_present follow unchanged.  PTX_ERROR_NOT_READY: no ptx_denoise since the
+ * last ptx_resize. */
+PTX_API int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

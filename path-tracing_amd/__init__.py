@@ -63,6 +63,8 @@ PTX_SYMBOLS = [
     "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency",
     "ptx_render_debug", "ptx_test_debug_eval",
     "ptx_present", "ptx_read_present", "ptx_device_present_ptr", "ptx_present_bytes",
+    "ptx_render_guides", "ptx_read_guide", "ptx_device_guide_ptr", "ptx_denoise", "ptx_read_denoised", "ptx_device_denoised_ptr",
+    "ptx_postprocess_denoised",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -156,6 +158,16 @@ class PresentDesc(C.Structure):
 # PTX_PRESENT_* of include/ptx.h: the swapchain's format, and the flag bit
 PRESENT_R8G8B8A8_SRGB, PRESENT_B8G8R8A8_SRGB, PRESENT_A2B10G10R10_UNORM, PRESENT_R16G16B16A16_SFLOAT = range(4)
 PRESENT_UI_ON_DEVICE = 1
+
+
+class DenoiseDesc(C.Structure):
+    _fields_ = [("totalSamples", C.c_uint32), ("iterations", C.c_uint32), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaPosition", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+GUIDE_NORMAL, GUIDE_POSITION, GUIDE_ALBEDO = range(3)  # PTX_GUIDE_* of include/ptx.h
+# The defaults of Renderer.denoise, chosen on 4-spp frames of three scenes against 512 spp (docs/NEXT_ROWS.md section 13)
+DENOISE_DEFAULTS = dict(iterations=3, sigma_color=1.5, sigma_normal=0.3, sigma_position=0.03)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -354,6 +366,15 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_present_ptr.restype = P
         lib.ptx_present_bytes.argtypes = [P]
         lib.ptx_present_bytes.restype = C.c_size_t
+        lib.ptx_render_guides.argtypes = [P, C.POINTER(RaygenUniformData)]
+        lib.ptx_read_guide.argtypes = [P, C.c_uint32, P, C.c_size_t]
+        lib.ptx_device_guide_ptr.argtypes = [P, C.c_uint32]
+        lib.ptx_device_guide_ptr.restype = P
+        lib.ptx_denoise.argtypes = [P, C.POINTER(DenoiseDesc)]
+        lib.ptx_read_denoised.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_denoised_ptr.argtypes = [P]
+        lib.ptx_device_denoised_ptr.restype = P
+        lib.ptx_postprocess_denoised.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32]
         _hip = lib
     return _hip
 
@@ -617,6 +638,40 @@ class Renderer:
 
     def present_bytes(self) -> int:
         return int(self.lib.ptx_present_bytes(self.handle))
+
+    def render_guides(self, uniform: RaygenUniformData):
+        """ptx_render_guides: the first hit's normal, position and base colour of every owned pixel, kept for denoise()."""
+        self._check(self.lib.ptx_render_guides(self.handle, C.byref(uniform)))
+
+    def read_guide(self, which: int) -> np.ndarray:
+        """One guide image (GUIDE_NORMAL / GUIDE_POSITION / GUIDE_ALBEDO), H x W x 4 float32."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.ptx_read_guide(self.handle, which, img.ctypes.data, img.nbytes))
+        return img
+
+    def guide_ptr(self, which: int) -> int:
+        return int(self.lib.ptx_device_guide_ptr(self.handle, which) or 0)
+
+    def denoise(self, total_samples: int, iterations: int = DENOISE_DEFAULTS["iterations"], sigma_color: float = DENOISE_DEFAULTS["sigma_color"],
+                sigma_normal: float = DENOISE_DEFAULTS["sigma_normal"], sigma_position: float = DENOISE_DEFAULTS["sigma_position"]):
+        """ptx_denoise: the edge-avoiding a-trous filter over the mean of the accumulation image, guided by render_guides()."""
+        d = DenoiseDesc(total_samples, iterations, sigma_color, sigma_normal, sigma_position, 0, 0)
+        self._check(self.lib.ptx_denoise(self.handle, C.byref(d)))
+
+    def read_denoised(self) -> np.ndarray:
+        """The denoised MEAN of the last denoise(), H x W x 4 float32, alpha 1."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.ptx_read_denoised(self.handle, img.ctypes.data, img.nbytes))
+        return img
+
+    def denoised_ptr(self) -> int:
+        return int(self.lib.ptx_device_denoised_ptr(self.handle) or 0)
+
+    def postprocess_denoised(self, total_samples: int = 1, exposure: float = 1.0, bloom_threshold: float = 1.0, bloom_intensity: float = 1.0,
+                             tone_mapping: int = TONE_MAPPING_SDR):
+        """ptx_postprocess_denoised: postprocess() on the denoised image; it holds the mean, so total_samples is taken as 1."""
+        u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
+        self._check(self.lib.ptx_postprocess_denoised(self.handle, C.byref(u), tone_mapping))
 
     def stats(self) -> Stats:
         s = Stats()

@@ -1,0 +1,246 @@
+// pt_denoise.hpp -- the denoiser (docs/NEXT_ROWS.md section 13): the one stage the reference does not have (it relies on accumulation;
+// DESIGN.md section 9 names this exception).  Two kernels, host side in pt_denoise_host.hpp:
+//
+//   k_render_guides  one primary ray through the centre of every owned pixel, exactly the debug view's (debugViewBody,
+//                    pt_debug_view.hpp), storing the first hit's shading normal, world position + hit distance and base colour
+//   k_denoise        one iteration of the edge-avoiding a-trous filter (a 5 x 5 B3-spline stencil dilated by `step`) over the
+//                    demodulated mean, guided by those three images; the first launch demodulates, the last remodulates
+//
+// The arithmetic is float32 and nothing here is compared with an oracle bit for bit: the filter's weights use the hardware's
+// exp2 (v_exp_f32) with the log2(e) factor folded into the exponent.
+#pragma once
+
+#include "pt_wavefront.hpp"
+
+// ---- the guide pass ----------------------------------------------------------------------------------------
+
+// debugRaygen.rgen:22-40 + debugClosestHit.rchit:164-202 without flags: the values of the debug view's Normal and WorldPosition
+// modes and the material's colour after the decal mix, from ONE traversal.  Every expression is the debug view's, in its order:
+// the normal and position images are the same bits as ptx_render_debug's.
+template <int MODE>
+PT_DEV void renderGuidesBody(const LaunchParams &p, const SceneView &sv, const TraceScene &sc, float4 *__restrict__ gNormal,
+                             float4 *__restrict__ gPosition, float4 *__restrict__ gAlbedo, uint32_t *__restrict__ counters, uint32_t *spill)
+{
+    constexpr bool TEX = MODE >= 1, ALPHA = MODE == 2;
+    PT_DECLARE_STACK(st, PT_TAIL_LDS, spill)
+    uint32_t nPix = 0;
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.slotsPerFrame; s += gridDim.x * blockDim.x)
+    {
+        const uint32_t pixel = slotPixel(p, s);
+        if (pixel == 0xffffffffu)
+            continue;
+        f3 ro, rd, rx, ry;
+        constructPrimaryRay<true>(pixel % p.width, pixel / p.width, p.width, p.height, p.u.ViewInverse, p.u.ProjInverse, F2(0.5f, 0.5f), ro, rd, rx, ry);
+        Hit h;
+        Decal decal = noDecal();
+        nPix++;
+        const bool hit = traceRay<false, false, ALPHA>(sc, ro, rd, 0.00001f, 10000.0f, st, h, nullptr, nullptr, ALPHA ? &decal : nullptr);
+        float4 gn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), gp = gn, ga = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        if (hit)
+        {
+            const f3 bary = F3(1.0f - h.u - h.v, h.u, h.v);
+            const DevPair pr = sv.pairs[h.pair];
+            const TriVertices tv3 = loadTriangle(&sv.shadeTris[h.slot]);
+            Vtx ov;
+            ov.Position = interp3(tv3.o[0].Position, tv3.o[1].Position, tv3.o[2].Position, bary);
+            ov.Normal = interp3(tv3.o[0].Normal, tv3.o[1].Normal, tv3.o[2].Normal, bary);
+            ov.Tangent = interp3(tv3.o[0].Tangent, tv3.o[1].Tangent, tv3.o[2].Tangent, bary);
+            ov.Bitangent = interp3(tv3.o[0].Bitangent, tv3.o[1].Bitangent, tv3.o[2].Bitangent, bary);
+            const Vtx vertex = transformVertex(pr, ov);
+            const f2 uv0 = tv3.uv[0], uv1 = tv3.uv[1], uv2 = tv3.uv[2];
+            const f2 texCoords = F2((uv0.x * bary.x + uv1.x * bary.y) + uv2.x * bary.z, (uv0.y * bary.x + uv1.y * bary.y) + uv2.y * bary.z);
+            const f3 P3[3] = { tv3.worldPosition[0], tv3.worldPosition[1], tv3.worldPosition[2] };
+            const f3 N3[3] = { tv3.worldNormal[0], tv3.worldNormal[1], tv3.worldNormal[2] };
+            const f2 UV3[3] = { uv0, uv1, uv2 };
+            f3 dpdu, dpdv, dndu, dndv, dpdx, dpdy;
+            computeDpnDuv(P3, N3, UV3, vertex.Tangent, vertex.Bitangent, dpdu, dpdv, dndu, dndv);
+            computeDpDxy(vertex.Position, ro, rx, ro, ry, vertex.Normal, dpdx, dpdy);
+            const f4 derivatives = computeDerivatives(dpdx, dpdy, dpdu, dpdv);
+            MaterialSample material = sampleMaterial<TEX>(sv, pr.materialId, texCoords, derivatives, false, false, false);
+            if (ALPHA && decal.dist != -1.0f && h.t > decal.dist)
+            {
+                const f4 c = hitBaseColor(sv, decal.pair, decal.slot, decal.u, decal.v);
+                material.Color = mix(material.Color, rgb(c), c.w);
+            }
+            mat3 TBN;
+            TBN.c0 = vertex.Tangent;
+            TBN.c1 = vertex.Bitangent;
+            TBN.c2 = vertex.Normal;
+            const f3 N = normalize(vertex.Normal + mul(TBN, material.Normal));
+            gn = make_float4(N.x, N.y, N.z, 1.0f);
+            gp = make_float4(vertex.Position.x, vertex.Position.y, vertex.Position.z, h.t);
+            ga = make_float4(material.Color.x, material.Color.y, material.Color.z, 1.0f);
+        }
+        gNormal[pixel] = gn;
+        gPosition[pixel] = gp;
+        gAlbedo[pixel] = ga;
+    }
+    if (st.overflow)
+        atomicAdd(&counters[C_OVERFLOW], 1u);
+    waveAddCounter(&counters[C_SEGMENTS], nPix);
+    waveAddCounter(&counters[C_SAMPLES], nPix);
+}
+
+// k_debug_view's class of kernel (the sampler and a traversal) and its occupancy attribute; register and scratch figures of the
+// three variants: docs/NEXT_ROWS.md section 13.
+#ifndef PT_GUIDES_ATTR
+#define PT_GUIDES_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
+#endif
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_render_guides(LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, float4 *gPosition,
+                                                           float4 *gAlbedo, uint32_t *counters, uint32_t *spill);
+#define PT_GUIDES_KERNEL(MODE)                                                                                                          \
+    template <>                                                                                                                         \
+    __global__ void __launch_bounds__(kBlock) PT_GUIDES_ATTR k_render_guides<MODE>(LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, \
+                                                                                   float4 *gPosition, float4 *gAlbedo, uint32_t *counters,  \
+                                                                                   uint32_t *spill)                                      \
+    {                                                                                                                                   \
+        renderGuidesBody<MODE>(p, sv, sc, gNormal, gPosition, gAlbedo, counters, spill);                                                \
+    }
+PT_GUIDES_KERNEL(0)
+PT_GUIDES_KERNEL(1)
+PT_GUIDES_KERNEL(2)
+#undef PT_GUIDES_KERNEL
+
+// ---- the filter --------------------------------------------------------------------------------------------
+
+struct DenoiseArgs
+{
+    const float4 *sum;      // the accumulation image (running sum)
+    const float4 *src;      // c_i of the previous launch: rgb, w = 1 on a valid pixel and 0 elsewhere (unused by the first launch)
+    float4 *dst;            // c_{i+1} in the same form, or the denoised mean with alpha 1 (the last launch)
+    const float4 *normal;   // the guides
+    const float4 *position;
+    const float4 *albedo;
+    uint32_t width, height;
+    int32_t step;           // 2^i
+    float totalSamples;
+    float invSigmaColor2;   // 1 / (sigmaColor 2^-i)^2; 0: no colour term
+    float invSigmaNormal2;  // 1 / sigmaNormal^2
+    float invSigmaPosition; // 1 / sigmaPosition
+};
+
+constexpr int kDenoiseTileX = 32, kDenoiseTileY = 8; // 256 threads; a row of the tile is 512 contiguous bytes of every image
+
+PT_DEV bool finite_(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+PT_DEV bool finite3_(f3 c) { return finite_(c.x) && finite_(c.y) && finite_(c.z); }
+PT_DEV f3 albedoFloor(float4 a) { return F3(fmax_(a.x, 0.01f), fmax_(a.y, 0.01f), fmax_(a.z, 0.01f)); }
+PT_DEV bool denoiseValid(f3 mean, float4 n, float t)
+{
+    return n.w == 1.0f && finite3_(mean) && finite_(n.x) && finite_(n.y) && finite_(n.z) && t > 0.0f && finite_(t);
+}
+
+// c_0 of pixel q: the mean, divided by the floored albedo where the pixel is valid
+PT_DEV f3 denoiseInput(const DenoiseArgs &a, uint32_t q, float4 nq, float tq, bool &valid)
+{
+    const float4 s = a.sum[q];
+    const f3 mean = F3(s.x, s.y, s.z) / a.totalSamples;
+    valid = denoiseValid(mean, nq, tq);
+    if (!valid)
+        return mean;
+    const f3 al = albedoFloor(a.albedo[q]);
+    return F3(div_(mean.x, al.x), div_(mean.y, al.y), div_(mean.z, al.z));
+}
+
+// One tap that passed the tests on q itself (inside the image, valid, finite colour): its weight, and its share of the sums
+PT_DEV void denoiseTap(const DenoiseArgs &a, f3 cp, f3 nP, f3 xP, float invDepth, f3 cq, float4 nq, float4 xq, float hh, f3 &acc, float &wsum)
+{
+    const f3 dn = nP - F3(nq.x, nq.y, nq.z);
+    const float plane = dot(nP, F3(xq.x, xq.y, xq.z) - xP) * invDepth;
+    float e = dot(dn, dn) * a.invSigmaNormal2 + plane * plane;
+    if (a.invSigmaColor2 != 0.0f)
+    {
+        const f3 dc = cp - cq;
+        e = dot(dc, dc) * a.invSigmaColor2 + e;
+    }
+    if (!(e >= 0.0f)) // a NaN
+        return;
+    const float w = hh * __builtin_amdgcn_exp2f(e * -1.44269504f);
+    acc = acc + cq * w;
+    wsum = wsum + w;
+}
+
+PT_DEV void denoiseStore(const DenoiseArgs &a, uint32_t p, f3 out, bool valid, bool last)
+{
+    if (last)
+    {
+        if (valid)
+            out = out * albedoFloor(a.albedo[p]);
+        a.dst[p] = make_float4(out.x, out.y, out.z, 1.0f);
+    }
+    else
+        a.dst[p] = make_float4(out.x, out.y, out.z, valid ? 1.0f : 0.0f);
+}
+
+// One thread per pixel.  A tap costs 16 B of colour and, where that says the pixel is valid, 32 B of normal and position; the
+// first launch also reads the sum and the albedo of every tap.  Nothing is staged in LDS: the 25 taps of neighbouring threads
+// overlap in L1 / L2 (docs/NEXT_ROWS.md section 13, cost).
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_denoise(DenoiseArgs a)
+{
+    const int x = (int)(blockIdx.x * kDenoiseTileX + threadIdx.x), y = (int)(blockIdx.y * kDenoiseTileY + threadIdx.y);
+    if (x >= (int)a.width || y >= (int)a.height)
+        return;
+    const uint32_t p = (uint32_t)y * a.width + (uint32_t)x;
+    const float4 np = a.normal[p];
+    const float4 xp = a.position[p];
+    bool valid;
+    f3 cp;
+    if (FIRST)
+        cp = denoiseInput(a, p, np, xp.w, valid);
+    else
+    {
+        const float4 c = a.src[p];
+        cp = F3(c.x, c.y, c.z);
+        valid = c.w != 0.0f;
+    }
+    f3 out = cp;
+    if (valid)
+    {
+        const float hk[5] = { 0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f };
+        const float invDepth = a.invSigmaPosition * rcp_(xp.w);
+        const f3 nP = F3(np.x, np.y, np.z), xP = F3(xp.x, xp.y, xp.z);
+        f3 acc = cp * (0.375f * 0.375f); // the centre tap, by rule
+        float wsum = 0.375f * 0.375f;
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++)
+        {
+            const int qy = y + dy * a.step;
+            if (qy < 0 || qy >= (int)a.height)
+                continue;
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++)
+            {
+                const int qx = x + dx * a.step;
+                if ((dx == 0 && dy == 0) || qx < 0 || qx >= (int)a.width)
+                    continue;
+                const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+                float4 nq, xq;
+                f3 cq;
+                bool qValid;
+                if (FIRST)
+                {
+                    nq = a.normal[q];
+                    xq = a.position[q];
+                    cq = denoiseInput(a, q, nq, xq.w, qValid);
+                }
+                else
+                {
+                    const float4 c = a.src[q];
+                    cq = F3(c.x, c.y, c.z);
+                    qValid = c.w != 0.0f;
+                }
+                if (!qValid || !finite3_(cq))
+                    continue;
+                if (!FIRST)
+                {
+                    nq = a.normal[q];
+                    xq = a.position[q];
+                }
+                denoiseTap(a, cp, nP, xP, invDepth, cq, nq, xq, hk[dx + 2] * hk[dy + 2], acc, wsum);
+            }
+        }
+        out = acc * rcp_(wsum);
+    }
+    denoiseStore(a, p, out, valid, LAST);
+}

@@ -1,0 +1,137 @@
+// pt_denoise_host.hpp -- host side of the denoiser (kernels: pt_denoise.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md section 13).
+// Included by pt_runtime.hpp: two stages on the render stream between ptx_render and the output stage, and their read-backs.
+#pragma once
+
+static float4 *guidePtr(PtxRenderer *r, uint32_t which)
+{
+    return r->guides.p + (size_t)which * r->width * r->height;
+}
+
+// ptx_render_guides: one launch, enqueued like ptx_render_debug's -- the counter block comes back with collectRender, which is
+// where a traversal-stack overflow fails the stream.
+static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
+{
+    if (!r || !uniform)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_guides: null argument");
+    if (!sceneUsable(r) || !imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_render_guides: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
+    if (r->boundShard)
+        return frameIsElsewhere(r, "ptx_render_guides");
+    HIP_TRY(r, hipSetDevice(r->device));
+    const size_t n = (size_t)r->width * r->height;
+    HIP_TRY(r, r->guides.alloc(n * PTX_GUIDE_COUNT));
+    static const PtxLightsUbo noLights = {}; // the pass reads no light
+    const LaunchParams p = makeParams(r, uniform, 0, 1);
+    if (const int rc = beginLaunch(r, &noLights, p, 0))
+        return rc;
+    if (!r->guidesReady) // pixels of other ranks' tiles read as misses that were not hit: all zeros
+        HIP_TRY(r, hipMemsetAsync(r->guides.p, 0, n * PTX_GUIDE_COUNT * sizeof(float4), r->stream));
+    if (p.slotsPerFrame)
+    {
+        const SceneView sv = makeSceneView(r);
+        const TraceScene sc = makeTraceScene(r);
+        // at most kMaxPersistentThreads threads: the global part of the traversal stack is sized for that many
+        const dim3 grid(gridFor(p.slotsPerFrame, kBlock, kMaxPersistentThreads / kBlock));
+        withMode(kernelMode(r), [&](auto M) {
+            k_render_guides<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, guidePtr(r, PTX_GUIDE_NORMAL), guidePtr(r, PTX_GUIDE_POSITION),
+                                                                                guidePtr(r, PTX_GUIDE_ALBEDO), r->counters.p, r->spill.p);
+        });
+    }
+    if (const int rc = endLaunch(r, { PendingLaunch::kDebugView })) // the counters are the kernel's own, as the debug view's
+        return rc;
+    r->guidesReady = true;
+    return PTX_OK;
+}
+
+// device -> host copy of one renderer-owned RGBA32F image of the render extent, synchronous
+static int readFrameImage(PtxRenderer *r, const float4 *image, void *host, size_t bytes, const char *who)
+{
+    if (bytes != (size_t)r->width * r->height * sizeof(float4))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: buffer must be width*height*16 bytes", who);
+    HIP_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipMemcpyAsync(host, image, bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    return collectRender(r); // an error of the launch that produced the image surfaces with it
+}
+
+static int readGuide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    if (!r || !host || which >= PTX_GUIDE_COUNT)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_guide: null argument or unknown guide %u", which);
+    if (!r->guidesReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_guide: call ptx_render_guides first");
+    return readFrameImage(r, guidePtr(r, which), host, bytes, "ptx_read_guide");
+}
+
+static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d)
+{
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_denoise: null argument");
+    const auto sigmaOk = [](float s) { return s >= 0.0f && s <= 3.402823466e38f; }; // finite and not negative (a NaN fails both)
+    if (d->iterations < 1u || d->iterations > 6u || d->totalSamples == 0u || !sigmaOk(d->sigmaColor) || !sigmaOk(d->sigmaNormal) ||
+        !sigmaOk(d->sigmaPosition) || d->sigmaNormal == 0.0f || d->sigmaPosition == 0.0f || d->flags != 0u || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_denoise: need 1 <= iterations <= 6 (%u), totalSamples > 0 (%u), sigmaColor >= 0 (%g), sigmaNormal > 0 (%g), "
+                    "sigmaPosition > 0 (%g), all finite, flags 0 (0x%x) and reserved 0 (%u)", d->iterations, d->totalSamples, (double)d->sigmaColor,
+                    (double)d->sigmaNormal, (double)d->sigmaPosition, d->flags, d->reserved);
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no accumulation image (call ptx_resize)");
+    if (r->boundShard)
+        return frameIsElsewhere(r, "ptx_denoise");
+    if (!r->guidesReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no guides for this extent (call ptx_render_guides)");
+    if (r->shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: this renderer holds one tile shard of %u; the filter's taps cross tiles", r->shard.worldSize);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const size_t n = (size_t)r->width * r->height;
+    HIP_TRY(r, r->denoisePing[0].alloc(n));
+    if (d->iterations > 1u)
+        HIP_TRY(r, r->denoisePing[1].alloc(n));
+    DenoiseArgs a;
+    a.sum = imagePtr(r);
+    a.normal = guidePtr(r, PTX_GUIDE_NORMAL);
+    a.position = guidePtr(r, PTX_GUIDE_POSITION);
+    a.albedo = guidePtr(r, PTX_GUIDE_ALBEDO);
+    a.width = r->width;
+    a.height = r->height;
+    a.totalSamples = (float)d->totalSamples;
+    a.invSigmaNormal2 = (float)(1.0 / ((double)d->sigmaNormal * d->sigmaNormal));
+    a.invSigmaPosition = (float)(1.0 / (double)d->sigmaPosition);
+    const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->width + kDenoiseTileX - 1) / kDenoiseTileX, (r->height + kDenoiseTileY - 1) / kDenoiseTileY);
+    for (uint32_t i = 0; i < d->iterations; i++)
+    {
+        a.src = i ? r->denoisePing[(i - 1u) & 1u].p : nullptr;
+        a.dst = r->denoisePing[i & 1u].p;
+        a.step = 1 << i;
+        const double sc = (double)d->sigmaColor / (double)(1u << i);
+        a.invSigmaColor2 = d->sigmaColor > 0.0f ? (float)(1.0 / (sc * sc)) : 0.0f;
+        const bool first = i == 0u, last = i + 1u == d->iterations;
+        if (first && last) k_denoise<true, true><<<grid, block, 0, r->stream>>>(a);
+        else if (first) k_denoise<true, false><<<grid, block, 0, r->stream>>>(a);
+        else if (last) k_denoise<false, true><<<grid, block, 0, r->stream>>>(a);
+        else k_denoise<false, false><<<grid, block, 0, r->stream>>>(a);
+    }
+    HIP_TRY(r, hipGetLastError());
+    r->denoisedIn = (int)((d->iterations - 1u) & 1u);
+    return PTX_OK;
+}
+
+static int readDenoised(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_denoised: null argument");
+    if (r->denoisedIn < 0)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_denoised: call ptx_denoise first");
+    return readFrameImage(r, r->denoisePing[r->denoisedIn].p, host, bytes, "ptx_read_denoised");
+}
+
+// ptx_postprocess's chain on the denoised image, which holds the mean: TotalSamples = 1
+static int postprocessDenoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+{
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess_denoised: bad argument");
+    if (r->denoisedIn < 0)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess_denoised: call ptx_denoise first");
+    PtxPostProcessingUniformData u = *uniform;
+    u.TotalSamples = 1u;
+    return postprocessImage(r, r->denoisePing[r->denoisedIn].p, &u, toneMappingMode);
+}

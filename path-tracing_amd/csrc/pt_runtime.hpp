@@ -18,6 +18,7 @@
 #include "pt_aux_kernels.hpp"
 #include "pt_bvh_build.hpp"
 #include "pt_debug_view.hpp"
+#include "pt_denoise.hpp"
 #include "pt_post.hpp"
 #include "pt_present.hpp"
 
@@ -324,6 +325,11 @@ struct PtxRenderer
     DevBuf<uint32_t> presentImage, presentUi;
     uint32_t presentWidth = 0, presentHeight = 0, presentFormat = 0;
     size_t presentBytes = 0; // 0: nothing presented yet
+    // denoiser (pt_denoise_host.hpp): the three guide images of the last ptx_render_guides, the two images the filter's iterations
+    // alternate between, and which of them holds the result of the last ptx_denoise
+    DevBuf<float4> guides, denoisePing[2];
+    bool guidesReady = false;
+    int denoisedIn = -1; // -1: nothing denoised since the last ptx_resize
     float4 *boundImage = nullptr; // external accumulation buffer, if bound
     float4 *boundShard = nullptr; // ... or the dense tile-major shard buffer the samples are accumulated in (ptx_bind_shard_accumulation)
     size_t boundShardBytes = 0;
@@ -1003,14 +1009,9 @@ static int bindShardAccumulation(PtxRenderer *r, void *devShard, size_t bytes)
 }
 
 // Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)
-static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+// the chain on `source` (width x height running sums of uniform->TotalSamples samples): the accumulation image, or the denoised mean
+static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
 {
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess: bad argument");
-    if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess: no accumulation image (call ptx_resize)");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_postprocess");
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t W = r->width, H = r->height, n = W * H;
     uint32_t levels = 1;
@@ -1035,7 +1036,7 @@ static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *unifo
         L[l].rgb = r->bloomRgb.p + off;
         off += (size_t)L[l].w * L[l].h * 3;
     }
-    k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(imagePtr(r), n, *uniform, r->postRgb.p, L[0].rgb);
+    k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->postRgb.p, L[0].rgb);
     for (uint32_t i = 0; i + 1 < used; i++)
         k_bloom_downsample<<<gridFor((size_t)L[i + 1].w * L[i + 1].h), kBlock, 0, r->stream>>>(L[i], L[i + 1]);
     for (uint32_t i = used - 1; i > 0; i--)
@@ -1045,6 +1046,17 @@ static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *unifo
     r->postUniform = *uniform;
     r->outputReady = true;
     return PTX_OK;
+}
+
+static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+{
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess: bad argument");
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess: no accumulation image (call ptx_resize)");
+    if (r->boundShard)
+        return frameIsElsewhere(r, "ptx_postprocess");
+    return postprocessImage(r, imagePtr(r), uniform, toneMappingMode);
 }
 
 // OutputSaver: blit of the tone-mapped image into its output image + readback (OutputSaver.cpp:64-86, :120-199)
@@ -1144,6 +1156,8 @@ static int readPresent(PtxRenderer *r, void *host, size_t bytes)
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;
 }
+
+#include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
 
 static int getStats(PtxRenderer *r, PtxStats *stats)
 {

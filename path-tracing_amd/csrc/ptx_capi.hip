@@ -1,6 +1,6 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
 // Renderer member it replaces in include/ptx.h; the implementations are in pt_runtime.hpp and the host files it includes
-// (pt_scene_host.hpp, pt_bvh_host.hpp, pt_render_host.hpp) and pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp
+// (pt_scene_host.hpp, pt_bvh_host.hpp, pt_render_host.hpp, pt_denoise_host.hpp) and pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp
 // (device side).  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
@@ -92,6 +92,8 @@ int ptx_resize(PtxRenderer *r, uint32_t width, uint32_t height)
     r->width = width;
     r->height = height;
     r->outputReady = false;
+    r->guidesReady = false; // the guides and the denoised image belong to the extent they were made for
+    r->denoisedIn = -1;
     r->boundImage = nullptr;
     r->boundShard = nullptr;
     r->boundShardBytes = 0;
@@ -275,6 +277,41 @@ void *ptx_device_present_ptr(PtxRenderer *r)
 size_t ptx_present_bytes(const PtxRenderer *r)
 {
     return r ? r->presentBytes : 0;
+}
+
+int ptx_render_guides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
+{
+    return renderGuides(r, uniform);
+}
+
+int ptx_read_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    return readGuide(r, which, host, bytes);
+}
+
+void *ptx_device_guide_ptr(PtxRenderer *r, uint32_t which)
+{
+    return r && r->guidesReady && which < PTX_GUIDE_COUNT ? guidePtr(r, which) : nullptr;
+}
+
+int ptx_denoise(PtxRenderer *r, const PtxDenoiseDesc *desc)
+{
+    return denoise(r, desc);
+}
+
+int ptx_read_denoised(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readDenoised(r, host, bytes);
+}
+
+void *ptx_device_denoised_ptr(PtxRenderer *r)
+{
+    return r && r->denoisedIn >= 0 ? r->denoisePing[r->denoisedIn].p : nullptr;
+}
+
+int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+{
+    return postprocessDenoised(r, uniform, toneMappingMode);
 }
 
 int ptx_write_accumulation(PtxRenderer *r, const float *rgba, size_t bytes)

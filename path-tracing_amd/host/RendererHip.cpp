@@ -87,8 +87,8 @@ void RendererHip::ResetAccumulationImage()
         Check(ptx_reset_accumulation(s_Renderer));
 }
 
-// Renderer.cpp:1686-1726
-void RendererHip::Render()
+// the raygen uniform of the active camera (Renderer.cpp:1686-1696)
+static PtxRaygenUniformData FillRaygenUniform()
 {
     Camera &camera = s_Scene->GetActiveCamera();
     camera.OnResize(s_Width, s_Height);
@@ -100,6 +100,13 @@ void RendererHip::Render()
     rgenData.FocalDistance = s_PathTracingSettings.FocalDistance;
     rgenData.SampleCount = s_SamplesPerFrame;
     rgenData.TotalSamples = s_TotalSamples;
+    return rgenData;
+}
+
+// Renderer.cpp:1686-1726
+void RendererHip::Render()
+{
+    const PtxRaygenUniformData rgenData = FillRaygenUniform();
     s_TotalSamples += s_SamplesPerFrame;
     const PtxLightsUbo lights = s_Scene->GetLightsUbo();
     if (s_DebugPipeline) // the debug raygen stores its one sample: nothing accumulates
@@ -139,13 +146,36 @@ void RendererHip::SetPostProcessSettings(const PostProcessSettings &settings)
     s_PostProcessSettings = settings;
 }
 
+static RendererHip::DenoiserSettings s_DenoiserSettings;
+
+void RendererHip::SetSettings(const DenoiserSettings &settings)
+{
+    s_DenoiserSettings = settings;
+}
+
+// The post-processing chain on the current frame: on the running sum, or -- with the denoiser enabled and the path-tracing pipeline
+// bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser").
+static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode)
+{
+    if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
+        return ptx_postprocess(s_Renderer, &u, mode);
+    const PtxRaygenUniformData rgenData = FillRaygenUniform();
+    if (const int rc = ptx_render_guides(s_Renderer, &rgenData))
+        return rc;
+    const PtxDenoiseDesc desc = { u.TotalSamples, s_DenoiserSettings.Iterations, s_DenoiserSettings.SigmaColor, s_DenoiserSettings.SigmaNormal,
+                                  s_DenoiserSettings.SigmaPosition, 0u, 0u };
+    if (const int rc = ptx_denoise(s_Renderer, &desc))
+        return rc;
+    return ptx_postprocess_denoised(s_Renderer, &u, mode);
+}
+
 void RendererHip::SaveOutput(const OutputInfo &info)
 {
     if (info.Extent.width != s_Width || info.Extent.height != s_Height)
         throw error("SaveOutput: the output extent must equal the render extent");
     const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
                                              s_PostProcessSettings.BloomIntensity };
-    Check(ptx_postprocess(s_Renderer, &u, s_PostProcessSettings.Hdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR));
+    Check(PostProcessFrame(u, s_PostProcessSettings.Hdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR));
     const uint32_t format = OutputSaver::SelectImageFormat(info.Format);
     std::vector<std::byte> bytes(static_cast<size_t>(s_Width) * s_Height * (format == PTX_OUTPUT_RGBA32F ? 16 : 4));
     Check(ptx_read_output(s_Renderer, format, bytes.data(), bytes.size()));
@@ -166,7 +196,7 @@ void RendererHip::Present(uint32_t width, uint32_t height, const uint8_t *ui)
     const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
                                              s_PostProcessSettings.BloomIntensity };
     const uint32_t mode = s_SurfaceIsHdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR; // Renderer.cpp:737-742
-    Check(ptx_postprocess(s_Renderer, &u, mode));
+    Check(PostProcessFrame(u, mode));
     const PtxPresentDesc desc = { width, height, s_SurfaceIsHdr ? (uint32_t)PTX_PRESENT_A2B10G10R10_UNORM : (uint32_t)PTX_PRESENT_R8G8B8A8_SRGB, mode, ui, 0u, 0u };
     Check(ptx_present(s_Renderer, &desc));
 }

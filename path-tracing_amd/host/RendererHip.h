@@ -2,7 +2,7 @@
 // (Path-Tracing/Renderer/Renderer.h:42-85) on top of the C-ABI in include/ptx.h, so
 // host code written against the static Renderer class keeps its call sequence:
 //   Init -> UpdateSceneData -> OnResize -> [SetSettings] -> Render ... -> Shutdown.
-// The path-tracing pass, the output stage (post-processing chain + OutputSaver, row N4) and the screen path (row D15:
+// The path-tracing pass, the output stage (post-processing chain + OutputSaver, row N4), the optional denoiser in front of it and the screen path (row D15:
 // scaling blit, tone mapping, UI composition, HDR10 encode, store in the swapchain's format) are implemented; the UI image
 // itself (ImGui), the window and the swapchain stay with the host.
 #pragma once
@@ -54,6 +54,19 @@ public:
         bool Hdr = false; // ToneMappingModeHDR
     };
     static void SetPostProcessSettings(const PostProcessSettings &settings);
+    // The denoiser (ptx.h "Denoiser"; the reference has none).  Enabled: SaveOutput and Present run ptx_render_guides -> ptx_denoise
+    // -> ptx_postprocess_denoised on the current running sum instead of ptx_postprocess; a debug-view frame is shown as it is.
+    // Disabled (the default): both do exactly what they did without it.  The defaults are the measured ones of
+    // docs/NEXT_ROWS.md section 13.
+    struct DenoiserSettings
+    {
+        bool Enabled = false;
+        uint32_t Iterations = 3;
+        float SigmaColor = 1.5f;
+        float SigmaNormal = 0.3f;
+        float SigmaPosition = 0.03f;
+    };
+    static void SetSettings(const DenoiserSettings &settings);
     // RecordPostProcessCommands + RecordSaveOutputCommands on the current running sum, then OutputSaver::WriteImage
     static void SaveOutput(const OutputInfo &info);
 

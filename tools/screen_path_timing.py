@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Times the calls between ptx_render and the window (docs/NEXT_ROWS.md sections 12 and 13): ptx_postprocess, ptx_present,
+ptx_render_guides, ptx_denoise and ptx_postprocess_denoised at 1920 x 1080 and 3840 x 2160, beside one 8-spp step of chess_like.
+
+Every figure is a device-synchronised wall-clock time: synchronise, enqueue the call `repeat` times, synchronise; `repeat` is chosen
+per shape so that a window lasts about five milliseconds, every shape is warmed up first, and the figure is the median of 20
+windows divided by `repeat`.  ptx_denoise is also given as a rate against its algorithmic traffic of 80 bytes per pixel and pass
+(16 B in, 16 B out, 48 B of guides) -- a rate, not a measured bandwidth: the 25 taps are served by the caches.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D]"""
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402,F401  (first, so the HIP library shares torch's HIP runtime)
+import __graft_entry__ as graft  # noqa: E402
+
+WINDOWS, WINDOW_MS, STEP_SPP, STEP_DEPTH = 20, 5.0, 8, 8
+POST = dict(exposure=1.0, bloom_threshold=0.8, bloom_intensity=0.35)
+DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
+
+
+def timed(r, call):
+    """Median over WINDOWS windows of the device-synchronised time of one call, in milliseconds."""
+    def window(repeat):
+        r.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(repeat):
+            call()
+        r.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / repeat
+    window(1)  # warm-up of the shape: allocations, code objects
+    repeat = max(1, math.ceil(WINDOW_MS / max(window(2), 1e-3)))
+    ms = np.array([window(repeat) for _ in range(WINDOWS)])
+    return {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max()), "repeat": repeat}
+
+
+def main():
+    pkg = graft.load_package()
+    detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
+    out = {}
+    scenes = {name: pkg.Scene(name, detail) for name in ("chess_like", "atrium_like")}
+    renderers = {}
+    for name, scene in scenes.items():
+        renderers[name] = pkg.Renderer()
+        renderers[name].upload(scene)
+    for w, h in ((1920, 1080), (3840, 2160)):
+        rec = {}
+        scene, r = scenes["chess_like"], renderers["chess_like"]
+        r.resize(w, h)
+        u = scene.uniform(w, h, bounces=STEP_DEPTH)
+        rec["render_8spp_step_chess_like"] = timed(r, lambda: r.render_frames(u, scene.lights, 0, STEP_SPP))
+        r.reset()
+        r.render_frames(u, scene.lights, 0, STEP_SPP)
+        rec["postprocess"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
+        screens = [(w, h)] + ([(3840, 2160)] if (w, h) == (1920, 1080) else [])
+        for sw, sh in screens:
+            r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_SDR, **POST)
+            rec[f"present_to_{sw}x{sh}_sdr_srgb8"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_R8G8B8A8_SRGB, pkg.TONE_MAPPING_SDR))
+            r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_HDR, **POST)
+            rec[f"present_to_{sw}x{sh}_hdr10"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_A2B10G10R10_UNORM, pkg.TONE_MAPPING_HDR))
+        rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
+        for it in (1, 3, 5):
+            t = timed(r, lambda: r.denoise(STEP_SPP, iterations=it))
+            t["algorithmic_GB_per_s"] = w * h * DENOISE_BYTES_PER_PIXEL_AND_PASS * it / (t["median_ms"] * 1e-3) / 1e9
+            rec[f"denoise_{it}_iterations"] = t
+        r.denoise(STEP_SPP)
+        rec["postprocess_denoised"] = timed(r, lambda: r.postprocess_denoised(**POST))
+        d = pkg.DENOISE_DEFAULTS
+        frame = rec["render_guides_chess_like"]["median_ms"] + rec[f"denoise_{d['iterations']}_iterations"]["median_ms"]
+        rec["guides_plus_default_denoise_share_of_8spp_step"] = frame / rec["render_8spp_step_chess_like"]["median_ms"]
+        a, ra = scenes["atrium_like"], renderers["atrium_like"]
+        ra.resize(w, h)
+        ua = a.uniform(w, h, bounces=STEP_DEPTH)
+        rec["render_guides_atrium_like"] = timed(ra, lambda: ra.render_guides(ua))
+        out[f"{w}x{h}"] = rec
+        for k, v in rec.items():
+            print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+    for r in renderers.values():
+        r.close()
+    if "--json" in sys.argv:
+        with open(sys.argv[sys.argv.index("--json") + 1], "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
