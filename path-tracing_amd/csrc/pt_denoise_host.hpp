@@ -4,7 +4,7 @@
 
 static float4 *guidePtr(PtxRenderer *r, uint32_t which)
 {
-    return r->guides.p + (size_t)which * r->width * r->height;
+    return r->guides.p + which * r->frame.pixels();
 }
 
 // ptx_render_guides: one launch, enqueued like ptx_render_debug's -- the counter block comes back with collectRender, which is
@@ -15,10 +15,10 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_guides: null argument");
     if (!sceneUsable(r) || !imagePtr(r))
         return fail(r, PTX_ERROR_NOT_READY, "ptx_render_guides: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
-    if (r->boundShard)
+    if (r->frame.boundShard)
         return frameIsElsewhere(r, "ptx_render_guides");
     HIP_TRY(r, hipSetDevice(r->device));
-    const size_t n = (size_t)r->width * r->height;
+    const size_t n = r->frame.pixels();
     HIP_TRY(r, r->guides.alloc(n * PTX_GUIDE_COUNT));
     static const PtxLightsUbo noLights = {}; // the pass reads no light
     const LaunchParams p = makeParams(r, uniform, 0, 1);
@@ -46,7 +46,7 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
 // device -> host copy of one renderer-owned RGBA32F image of the render extent, synchronous
 static int readFrameImage(PtxRenderer *r, const float4 *image, void *host, size_t bytes, const char *who)
 {
-    if (bytes != (size_t)r->width * r->height * sizeof(float4))
+    if (bytes != r->frame.bytes())
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: buffer must be width*height*16 bytes", who);
     HIP_TRY(r, hipSetDevice(r->device));
     HIP_TRY(r, hipMemcpyAsync(host, image, bytes, hipMemcpyDeviceToHost, r->stream));
@@ -75,14 +75,14 @@ static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d)
                     (double)d->sigmaNormal, (double)d->sigmaPosition, d->flags, d->reserved);
     if (!imagePtr(r))
         return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no accumulation image (call ptx_resize)");
-    if (r->boundShard)
+    if (r->frame.boundShard)
         return frameIsElsewhere(r, "ptx_denoise");
     if (!r->guidesReady)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no guides for this extent (call ptx_render_guides)");
-    if (r->shard.worldSize > 1u)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: this renderer holds one tile shard of %u; the filter's taps cross tiles", r->shard.worldSize);
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: this renderer holds one tile shard of %u; the filter's taps cross tiles", r->frame.shard.worldSize);
     HIP_TRY(r, hipSetDevice(r->device));
-    const size_t n = (size_t)r->width * r->height;
+    const size_t n = r->frame.pixels();
     HIP_TRY(r, r->denoisePing[0].alloc(n));
     if (d->iterations > 1u)
         HIP_TRY(r, r->denoisePing[1].alloc(n));
@@ -91,12 +91,12 @@ static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d)
     a.normal = guidePtr(r, PTX_GUIDE_NORMAL);
     a.position = guidePtr(r, PTX_GUIDE_POSITION);
     a.albedo = guidePtr(r, PTX_GUIDE_ALBEDO);
-    a.width = r->width;
-    a.height = r->height;
+    a.width = r->frame.width;
+    a.height = r->frame.height;
     a.totalSamples = (float)d->totalSamples;
     a.invSigmaNormal2 = (float)(1.0 / ((double)d->sigmaNormal * d->sigmaNormal));
     a.invSigmaPosition = (float)(1.0 / (double)d->sigmaPosition);
-    const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->width + kDenoiseTileX - 1) / kDenoiseTileX, (r->height + kDenoiseTileY - 1) / kDenoiseTileY);
+    const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->frame.width + kDenoiseTileX - 1) / kDenoiseTileX, (r->frame.height + kDenoiseTileY - 1) / kDenoiseTileY);
     for (uint32_t i = 0; i < d->iterations; i++)
     {
         a.src = i ? r->denoisePing[(i - 1u) & 1u].p : nullptr;

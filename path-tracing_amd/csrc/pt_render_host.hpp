@@ -118,7 +118,7 @@ static int fetchCounters(PtxRenderer *r)
 
 static void launchAccumulate(PtxRenderer *r, const LaunchParams &p)
 {
-    k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->paths.slotRad.p, accumTarget(r), nullptr, r->boundShard ? 1u : 0u);
+    k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->paths.slotRad.p, accumTarget(r), nullptr, r->frame.boundShard ? 1u : 0u);
 }
 
 // k_tail on the auxiliary stream, a thread per path of `queue` for up to `paths` of them (grid-stride; the spill region holds kMaxPersistentThreads)
@@ -520,7 +520,7 @@ static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, cons
                     view->raygenFlags, view->hitGroupFlags, view->reserved);
     if (!sceneUsable(r) || !imagePtr(r))
         return fail(r, PTX_ERROR_NOT_READY, "ptx_render_debug: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
-    if (r->boundShard)
+    if (r->frame.boundShard)
         return frameIsElsewhere(r, "ptx_render_debug");
     if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_debug: LightCount %u exceeds MaxLightCount", lights->LightCount);
@@ -544,6 +544,6 @@ static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, cons
     }
     if (const int rc = endLaunch(r, { PendingLaunch::kDebugView }))
         return rc;
-    r->outputReady = false;
+    r->output.invalidate();
     return PTX_OK;
 }

@@ -1,7 +1,11 @@
-// pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle, its device buffers, scene
-// upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp), the render launches with the bounce schedule
-// of the wavefront backend (pt_render_host.hpp), read-back, the output stage.  Functions here take a valid handle; include/ptx.h's
-// entry points (ptx_capi.hip) are thin wrappers around them.
+// pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle (its state one struct per stage),
+// the environment switches, createRenderer / destroyRenderer, the grid helpers, makeParams and the scene views, ptx_update_animation,
+// ptx_get_stats and the ptx_test_* / ptx_trace_rays entry points.  The stages are host files of their own, included below in the
+// order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp),
+// the render launches with the bounce schedule of the wavefront backend (pt_render_host.hpp), the frame's hand-over -- accumulation
+// image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the denoiser
+// (pt_denoise_host.hpp).  Their functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line
+// wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
@@ -21,6 +25,7 @@
 #include "pt_denoise.hpp"
 #include "pt_post.hpp"
 #include "pt_present.hpp"
+#include "pt_shard_layout.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -249,6 +254,61 @@ struct ScheduleHint
     void forget() { slots = 0u; } // (no launch has 0 slots: the next one is driven from the host and learns again)
 };
 
+// The frame between "the samples are accumulated" and "the host has them" (pt_frame_host.hpp): extent and tile shard, the
+// accumulation image and what may stand in for it, and the pipelined copy to the host.  The stream and the events are released by
+// destroyRenderer, not by a destructor.
+struct FrameState
+{
+    uint32_t width = 0, height = 0;
+    PtxTileShard shard = { 0, 1, 32 };
+    DevBuf<float4> image;
+    float4 *boundImage = nullptr; // external accumulation buffer, if bound
+    float4 *boundShard = nullptr; // ... or the dense tile-major shard buffer the samples are accumulated in (ptx_bind_shard_accumulation)
+    size_t boundShardBytes = 0;
+    // device alias of the page-locked host frame last used by a read-back / unpack (hipHostGetDevicePointer once per buffer)
+    const void *hostAliasOf = nullptr;
+    size_t hostAliasBytes = 0;
+    float4 *hostAlias = nullptr;
+    // pipelined read-back (ptx_readback_begin / _end): snapshot of the image, copied out on its own stream
+    DevBuf<float4> staging;
+    hipStream_t copyStream = nullptr;
+    hipEvent_t evSnapshot = nullptr, evCopied = nullptr;
+    bool copyInFlight = false;
+
+    size_t pixels() const { return (size_t)width * height; }
+    size_t bytes() const { return pixels() * sizeof(float4); } // of the row-major frame
+    float4 *accum() const { return boundImage ? boundImage : image.p; }
+    // where k_accumulate adds the samples: the row-major frame, or this rank's dense tile-major shard
+    float4 *target() const { return boundShard ? boundShard : accum(); }
+    ShardLayout layout(uint32_t rank) const { return shardLayout(width, height, rank, shard.worldSize, shard.tileSize); }
+    void unbindShard() // the bound buffer was laid out for another shard or extent
+    {
+        boundShard = nullptr;
+        boundShardBytes = 0;
+    }
+    void unbind() // a new extent: the caller's buffers have the old size, and a host frame of the new size is another registration
+    {
+        boundImage = nullptr;
+        unbindShard();
+        hostAlias = nullptr;
+    }
+};
+
+// The output stage (row N4) and the screen path (row D15), pt_output_host.hpp.
+struct OutputState
+{
+    DevBuf<float> postRgb, bloomRgb; // rgba16f-valued post-process image and bloom mip chain (3 floats per texel)
+    DevBuf<float4> outLinear;        // tone-mapped image (OutputSaver's m_LinearImage)
+    DevBuf<uint32_t> outSrgb8;
+    bool ready = false;              // a ptx_postprocess since the last ptx_resize / ptx_render_debug
+    PtxPostProcessingUniformData postUniform = {}; // of the last ptx_postprocess (composition.comp's BloomIntensity)
+    // the swapchain image of the last ptx_present and the caller's UI image
+    DevBuf<uint32_t> presentImage, presentUi;
+    uint32_t presentWidth = 0, presentHeight = 0, presentFormat = 0;
+    size_t presentBytes = 0; // 0: nothing presented yet
+    void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
+};
+
 struct PtxRenderer
 {
     EnvSwitches env;
@@ -311,37 +371,13 @@ struct PtxRenderer
     DevBuf<Tri> tris;
     DevBuf<ShadeTri> shadeTris; // deindexed vertices per triangle slot (leaf order), written by k_emit
 
-    // frame
-    uint32_t width = 0, height = 0;
-    PtxTileShard shard = { 0, 1, 32 };
-    DevBuf<float4> image;
-    // output stage (row N4)
-    DevBuf<float> postRgb, bloomRgb; // rgba16f-valued post-process image and bloom mip chain (3 floats per texel)
-    DevBuf<float4> outLinear;        // tone-mapped image (OutputSaver's m_LinearImage)
-    DevBuf<uint32_t> outSrgb8;
-    bool outputReady = false;
-    // screen path (row D15): the swapchain image of the last ptx_present and the caller's UI image
-    PtxPostProcessingUniformData postUniform = {}; // of the last ptx_postprocess (composition.comp's BloomIntensity)
-    DevBuf<uint32_t> presentImage, presentUi;
-    uint32_t presentWidth = 0, presentHeight = 0, presentFormat = 0;
-    size_t presentBytes = 0; // 0: nothing presented yet
+    FrameState frame;
+    OutputState output;
     // denoiser (pt_denoise_host.hpp): the three guide images of the last ptx_render_guides, the two images the filter's iterations
     // alternate between, and which of them holds the result of the last ptx_denoise
     DevBuf<float4> guides, denoisePing[2];
     bool guidesReady = false;
     int denoisedIn = -1; // -1: nothing denoised since the last ptx_resize
-    float4 *boundImage = nullptr; // external accumulation buffer, if bound
-    float4 *boundShard = nullptr; // ... or the dense tile-major shard buffer the samples are accumulated in (ptx_bind_shard_accumulation)
-    size_t boundShardBytes = 0;
-    // device alias of the page-locked host frame last used by a read-back / unpack (hipHostGetDevicePointer once per buffer)
-    const void *hostAliasOf = nullptr;
-    size_t hostAliasBytes = 0;
-    float4 *hostAlias = nullptr;
-    // pipelined read-back (ptx_readback_begin / _end): snapshot of the image, copied out on its own stream
-    DevBuf<float4> staging;
-    hipStream_t copyStream = nullptr;
-    hipEvent_t evSnapshot = nullptr, evCopied = nullptr;
-    bool copyInFlight = false;
 
     // wavefront state
     PathState paths;
@@ -433,15 +469,8 @@ static void quiesceSharers(PtxRenderer *r)
     }
 }
 
-static float4 *imagePtr(PtxRenderer *r)
-{
-    return r->boundImage ? r->boundImage : r->image.p;
-}
-// where k_accumulate adds the samples: the row-major frame, or this rank's dense tile-major shard (ptx_bind_shard_accumulation)
-static float4 *accumTarget(PtxRenderer *r)
-{
-    return r->boundShard ? r->boundShard : imagePtr(r);
-}
+static float4 *imagePtr(const PtxRenderer *r) { return r->frame.accum(); }
+static float4 *accumTarget(const PtxRenderer *r) { return r->frame.target(); }
 static int frameIsElsewhere(PtxRenderer *r, const char *who)
 {
     return fail(r, PTX_ERROR_NOT_READY, "%s: the accumulation of this renderer lives in a shard buffer (ptx_bind_shard_accumulation); the frame "
@@ -499,22 +528,25 @@ static uint32_t residentBlocksOf(K kernel, int device)
     return (uint32_t)perCu * (uint32_t)cus;
 }
 
-static LaunchParams makeParams(const PtxRenderer *r, const PtxRaygenUniformData *u, uint32_t firstFrame, uint32_t frames)
+// The parameters of a launch over `rank`'s shard of the handle's frame (the geometry: pt_shard_layout.hpp).  Another rank's than the
+// handle's own is what the unpack kernel of a gathered frame reads.
+static LaunchParams makeParams(const PtxRenderer *r, const PtxRaygenUniformData *u, uint32_t firstFrame, uint32_t frames, uint32_t rank)
 {
     LaunchParams p;
     std::memset(&p, 0, sizeof(p));
     if (u)
         p.u = *u;
-    p.width = r->width;
-    p.height = r->height;
-    p.rank = r->shard.rank;
-    p.worldSize = r->shard.worldSize;
-    p.tileSize = r->shard.tileSize;
-    p.tilesX = (r->width + p.tileSize - 1) / p.tileSize;
-    const uint32_t tilesY = (r->height + p.tileSize - 1) / p.tileSize;
-    p.numTiles = p.tilesX * tilesY;
-    p.ownedTiles = p.numTiles > p.rank ? (p.numTiles - p.rank + p.worldSize - 1) / p.worldSize : 0;
-    p.slotsPerFrame = p.ownedTiles * p.tileSize * p.tileSize;
+    const ShardLayout s = r->frame.layout(rank);
+    p.width = r->frame.width;
+    p.height = r->frame.height;
+    p.rank = rank;
+    p.worldSize = r->frame.shard.worldSize;
+    p.tileSize = r->frame.shard.tileSize;
+    p.tilesX = s.tilesX;
+    p.numTiles = s.numTiles;
+    p.ownedTiles = s.ownedTiles;
+    p.slotsPerFrame = s.slotsPerFrame;
+    p.ownedPixels = s.ownedPixels;
     p.frames = frames;
     p.firstFrame = firstFrame;
     p.numSlots = p.slotsPerFrame * frames;
@@ -522,14 +554,11 @@ static LaunchParams makeParams(const PtxRenderer *r, const PtxRaygenUniformData 
     p.framesPerWave = 1;
     while (p.framesPerWave < maxPerWave && p.framesPerWave < 8u && frames % (p.framesPerWave * 2u) == 0u)
         p.framesPerWave *= 2u;
-    for (uint32_t t = p.rank; t < p.numTiles; t += p.worldSize)
-    {
-        const uint32_t x0 = (t % p.tilesX) * p.tileSize, y0 = (t / p.tilesX) * p.tileSize;
-        const uint32_t w = r->width - x0 < p.tileSize ? r->width - x0 : p.tileSize;
-        const uint32_t h = r->height - y0 < p.tileSize ? r->height - y0 : p.tileSize;
-        p.ownedPixels += w * h;
-    }
     return p;
+}
+static LaunchParams makeParams(const PtxRenderer *r, const PtxRaygenUniformData *u, uint32_t firstFrame, uint32_t frames)
+{
+    return makeParams(r, u, firstFrame, frames, r->frame.shard.rank);
 }
 
 // Every frame in flight owns two HIP streams (main + auxiliary), and the runtime multiplexes all streams of a process
@@ -700,9 +729,9 @@ static void destroyRenderer(PtxRenderer *r)
         for (hipEvent_t ev : { e.t0, e.t1, e.t2, e.x0, e.x1, e.x2 })
             if (ev)
                 (void)hipEventDestroy(ev);
-    if (r->copyStream) { (void)hipStreamSynchronize(r->copyStream); (void)hipStreamDestroy(r->copyStream); }
-    if (r->evSnapshot) (void)hipEventDestroy(r->evSnapshot);
-    if (r->evCopied) (void)hipEventDestroy(r->evCopied);
+    if (r->frame.copyStream) { (void)hipStreamSynchronize(r->frame.copyStream); (void)hipStreamDestroy(r->frame.copyStream); }
+    if (r->frame.evSnapshot) (void)hipEventDestroy(r->frame.evSnapshot);
+    if (r->frame.evCopied) (void)hipEventDestroy(r->frame.evCopied);
     if (r->hostCounters)
         (void)hipHostFree(r->hostCounters);
     if (r->evA) (void)hipEventDestroy(r->evA);
@@ -802,6 +831,9 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
 }
 
 #include "pt_render_host.hpp" // ptx_render, ptx_render_debug: renderImpl and its stages, collectRender, renderDebug
+#include "pt_frame_host.hpp" // accumulation image and its bindings, tile shards, read-back: resizeFrame ... unpackShards
+#include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
+#include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
 
 static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
 {
@@ -820,344 +852,6 @@ static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float 
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;
 }
-
-// Device alias of a page-locked host frame (hipHostMalloc / hipHostRegister memory), looked up once per (pointer, size): the
-// owner of a gathered frame passes the same few buffers step after step.  nullptr: the device cannot address the buffer.
-static float4 *hostFrameAlias(PtxRenderer *r, const void *pinnedHost, size_t bytes)
-{
-    if (r->hostAlias && r->hostAliasOf == pinnedHost && r->hostAliasBytes == bytes)
-        return r->hostAlias;
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, const_cast<void *>(pinnedHost), 0) != hipSuccess || !dp)
-    {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    r->hostAliasOf = pinnedHost;
-    r->hostAliasBytes = bytes;
-    r->hostAlias = static_cast<float4 *>(dp);
-    return r->hostAlias;
-}
-
-// Read-back that overlaps the next launches: a device-to-device snapshot of the image on the render stream (33 MB at
-// 1080p: ~20 us), then the PCIe copy on a second stream while the render stream goes on.  The reference reads its
-// output back the same way, a frame late (OutputSaver.cpp:120-199).
-static int readbackBegin(PtxRenderer *r, float *pinnedHost, size_t bytes)
-{
-    if (!r || !pinnedHost || !imagePtr(r) || bytes != (size_t)r->width * r->height * sizeof(float4))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_readback_begin: buffer must be width*height*16 bytes");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_readback_begin");
-    HIP_TRY(r, hipSetDevice(r->device));
-    if (!r->evSnapshot)
-    {
-        HIP_TRY(r, hipEventCreateWithFlags(&r->evSnapshot, hipEventDisableTiming));
-        // The copy may be a kernel storing to host memory (k_copy_out): the event the host waits on must release those stores to
-        // the system scope, also for page-locked memory that is not host-coherent.
-        HIP_TRY(r, hipEventCreateWithFlags(&r->evCopied, hipEventDisableTiming | hipEventReleaseToSystem));
-    }
-    // The copy to the host rides on the renderer's auxiliary stream -- idle once the frame's shadow and tail kernels are done,
-    // and not needed again before this renderer's next frame -- instead of a third stream per frame in flight: the streams of a
-    // process share GPU_MAX_HW_QUEUES hardware queues, and streams on one queue run one after the other.
-    if (!r->auxStream && !r->copyStream)
-        HIP_TRY(r, hipStreamCreateWithFlags(&r->copyStream, hipStreamNonBlocking));
-    const hipStream_t copyOn = r->auxStream ? r->auxStream : r->copyStream;
-    HIP_TRY(r, r->staging.alloc((size_t)r->width * r->height));
-    if (r->copyInFlight) // the previous copy still reads the staging image
-        HIP_TRY(r, hipStreamWaitEvent(r->stream, r->evCopied, 0));
-    // the snapshot by a copy KERNEL (33 MB at the memory's rate: ~20 us), not hipMemcpyAsync: the runtime's device-to-device copy
-    // took 0.5 ms per 1080p image and the copies of the frames in flight queue behind one another -- a floor of 0.5 ms per step
-    // under every renderer that reads back, half the step of a 1 / 8 tile shard (tools/experiments/gather_cost.sh, round 5)
-    if (r->env.snapshotMemcpy)
-        HIP_TRY(r, hipMemcpyAsync(r->staging.p, imagePtr(r), bytes, hipMemcpyDeviceToDevice, r->stream));
-    else
-    {
-        k_copy_out<<<1024, kBlock, 0, r->stream>>>(imagePtr(r), r->staging.p, (uint32_t)(bytes / sizeof(float4)));
-        HIP_TRY(r, hipGetLastError()); // (a failed launch would hand the host a stale staging image)
-    }
-    HIP_TRY(r, hipEventRecord(r->evSnapshot, r->stream));
-    HIP_TRY(r, hipStreamWaitEvent(copyOn, r->evSnapshot, 0));
-    // The snapshot leaves through ONE workgroup writing to the page-locked buffer (posted writes over PCIe, 33 MB in a few ms)
-    // rather than through hipMemcpyAsync: a DMA burst at the link's full rate delays the completion signals and packet fetches
-    // of every other frame in flight for its 1.2 ms -- measured on chess_like with 8 frames in flight: no read-back 2,600
-    // Msamples/s, hipMemcpyAsync (SDMA) 2,416 / 2,422, copy kernel with 256 / 64 / 8 / 4 / 2 / 1 workgroups 2,359 / 2,395 / 2,445
-    // / 2,441 / 2,465 / 2,483-2,494.  Host memory the device cannot address (not page-locked) takes the runtime's copy.
-    float4 *const hostOnDevice = hostFrameAlias(r, pinnedHost, bytes);
-    if (hostOnDevice)
-    {
-        // ... for a whole frame on one GPU.  Rank 0 of an N-GPU job renders 1 / N of the frame per step and still reads ALL of it
-        // back: there the link, not the rendering, sets the pace, and one workgroup's 8 GB/s (4.1 ms per 1080p image) made a 1 / 8
-        // step of chess_like 2.2 ms instead of 0.96 (tools/experiments/gather_cost.sh) -- more workgroups with more ranks.
-        const uint32_t groups = r->env.copyGroups ? r->env.copyGroups : (r->shard.worldSize > 1 ? std::min(16u, 2u * r->shard.worldSize) : 1u);
-        k_copy_out<<<groups, kBlock, 0, copyOn>>>(r->staging.p, hostOnDevice, (uint32_t)(bytes / sizeof(float4)));
-        HIP_TRY(r, hipGetLastError());
-    }
-    else
-        HIP_TRY(r, hipMemcpyAsync(pinnedHost, r->staging.p, bytes, hipMemcpyDeviceToHost, copyOn));
-    HIP_TRY(r, hipEventRecord(r->evCopied, copyOn));
-    r->copyInFlight = true;
-    return PTX_OK;
-}
-
-static int unpackShard(PtxRenderer *r, uint32_t rank, const void *devSrc, float *pinnedHost = nullptr, size_t hostBytes = 0)
-{
-    if (!r || !devSrc || !imagePtr(r) || rank >= r->shard.worldSize)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shard: bad argument");
-    float4 *hostOnDevice = nullptr;
-    if (pinnedHost)
-    {
-        if (hostBytes != (size_t)r->width * r->height * sizeof(float4))
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shard_host: buffer must be width*height*16 bytes");
-        HIP_TRY(r, hipSetDevice(r->device));
-        hostOnDevice = hostFrameAlias(r, pinnedHost, hostBytes);
-        if (!hostOnDevice)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shard_host: the buffer is not page-locked memory the device can address");
-        if (!r->evSnapshot)
-        {
-            HIP_TRY(r, hipEventCreateWithFlags(&r->evSnapshot, hipEventDisableTiming));
-            HIP_TRY(r, hipEventCreateWithFlags(&r->evCopied, hipEventDisableTiming | hipEventReleaseToSystem));
-        }
-    }
-    PtxRenderer tmp;
-    tmp.width = r->width;
-    tmp.height = r->height;
-    tmp.shard = r->shard;
-    tmp.shard.rank = rank;
-    const LaunchParams p = makeParams(&tmp, nullptr, 0, 1);
-    if (p.slotsPerFrame)
-    {
-        // towards the host a FEW workgroups (PTX_COPY_GROUPS; default 4 per shard): what the link carries in a burst, the command
-        // processor's own traffic over it waits behind -- 2 / 4 / 8 / 16 / 64 / 2,048 workgroups: 1.45 / 1.38 / 1.42 / 1.47 / 1.50 /
-        // 1.51 ms per 1 / 8 step of chess_like (profiles/r05_unpack_groups.txt)
-        uint32_t grid = gridFor(p.slotsPerFrame);
-        if (hostOnDevice)
-            grid = std::min(grid, r->env.copyGroups ? r->env.copyGroups : 4u);
-        k_unpack_shard<<<grid, kBlock, 0, r->stream>>>(p, static_cast<const float4 *>(devSrc), imagePtr(r), hostOnDevice);
-    }
-    HIP_TRY(r, hipGetLastError());
-    if (hostOnDevice) // ptx_readback_end waits for the LAST of these: the stores of every unpack before it are released with it
-    {
-        HIP_TRY(r, hipEventRecord(r->evCopied, r->stream));
-        r->copyInFlight = true;
-    }
-    return PTX_OK;
-}
-
-// The whole gathered frame in ONE launch (k_gather_frame): `devSrc` holds the shards of ranks 0 .. worldSize-1, `strideBytes`
-// apart, each in ptx_pack_shard's layout.  Targets: the device image (toDeviceImage), the host's page-locked frame, or both --
-// a rank that only hands the frame to the host (OutputSaver's role, OutputSaver.cpp:120-199) never rewrites its device image.
-static int unpackShards(PtxRenderer *r, const void *devSrc, size_t strideBytes, int toDeviceImage, float *pinnedHost, size_t hostBytes)
-{
-    if (!r || !devSrc || !r->width || (!toDeviceImage && !pinnedHost))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shards: need the gathered shards and at least one target");
-    if (toDeviceImage && !imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_unpack_shards: no accumulation image (call ptx_resize)");
-    size_t largest = 0;
-    for (uint32_t k = 0; k < r->shard.worldSize; k++)
-        largest = std::max(largest, ptx_shard_bytes(r, k));
-    if (strideBytes < largest || strideBytes % sizeof(float4) != 0 || strideBytes / sizeof(float4) > 0xffffffffull)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shards: the stride must be a multiple of 16 bytes and at least the largest shard (%zu bytes)", largest);
-    HIP_TRY(r, hipSetDevice(r->device));
-    float4 *hostOnDevice = nullptr;
-    if (pinnedHost)
-    {
-        if (hostBytes != (size_t)r->width * r->height * sizeof(float4))
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shards: the host buffer must be width*height*16 bytes");
-        hostOnDevice = hostFrameAlias(r, pinnedHost, hostBytes);
-        if (!hostOnDevice)
-            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_unpack_shards: the host buffer is not page-locked memory the device can address");
-        if (!r->evSnapshot)
-        {
-            HIP_TRY(r, hipEventCreateWithFlags(&r->evSnapshot, hipEventDisableTiming));
-            HIP_TRY(r, hipEventCreateWithFlags(&r->evCopied, hipEventDisableTiming | hipEventReleaseToSystem));
-        }
-    }
-    GatherParams g;
-    g.width = r->width;
-    g.height = r->height;
-    g.tileSize = r->shard.tileSize;
-    g.tilesX = (r->width + g.tileSize - 1) / g.tileSize;
-    g.worldSize = r->shard.worldSize;
-    g.strideSlots = (uint32_t)(strideBytes / sizeof(float4));
-    // towards the host a FEW workgroups (PTX_COPY_GROUPS): what the link carries in a burst, the command processor's own traffic
-    // over it waits behind (profiles/r05_unpack_groups.txt); device-only: the memory's rate
-    uint32_t grid = gridFor((size_t)r->width * r->height);
-    if (hostOnDevice)
-        grid = std::min(grid, r->env.copyGroups ? r->env.copyGroups : 16u);
-    k_gather_frame<<<grid, kBlock, 0, r->stream>>>(g, static_cast<const float4 *>(devSrc), toDeviceImage ? imagePtr(r) : nullptr, hostOnDevice);
-    HIP_TRY(r, hipGetLastError());
-    if (hostOnDevice) // ptx_readback_end waits for it
-    {
-        HIP_TRY(r, hipEventRecord(r->evCopied, r->stream));
-        r->copyInFlight = true;
-    }
-    return PTX_OK;
-}
-
-// ptx_bind_shard_accumulation: the samples of a tile-sharded renderer are accumulated IN the dense tile-major buffer that is the
-// message of the gather (k_accumulate's shard-major target) -- no ptx_pack_shard pass, no row-major frame on a rank that is not
-// the frame's owner.  The buffer must hold this rank's shard (ptx_shard_bytes); entries of ragged tiles outside the image stay 0.
-static int bindShardAccumulation(PtxRenderer *r, void *devShard, size_t bytes)
-{
-    if (!r || !r->width)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_bind_shard_accumulation: call ptx_resize and ptx_set_tile_shard first");
-    if (devShard && bytes < ptx_shard_bytes(r, r->shard.rank))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_bind_shard_accumulation: the buffer must hold ptx_shard_bytes() = %zu bytes", ptx_shard_bytes(r, r->shard.rank));
-    r->boundShard = static_cast<float4 *>(devShard);
-    r->boundShardBytes = devShard ? ptx_shard_bytes(r, r->shard.rank) : 0;
-    return PTX_OK;
-}
-
-// Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)
-// the chain on `source` (width x height running sums of uniform->TotalSamples samples): the accumulation image, or the denoised mean
-static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
-{
-    HIP_TRY(r, hipSetDevice(r->device));
-    const uint32_t W = r->width, H = r->height, n = W * H;
-    uint32_t levels = 1;
-    for (uint32_t m = W > H ? W : H; m > 1; m >>= 1)
-        levels++;
-    // mips 0 .. maxMipLevel-1 take part, maxMipLevel = min(levels - 3, MaxBloomMipmapLevel) (Renderer.cpp:955-956)
-    uint32_t used = levels >= 5 ? (levels - 3 < 12 ? levels - 3 : 12) : 1;
-    BloomLevel L[13];
-    size_t total = 0;
-    for (uint32_t l = 0; l < used; l++)
-    {
-        L[l].w = (W >> l) ? (W >> l) : 1;
-        L[l].h = (H >> l) ? (H >> l) : 1;
-        total += (size_t)L[l].w * L[l].h * 3;
-    }
-    HIP_TRY(r, r->postRgb.alloc((size_t)n * 3));
-    HIP_TRY(r, r->bloomRgb.alloc(total));
-    HIP_TRY(r, r->outLinear.alloc(n));
-    size_t off = 0;
-    for (uint32_t l = 0; l < used; l++)
-    {
-        L[l].rgb = r->bloomRgb.p + off;
-        off += (size_t)L[l].w * L[l].h * 3;
-    }
-    k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->postRgb.p, L[0].rgb);
-    for (uint32_t i = 0; i + 1 < used; i++)
-        k_bloom_downsample<<<gridFor((size_t)L[i + 1].w * L[i + 1].h), kBlock, 0, r->stream>>>(L[i], L[i + 1]);
-    for (uint32_t i = used - 1; i > 0; i--)
-        k_bloom_upsample<<<gridFor((size_t)L[i - 1].w * L[i - 1].h), kBlock, 0, r->stream>>>(L[i], L[i - 1]);
-    k_compose_tonemap<<<gridFor(n), kBlock, 0, r->stream>>>(r->postRgb.p, L[0].rgb, n, *uniform, toneMappingMode, r->outLinear.p);
-    HIP_TRY(r, hipGetLastError());
-    r->postUniform = *uniform;
-    r->outputReady = true;
-    return PTX_OK;
-}
-
-static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
-{
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess: bad argument");
-    if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess: no accumulation image (call ptx_resize)");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_postprocess");
-    return postprocessImage(r, imagePtr(r), uniform, toneMappingMode);
-}
-
-// OutputSaver: blit of the tone-mapped image into its output image + readback (OutputSaver.cpp:64-86, :120-199)
-static int readOutput(PtxRenderer *r, uint32_t outputFormat, void *host, size_t bytes)
-{
-    if (!r || !host || outputFormat > PTX_OUTPUT_RGBA32F)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_output: bad argument");
-    if (!r->outputReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_output: call ptx_postprocess first");
-    const uint32_t n = r->width * r->height;
-    const size_t want = (size_t)n * (outputFormat == PTX_OUTPUT_RGBA32F ? 16 : 4);
-    if (bytes != want)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_output: buffer must be %zu bytes", want);
-    HIP_TRY(r, hipSetDevice(r->device));
-    if (outputFormat == PTX_OUTPUT_RGBA32F)
-        HIP_TRY(r, hipMemcpyAsync(host, r->outLinear.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    else
-    {
-        HIP_TRY(r, r->outSrgb8.alloc(n));
-        k_encode_srgb8<<<gridFor(n), kBlock, 0, r->stream>>>(r->outLinear.p, n, r->outSrgb8.p);
-        HIP_TRY(r, hipMemcpyAsync(host, r->outSrgb8.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    }
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-// The screen path: RecordPostProcessCommands' final blit + RecordUICommands (Renderer.cpp:1075-1203) in one launch of k_present
-static int present(PtxRenderer *r, const PtxPresentDesc *d)
-{
-    if (!r || !d)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: null argument");
-    if (!d->width || !d->height || d->width > 16384u || d->height > 16384u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: bad screen extent %ux%u (1 .. 16384 each)", d->width, d->height);
-    if (d->format > PTX_PRESENT_R16G16B16A16_SFLOAT || d->toneMappingMode > PTX_TONE_MAPPING_HDR || (d->flags & ~(uint32_t)PTX_PRESENT_UI_ON_DEVICE) || d->reserved)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: unknown format %u, mode %u or flags 0x%x, or reserved != 0", d->format, d->toneMappingMode, d->flags);
-    const bool hdr = d->toneMappingMode == PTX_TONE_MAPPING_HDR;
-    if ((hdr && d->format <= PTX_PRESENT_B8G8R8A8_SRGB) || (!hdr && d->format == PTX_PRESENT_A2B10G10R10_UNORM))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)");
-    if (!r->outputReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_present: call ptx_postprocess first");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_present");
-    HIP_TRY(r, hipSetDevice(r->device));
-    const uint32_t n = d->width * d->height;
-    const size_t words = (size_t)n * (d->format == PTX_PRESENT_R16G16B16A16_SFLOAT ? 2 : 1);
-    if (words > r->presentImage.n || !r->presentImage.p) // a failed allocation keeps the previous image
-    {
-        DevBuf<uint32_t> grown;
-        HIP_TRY(r, grown.alloc(words));
-        r->presentImage.swap(grown);
-    }
-    PresentArgs a;
-    a.post = r->postRgb.p;
-    a.bloom0 = r->bloomRgb.p; // level 0 of the chain
-    a.ui = static_cast<const uint32_t *>(d->ui);
-    a.out = r->presentImage.p;
-    a.u = r->postUniform;
-    a.W = r->width; a.H = r->height; a.SW = d->width; a.SH = d->height;
-    if (d->ui && !(d->flags & PTX_PRESENT_UI_ON_DEVICE))
-    {
-        HIP_TRY(r, r->presentUi.alloc(n));
-        HIP_TRY(r, hipMemcpyAsync(r->presentUi.p, d->ui, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
-        a.ui = r->presentUi.p;
-    }
-    const uint32_t grid = (n + kPresentBlock - 1) / kPresentBlock;
-    switch (d->format)
-    {
-    case PTX_PRESENT_R8G8B8A8_SRGB: k_present<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    case PTX_PRESENT_B8G8R8A8_SRGB: k_present<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    case PTX_PRESENT_A2B10G10R10_UNORM: k_present<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    default:
-        if (hdr)
-            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a);
-        else
-            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a);
-    }
-    HIP_TRY(r, hipGetLastError());
-    r->presentWidth = d->width;
-    r->presentHeight = d->height;
-    r->presentFormat = d->format;
-    r->presentBytes = words * 4;
-    return PTX_OK;
-}
-
-static int readPresent(PtxRenderer *r, void *host, size_t bytes)
-{
-    if (!r || !host)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: null argument");
-    if (!r->presentBytes)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: nothing presented yet (call ptx_present)");
-    if (bytes != r->presentBytes)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: buffer must be %zu bytes", r->presentBytes);
-    HIP_TRY(r, hipSetDevice(r->device));
-    HIP_TRY(r, hipMemcpyAsync(host, r->presentImage.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-#include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
 
 static int getStats(PtxRenderer *r, PtxStats *stats)
 {

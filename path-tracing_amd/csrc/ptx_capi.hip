@@ -1,7 +1,8 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
-// Renderer member it replaces in include/ptx.h; the implementations are in pt_runtime.hpp and the host files it includes
-// (pt_scene_host.hpp, pt_bvh_host.hpp, pt_render_host.hpp, pt_denoise_host.hpp) and pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp
-// (device side).  No exceptions cross this boundary: status codes + ptx_last_error.
+// Renderer member it replaces in include/ptx.h; here each is ONE line (ptx_set_backend, ptx_synchronize and the trivial getters
+// apart) that calls the implementation in pt_runtime.hpp or one of the host files it includes (pt_scene_host.hpp, pt_bvh_host.hpp,
+// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp); device side: pt_wavefront.hpp / pt_bvh.hpp /
+// pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
 extern "C" {
@@ -86,44 +87,17 @@ int ptx_update_animation(PtxRenderer *r, const PtxTransform *instanceTransforms,
 
 int ptx_resize(PtxRenderer *r, uint32_t width, uint32_t height)
 {
-    if (!r || !width || !height || (uint64_t)width * height > 0x7fffffffull)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_resize: bad extent %ux%u", width, height);
-    HIP_TRY(r, hipSetDevice(r->device));
-    r->width = width;
-    r->height = height;
-    r->outputReady = false;
-    r->guidesReady = false; // the guides and the denoised image belong to the extent they were made for
-    r->denoisedIn = -1;
-    r->boundImage = nullptr;
-    r->boundShard = nullptr;
-    r->boundShardBytes = 0;
-    r->hostAlias = nullptr; // (a frame buffer of the new size is another registration)
-    HIP_TRY(r, r->image.alloc((size_t)width * height));
-    return ptx_reset_accumulation(r);
+    return resizeFrame(r, width, height);
 }
 
 int ptx_set_tile_shard(PtxRenderer *r, const PtxTileShard *s)
 {
-    if (!r || !s || !s->worldSize || s->rank >= s->worldSize || !s->tileSize || (s->tileSize % 8) != 0 || s->tileSize > 1024)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_set_tile_shard: need rank < worldSize and tileSize a multiple of 8");
-    if (r->boundShard && (r->shard.rank != s->rank || r->shard.worldSize != s->worldSize || r->shard.tileSize != s->tileSize))
-    {
-        r->boundShard = nullptr; // the bound buffer was laid out for the previous shard
-        r->boundShardBytes = 0;
-    }
-    r->shard = *s;
-    return PTX_OK;
+    return setTileShard(r, s);
 }
 
 int ptx_reset_accumulation(PtxRenderer *r)
 {
-    if (!r || !imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_reset_accumulation: no accumulation image (call ptx_resize)");
-    if (r->boundShard)
-        HIP_TRY(r, hipMemsetAsync(r->boundShard, 0, r->boundShardBytes, r->stream));
-    else
-        HIP_TRY(r, hipMemsetAsync(imagePtr(r), 0, (size_t)r->width * r->height * sizeof(float4), r->stream));
-    return PTX_OK;
+    return resetAccumulation(r);
 }
 
 int ptx_render(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights)
@@ -161,13 +135,7 @@ int ptx_synchronize(PtxRenderer *r)
 
 int ptx_readback(PtxRenderer *r, float *rgba, size_t bytes)
 {
-    if (!r || !rgba || !imagePtr(r) || bytes != (size_t)r->width * r->height * sizeof(float4))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_readback: buffer must be width*height*16 bytes");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_readback");
-    HIP_TRY(r, hipMemcpyAsync(rgba, imagePtr(r), bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    return collectRender(r); // an error of the launch that produced the image surfaces with it
+    return readback(r, rgba, bytes);
 }
 
 int ptx_readback_begin(PtxRenderer *r, float *pinnedHost, size_t bytes)
@@ -177,14 +145,7 @@ int ptx_readback_begin(PtxRenderer *r, float *pinnedHost, size_t bytes)
 
 int ptx_readback_end(PtxRenderer *r)
 {
-    if (!r)
-        return PTX_ERROR_INVALID_ARGUMENT;
-    if (r->copyInFlight)
-    {
-        HIP_TRY(r, hipEventSynchronize(r->evCopied));
-        r->copyInFlight = false;
-    }
-    return PTX_OK;
+    return readbackEnd(r);
 }
 
 void *ptx_device_accum_ptr(PtxRenderer *r)
@@ -194,37 +155,17 @@ void *ptx_device_accum_ptr(PtxRenderer *r)
 
 size_t ptx_accum_bytes(const PtxRenderer *r)
 {
-    return r ? (size_t)r->width * r->height * sizeof(float4) : 0;
+    return r ? r->frame.bytes() : 0;
 }
 
 size_t ptx_shard_bytes(const PtxRenderer *r, uint32_t rank)
 {
-    if (!r || !r->width || rank >= r->shard.worldSize)
-        return 0;
-    PtxRenderer tmp;
-    tmp.width = r->width;
-    tmp.height = r->height;
-    tmp.shard = r->shard;
-    tmp.shard.rank = rank;
-    const LaunchParams p = makeParams(&tmp, nullptr, 0, 1);
-    return (size_t)p.slotsPerFrame * sizeof(float4);
+    return shardBytes(r, rank);
 }
 
 int ptx_pack_shard(PtxRenderer *r, void *devDst)
 {
-    if (!r || !devDst || !imagePtr(r))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_pack_shard: null argument");
-    const LaunchParams p = makeParams(r, nullptr, 0, 1);
-    if (r->boundShard) // the accumulation already IS the packed shard (ptx_bind_shard_accumulation)
-    {
-        if (devDst != r->boundShard && p.slotsPerFrame)
-            HIP_TRY(r, hipMemcpyAsync(devDst, r->boundShard, (size_t)p.slotsPerFrame * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
-        return PTX_OK;
-    }
-    if (p.slotsPerFrame)
-        k_pack_shard<<<gridFor(p.slotsPerFrame), kBlock, 0, r->stream>>>(p, imagePtr(r), static_cast<float4 *>(devDst));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
+    return packShard(r, devDst);
 }
 
 int ptx_unpack_shard(PtxRenderer *r, uint32_t rank, const void *devSrc)
@@ -271,12 +212,12 @@ int ptx_read_present(PtxRenderer *r, void *host, size_t bytes)
 
 void *ptx_device_present_ptr(PtxRenderer *r)
 {
-    return r && r->presentBytes ? r->presentImage.p : nullptr;
+    return r && r->output.presentBytes ? r->output.presentImage.p : nullptr;
 }
 
 size_t ptx_present_bytes(const PtxRenderer *r)
 {
-    return r ? r->presentBytes : 0;
+    return r ? r->output.presentBytes : 0;
 }
 
 int ptx_render_guides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
@@ -316,13 +257,7 @@ int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData 
 
 int ptx_write_accumulation(PtxRenderer *r, const float *rgba, size_t bytes)
 {
-    if (!r || !rgba || !imagePtr(r) || bytes != (size_t)r->width * r->height * sizeof(float4))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_write_accumulation: buffer must be width*height*16 bytes");
-    if (r->boundShard)
-        return frameIsElsewhere(r, "ptx_write_accumulation");
-    HIP_TRY(r, hipMemcpyAsync(imagePtr(r), rgba, bytes, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    return PTX_OK;
+    return writeAccumulation(r, rgba, bytes);
 }
 
 int ptx_get_stats(PtxRenderer *r, PtxStats *stats)
@@ -357,12 +292,7 @@ int ptx_trace_rays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, fl
 
 int ptx_bind_accumulation(PtxRenderer *r, void *devPtr, size_t bytes)
 {
-    if (!r || !r->width)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_bind_accumulation: call ptx_resize first");
-    if (devPtr && bytes != (size_t)r->width * r->height * sizeof(float4))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_bind_accumulation: buffer must be width*height*16 bytes");
-    r->boundImage = static_cast<float4 *>(devPtr);
-    return PTX_OK;
+    return bindAccumulation(r, devPtr, bytes);
 }
 
 } // extern "C"
