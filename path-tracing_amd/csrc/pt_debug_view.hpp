@@ -236,7 +236,7 @@ PT_DEV void debugViewBody(const LaunchParams &p, const SceneView &sv, const Trac
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.slotsPerFrame; s += gridDim.x * blockDim.x)
     {
         const uint32_t pixel = slotPixel(p, s);
-        if (pixel == 0xffffffffu)
+        if (pixel == kNoPixel)
             continue;
         f3 ro, rd, rx, ry;
         constructPrimaryRay<true>(pixel % p.width, pixel / p.width, p.width, p.height, p.u.ViewInverse, p.u.ProjInverse, F2(0.5f, 0.5f), ro, rd, rx, ry); // :25

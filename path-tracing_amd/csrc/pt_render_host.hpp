@@ -1,6 +1,7 @@
 // pt_render_host.hpp -- ptx_render / ptx_render_frames / ptx_render_debug: the bounce schedule of the wavefront backend as named
 // stages, the megakernel and zero-bounce launches beside it, and what a launch leaves for the next one (collectRender).
-// Included by pt_runtime.hpp after pt_bvh_host.hpp; the state is three members of the handle: PathState, PendingLaunch, ScheduleHint.
+// Included by pt_runtime.hpp after pt_bvh_host.hpp; the state is three members of the handle: PathState (the per-slot buffers: the
+// list, their growth and the kernels' view of them are that one struct), PendingLaunch, ScheduleHint.
 #pragma once
 
 #include <type_traits>
@@ -17,27 +18,6 @@ template <typename F> static void withFlag(bool flag, F &&f)
 {
     if (flag) f(std::true_type());
     else f(std::false_type());
-}
-
-// Per-slot buffers for `slots` paths: grow-only; differentials and decals a scene needs later come at the largest size asked for.
-static int ensureSlots(PtxRenderer *r, size_t slots)
-{
-    PathState &ps = r->paths;
-    const size_t want = std::max(slots, ps.slotRad.n);
-    const int mode = kernelMode(r);
-    if (mode >= 1)
-        HIP_TRY(r, ps.diffs.alloc(3 * want));
-    if (mode == 2)
-    {
-        HIP_TRY(r, ps.decal.alloc(want)); HIP_TRY(r, ps.decalT.alloc(want));
-    }
-    HIP_TRY(r, ps.slotRad.alloc(want));
-    HIP_TRY(r, ps.rayO.alloc(want)); HIP_TRY(r, ps.rayD.alloc(want)); HIP_TRY(r, ps.thr.alloc(want)); HIP_TRY(r, ps.rad.alloc(want));
-    HIP_TRY(r, ps.hit.alloc(want)); HIP_TRY(r, ps.shD.alloc(want)); HIP_TRY(r, ps.shC.alloc(want));
-    HIP_TRY(r, ps.hitPair.alloc(want));
-    HIP_TRY(r, ps.queue0.alloc(want)); HIP_TRY(r, ps.queue1.alloc(want)); HIP_TRY(r, ps.shadowQueue.alloc(want)); HIP_TRY(r, ps.shadowResult.alloc(want));
-    HIP_TRY(r, ps.restartQueue.alloc(want));
-    return PTX_OK;
 }
 
 // 3,120 + 204 bytes as kernel arguments: no staging buffer to keep alive.  The launch parameters go with the lights: the first
@@ -193,7 +173,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
         // times the paths alive still finds a thread per path (blocks beyond the queue return at once), anything beyond that
         // strides.
         const uint32_t room = tail == 2 ? 4u * pl.tailBelow : pl.tailBelow;
-        launchTail(r, pl, qout, est < room ? est : room, { b, tail == 2 ? 0xffffffffu : pl.tailBelow });
+        launchTail(r, pl, qout, est < room ? est : room, { b, tail == 2 ? kTailAnyLength : pl.tailBelow });
     }
     HIP_TRY(r, hipEventRecord(ev.x2, X));
     return PTX_OK;
@@ -258,7 +238,7 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
             if (b < pl.bounces && est <= pl.tailBelow)
             {
                 // the queue is short: k_tail finishes it, behind the shadow kernel of this bounce on its stream
-                launchTail(r, pl, qin, est, { b, 0xffffffffu });
+                launchTail(r, pl, qin, est, { b, kTailAnyLength });
                 // re-recorded behind the tail: what the stream waits for below
                 HIP_TRY(r, hipEventRecord(r->bounceEvents[(b - 1) % r->bounceEvents.size()].x2, r->auxStream));
                 break;
@@ -351,8 +331,8 @@ static int beginLaunch(PtxRenderer *r, const PtxLightsUbo *lights, const LaunchP
         return rc;
     if (slots > 0x7fffffffull)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: too many path slots in one batch");
-    if (const int rc = slots ? ensureSlots(r, (size_t)slots) : PTX_OK)
-        return rc;
+    if (slots)
+        HIP_TRY(r, r->paths.ensure(kernelMode(r), (size_t)slots));
     k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, p, r->lights.p, r->launchParams.p);
     HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
     r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = r->stats.tracedRays = 0;
@@ -485,7 +465,7 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: null argument");
     if (!sceneUsable(r) || !imagePtr(r))
         return fail(r, PTX_ERROR_NOT_READY, "ptx_render: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
-    if (uniform->SampleCount == 0 || uniform->SampleCount > 0xffffu || uniform->BounceCount > 0xffffu || frames == 0)
+    if (uniform->SampleCount == 0 || uniform->SampleCount > kMaxSampleCount || uniform->BounceCount > kMaxBounceCount || frames == 0)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: SampleCount must be in [1, 65535], BounceCount <= 65535");
     if (lights->LightCount > PTX_MAX_LIGHT_COUNT)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: LightCount %u exceeds MaxLightCount", lights->LightCount);

@@ -206,7 +206,7 @@ struct SceneData
     std::shared_ptr<struct TextureStreaming> streaming;
 };
 
-// Per-slot state of the paths in flight (the Wavefront of pt_wavefront.hpp, owned), grown by ensureSlots (pt_render_host.hpp).
+// Per-slot state of the paths in flight (the Wavefront of pt_path_state.hpp, owned).
 struct PathState
 {
     DevBuf<float4> rayO, rayD, thr, rad, hit, shD, shC, slotRad;
@@ -214,6 +214,27 @@ struct PathState
     DevBuf<uint8_t> shadowResult;
     DevBuf<float4> diffs; // three planes of ray differentials, only for scenes with textures (kernel mode >= 1)
     DevBuf<float4> decal; DevBuf<float> decalT; // nearest ignored any-hit candidate and its distance, only for non-opaque geometry (mode 2)
+    // Room for `slots` paths of a scene in kernel mode `mode`: grow-only; differentials and decals a scene needs later come at the
+    // largest size asked for.
+    hipError_t ensure(int mode, size_t slots)
+    {
+        const size_t want = std::max(slots, slotRad.n);
+        hipError_t e = hipSuccess;
+        const auto grow = [&](auto &buf, size_t n) { if (e == hipSuccess) e = buf.alloc(n); };
+        if (mode >= 1)
+            grow(diffs, 3 * want);
+        if (mode == 2)
+        {
+            grow(decal, want); grow(decalT, want);
+        }
+        grow(slotRad, want);
+        grow(rayO, want); grow(rayD, want); grow(thr, want); grow(rad, want);
+        grow(hit, want); grow(shD, want); grow(shC, want);
+        grow(hitPair, want);
+        grow(queue0, want); grow(queue1, want); grow(shadowQueue, want); grow(shadowResult, want);
+        grow(restartQueue, want);
+        return e;
+    }
     Wavefront view(int mode, uint32_t *counters, uint32_t *spill) const
     {
         Wavefront wf;

@@ -18,8 +18,9 @@
 //
 // Every path slot is (frame, pixel); its state lives in SoA arrays in HBM; queues hold
 // slot indices and are compacted by wave-aggregated atomics.  The state is 16-byte records only, each written by one kernel
-// and read once by the next (struct Wavefront): the RNG state and the bounce / sample counters ride in their spare .w words,
-// the shadow ray shares its origin with the continuation ray, pixel and frame are recomputed from the slot.  A bring-up MEGAKERNEL
+// and read once by the next: struct Wavefront, the table of who writes and who reads each record and the named load / store of
+// every record are in pt_path_state.hpp, the words packed into the records' spare .w (RNG state, bounce | smpl << 16, the flags)
+// and the reserved ids in pt_path_words.hpp.  No kernel here builds a record by hand.  A bring-up MEGAKERNEL
 // (one thread per slot running the loop 1:1) shares all device functions and is kept as
 // the in-tree A/B reference of the wavefront.
 //
@@ -29,74 +30,13 @@
 #include <hip/hip_runtime.h>
 
 #include "pt_bvh.hpp"
+#include "pt_path_state.hpp"
 
 using namespace ptd;
 
 // =====================================================================================
 // Launch parameters
 // =====================================================================================
-
-// Per-slot path state is written by one kernel and read once by the next: a stream.  Its loads and stores carry the
-// non-temporal hint (global_load / global_store ... nt), so that the 4 MB of L2 an XCD has keep tree nodes and texels instead
-// of records nobody reads twice.  Measured (1 MI355X, 1080p, 8 spp, two runs each in one call, plain -> nt): atrium_like
-// 788 / 789 -> 811 / 823 Msamples/s, chess_like 2,248 / 2,229 -> 2,267 / 2,262, temple_like 898 / 883 -> 905 / 895, street_like
-// flat; the hint on the loads alone or on the stores alone gives half of it; on the ShadeTri reads it costs 4 % (the samples
-// of one pixel sit in neighbouring lanes and share them).
-template <typename T> struct StreamWord { typedef T type; };
-template <> struct StreamWord<float4> { typedef float type __attribute__((ext_vector_type(4))); };
-template <> struct StreamWord<uint4> { typedef uint32_t type __attribute__((ext_vector_type(4))); };
-template <typename T> struct StreamRef
-{
-    T *p;
-    typedef typename StreamWord<T>::type W;
-    PT_DEV operator T() const
-    {
-        const W w = __builtin_nontemporal_load(reinterpret_cast<const W *>(p));
-        T v;
-        __builtin_memcpy(&v, &w, sizeof(T));
-        return v;
-    }
-    PT_DEV void operator=(const T &v) const
-    {
-        W w;
-        __builtin_memcpy(&w, &v, sizeof(T));
-        __builtin_nontemporal_store(w, reinterpret_cast<W *>(p));
-    }
-};
-template <typename T> struct Stream // wf.rayO[slot] reads and writes as before; wf.rayO.p[slot] is the plain access
-{
-    T *p;
-    PT_DEV StreamRef<T> operator[](size_t i) const { return StreamRef<T>{p + i}; }
-    __host__ __device__ Stream &operator=(T *q) { p = q; return *this; }
-    __host__ __device__ explicit operator bool() const { return p != nullptr; }
-};
-
-struct Wavefront // device pointers of the per-slot state (SoA)
-{
-    // The two words of a path that are no float -- the RNG state and bounce | smpl << 16 -- ride as bit patterns in the .w of
-    // records that travel anyway (there is no record of their own); pixel and frame are functions of the slot (slotFrame,
-    // slotPixel) and are stored nowhere.
-    Stream<float4> rayO;   // origin.xyz = origin of the shadow ray of the bounce before; w = MaxRoughness (payload.MaxRoughness),
-                           // or, for a path that ended with its shadow query pending, the RNG state (k_apply_shadow's restarts)
-    Stream<float4> rayD;   // direction.xyz, w = bounce | smpl << 16, or kDeadWord (k_generate: slot outside the image)
-    Stream<float4> thr;    // throughput.rgb, w = RNG state
-    Stream<float4> rad;    // radiance.rgb accumulated over the samples of this launch
-    Stream<float4> hit;    // t, u, v, triangle slot in leaf order (bits)
-    Stream<uint32_t> hitPair;
-    Stream<float4> shD;    // shadow direction.xyz, w = tmax (LightDistance), sign bit set if the path ends after this bounce
-    Stream<float4> shC;    // NEE contribution throughput * DirectLight / DirectLightPdf, w = bounce | smpl << 16
-    Stream<float4> slotRad; // final radiance of the slot (consumed by k_accumulate)
-    Stream<float4> decal;   // nearest ignored any-hit candidate: (triangle slot, u, v, pair) -- k_shade fetches its colour and alpha
-    Stream<float> decalT;   // (payload.LightDirection / LightDistance) if the hit lies behind it; null unless the scene has non-opaque
-                     // geometry.  decalT = its distance or -1 (payload.DirectLightPdf)
-    Stream<float4> diff[3]; // payload.RayDifferentials0..2 (rx origin, rx dir, ry origin, ry dir); null unless the scene has textures
-    uint32_t *queue[2];
-    uint32_t *shadowQueue;
-    uint8_t *shadowResult; // per shadow queue entry: bit 0 = the light is visible, bit 1 = the path ends here (k_apply_shadow)
-    uint32_t *restartQueue;
-    uint32_t *counters; // see enum Counter
-    uint32_t *spill;    // traversal stack overflow region [kGlobalSpill][kMaxPersistentThreads]
-};
 
 // Every counter sits on its own 128-byte line: atomics to one L2 line serialise (~11 ns each on MI355X) whatever
 // word they touch, and the queue, chunk and statistics counters are all hot in the same kernels.
@@ -137,6 +77,7 @@ struct BounceCtl
     uint32_t bounce;    // 1-based index inside the round
     uint32_t tailBelow; // queues of at most this many paths go to k_tail (never the first bounce of a round)
 };
+constexpr uint32_t kTailAnyLength = 0xffffffffu; // tailBelow of a k_tail that takes its queue whatever its length
 PT_DEV bool bounceRuns(const BounceCtl &c, uint32_t count) { return count != 0u && (c.bounce <= 1u || count > c.tailBelow); }
 
 __global__ void k_prologue(Wavefront wf, int qin, BounceCtl ctl)
@@ -193,7 +134,7 @@ PT_DEV uint32_t slotPixel(const LaunchParams &p, uint32_t slotInFrame)
     const uint32_t x = (tile % p.tilesX) * ts + (blk % bpr) * 8 + (ib % 8);
     const uint32_t y = (tile / p.tilesX) * ts + (blk / bpr) * 8 + (ib / 8);
     if (tile >= p.numTiles || x >= p.width || y >= p.height)
-        return 0xffffffffu;
+        return kNoPixel;
     return y * p.width + x;
 }
 
@@ -224,24 +165,6 @@ PT_DEV void startSample(const LaunchParams &p, uint32_t pixel, uint32_t &rng, f3
         diff.ryOrigin = origin;
         diff.ryDirection = ry;
     }
-}
-
-// the payload packing of raygen.rgen:56-58 / closestHit.rchit:157-159
-PT_DEV void storeDiff(const Wavefront &wf, uint32_t slot, const DiffRays &d)
-{
-    wf.diff[0][slot] = make_float4(d.rxOrigin.x, d.rxOrigin.y, d.rxOrigin.z, d.rxDirection.x);
-    wf.diff[1][slot] = make_float4(d.rxDirection.y, d.rxDirection.z, d.ryOrigin.x, d.ryOrigin.y);
-    wf.diff[2][slot] = make_float4(d.ryOrigin.z, d.ryDirection.x, d.ryDirection.y, d.ryDirection.z);
-}
-PT_DEV DiffRays loadDiff(const Wavefront &wf, uint32_t slot)
-{
-    const float4 a = wf.diff[0][slot], b = wf.diff[1][slot], c = wf.diff[2][slot];
-    DiffRays d;
-    d.rxOrigin = F3(a.x, a.y, a.z);
-    d.rxDirection = F3(a.w, b.x, b.y);
-    d.ryOrigin = F3(b.z, b.w, c.x);
-    d.ryDirection = F3(c.y, c.z, c.w);
-    return d;
 }
 
 // new primary ray of a slot; the differentials go straight to the slot state when the scene carries them
@@ -317,20 +240,23 @@ PT_DEV void blockAddCounter(uint32_t *__restrict__ counter, uint32_t v)
 #define PT_SHADE_ITEMS 4
 #endif
 constexpr uint32_t kShadeItems = PT_SHADE_ITEMS; // queue entries per thread per block-wide append in k_shade
-constexpr uint32_t kDeadPair = 0xfffffffeu; // hitPair of a slot outside the image (ragged edge tiles)
-// rayD.w of such a slot under PTX_FIRST_BOUNCE=0: the one pattern bounce | smpl << 16 never takes.  A stored smpl is below
-// SampleCount, and renderImpl (pt_render_host.hpp) refuses SampleCount > 0xffff, so the upper half of a live word is at most
-// 0xfffe.  The sign bit alone would not do -- smpl >= 0x8000 sets it in a live word -- so ClosestIO::load compares the whole
-// pattern; as floats the words are denormals and NaNs, and no float comparison is made on them anywhere.
-constexpr uint32_t kDeadWord = 0xffffffffu;
 
-// pixel (or 0xffffffff) of a slot: what k_generate and the first bounce's kernels start a slot from, and what the kernels
-// that start a LATER sample of it (k_restart, k_tail, k_finish_restarts) recompute instead of reading it from the slot state
+// pixel (or kNoPixel) of a slot: what the kernels that start a LATER sample of it (k_restart, k_finish_restarts) recompute instead
+// of reading it from the slot state
 PT_DEV uint32_t pixelOfSlot(const LaunchParams &p, uint32_t slot)
 {
     uint32_t f, s;
     slotFrame(p, slot, f, s);
     return slotPixel(p, s);
+}
+// ... and what k_generate, the first bounce's kernels and the megakernel start a slot from: its pixel and the RNG state of its
+// first sample (raygen.rgen:38).  The state is of no use where the pixel is kNoPixel.
+PT_DEV void slotStart(const LaunchParams &p, uint32_t slot, uint32_t &pixel, uint32_t &rng)
+{
+    uint32_t f, s;
+    slotFrame(p, slot, f, s);
+    pixel = slotPixel(p, s);
+    rng = initRng(pixel % p.width, pixel / p.width, p.width, p.firstFrame + f);
 }
 
 // The schedule of rounds 1-6 (PTX_FIRST_BOUNCE=0; the default computes all this in the first bounce's kernels, FirstClosestIO).
@@ -340,26 +266,23 @@ __global__ void __launch_bounds__(kBlock) k_generate(LaunchParams p, Wavefront w
 {
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < p.numSlots; slot += gridDim.x * blockDim.x)
     {
-        uint32_t f, s;
-        slotFrame(p, slot, f, s);
-        const uint32_t pixel = slotPixel(p, s);
-        const uint32_t frame = p.firstFrame + f;
+        uint32_t pixel, rng;
+        slotStart(p, slot, pixel, rng);
         wf.queue[0][slot] = slot;
-        if (pixel != 0xffffffffu)
+        if (pixel != kNoPixel)
         {
-            uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
             f3 o, d;
             startSlotSample(p, wf, slot, pixel, rng, o, d);
-            wf.rayO[slot] = make_float4(o.x, o.y, o.z, 0.0f); // MaxRoughness = 0, raygen.rgen:60
-            wf.rayD[slot] = make_float4(d.x, d.y, d.z, 0.0f); // bounce | smpl << 16 = 0
-            wf.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(rng)); // raygen.rgen:52
-            // rad[slot] = 0 is implied by rayD.w == 0 (first bounce of the first sample): neither written here nor read by
+            storeRayOrigin(wf, slot, o, 0.0f); // MaxRoughness = 0, raygen.rgen:60
+            storeRayDirection(wf, slot, d, packState(0u, 0u));
+            storeThroughput(wf, slot, F3s(1.0f), rng); // raygen.rgen:52
+            // rad[slot] = 0 is implied by the state word 0 (first bounce of the first sample): neither written here nor read by
             // the first k_shade
         }
         else
         {
-            wf.rayD[slot] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kDeadWord));
-            wf.slotRad[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            storeDeadSlot(wf, slot);
+            storeFinal(wf, slot, F3s(0.0f));
         }
     }
 }
@@ -377,44 +300,43 @@ struct ClosestIO
     PT_DEV void setEntry(uint32_t s) { slot = s; }
     PT_DEV bool load(uint32_t item, f3 &o, f3 &d, float &tmin, float &tmax)
     {
-        const float4 d4 = wf.rayD[slot];
-        if (__float_as_uint(d4.w) == kDeadWord)
+        f3 direction;
+        uint32_t state;
+        loadRayDirection(wf, slot, direction, state);
+        if (state == kDeadWord)
         {
-            wf.hitPair[slot] = kDeadPair;
+            storeHitPair(wf, slot, kDeadPair);
             return false;
         }
-        const float4 o4 = wf.rayO[slot];
-        o = F3(o4.x, o4.y, o4.z);
-        d = F3(d4.x, d4.y, d4.z);
+        float maxRoughness; // the next k_shade's
+        loadRayOrigin(wf, slot, o, maxRoughness);
+        d = direction;
         tmin = 0.00001f; // ray.glsl:79-80: tmin = 1e-5, tmax = 1e4 on every segment
         tmax = 10000.0f;
         if (wf.decalT)
-            wf.decalT[slot] = -1.0f; // anyhit.rahit state of a fresh ray: nothing ignored yet
+            storeDecalDistance(wf, slot, -1.0f);
         return true;
     }
-    PT_DEV void improve(uint32_t, float t, float u, float v, uint32_t triSlot)
-    {
-        wf.hit[slot] = make_float4(t, u, v, __uint_as_float(triSlot)); // w = triangle slot in leaf order
-    }
-    PT_DEV uint32_t bestSlot(uint32_t) const { return __float_as_uint(wf.hit.p[slot].w); }
-    PT_DEV void store(uint32_t, const Hit &h, bool, bool) { wf.hitPair[slot] = h.pair; }
+    PT_DEV void improve(uint32_t, float t, float u, float v, uint32_t triSlot) { storeHit(wf, slot, t, u, v, triSlot); }
+    PT_DEV uint32_t bestSlot(uint32_t) const { return hitTriSlot(wf, slot); }
+    PT_DEV void store(uint32_t, const Hit &h, bool, bool) { storeHitPair(wf, slot, h.pair); } // a miss: h.pair == kMissPair
     // anyhit.rahit:54-61: the nearest ignored candidate (ties: smaller (pair, prim)) is the decal.  It lives in the slot's
     // record -- (triangle slot, u, v, pair) + its distance -- and k_shade fetches its colour if the hit lies behind it.
     // The ids come from the triangle record when they are needed (the tie, the store), not as arguments held in registers.
     PT_DEV void ignored(float t, float u, float v, uint32_t triSlot, const TraceScene &sc)
     {
-        const float cur = wf.decalT[slot];
+        const float cur = decalDistance(wf, slot);
         bool nearer = cur == -1.0f || t < cur;
         if (!nearer && t == cur)
         {
-            const float4 mine = sc.tris[triSlot].c, other = sc.tris[__float_as_uint(wf.decal.p[slot].x)].c;
+            const float4 mine = sc.tris[triSlot].c, other = sc.tris[decalTriSlot(wf, slot)].c;
             const uint32_t pair = __float_as_uint(mine.y), curPair = __float_as_uint(other.y);
             nearer = pair < curPair || (pair == curPair && __float_as_uint(mine.z) < __float_as_uint(other.z));
         }
         if (nearer)
         {
-            wf.decalT[slot] = t;
-            wf.decal[slot] = make_float4(__uint_as_float(triSlot), u, v, sc.tris[triSlot].c.y);
+            storeDecalDistance(wf, slot, t);
+            storeDecal(wf, slot, triSlot, u, v, sc.tris[triSlot].c.y);
         }
     }
 };
@@ -464,22 +386,20 @@ struct FirstClosestIO : ClosestIO
     {
         const LaunchParams &p = *gp;
         slot = item;
-        uint32_t f, s;
-        slotFrame(p, slot, f, s);
-        const uint32_t pixel = slotPixel(p, s);
-        if (pixel == 0xffffffffu) // outside the image (ragged edge tiles): dead for the whole launch, k_accumulate skips it
+        uint32_t pixel, rng;
+        slotStart(p, slot, pixel, rng);
+        if (pixel == kNoPixel) // outside the image (ragged edge tiles): dead for the whole launch, k_accumulate skips it
         {
-            wf.hitPair[slot] = kDeadPair;
-            wf.slotRad[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            storeHitPair(wf, slot, kDeadPair);
+            storeFinal(wf, slot, F3s(0.0f));
             return false;
         }
-        uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, p.firstFrame + f); // raygen.rgen:38
         DiffRays diff;
         startSample<false>(p, pixel, rng, o, d, diff); // the differentials are the first k_shade's
         tmin = 0.00001f;
         tmax = 10000.0f;
         if (wf.decalT)
-            wf.decalT[slot] = -1.0f;
+            storeDecalDistance(wf, slot, -1.0f);
         return true;
     }
 };
@@ -527,12 +447,12 @@ __global__ void __launch_bounds__(kBlock) PT_ALPHA_CLOSEST_ATTR k_trace_closest<
 // The ray is NOT constructed here: the camera matrices, the lens and the differential code would sit in the register
 // and instruction-cache budget of the shading and traversal kernels for a path the canonical schedule
 // (SampleCount = 1) takes only after a NaN.
-// `state` = bounce | smpl << 16 of the path that ended; where true is returned it becomes that of the next sample, and the
+// `state` = the state word of the path that ended; where true is returned it becomes that of the next sample, and the
 // caller hands it on with the RNG state (storeRestart).
 PT_DEV bool finishSample(const LaunchParams &p, const Wavefront &wf, uint32_t slot, uint32_t &state, f3 &radiance,
                          uint32_t &nSamples, uint32_t &nRetries)
 {
-    uint32_t smpl = state >> 16;
+    uint32_t smpl = stateSample(state);
     nSamples++;
     if (badRadiance(radiance))
     {
@@ -544,42 +464,19 @@ PT_DEV bool finishSample(const LaunchParams &p, const Wavefront &wf, uint32_t sl
         smpl = smpl + 1;
     if (smpl < p.u.SampleCount)
     {
-        state = smpl << 16; // bounce = 0
-        wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+        state = packState(0u, smpl);
+        storeRadiance(wf, slot, radiance);
         return true;
     }
-    wf.slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+    storeFinal(wf, slot, radiance);
     return false;
-}
-
-// What a slot in the restart queue hands to k_restart / k_finish_restarts beside rad[slot]: the RNG state, carried on, and
-// smpl << 16 of its next sample, as single words where a live path has them (thr.w, rayD.w).  Rare in a canonical launch (a NaN).
-PT_DEV void storeRestart(const Wavefront &wf, uint32_t slot, uint32_t rng, uint32_t state)
-{
-    wf.thr.p[slot].w = __uint_as_float(rng);
-    wf.rayD.p[slot].w = __uint_as_float(state);
-}
-PT_DEV void loadRestart(const Wavefront &wf, uint32_t slot, uint32_t &rng, uint32_t &state)
-{
-    rng = __float_as_uint(wf.thr.p[slot].w);
-    state = __float_as_uint(wf.rayD.p[slot].w);
 }
 
 // Appends the slots of the calling lanes (restart == true) to the restart queue with one atomic per wave.  May be
 // called under divergent control flow: the ballot sees the active lanes only.
 PT_DEV void pushRestarts(const Wavefront &wf, bool restart, uint32_t slot)
 {
-    const uint64_t mask = __ballot(restart);
-    if (!mask)
-        return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const int leader = __ffsll((unsigned long long)mask) - 1;
-    uint32_t base = 0;
-    if ((int)lane == leader)
-        base = atomicAdd(&wf.counters[C_RESTART], (uint32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (restart)
-        wf.restartQueue[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = slot;
+    wavePush(wf.restartQueue, &wf.counters[C_RESTART], restart, slot);
 }
 
 // SORT: the material-sorted shade queue (below), chosen on the host for scenes that mix material types.  The plain kernels
@@ -677,7 +574,6 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
       // by side) 1,313 -> 1,536 Msamples/s, k_shade 8.06 -> 6.29 ms; scenes of ONE material type pay for the sort and get
       // nothing back (temple_like 614 -> 600, chess_like +-0.5 %), hence the two kernels (k_shade_sorted for mixed scenes).
       __shared__ uint32_t s_sorted[SORT ? kBlock * kShadeItems : 1];
-      constexpr uint32_t kPadSlot = 0xffffffffu; // never a slot: 152 B of state per slot bound the count far below
       if (SORT)
       {
         constexpr uint32_t kKeys = 9, kWaves = kBlock / 64;
@@ -698,8 +594,8 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
             if (i < count)
             {
                 sl = FIRST ? i : wf.queue[qin][i];
-                const uint32_t pr = wf.hitPair[sl];
-                if (pr == 0xffffffffu)
+                const uint32_t pr = loadHitPair(wf, sl);
+                if (pr == kMissPair)
                     key = 0u;
                 else if (pr != kDeadPair)
                 {
@@ -757,70 +653,55 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
             // entries past the block's share of the queue were sorted last, with the dead slots
             slot = SORT ? s_sorted[item * blockDim.x + threadIdx.x] : FIRST ? i : wf.queue[qin][i];
             if (slot != kPadSlot)
-                pair = wf.hitPair[slot];
+                pair = loadHitPair(wf, slot);
             else
                 slot = 0;
         }
         if (pair != kDeadPair)
         {
-            uint32_t rng, state; // state = bounce | smpl << 16
-            float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d4 = o4; // FIRST: rayO.w = MaxRoughness = 0, raygen.rgen:60
+            uint32_t rng, state;
+            f3 origin, direction; // (the origin is the traversal's: only MaxRoughness is read from its record here)
+            float maxRoughness = 0.0f; // FIRST: raygen.rgen:60
             // first bounce of a sample: throughput = 1 (raygen.rgen:52); and of the first sample: radiance = 0 (:42)
-            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t4 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+            f3 radiance = F3s(0.0f), throughput = F3s(1.0f);
             DiffRays diff;
             if (FIRST)
             {
-                uint32_t f, s;
-                slotFrame(p, slot, f, s);
-                const uint32_t pixel = slotPixel(p, s), frame = p.firstFrame + f;
-                rng = initRng(pixel % p.width, pixel / p.width, p.width, frame); // raygen.rgen:38
-                f3 o, d;
-                startSample<TEX>(p, pixel, rng, o, d, diff);
-                o4 = make_float4(o.x, o.y, o.z, 0.0f);
-                d4 = make_float4(d.x, d.y, d.z, 0.0f);
-                state = 0u;
+                uint32_t pixel;
+                slotStart(p, slot, pixel, rng); // a pixel: the slot's pair is not kDeadPair
+                startSample<TEX>(p, pixel, rng, origin, direction, diff);
+                state = packState(0u, 0u);
             }
             else
             {
                 // both records are read whole on every segment anyway; at bounce 0 (a round k_restart started, k_generate's
                 // schedule) thr.xyz holds the 1 that used to be implied: its .w is the only copy of the RNG state
-                d4 = wf.rayD[slot];
-                t4 = wf.thr[slot];
-                state = __float_as_uint(d4.w);
-                rng = __float_as_uint(t4.w);
+                loadRayDirection(wf, slot, direction, state);
+                loadThroughput(wf, slot, throughput, rng);
             }
-            const float4 hit = wf.hit[slot];
+            float hitT, hitU, hitV;
+            uint32_t hitTri;
+            loadHit(wf, slot, hitT, hitU, hitV, hitTri);
             if (state != 0u)
-                r4 = wf.rad[slot];
-            f3 radiance = F3(r4.x, r4.y, r4.z), throughput = F3(t4.x, t4.y, t4.z);
+                radiance = loadRadiance(wf, slot);
 
-            if (pair == 0xffffffffu)
+            if (pair == kMissPair)
             {
                 // miss.rmiss:16-39: sky colour / skybox lookup, Pdf = -1 -> raygen.rgen:71-75
-                radiance = radiance + throughput * missEmissive(sv, F3(d4.x, d4.y, d4.z));
+                radiance = radiance + throughput * missEmissive(sv, direction);
                 restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
             }
             else
             {
                 if (!FIRST)
-                    o4 = wf.rayO[slot];
+                    loadRayOrigin(wf, slot, origin, maxRoughness);
                 HitOut out;
                 if (TEX && !FIRST)
                     diff = loadDiff(wf, slot);
                 Decal decal = noDecal();
                 if (TEX && wf.decalT)
-                {
-                    decal.dist = wf.decalT[slot];
-                    if (decal.dist != -1.0f)
-                    {
-                        const float4 dq = wf.decal[slot];
-                        decal.slot = __float_as_uint(dq.x);
-                        decal.u = dq.y;
-                        decal.v = dq.z;
-                        decal.pair = __float_as_uint(dq.w);
-                    }
-                }
-                closestHit<TEX>(sv, F3(d4.x, d4.y, d4.z), hit.x, hit.y, hit.z, pair, __float_as_uint(hit.w), o4.w, rng, out, diff, decal);
+                    decal = loadDecal(wf, slot);
+                closestHit<TEX>(sv, direction, hitT, hitU, hitV, pair, hitTri, maxRoughness, rng, out, diff, decal);
                 nHits++;
 
                 radiance = radiance + throughput * out.Emissive; // raygen.rgen:77
@@ -839,7 +720,7 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
 
                 bool finished = false;
                 const float prob = fmin_(maxComponent(throughput), 1.0f); // :86
-                uint32_t bounce = state & 0xffffu;
+                uint32_t bounce = stateBounce(state);
                 if (prob < 0.001f)
                     finished = true;
                 else if (prob < rnd(rng)) // :90
@@ -851,30 +732,20 @@ PT_DEV void shadeBody(const LaunchParams &p, const SceneView &sv, const Wavefron
                     if (bounce >= p.u.BounceCount)
                         finished = true;
                 }
-                state = (state & 0xffff0000u) | bounce;
+                state = withBounce(state, bounce);
 
-                if (pushShadow)
-                {
-                    // the shadow ray leaves out.Position, which is rayO.xyz below (ShadowIO::load); its record carries what
-                    // k_apply_shadow needs to finish a path that ends here: `state` beside the contribution, the finished flag
-                    // as the sign bit of the light distance (a length or 100000: never negative; set on the bit pattern)
-                    const f3 sd = -normalize(out.LightDirection); // raygen.rgen:24
-                    const uint32_t tmax = (__float_as_uint(out.LightDistance) & 0x7fffffffu) | (finished ? 0x80000000u : 0u);
-                    wf.shD[slot] = make_float4(sd.x, sd.y, sd.z, __uint_as_float(tmax));
-                    wf.shC[slot] = make_float4(contribution.x, contribution.y, contribution.z, __uint_as_float(state));
-                }
+                if (pushShadow) // the shadow ray leaves out.Position: the hit point stored below (raygen.rgen:24)
+                    storeShadowQuery(wf, slot, -normalize(out.LightDirection), out.LightDistance, finished, contribution, state);
                 if (finished && !pushShadow)
                     restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
                 else
                 {
-                    wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
-                    // a path that ends with its shadow query pending has no use for MaxRoughness: its rayO.w keeps the RNG state
-                    // for the restart k_apply_shadow may find it due (next sample of a multi-sample launch, NaN)
-                    wf.rayO[slot] = make_float4(out.Position.x, out.Position.y, out.Position.z, finished ? __uint_as_float(rng) : out.MaxRoughness);
+                    storeRadiance(wf, slot, radiance);
+                    storeHitPoint(wf, slot, out.Position, finished, out.MaxRoughness, rng);
                     if (!finished)
                     {
-                        wf.rayD[slot] = make_float4(out.Direction.x, out.Direction.y, out.Direction.z, __uint_as_float(state));
-                        wf.thr[slot] = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(rng));
+                        storeRayDirection(wf, slot, out.Direction, state);
+                        storeThroughput(wf, slot, throughput, rng);
                         if (TEX)
                             storeDiff(wf, slot, diff);
                         pushNext = true; // a pending shadow query only adds to rad[slot] before the next bounce
@@ -938,21 +809,17 @@ struct ShadowIO
     static constexpr bool kNeedsPrim = false;
     static constexpr bool kHasQueue = true;
     const Wavefront &wf;
-    float finished; // shD.w of the ray in flight: the sign bit says that its path ends after this bounce
+    uint32_t lengthWord; // shD.w of the ray in flight: shadowEndsPath says that its path ends after this bounce
     uint32_t staged;
     PT_DEV uint32_t queueEntry(uint32_t item) const { return wf.shadowQueue[item]; }
     PT_DEV void setEntry(uint32_t s) { staged = s; }
     PT_DEV bool load(uint32_t item, f3 &o, f3 &d, float &tmin, float &tmax)
     {
         const uint32_t slot = staged;
-        // the origin is the hit point k_shade left in rayO.xyz (of the continuation ray, or of a path that ended there);
-        // shD.w = the light distance, its sign bit the finished flag
-        const float4 o4 = wf.rayO[slot], d4 = wf.shD[slot];
-        o = F3(o4.x, o4.y, o4.z);
-        d = F3(d4.x, d4.y, d4.z);
+        // the origin is the hit point k_shade left (of the continuation ray, or of a path that ended there)
+        loadShadowRay(wf, slot, o, d, lengthWord);
         tmin = 0.00001f; // raygen.rgen:26-31: tmin = 1e-5, tmax = LightDistance, terminate on first hit
-        tmax = __uint_as_float(__float_as_uint(d4.w) & 0x7fffffffu);
-        finished = d4.w;
+        tmax = shadowLength(lengthWord);
         return true;
     }
     PT_DEV void ignored(float, float, float, uint32_t, const TraceScene &) {} // shadow rays keep no decal
@@ -961,7 +828,7 @@ struct ShadowIO
     // The traversal only records the answer.  What follows from it -- the NEE add into rad[slot], finishing the sample of a
     // path that ended on this bounce -- is k_apply_shadow's: inside the traversal loop those dependent loads and stores
     // sat in the retire phase of nearly every round for a handful of lanes (shadow rounds took 1.8x a closest round).
-    PT_DEV void store(uint32_t item, const Hit &, bool occluded, bool) { wf.shadowResult[item] = (uint8_t)((occluded ? 0u : 1u) | (__float_as_uint(finished) >> 31 ? 2u : 0u)); }
+    PT_DEV void store(uint32_t item, const Hit &, bool occluded, bool) { wf.shadowResult[item] = packShadowResult(occluded, shadowEndsPath(lengthWord)); }
 };
 
 template <bool ALPHA>
@@ -971,7 +838,7 @@ PT_DEV void traceShadowBody(const LaunchParams &p, const TraceScene &sc, const W
     if (count == 0u)
         return;
     PT_DECLARE_STACK(st, kLdsStack, wf.spill)
-    ShadowIO io = { wf, 0.0f, 0u };
+    ShadowIO io = { wf, 0u, 0u };
     persistentTrace<true, ALPHA>(sc, io, count, &wf.counters[shadowChunkCounter(parity)], st);
     if (st.overflow)
         atomicAdd(&wf.counters[C_OVERFLOW], 1u);
@@ -996,26 +863,21 @@ __global__ void __launch_bounds__(kBlock) k_apply_shadow(LaunchParams p, Wavefro
             slot = wf.shadowQueue[item];
             if (result)
             {
-                float4 r4 = wf.rad[slot];
-                // the record is read for its contribution or for its bounce | smpl << 16: an occluded light on a path that
-                // ended is the one case that reads it for the word alone
-                const float4 c = wf.shC[slot];
-                if (result & 1u)
+                f3 radiance = loadRadiance(wf, slot), contribution;
+                // the record is read for its contribution or for its state word: an occluded light on a path that ended is
+                // the one case that reads it for the word alone
+                uint32_t state;
+                loadShadowContribution(wf, slot, contribution, state);
+                if (result & kShadowLightVisible)
+                    radiance = radiance + contribution;
+                if (result & kShadowEndsPath)
                 {
-                    r4.x = r4.x + c.x;
-                    r4.y = r4.y + c.y;
-                    r4.z = r4.z + c.z;
-                }
-                if (result & 2u)
-                {
-                    uint32_t state = __float_as_uint(c.w);
-                    f3 radiance = F3(r4.x, r4.y, r4.z);
                     restart = finishSample(p, wf, slot, state, radiance, nSamples, nRetries);
-                    if (restart) // k_shade left the RNG state of a path that ended in rayO.w
-                        storeRestart(wf, slot, __float_as_uint(wf.rayO.p[slot].w), state);
+                    if (restart) // k_shade left the RNG state of a path that ended with the hit point
+                        storeRestart(wf, slot, endedPathRng(wf, slot), state);
                 }
                 else
-                    wf.rad[slot] = r4; // the slot is already in the next queue (k_shade)
+                    storeRadiance(wf, slot, radiance); // the slot is already in the next queue (k_shade)
             }
         }
         // the slot cannot join the next queue directly: k_trace_closest of the next bounce may already be consuming it
@@ -1047,9 +909,9 @@ __global__ void __launch_bounds__(kBlock) k_restart(LaunchParams p, Wavefront wf
         loadRestart(wf, slot, rng, state);
         f3 o, d;
         startSlotSample(p, wf, slot, pixelOfSlot(p, slot), rng, o, d);
-        wf.rayO[slot] = make_float4(o.x, o.y, o.z, 0.0f);
-        wf.rayD[slot] = make_float4(d.x, d.y, d.z, __uint_as_float(state)); // smpl << 16: bounce 0
-        wf.thr[slot] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(rng)); // raygen.rgen:52
+        storeRayOrigin(wf, slot, o, 0.0f);
+        storeRayDirection(wf, slot, d, state); // bounce 0 of the next sample
+        storeThroughput(wf, slot, F3s(1.0f), rng); // raygen.rgen:52
     }
 }
 
@@ -1073,7 +935,7 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(LaunchParams p, const flo
     {
         const uint32_t chunk = base >> 6, s = chunk * pixelsPerWave + lane / g;
         const uint32_t pixel = slotPixel(p, s);
-        const bool owner = sub == 0u && pixel != 0xffffffffu;
+        const bool owner = sub == 0u && pixel != kNoPixel;
         const uint32_t at = shardMajor ? s : pixel;
         float4 acc = owner ? image[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         for (uint32_t group = 0; group < groups; group++)
@@ -1107,6 +969,19 @@ struct PathCounters
 {
     uint32_t nSeg = 0, nHit = 0, nSmp = 0, nRetry = 0;
     bool stuck = false; // some path never produced a finite sample and was given up (kMaxSampleRetries)
+    // Kernel exit: the traversal stack's overflow flag, the stuck flag where the kernel can start a sample (`reportStuck`), the four
+    // statistics with one atomic per wave each.  Every lane of the wave must call it.
+    PT_DEV void flush(uint32_t *__restrict__ counters, bool overflow, bool reportStuck) const
+    {
+        if (overflow)
+            atomicAdd(&counters[C_OVERFLOW], 1u);
+        if (reportStuck && stuck)
+            atomicAdd(&counters[C_OVERFLOW + 1], 1u);
+        waveAddCounter(&counters[C_SEGMENTS], nSeg);
+        waveAddCounter(&counters[C_HITS], nHit);
+        waveAddCounter(&counters[C_SAMPLES], nSmp);
+        waveAddCounter(&counters[C_RETRIES], nRetry);
+    }
 };
 // A slot whose samples keep coming out NaN / Inf would spin for ever (it hangs the GPU in the reference): after this many
 // restarts in a row it is given up with radiance 0 and the launch reports an error.
@@ -1199,30 +1074,21 @@ __global__ void __launch_bounds__(kBlock) k_megakernel(LaunchParams p, SceneView
 {
     PT_DECLARE_STACK(st, kLdsStackMega, (uint32_t *)nullptr)
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t f = 0, s = 0;
+    uint32_t pixel = kNoPixel, rng = 0u;
     if (slot < p.numSlots)
-        slotFrame(p, slot, f, s);
-    const uint32_t pixel = slot < p.numSlots ? slotPixel(p, s) : 0xffffffffu;
+        slotStart(p, slot, pixel, rng);
     PathCounters pc;
     f3 radiance = F3s(0.0f);
-    if (pixel != 0xffffffffu)
+    if (pixel != kNoPixel)
     {
-        uint32_t rng = initRng(pixel % p.width, pixel / p.width, p.width, p.firstFrame + f);
         DiffRays diff;
         diff.rxOrigin = diff.rxDirection = diff.ryOrigin = diff.ryDirection = F3s(0.0f);
         int smpl = 0;
         radiance = runPath<MODE>(p, sv, sc, st, pixel, rng, F3s(0.0f), F3s(1.0f), F3s(0.0f), F3s(0.0f), diff, 0.0f, 0u, smpl, true, pc);
     }
     if (slot < p.numSlots)
-        slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
-    if (st.overflow)
-        atomicAdd(&counters[C_OVERFLOW], 1u);
-    if (pc.stuck)
-        atomicAdd(&counters[C_OVERFLOW + 1], 1u);
-    waveAddCounter(&counters[C_SEGMENTS], pc.nSeg);
-    waveAddCounter(&counters[C_HITS], pc.nHit);
-    waveAddCounter(&counters[C_SAMPLES], pc.nSmp);
-    waveAddCounter(&counters[C_RETRIES], pc.nRetry);
+        slotRad[slot] = record(radiance, 0.0f); // (a plain pointer, no Wavefront: the final record of storeFinal)
+    pc.flush(counters, st.overflow, true);
 }
 
 // The slots of queue `qin` sit at a bounce boundary (ray, throughput, radiance, RNG and
@@ -1292,39 +1158,36 @@ PT_DEV void tailBody(const LaunchParams &p, const SceneView &sv, const TraceScen
         if (i < count)
         {
             const uint32_t slot = wf.queue[qin][i];
-            const float4 o4 = wf.rayO[slot], d4 = wf.rayD[slot], t4 = wf.thr[slot];
-            const uint32_t state = __float_as_uint(d4.w); // bounce | smpl << 16 and, in thr.w, the RNG state: see k_shade
-            float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            f3 origin, direction, throughput, radiance = F3s(0.0f);
+            float maxRoughness;
+            uint32_t state, rng;
+            loadRayOrigin(wf, slot, origin, maxRoughness);
+            loadRayDirection(wf, slot, direction, state);
+            loadThroughput(wf, slot, throughput, rng);
             if (state != 0u)
-                r4 = wf.rad[slot];
-            uint32_t rng = __float_as_uint(t4.w);
+                radiance = loadRadiance(wf, slot);
             DiffRays diff;
             if (MODE >= 1)
                 diff = loadDiff(wf, slot);
             else
                 diff.rxOrigin = diff.rxDirection = diff.ryOrigin = diff.ryDirection = F3s(0.0f);
-            int smpl = (int)(state >> 16);
+            int smpl = (int)stateSample(state);
             // (ONE_SAMPLE starts no sample: the pixel is not needed)
-            const f3 radiance = runPath<MODE, true>(p, sv, sc, st, 0u, rng, F3(r4.x, r4.y, r4.z), F3(t4.x, t4.y, t4.z), F3(o4.x, o4.y, o4.z),
-                                                   F3(d4.x, d4.y, d4.z), diff, o4.w, state & 0xffffu, smpl, false, pc);
+            radiance = runPath<MODE, true>(p, sv, sc, st, 0u, rng, radiance, throughput, origin, direction, diff, maxRoughness, stateBounce(state),
+                                           smpl, false, pc);
             if (smpl < (int)p.u.SampleCount)
             {
-                wf.rad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
-                storeRestart(wf, slot, rng, (uint32_t)smpl << 16);
+                storeRadiance(wf, slot, radiance);
+                storeRestart(wf, slot, rng, packState(0u, (uint32_t)smpl));
                 restart = true;
                 restartSlot = slot;
             }
             else
-                wf.slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+                storeFinal(wf, slot, radiance);
         }
         pushRestarts(wf, restart, restartSlot); // k_restart draws the next primary ray before the queue is consumed
     }
-    if (st.overflow)
-        atomicAdd(&wf.counters[C_OVERFLOW], 1u);
-    waveAddCounter(&wf.counters[C_SEGMENTS], pc.nSeg);
-    waveAddCounter(&wf.counters[C_HITS], pc.nHit);
-    waveAddCounter(&wf.counters[C_SAMPLES], pc.nSmp);
-    waveAddCounter(&wf.counters[C_RETRIES], pc.nRetry);
+    pc.flush(wf.counters, st.overflow, false); // ONE_SAMPLE: a restart ends the sample, none happens twice in a row
 }
 
 // The rare slots whose sample came out NaN / Inf in a canonical (SampleCount = 1) launch: raygen.rgen:99-112 restarts
@@ -1346,22 +1209,15 @@ __global__ void __launch_bounds__(kBlock) PT_TAIL_TEX_ATTR k_finish_restarts(Lau
         const uint32_t slot = wf.restartQueue[i];
         uint32_t rng, state;
         loadRestart(wf, slot, rng, state);
-        const float4 r4 = wf.rad[slot];
+        const f3 carried = loadRadiance(wf, slot);
         DiffRays diff;
         diff.rxOrigin = diff.rxDirection = diff.ryOrigin = diff.ryDirection = F3s(0.0f);
-        int smpl = (int)(state >> 16);
-        const f3 radiance = runPath<MODE>(p, sv, sc, st, pixelOfSlot(p, slot), rng, F3(r4.x, r4.y, r4.z), F3s(1.0f), F3s(0.0f), F3s(0.0f), diff, 0.0f, 0u,
+        int smpl = (int)stateSample(state);
+        const f3 radiance = runPath<MODE>(p, sv, sc, st, pixelOfSlot(p, slot), rng, carried, F3s(1.0f), F3s(0.0f), F3s(0.0f), diff, 0.0f, 0u,
                                           smpl, true, pc);
-        wf.slotRad[slot] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+        storeFinal(wf, slot, radiance);
     }
-    if (st.overflow)
-        atomicAdd(&wf.counters[C_OVERFLOW], 1u);
-    if (pc.stuck)
-        atomicAdd(&wf.counters[C_OVERFLOW + 1], 1u);
-    waveAddCounter(&wf.counters[C_SEGMENTS], pc.nSeg);
-    waveAddCounter(&wf.counters[C_HITS], pc.nHit);
-    waveAddCounter(&wf.counters[C_SAMPLES], pc.nSmp);
-    waveAddCounter(&wf.counters[C_RETRIES], pc.nRetry);
+    pc.flush(wf.counters, st.overflow, true);
 }
 
 // =====================================================================================
@@ -1483,7 +1339,7 @@ __global__ void k_pack_shard(LaunchParams p, const float4 *__restrict__ image, f
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.slotsPerFrame; s += gridDim.x * blockDim.x)
     {
         const uint32_t pixel = slotPixel(p, s);
-        dst[s] = pixel == 0xffffffffu ? make_float4(0, 0, 0, 0) : image[pixel];
+        dst[s] = pixel == kNoPixel ? make_float4(0, 0, 0, 0) : image[pixel];
     }
 }
 // host != nullptr: the same pixels also go straight to the page-locked frame of the host (ptx_unpack_shard_host: rank 0 of an
@@ -1493,7 +1349,7 @@ __global__ void k_unpack_shard(LaunchParams p, const float4 *__restrict__ src, f
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < p.slotsPerFrame; s += gridDim.x * blockDim.x)
     {
         const uint32_t pixel = slotPixel(p, s);
-        if (pixel != 0xffffffffu)
+        if (pixel != kNoPixel)
         {
             const float4 v = src[s];
             image[pixel] = v;
