@@ -70,6 +70,22 @@ def bits_equal_or_both_nan(a_u32, b_u32):
     return (a_u32 == b_u32) | (np.isnan(af) & np.isnan(bf))
 
 
+def ulp_error(got, truth):
+    """|got - truth| in units of the binary32 spacing at `truth` (a float64 array): 2^(e - 23) for 2^e <= |truth| < 2^(e + 1),
+    and the denormal spacing 2^-149 everywhere below 2^-126.  For finite `truth` inside the binary32 range."""
+    truth = np.asarray(truth, np.float64)
+    _, e = np.frexp(truth)  # |truth| = m * 2^e with m in [0.5, 1)
+    spacing = np.ldexp(1.0, np.maximum(e - 1, -126) - 23)
+    return np.abs(np.asarray(got, np.float64) - truth) / spacing
+
+
+def half_ordinal(x):
+    """The position of every value of `x` (binary16-valued floats, infinities included) on the binary16 number line: the sign
+    times the magnitude's bit pattern, so neighbouring binary16 values differ by one and +-0 are both 0."""
+    h = np.asarray(x).astype(np.float16).view(np.uint16).astype(np.int64)
+    return np.where(h & 0x8000, -(h & 0x7fff), h & 0x7fff)
+
+
 def rel_l2(img, ref):
     return float(np.linalg.norm((img[..., :3] - ref[..., :3]).astype(np.float64)) /
                  max(np.linalg.norm(ref[..., :3].astype(np.float64)), 1e-30))
