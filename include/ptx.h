@@ -818,6 +818,72 @@ PTX_API void *ptx_device_denoised_ptr(PtxRenderer *r);
  * last ptx_resize. */
 PTX_API int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode);
 
+/* ------------------------------------------------------------------------- */
+/* Temporal accumulation (docs/NEXT_ROWS.md section 14): the history of the   */
+/* previous frames, reprojected through the position guide, ahead of the       */
+/* filter.  Like the denoiser it has no counterpart in the reference.          */
+/* ------------------------------------------------------------------------- */
+
+enum { PTX_TEMPORAL_RESET = 1 }; /* PtxTemporalDesc.flags: ignore the history, start a new one */
+
+typedef struct PtxTemporalDesc {
+    float View[16], Proj[16];   /* FORWARD matrices of the camera the current guides were rendered with, column-major like ViewInverse */
+    uint32_t totalSamples;      /* samples in the accumulation image */
+    float maxHistory;           /* >= 1, finite: cap of the history length L; the blend weight is 1 / L */
+    float normalThreshold;      /* > 0 */
+    float positionThreshold;    /* > 0, relative to the pixel's hit distance */
+    uint32_t flags;             /* PTX_TEMPORAL_RESET = 1: ignore the history */
+    uint32_t reserved;          /* 0 */
+} PtxTemporalDesc;
+
+/* Temporal accumulation.  Input: the accumulation image S, the three guides and the history the previous accepted call on this
+ * handle left; output: a renderer-owned RGBA32F image T of the MEAN with the history length in alpha, and the next call's history.
+ * Neither S nor the guides are written.  View and Proj are the forward matrices (world -> view, view -> clip with w = view depth,
+ * x and y in -1 .. 1 over the image) whose inverses the uniform of ptx_render_guides carried: keeping them consistent with the
+ * guides is the CALLER's duty, nothing here inverts a matrix or can check it.
+ *
+ * With the denoiser's definitions -- m(p) = S(p).rgb / totalSamples, a_p = max(albedo_p, 0.01) per channel, p VALID when it was
+ * hit, m(p), n_p and t_p are finite and t_p > 0 -- the demodulated colour is c(p) = m(p) / a_p.  The history is, per pixel q, the
+ * demodulated colour H(q), the length L'(q) (0 on a pixel that was not valid), the normal N'(q) and the position X'(q), and that
+ * call's View' and Proj'.  For a valid p, with a history and without PTX_TEMPORAL_RESET:
+ *   1. Project.  view = View' (x_p, 1), clip = Proj' view (column-major: out_i = M[i] x + M[4+i] y + M[8+i] z + M[12+i] w).
+ *      If clip.w <= 0, or u or v below is not finite, there is no history.  Otherwise, for a W x H image,
+ *          u = (clip.x / clip.w * 0.5 + 0.5) W - 0.5,   v = (clip.y / clip.w * 0.5 + 0.5) H - 0.5
+ *      (the inverse of the primary ray's pixel-centre convention).
+ *      SAME-CAMERA RULE: if View' and Proj' equal this call's View and Proj bit for bit, nothing is projected and the history is
+ *      read at p itself, one tap of weight 1: a still camera does not blur its history by rounding (ptx_present's unfiltered
+ *      axis is the precedent).
+ *   2. Gather.  The taps are the four texels around (u, v): x0 = floor(u), y0 = floor(v), fx = u - x0, fy = v - y0, the texel
+ *      (x0 + i, y0 + j) with the bilinear weight (i ? fx : 1 - fx) (j ? fy : 1 - fy).  A tap q COUNTS only if q is inside the
+ *      image, L'(q) > 0, H(q) is finite, |n_p - N'(q)|^2 <= normalThreshold^2 and
+ *      |dot(n_p, X'(q) - x_p)| <= positionThreshold t_p (the plane distance, the filter's own position term).
+ *      The history is FOUND iff the weights of the taps that count sum to >= 1/64 (a rule, like the albedo floor: it bounds how
+ *      much the renormalisation amplifies rounding).
+ *   3. Blend.  c_h = sum w H(q) / sum w, L_h = sum w L'(q) / sum w over the taps that count, L = min(L_h + 1, maxHistory),
+ *      c_acc = c_h + (c(p) - c_h) / L.
+ * Without a history, with PTX_TEMPORAL_RESET or where none is found: c_acc = c(p), L = 1.
+ * T(p) = (c_acc a_p, L) on valid pixels and (m(p), 0) elsewhere: a miss, NaN or Inf pixel keeps its class and takes part in no
+ * other pixel.  float32 throughout.  The call stores c_acc, L, n_p, (x_p, t_p), View and Proj as the next call's history (L = 0
+ * on pixels that are not valid).
+ *
+ * One launch, asynchronous on the render stream; works on a borrower.  Moving geometry is handled conservatively: its previous
+ * position fails the plane test and the pixel restarts; there are no per-object motion vectors.  The history is three RGBA32F
+ * images kept twice (a thread reads q while its neighbour writes it), with T 112 bytes per pixel.
+ * PTX_ERROR_INVALID_ARGUMENT: totalSamples 0, maxHistory < 1 or not finite, a threshold <= 0 or not finite, unknown flags,
+ * reserved != 0.  PTX_ERROR_NOT_READY: no image, no ptx_render_guides since the last ptx_resize, a shard accumulation buffer is
+ * bound, or a tile shard with worldSize > 1.  A refused call leaves T and the history intact; ptx_resize drops both. */
+PTX_API int ptx_temporal_accumulate(PtxRenderer *r, const PtxTemporalDesc *desc);
+/* T, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_INVALID_ARGUMENT: a buffer of another size;
+ * PTX_ERROR_NOT_READY: no ptx_temporal_accumulate since the last ptx_resize. */
+PTX_API int ptx_read_temporal(PtxRenderer *r, void *host, size_t bytes);
+/* ... or its device address (NULL without one). */
+PTX_API void *ptx_device_temporal_ptr(PtxRenderer *r);
+/* ptx_denoise with T.rgb as the source and totalSamples taken as 1 (the desc's own value is ignored): the same kernels on another
+ * pointer, as ptx_postprocess_denoised relates to ptx_postprocess.  The result lands where ptx_denoise's does: ptx_read_denoised,
+ * ptx_postprocess_denoised and ptx_present follow unchanged.  Refusals as ptx_denoise's, and PTX_ERROR_NOT_READY: no
+ * ptx_temporal_accumulate since the last ptx_resize. */
+PTX_API int ptx_denoise_temporal(PtxRenderer *r, const PtxDenoiseDesc *desc);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

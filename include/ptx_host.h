@@ -39,6 +39,9 @@ PTX_API uint64_t pth_scene_triangle_count(PthScene *s); /* instanced (flattened)
 PTX_API int pth_scene_raygen_uniform(PthScene *s, uint32_t width, uint32_t height, uint32_t bounceCount,
                                      float lensRadius, float focalDistance, uint32_t sampleCount,
                                      uint32_t totalSamples, PtxRaygenUniformData *out);
+/* The FORWARD matrices of the active camera at this extent, column-major: pth_scene_raygen_uniform's ViewInverse and ProjInverse
+ * are their inverses.  What PtxTemporalDesc.View / Proj take for guides rendered with that uniform. */
+PTX_API int pth_scene_camera_matrices(PthScene *s, uint32_t width, uint32_t height, float view[16], float proj[16]);
 /* -1 = the InputCamera (Scene.h:259-260), >= 0 = scene camera */
 PTX_API int pth_scene_set_active_camera(PthScene *s, int32_t cameraId);
 PTX_API int pth_scene_set_camera_pose(PthScene *s, const float position[3], const float direction[3]);

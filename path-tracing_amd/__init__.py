@@ -65,10 +65,11 @@ PTX_SYMBOLS = [
     "ptx_present", "ptx_read_present", "ptx_device_present_ptr", "ptx_present_bytes",
     "ptx_render_guides", "ptx_read_guide", "ptx_device_guide_ptr", "ptx_denoise", "ptx_read_denoised", "ptx_device_denoised_ptr",
     "ptx_postprocess_denoised",
+    "ptx_temporal_accumulate", "ptx_read_temporal", "ptx_device_temporal_ptr", "ptx_denoise_temporal",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
-    "pth_scene_lights", "pth_scene_triangle_count", "pth_scene_raygen_uniform", "pth_scene_set_active_camera",
+    "pth_scene_lights", "pth_scene_triangle_count", "pth_scene_raygen_uniform", "pth_scene_camera_matrices", "pth_scene_set_active_camera",
     "pth_scene_set_camera_pose", "pth_scene_update", "pth_scene_bone_count", "pth_scene_animation_state", "pth_decode_image", "pth_decode_image_levels", "pth_write_image", "pth_save_checkpoint", "pth_load_checkpoint",
 ]
 
@@ -168,6 +169,19 @@ class DenoiseDesc(C.Structure):
 GUIDE_NORMAL, GUIDE_POSITION, GUIDE_ALBEDO = range(3)  # PTX_GUIDE_* of include/ptx.h
 # The defaults of Renderer.denoise, chosen on 4-spp frames of three scenes against 512 spp (docs/NEXT_ROWS.md section 13)
 DENOISE_DEFAULTS = dict(iterations=3, sigma_color=1.5, sigma_normal=0.3, sigma_position=0.03)
+
+
+
+class TemporalDesc(C.Structure):
+    _fields_ = [("View", C.c_float * 16), ("Proj", C.c_float * 16), ("totalSamples", C.c_uint32), ("maxHistory", C.c_float),
+                ("normalThreshold", C.c_float), ("positionThreshold", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+TEMPORAL_RESET = 1  # PTX_TEMPORAL_RESET
+# The defaults of Renderer.temporal_accumulate: the thresholds are the filter's sigmas and nobody has tuned them; the defaults of the
+# filter behind it come first in the sweep of tools/temporal_quality.py (docs/NEXT_ROWS.md section 14)
+TEMPORAL_DEFAULTS = dict(max_history=32.0, normal_threshold=0.3, position_threshold=0.03)
+TEMPORAL_DENOISE_DEFAULTS = dict(iterations=2, sigma_color=0.5, sigma_normal=0.3, sigma_position=0.03)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -275,6 +289,7 @@ def load_host() -> C.CDLL:
         lib.pth_scene_triangle_count.argtypes = [C.c_void_p]
         lib.pth_scene_raygen_uniform.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                                  C.c_uint32, C.c_uint32, C.POINTER(RaygenUniformData)]
+        lib.pth_scene_camera_matrices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.pth_scene_set_active_camera.argtypes = [C.c_void_p, C.c_int32]
         lib.pth_scene_set_camera_pose.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.pth_scene_update.argtypes = [C.c_void_p, C.c_float]
@@ -375,6 +390,11 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_denoised_ptr.argtypes = [P]
         lib.ptx_device_denoised_ptr.restype = P
         lib.ptx_postprocess_denoised.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32]
+        lib.ptx_temporal_accumulate.argtypes = [P, C.POINTER(TemporalDesc)]
+        lib.ptx_read_temporal.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_temporal_ptr.argtypes = [P]
+        lib.ptx_device_temporal_ptr.restype = P
+        lib.ptx_denoise_temporal.argtypes = [P, C.POINTER(DenoiseDesc)]
         _hip = lib
     return _hip
 
@@ -428,6 +448,15 @@ class Scene:
         if rc:
             raise PtxError("pth_scene_raygen_uniform failed")
         return u
+
+    def camera_matrices(self, width, height):
+        """(View, Proj): the forward matrices of the active camera at this extent, 16 float32 each, column-major -- the inverses of
+        uniform()'s ViewInverse and ProjInverse, as TemporalDesc takes them."""
+        view, proj = np.zeros(16, np.float32), np.zeros(16, np.float32)
+        FP = C.POINTER(C.c_float)
+        if self.lib.pth_scene_camera_matrices(self.handle, width, height, view.ctypes.data_as(FP), proj.ctypes.data_as(FP)):
+            raise PtxError("pth_scene_camera_matrices failed")
+        return view, proj
 
     def update(self, time_step: float) -> bool:
         """Scene::Update(timeStep): True if something the renderer consumes has moved."""
@@ -672,6 +701,33 @@ class Renderer:
         """ptx_postprocess_denoised: postprocess() on the denoised image; it holds the mean, so total_samples is taken as 1."""
         u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
         self._check(self.lib.ptx_postprocess_denoised(self.handle, C.byref(u), tone_mapping))
+
+    def temporal_accumulate(self, total_samples: int, view, proj, max_history: float = TEMPORAL_DEFAULTS["max_history"],
+                            normal_threshold: float = TEMPORAL_DEFAULTS["normal_threshold"],
+                            position_threshold: float = TEMPORAL_DEFAULTS["position_threshold"], flags: int = 0):
+        """ptx_temporal_accumulate: blend the demodulated mean of the accumulation image with the history of the previous calls,
+        reprojected through the position guide.  view, proj: the forward matrices of the camera render_guides() was given
+        (Scene.camera_matrices)."""
+        d = TemporalDesc()
+        d.View[:] = [float(v) for v in np.asarray(view, np.float32).reshape(16)]
+        d.Proj[:] = [float(v) for v in np.asarray(proj, np.float32).reshape(16)]
+        d.totalSamples, d.maxHistory, d.normalThreshold, d.positionThreshold, d.flags = total_samples, max_history, normal_threshold, position_threshold, flags
+        self._check(self.lib.ptx_temporal_accumulate(self.handle, C.byref(d)))
+
+    def read_temporal(self) -> np.ndarray:
+        """T of the last temporal_accumulate(): the accumulated MEAN, H x W x 4 float32, alpha = the history length (0: not valid)."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.ptx_read_temporal(self.handle, img.ctypes.data, img.nbytes))
+        return img
+
+    def temporal_ptr(self) -> int:
+        return int(self.lib.ptx_device_temporal_ptr(self.handle) or 0)
+
+    def denoise_temporal(self, iterations: int = TEMPORAL_DENOISE_DEFAULTS["iterations"], sigma_color: float = TEMPORAL_DENOISE_DEFAULTS["sigma_color"],
+                         sigma_normal: float = TEMPORAL_DENOISE_DEFAULTS["sigma_normal"], sigma_position: float = TEMPORAL_DENOISE_DEFAULTS["sigma_position"]):
+        """ptx_denoise_temporal: denoise() on T, which holds the mean; the result is read with read_denoised()."""
+        d = DenoiseDesc(1, iterations, sigma_color, sigma_normal, sigma_position, 0, 0)
+        self._check(self.lib.ptx_denoise_temporal(self.handle, C.byref(d)))
 
     def stats(self) -> Stats:
         s = Stats()

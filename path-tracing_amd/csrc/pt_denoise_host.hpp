@@ -63,37 +63,41 @@ static int readGuide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
     return readFrameImage(r, guidePtr(r, which), host, bytes, "ptx_read_guide");
 }
 
-static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d)
+// The filter over the mean `source` / `totalSamples`: ptx_denoise passes the accumulation image and the desc's count (source null:
+// the image is looked up after the checks, in their order), ptx_denoise_temporal (pt_temporal_host.hpp) T and 1.
+static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d, const float4 *source = nullptr, uint32_t totalSamples = 0u, const char *who = "ptx_denoise")
 {
     if (!r || !d)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_denoise: null argument");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (!source)
+        totalSamples = d->totalSamples;
     const auto sigmaOk = [](float s) { return s >= 0.0f && s <= 3.402823466e38f; }; // finite and not negative (a NaN fails both)
-    if (d->iterations < 1u || d->iterations > 6u || d->totalSamples == 0u || !sigmaOk(d->sigmaColor) || !sigmaOk(d->sigmaNormal) ||
+    if (d->iterations < 1u || d->iterations > 6u || totalSamples == 0u || !sigmaOk(d->sigmaColor) || !sigmaOk(d->sigmaNormal) ||
         !sigmaOk(d->sigmaPosition) || d->sigmaNormal == 0.0f || d->sigmaPosition == 0.0f || d->flags != 0u || d->reserved != 0u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_denoise: need 1 <= iterations <= 6 (%u), totalSamples > 0 (%u), sigmaColor >= 0 (%g), sigmaNormal > 0 (%g), "
-                    "sigmaPosition > 0 (%g), all finite, flags 0 (0x%x) and reserved 0 (%u)", d->iterations, d->totalSamples, (double)d->sigmaColor,
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need 1 <= iterations <= 6 (%u), totalSamples > 0 (%u), sigmaColor >= 0 (%g), sigmaNormal > 0 (%g), "
+                    "sigmaPosition > 0 (%g), all finite, flags 0 (0x%x) and reserved 0 (%u)", who, d->iterations, totalSamples, (double)d->sigmaColor,
                     (double)d->sigmaNormal, (double)d->sigmaPosition, d->flags, d->reserved);
     if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no accumulation image (call ptx_resize)");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
     if (r->frame.boundShard)
-        return frameIsElsewhere(r, "ptx_denoise");
+        return frameIsElsewhere(r, who);
     if (!r->guidesReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: no guides for this extent (call ptx_render_guides)");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no guides for this extent (call ptx_render_guides)", who);
     if (r->frame.shard.worldSize > 1u)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise: this renderer holds one tile shard of %u; the filter's taps cross tiles", r->frame.shard.worldSize);
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; the filter's taps cross tiles", who, r->frame.shard.worldSize);
     HIP_TRY(r, hipSetDevice(r->device));
     const size_t n = r->frame.pixels();
     HIP_TRY(r, r->denoisePing[0].alloc(n));
     if (d->iterations > 1u)
         HIP_TRY(r, r->denoisePing[1].alloc(n));
     DenoiseArgs a;
-    a.sum = imagePtr(r);
+    a.sum = source ? source : imagePtr(r);
     a.normal = guidePtr(r, PTX_GUIDE_NORMAL);
     a.position = guidePtr(r, PTX_GUIDE_POSITION);
     a.albedo = guidePtr(r, PTX_GUIDE_ALBEDO);
     a.width = r->frame.width;
     a.height = r->frame.height;
-    a.totalSamples = (float)d->totalSamples;
+    a.totalSamples = (float)totalSamples;
     a.invSigmaNormal2 = (float)(1.0 / ((double)d->sigmaNormal * d->sigmaNormal));
     a.invSigmaPosition = (float)(1.0 / (double)d->sigmaPosition);
     const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->frame.width + kDenoiseTileX - 1) / kDenoiseTileX, (r->frame.height + kDenoiseTileY - 1) / kDenoiseTileY);

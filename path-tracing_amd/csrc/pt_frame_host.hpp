@@ -26,6 +26,8 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->output.invalidate();
     r->guidesReady = false; // the guides and the denoised image belong to the extent they were made for
     r->denoisedIn = -1;
+    r->temporalReady = false; // ... and so do T and the history
+    r->temporalHistoryIn = -1;
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     return resetAccumulation(r);
 }

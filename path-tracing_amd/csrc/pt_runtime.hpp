@@ -4,8 +4,8 @@
 // order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp),
 // the render launches with the bounce schedule of the wavefront backend (pt_render_host.hpp), the frame's hand-over -- accumulation
 // image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the denoiser
-// (pt_denoise_host.hpp).  Their functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line
-// wrappers around them.
+// (pt_denoise_host.hpp), the temporal accumulation ahead of it (pt_temporal_host.hpp).  Their functions take a valid or null handle;
+// include/ptx.h's entry points (ptx_capi.hip) are one-line wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
@@ -26,6 +26,7 @@
 #include "pt_post.hpp"
 #include "pt_present.hpp"
 #include "pt_shard_layout.hpp"
+#include "pt_temporal.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -399,6 +400,12 @@ struct PtxRenderer
     DevBuf<float4> guides, denoisePing[2];
     bool guidesReady = false;
     int denoisedIn = -1; // -1: nothing denoised since the last ptx_resize
+    // temporal accumulation (pt_temporal_host.hpp): T, the two copies of the three history images the calls alternate between, which
+    // of them the last accepted call wrote (-1: no history since the last ptx_resize) and the matrices it was given
+    DevBuf<float4> temporalImage, temporalHistory[2];
+    bool temporalReady = false;
+    int temporalHistoryIn = -1;
+    float temporalView[16] = {}, temporalProj[16] = {};
 
     // wavefront state
     PathState paths;
@@ -855,6 +862,7 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
 #include "pt_frame_host.hpp" // accumulation image and its bindings, tile shards, read-back: resizeFrame ... unpackShards
 #include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
 #include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
+#include "pt_temporal_host.hpp" // ptx_temporal_accumulate, ptx_denoise_temporal and the read-back of T
 
 static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
 {

@@ -1,0 +1,78 @@
+// pt_temporal_host.hpp -- host side of the temporal accumulation (kernel: pt_temporal.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md
+// section 14).  Included by pt_runtime.hpp after pt_denoise_host.hpp: one stage on the render stream between ptx_render_guides and
+// the filter, its read-back, and the filter on its result.
+#pragma once
+
+static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d)
+{
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate: null argument");
+    const auto positive = [](float v) { return v > 0.0f && v <= 3.402823466e38f; }; // finite and above zero (a NaN fails both)
+    if (d->totalSamples == 0u || !(d->maxHistory >= 1.0f) || !positive(d->maxHistory) || !positive(d->normalThreshold) || !positive(d->positionThreshold) ||
+        (d->flags & ~(uint32_t)PTX_TEMPORAL_RESET) != 0u || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate: need totalSamples > 0 (%u), maxHistory >= 1 (%g), normalThreshold > 0 (%g), "
+                    "positionThreshold > 0 (%g), all finite, flags 0 or PTX_TEMPORAL_RESET (0x%x) and reserved 0 (%u)", d->totalSamples, (double)d->maxHistory,
+                    (double)d->normalThreshold, (double)d->positionThreshold, d->flags, d->reserved);
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: no accumulation image (call ptx_resize)");
+    if (r->frame.boundShard)
+        return frameIsElsewhere(r, "ptx_temporal_accumulate");
+    if (!r->guidesReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: no guides for this extent (call ptx_render_guides)");
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: this renderer holds one tile shard of %u; the history's taps cross tiles",
+                    r->frame.shard.worldSize);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const size_t n = r->frame.pixels();
+    HIP_TRY(r, r->temporalImage.alloc(n));
+    HIP_TRY(r, r->temporalHistory[0].alloc(n * kTemporalHistoryImages));
+    HIP_TRY(r, r->temporalHistory[1].alloc(n * kTemporalHistoryImages));
+    const bool useHistory = r->temporalHistoryIn >= 0 && !(d->flags & PTX_TEMPORAL_RESET);
+    const int dst = r->temporalHistoryIn == 0 ? 1 : 0; // the history ping-pongs: a thread reads q while its neighbour writes it
+    TemporalArgs a;
+    a.sum = imagePtr(r);
+    a.normal = guidePtr(r, PTX_GUIDE_NORMAL);
+    a.position = guidePtr(r, PTX_GUIDE_POSITION);
+    a.albedo = guidePtr(r, PTX_GUIDE_ALBEDO);
+    a.histIn = useHistory ? r->temporalHistory[r->temporalHistoryIn].p : nullptr;
+    a.histOut = r->temporalHistory[dst].p;
+    a.out = r->temporalImage.p;
+    a.width = r->frame.width;
+    a.height = r->frame.height;
+    a.pixels = (uint32_t)n;
+    a.totalSamples = (float)d->totalSamples;
+    a.maxHistory = d->maxHistory;
+    a.normalThreshold2 = d->normalThreshold * d->normalThreshold;
+    a.positionThreshold = d->positionThreshold;
+    memcpy(a.view, r->temporalView, sizeof a.view);
+    memcpy(a.proj, r->temporalProj, sizeof a.proj);
+    const bool sameCamera = useHistory && !memcmp(d->View, r->temporalView, sizeof d->View) && !memcmp(d->Proj, r->temporalProj, sizeof d->Proj);
+    const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->frame.width + kDenoiseTileX - 1) / kDenoiseTileX, (r->frame.height + kDenoiseTileY - 1) / kDenoiseTileY);
+    if (sameCamera) k_temporal<true><<<grid, block, 0, r->stream>>>(a);
+    else k_temporal<false><<<grid, block, 0, r->stream>>>(a);
+    HIP_TRY(r, hipGetLastError());
+    r->temporalHistoryIn = dst;
+    r->temporalReady = true;
+    memcpy(r->temporalView, d->View, sizeof d->View);
+    memcpy(r->temporalProj, d->Proj, sizeof d->Proj);
+    return PTX_OK;
+}
+
+static int readTemporal(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_temporal: null argument");
+    if (!r->temporalReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_temporal: call ptx_temporal_accumulate first");
+    return readFrameImage(r, r->temporalImage.p, host, bytes, "ptx_read_temporal");
+}
+
+// ptx_denoise's filter on T, which holds the mean: totalSamples = 1
+static int denoiseTemporal(PtxRenderer *r, const PtxDenoiseDesc *d)
+{
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_denoise_temporal: null argument");
+    if (!r->temporalReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_denoise_temporal: call ptx_temporal_accumulate first");
+    return denoise(r, d, r->temporalImage.p, 1u, "ptx_denoise_temporal");
+}

@@ -1,8 +1,8 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
 // Renderer member it replaces in include/ptx.h; here each is ONE line (ptx_set_backend, ptx_synchronize and the trivial getters
 // apart) that calls the implementation in pt_runtime.hpp or one of the host files it includes (pt_scene_host.hpp, pt_bvh_host.hpp,
-// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp); device side: pt_wavefront.hpp / pt_bvh.hpp /
-// pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
+// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp, pt_temporal_host.hpp); device side:
+// pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
 extern "C" {
@@ -253,6 +253,26 @@ void *ptx_device_denoised_ptr(PtxRenderer *r)
 int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
 {
     return postprocessDenoised(r, uniform, toneMappingMode);
+}
+
+int ptx_temporal_accumulate(PtxRenderer *r, const PtxTemporalDesc *desc)
+{
+    return temporalAccumulate(r, desc);
+}
+
+int ptx_read_temporal(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readTemporal(r, host, bytes);
+}
+
+void *ptx_device_temporal_ptr(PtxRenderer *r)
+{
+    return r && r->temporalReady ? r->temporalImage.p : nullptr;
+}
+
+int ptx_denoise_temporal(PtxRenderer *r, const PtxDenoiseDesc *desc)
+{
+    return denoiseTemporal(r, desc);
 }
 
 int ptx_write_accumulation(PtxRenderer *r, const float *rgba, size_t bytes)

@@ -30,14 +30,15 @@ void Camera::SetPose(Vec3 position, Vec3 direction)
 // Camera.cpp:52-63
 void Camera::UpdateInvView()
 {
-    m_InvView = Inverse(LookAtLH(m_Position, m_Position + m_Direction, m_UpDirection));
+    m_View = LookAtLH(m_Position, m_Position + m_Direction, m_UpDirection);
+    m_InvView = Inverse(m_View);
 }
 
 // Camera.cpp:65-71
 void Camera::UpdateInvProjection()
 {
-    m_InvProjection = Inverse(PerspectiveFovLH_ZO(Radians(m_VerticalFOV), static_cast<float>(m_Width),
-                                                  static_cast<float>(m_Height), m_NearClip, m_FarClip));
+    m_Projection = PerspectiveFovLH_ZO(Radians(m_VerticalFOV), static_cast<float>(m_Width), static_cast<float>(m_Height), m_NearClip, m_FarClip);
+    m_InvProjection = Inverse(m_Projection);
 }
 
 InputCamera::InputCamera(float verticalFOV, float nearClip, float farClip, Vec3 position, Vec3 direction)

@@ -23,6 +23,9 @@ public:
     [[nodiscard]] std::pair<uint32_t, uint32_t> GetExtent() const { return { m_Width, m_Height }; }
     [[nodiscard]] Mat4 GetInvViewMatrix() const { return m_InvView; }
     [[nodiscard]] Mat4 GetInvProjectionMatrix() const { return m_InvProjection; }
+    // the forward matrices the two above are the inverses of (world -> view, view -> clip): what ptx_temporal_accumulate takes
+    [[nodiscard]] Mat4 GetViewMatrix() const { return m_View; }
+    [[nodiscard]] Mat4 GetProjectionMatrix() const { return m_Projection; }
 
     void SetPose(Vec3 position, Vec3 direction);
 
@@ -41,6 +44,7 @@ private:
     uint32_t m_Width = 0, m_Height = 0;
     Mat4 m_InvView;
     Mat4 m_InvProjection;
+    Mat4 m_View = Mat4::Identity(), m_Projection = Mat4::Identity();
 };
 
 class InputCamera : public Camera

@@ -13,6 +13,7 @@ uint32_t s_TotalSamples = 0;
 uint32_t s_Width = 0, s_Height = 0;
 bool s_DebugPipeline = false; // s_ActiveRaytracingPipeline == the debug pipeline (Renderer.cpp:579-610)
 PtxDebugViewDesc s_DebugView = { PTX_DEBUG_MODE_COLOR, 0u, 0u, 0u };
+bool s_AccumulationRestarted = true; // since the last temporal accumulation: the sum holds samples of a frame the history has not seen
 }
 
 void RendererHip::Check(int status)
@@ -83,6 +84,7 @@ void RendererHip::SetTileShard(uint32_t rank, uint32_t worldSize, uint32_t tileS
 void RendererHip::ResetAccumulationImage()
 {
     s_TotalSamples = 0;
+    s_AccumulationRestarted = true;
     if (s_Renderer && s_Width)
         Check(ptx_reset_accumulation(s_Renderer));
 }
@@ -153,8 +155,16 @@ void RendererHip::SetSettings(const DenoiserSettings &settings)
     s_DenoiserSettings = settings;
 }
 
+static RendererHip::TemporalSettings s_TemporalSettings;
+
+void RendererHip::SetSettings(const TemporalSettings &settings)
+{
+    s_TemporalSettings = settings;
+}
+
 // The post-processing chain on the current frame: on the running sum, or -- with the denoiser enabled and the path-tracing pipeline
-// bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser").
+// bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser"); with the temporal accumulation enabled as well
+// the filter runs on its result (ptx.h, "Temporal accumulation").
 static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode)
 {
     if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
@@ -164,6 +174,21 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         return rc;
     const PtxDenoiseDesc desc = { u.TotalSamples, s_DenoiserSettings.Iterations, s_DenoiserSettings.SigmaColor, s_DenoiserSettings.SigmaNormal,
                                   s_DenoiserSettings.SigmaPosition, 0u, 0u };
+    if (s_TemporalSettings.Enabled)
+    {
+        // a sum that continued from the previous frame already holds every sample of the history: start a new one from it
+        PtxTemporalDesc temporal = { {}, {}, u.TotalSamples, s_TemporalSettings.MaxHistory, s_TemporalSettings.NormalThreshold,
+                                     s_TemporalSettings.PositionThreshold, s_AccumulationRestarted ? 0u : (uint32_t)PTX_TEMPORAL_RESET, 0u };
+        const Camera &camera = s_Scene->GetActiveCamera(); // FillRaygenUniform brought it to the extent
+        ToColumnMajor(camera.GetViewMatrix(), temporal.View);
+        ToColumnMajor(camera.GetProjectionMatrix(), temporal.Proj);
+        if (const int rc = ptx_temporal_accumulate(s_Renderer, &temporal))
+            return rc;
+        s_AccumulationRestarted = false;
+        if (const int rc = ptx_denoise_temporal(s_Renderer, &desc))
+            return rc;
+        return ptx_postprocess_denoised(s_Renderer, &u, mode);
+    }
     if (const int rc = ptx_denoise(s_Renderer, &desc))
         return rc;
     return ptx_postprocess_denoised(s_Renderer, &u, mode);

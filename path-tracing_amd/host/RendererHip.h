@@ -67,6 +67,19 @@ public:
         float SigmaPosition = 0.03f;
     };
     static void SetSettings(const DenoiserSettings &settings);
+    // Temporal accumulation (ptx.h "Temporal accumulation").  Enabled together with the denoiser: SaveOutput and Present run
+    // ptx_render_guides -> ptx_temporal_accumulate -> ptx_denoise_temporal -> ptx_postprocess_denoised, with the forward matrices of
+    // the active camera; a frame whose accumulation continued from the previous one (nothing moved: the sum already holds every
+    // sample) passes PTX_TEMPORAL_RESET.  Disabled (the default), or without the denoiser: everything does exactly what it did
+    // without it.  The thresholds are the filter's sigmas; nobody has tuned them (docs/NEXT_ROWS.md section 14).
+    struct TemporalSettings
+    {
+        bool Enabled = false;
+        float MaxHistory = 32.0f;
+        float NormalThreshold = 0.3f;
+        float PositionThreshold = 0.03f;
+    };
+    static void SetSettings(const TemporalSettings &settings);
     // RecordPostProcessCommands + RecordSaveOutputCommands on the current running sum, then OutputSaver::WriteImage
     static void SaveOutput(const OutputInfo &info);
 

@@ -96,6 +96,17 @@ int pth_scene_raygen_uniform(PthScene *s, uint32_t width, uint32_t height, uint3
     return PTX_OK;
 }
 
+int pth_scene_camera_matrices(PthScene *s, uint32_t width, uint32_t height, float view[16], float proj[16])
+{
+    if (!s || !view || !proj || !width || !height)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    Camera &camera = s->scene->GetActiveCamera();
+    camera.OnResize(width, height);
+    ToColumnMajor(camera.GetViewMatrix(), view);
+    ToColumnMajor(camera.GetProjectionMatrix(), proj);
+    return PTX_OK;
+}
+
 int pth_scene_set_active_camera(PthScene *s, int32_t cameraId)
 {
     if (!s || cameraId < -1 || cameraId >= static_cast<int32_t>(s->scene->GetSceneCamerasCount()))

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Times the calls between ptx_render and the window (docs/NEXT_ROWS.md sections 12 and 13): ptx_postprocess, ptx_present,
-ptx_render_guides, ptx_denoise and ptx_postprocess_denoised at 1920 x 1080 and 3840 x 2160, beside one 8-spp step of chess_like.
+"""Times the calls between ptx_render and the window (docs/NEXT_ROWS.md sections 12, 13 and 14): ptx_postprocess, ptx_present,
+ptx_render_guides, ptx_temporal_accumulate (both variants), ptx_denoise and ptx_postprocess_denoised at 1920 x 1080 and
+3840 x 2160, beside one 8-spp step of chess_like.
 
 Every figure is a device-synchronised wall-clock time: synchronise, enqueue the call `repeat` times, synchronise; `repeat` is chosen
 per shape so that a window lasts about five milliseconds, every shape is warmed up first, and the figure is the median of 20
 windows divided by `repeat`.  ptx_denoise is also given as a rate against its algorithmic traffic of 80 bytes per pixel and pass
 (16 B in, 16 B out, 48 B of guides) -- a rate, not a measured bandwidth: the 25 taps are served by the caches.
+ptx_temporal_accumulate likewise against 176 bytes per pixel (64 B of sum and guides and 48 B of history in, T and 48 B of history
+out); its projected variant is called with two cameras a fraction of a pixel apart in turn, so that every call gathers four taps.
 
 Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D]"""
 import json
@@ -24,6 +27,7 @@ import __graft_entry__ as graft  # noqa: E402
 WINDOWS, WINDOW_MS, STEP_SPP, STEP_DEPTH = 20, 5.0, 8, 8
 POST = dict(exposure=1.0, bloom_threshold=0.8, bloom_intensity=0.35)
 DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
+TEMPORAL_BYTES_PER_PIXEL = 176
 
 
 def timed(r, call):
@@ -66,6 +70,20 @@ def main():
             r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_HDR, **POST)
             rec[f"present_to_{sw}x{sh}_hdr10"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_A2B10G10R10_UNORM, pkg.TONE_MAPPING_HDR))
         rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
+        cams = [scene.camera_matrices(w, h)]
+        pos, fwd, right = (np.frombuffer(u.ViewInverse, np.float32).reshape(4, 4).T[0:3, k].astype(np.float64) for k in (3, 2, 0))
+        scene.set_camera_pose(pos + right * 0.002, fwd)
+        cams.append(scene.camera_matrices(w, h))
+        scene.set_camera_pose(pos, fwd)
+        calls = [0]
+
+        def accumulate(moving):
+            calls[0] += 1
+            r.temporal_accumulate(STEP_SPP, *cams[calls[0] % 2 if moving else 0])
+        for key, moving in (("temporal_accumulate_same_camera", False), ("temporal_accumulate_projected", True)):
+            t = timed(r, lambda: accumulate(moving))
+            t["algorithmic_GB_per_s"] = w * h * TEMPORAL_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
+            rec[key] = t
         for it in (1, 3, 5):
             t = timed(r, lambda: r.denoise(STEP_SPP, iterations=it))
             t["algorithmic_GB_per_s"] = w * h * DENOISE_BYTES_PER_PIXEL_AND_PASS * it / (t["median_ms"] * 1e-3) / 1e9
