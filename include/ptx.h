@@ -393,11 +393,13 @@ typedef struct PtxStats {
 typedef struct PtxRenderer PtxRenderer;
 
 /* Renderer::Init / Renderer::Shutdown (Renderer.cpp:77-218).  One handle = one frame in flight (the reference's per-frame
- * rendering resources, Renderer.cpp:1454-1460): two HIP streams each.  The HIP runtime maps a process's streams onto
- * GPU_MAX_HW_QUEUES hardware queues (4 by default, which serialises frames in flight): a host that keeps several handles
- * exports GPU_MAX_HW_QUEUES=16 before its first HIP call.  The library does not touch the environment; it
- * reports what it finds (PtxStats::hardwareQueues) and the first handle whose streams no longer fit leaves a note in
- * ptx_last_error although ptx_create returned PTX_OK. */
+ * rendering resources, Renderer.cpp:1454-1460): two HIP streams each while the streams of every live handle fit the hardware
+ * queues of the process, one otherwise.  The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by
+ * default), and streams that share a queue run one after the other: a host that keeps several handles exports
+ * GPU_MAX_HW_QUEUES=16 before its first HIP call.  The library does not touch the environment; it reports what
+ * it finds (PtxStats::hardwareQueues), every launch takes the schedule that fits it (PTX_STREAM_PLAN=0: always two streams), and
+ * the first handle whose streams no longer fit leaves a note that names its schedule in ptx_last_error although ptx_create
+ * returned PTX_OK.  Images and statistics do not depend on the schedule. */
 PTX_API int ptx_create(const PtxDeviceDesc *desc, PtxRenderer **out);
 PTX_API void ptx_destroy(PtxRenderer *r);
 PTX_API const char *ptx_last_error(const PtxRenderer *r);

@@ -155,7 +155,7 @@ static int markHostStoresPending(PtxRenderer *r, hipStream_t stream)
 // traffic over it -- the completion signals and packet fetches of every other frame in flight -- waits behind.  PTX_COPY_GROUPS
 // overrides each of the three.
 enum HostCopy { kCopyReadback, kCopyUnpackShard, kCopyGather };
-static uint32_t hostCopyGroups(const PtxRenderer *r, HostCopy kind)
+static uint32_t hostCopyGroups(const PtxRenderer *r, HostCopy kind, uint32_t planGroups = 1u)
 {
     if (r->env.copyGroups)
         return r->env.copyGroups;
@@ -170,7 +170,10 @@ static uint32_t hostCopyGroups(const PtxRenderer *r, HostCopy kind)
         // ... for a whole frame on one GPU.  Rank 0 of an N-GPU job renders 1 / N of the frame per step and still reads ALL of it
         // back: there the link, not the rendering, sets the pace, and one workgroup's 8 GB/s (4.1 ms per 1080p image) made a 1 / 8
         // step of chess_like 2.2 ms instead of 0.96 (tools/experiments/gather_cost.sh) -- more workgroups with more ranks.
-        return r->frame.shard.worldSize > 1 ? std::min(16u, 2u * r->frame.shard.worldSize) : 1u;
+        // ... and all of that where the copy's stream has a hardware queue to itself.  Where it shares one with other frames' streams
+        // (`planGroups` of the call's StreamPlan), a copy that trickles for 4-5 ms holds THEIR kernels back for as long: it leaves
+        // through as many workgroups as move it in well under a millisecond.
+        return std::max(planGroups, r->frame.shard.worldSize > 1 ? std::min(16u, 2u * r->frame.shard.worldSize) : 1u);
     case kCopyUnpackShard:
         // 4 per shard -- 2 / 4 / 8 / 16 / 64 / 2,048 workgroups: 1.45 / 1.38 / 1.42 / 1.47 / 1.50 / 1.51 ms per 1 / 8 step of
         // chess_like (profiles/r05_unpack_groups.txt)
@@ -196,10 +199,13 @@ static int readbackBegin(PtxRenderer *r, float *pinnedHost, size_t bytes)
         return rc;
     // The copy to the host rides on the renderer's auxiliary stream -- idle once the frame's shadow and tail kernels are done,
     // and not needed again before this renderer's next frame -- instead of a third stream per frame in flight: the streams of a
-    // process share GPU_MAX_HW_QUEUES hardware queues, and streams on one queue run one after the other.
-    if (!r->auxStream && !f.copyStream)
+    // process share GPU_MAX_HW_QUEUES hardware queues, and streams on one queue run one after the other.  Where the call's plan
+    // keeps the handle to ONE stream (pt_stream_plan.hpp: its two do not fit the queues), the copy follows the snapshot on the main
+    // stream: a second stream's wait for the snapshot would hold whichever queue that stream shares until this frame is done.
+    const StreamPlan plan = planFor(r);
+    if (!plan.copyOnMain && !r->auxStream && !f.copyStream)
         HIP_TRY(r, hipStreamCreateWithFlags(&f.copyStream, hipStreamNonBlocking));
-    const hipStream_t copyOn = r->auxStream ? r->auxStream : f.copyStream;
+    const hipStream_t copyOn = plan.copyOnMain ? r->stream : r->auxStream ? r->auxStream : f.copyStream;
     HIP_TRY(r, f.staging.alloc(f.pixels()));
     if (f.copyInFlight) // the previous copy still reads the staging image
         HIP_TRY(r, hipStreamWaitEvent(r->stream, f.evCopied, 0));
@@ -213,12 +219,16 @@ static int readbackBegin(PtxRenderer *r, float *pinnedHost, size_t bytes)
         k_copy_out<<<1024, kBlock, 0, r->stream>>>(f.accum(), f.staging.p, (uint32_t)(bytes / sizeof(float4)));
         HIP_TRY(r, hipGetLastError()); // (a failed launch would hand the host a stale staging image)
     }
-    HIP_TRY(r, hipEventRecord(f.evSnapshot, r->stream));
-    HIP_TRY(r, hipStreamWaitEvent(copyOn, f.evSnapshot, 0));
-    // Host memory the device cannot address (not page-locked) takes the runtime's copy.
-    if (float4 *const hostOnDevice = hostFrameAlias(r, pinnedHost, bytes))
+    if (!plan.copyOnMain || r->auxIsMain) // (a handle that asked for one stream: enqueued exactly as before)
     {
-        k_copy_out<<<hostCopyGroups(r, kCopyReadback), kBlock, 0, copyOn>>>(f.staging.p, hostOnDevice, (uint32_t)(bytes / sizeof(float4)));
+        HIP_TRY(r, hipEventRecord(f.evSnapshot, r->stream));
+        HIP_TRY(r, hipStreamWaitEvent(copyOn, f.evSnapshot, 0));
+    }
+    // Host memory the device cannot address (not page-locked) takes the runtime's copy.
+    float4 *const hostOnDevice = r->env.copyRuntime ? nullptr : hostFrameAlias(r, pinnedHost, bytes);
+    if (hostOnDevice)
+    {
+        k_copy_out<<<hostCopyGroups(r, kCopyReadback, plan.copyGroups), kBlock, 0, copyOn>>>(f.staging.p, hostOnDevice, (uint32_t)(bytes / sizeof(float4)));
         HIP_TRY(r, hipGetLastError());
     }
     else

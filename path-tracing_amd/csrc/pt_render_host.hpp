@@ -36,7 +36,9 @@ __global__ void k_upload_lights(PtxLightsUbo lights, LaunchParams params, PtxLig
         dP[i] = srcP[i];
 }
 
-static int ensureRenderResources(PtxRenderer *r, uint32_t bounces)
+// What a wavefront launch needs beside the path state.  The auxiliary stream is made by the first launch whose plan puts work on it
+// (a handle whose streams never fit the queues never makes one) and stays; nothing here runs again in the steady state.
+static int ensureRenderResources(PtxRenderer *r, uint32_t bounces, const StreamPlan &plan)
 {
     if (!r->auxStream)
     {
@@ -48,10 +50,11 @@ static int ensureRenderResources(PtxRenderer *r, uint32_t bounces)
             r->auxStream = r->stream;
             r->auxIsMain = true;
         }
-        else
+        else if (!plan.auxOnMain)
             HIP_TRY(r, createStreamOn(&r->auxStream, r->auxXcds, r->device));
-        HIP_TRY(r, r->spillAux.alloc((size_t)kGlobalSpill * kMaxPersistentThreads));
     }
+    if (!r->spillAux.p)
+        HIP_TRY(r, r->spillAux.alloc((size_t)kGlobalSpill * kMaxPersistentThreads));
     const size_t want = bounces < (uint32_t)kMaxTimedBounces ? bounces : (uint32_t)kMaxTimedBounces;
     while (r->bounceEvents.size() < want)
     {
@@ -74,6 +77,10 @@ struct RenderPlan
     uint32_t tailBelow; // queues of at most this many paths are finished by k_tail
     uint32_t sortShade; // material-sorted shade queue (scenes that mix material types; PTX_SHADE_SORT=0 / 1 overrides)
     Wavefront wf, wfAux;
+    // of this launch's StreamPlan: the stream of the shadow, k_apply_shadow and tail kernels (the auxiliary stream or the main one),
+    // and whether the two streams order themselves by events (no: everything is on one stream, whose order is all it needs)
+    hipStream_t aux;
+    bool crossWaits;
 };
 
 // The two failures a counter block reports, from the host's copy of it.
@@ -101,11 +108,11 @@ static void launchAccumulate(PtxRenderer *r, const LaunchParams &p)
     k_accumulate<<<gridFor((size_t)p.slotsPerFrame * p.framesPerWave), kBlock, 0, r->stream>>>(p, r->paths.slotRad.p, accumTarget(r), nullptr, r->frame.boundShard ? 1u : 0u);
 }
 
-// k_tail on the auxiliary stream, a thread per path of `queue` for up to `paths` of them (grid-stride; the spill region holds kMaxPersistentThreads)
+// k_tail on the stream of the auxiliary work, a thread per path of `queue` for up to `paths` of them (grid-stride; the spill region holds kMaxPersistentThreads)
 static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t paths, BounceCtl ctl)
 {
     const dim3 grid(gridFor(paths, kBlock, kMaxPersistentThreads / kBlock));
-    withMode(pl.mode, [&](auto M) { k_tail<decltype(M)::value><<<grid, kBlock, 0, r->auxStream>>>(pl.p, pl.sv, pl.sc, pl.wfAux, queue, ctl); });
+    withMode(pl.mode, [&](auto M) { k_tail<decltype(M)::value><<<grid, kBlock, 0, pl.aux>>>(pl.p, pl.sv, pl.sc, pl.wfAux, queue, ctl); });
 }
 
 // One BOUNCE of the wavefront over queue `qin` (length in the counter block, at most `est`), enqueued without waiting
@@ -113,6 +120,14 @@ static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t
 //
 //   stream     P(b)  closest(b)  [wait aux(b-1)]  shade(b)                      P(b+1) closest(b+1) ...
 //   auxStream                                     [wait shade(b)] shadow(b) [tail(b)]
+//
+// ... where the launch's plan gives the auxiliary work its own stream.  Where it rides the main stream (pl.aux == r->stream: the
+// handle's two streams do not fit the hardware queues, or it asked for one), the same kernels in the same order on one stream,
+//
+//   stream     P(b)  closest(b)  shade(b)  shadow(b)  apply(b)  [tail(b)]  P(b+1) closest(b+1) ...
+//
+// and no event is waited for: a wait for another stream holds the hardware queue of the waiting stream, and with it every other
+// frame whose stream shares that queue.  The events are still recorded: they time the kernels (collectRender).
 //
 // `fresh`: b is bounce 1 of the round renderWavefront starts, whose queue is every slot of the launch.  closest(1) and shade(1)
 // are then the <FirstBounce, ..> variants, which compute the primary ray of a slot from the launch parameters -- no k_generate in front:
@@ -131,7 +146,7 @@ static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t
 // its length (nothing is enqueued behind this bounce).
 static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, int tail, bool fresh)
 {
-    hipStream_t S = r->stream, X = r->auxStream;
+    hipStream_t S = r->stream, X = pl.aux;
     PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
     const BounceCtl ctl = { b, 0u };
     const int qout = qin ^ 1, parity = (int)(b & 1u);
@@ -145,7 +160,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
             k_trace_closest<decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
     });
     HIP_TRY(r, hipEventRecord(ev.t1, S));
-    if (b > 1) // shade reads rad[slot] and overwrites rayO[slot]: the previous bounce's shadow adds must have landed, its rays been read
+    if (b > 1 && pl.crossWaits) // shade reads rad[slot] and overwrites rayO[slot]: the previous bounce's shadow adds must have landed, its rays been read
         HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
     const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
     withFlag(pl.mode >= 1, [&](auto TEXTURED) {
@@ -160,7 +175,8 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
             k_shade<TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
     });
     HIP_TRY(r, hipEventRecord(ev.t2, S));
-    HIP_TRY(r, hipStreamWaitEvent(X, ev.t2, 0));
+    if (pl.crossWaits)
+        HIP_TRY(r, hipStreamWaitEvent(X, ev.t2, 0));
     HIP_TRY(r, hipEventRecord(ev.x0, X));
     withFlag(pl.mode == 2, [&](auto ALPHA) {
         k_trace_shadow<decltype(ALPHA)::value><<<traceGridFor(est, r->residentShadow[decltype(ALPHA)::value]), kBlock, 0, X>>>(pl.p, pl.sc, pl.wfAux, qout, parity);
@@ -240,12 +256,12 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
                 // the queue is short: k_tail finishes it, behind the shadow kernel of this bounce on its stream
                 launchTail(r, pl, qin, est, { b, kTailAnyLength });
                 // re-recorded behind the tail: what the stream waits for below
-                HIP_TRY(r, hipEventRecord(r->bounceEvents[(b - 1) % r->bounceEvents.size()].x2, r->auxStream));
+                HIP_TRY(r, hipEventRecord(r->bounceEvents[(b - 1) % r->bounceEvents.size()].x2, pl.aux));
                 break;
             }
         }
     }
-    if (last)
+    if (last && pl.crossWaits)
         HIP_TRY(r, hipStreamWaitEvent(r->stream, r->bounceEvents[(last - 1) % r->bounceEvents.size()].x2, 0));
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;
@@ -429,8 +445,13 @@ static int runSampleRounds(PtxRenderer *r, const RenderPlan &pl, uint32_t sample
 static int renderWavefront(PtxRenderer *r, RenderPlan &pl, uint32_t sampleCount)
 {
     const LaunchParams &p = pl.p;
-    if (const int rc = ensureRenderResources(r, pl.bounces))
+    // per launch: the handles of the process come and go (pt_stream_plan.hpp).  A handle that ASKED for one stream is enqueued exactly
+    // as before, its (same-stream) waits included: only the plan's own one-stream launches leave them out.
+    const StreamPlan plan = planFor(r);
+    if (const int rc = ensureRenderResources(r, pl.bounces, plan))
         return rc;
+    pl.aux = plan.auxOnMain ? r->stream : r->auxStream;
+    pl.crossWaits = !plan.auxOnMain || r->auxIsMain;
     pl.sortShade = r->env.shadeSort >= 0 ? (uint32_t)r->env.shadeSort : (sceneOf(r)->scene.mixedMaterialTypes || sceneOf(r)->scene.mixedTextured) ? 1u : 0u;
     // measured with 16 hardware queues (chess_like, ms per step at 25 / 50 / 75 / 100 / 200 / 400 K live paths): whole frame 8.04 / 7.82 /
     // 7.85 / 7.80 / 8.14 / 8.13, a rank's tile shard of 8: 1.44 / 1.44 / 1.39 / 1.39 / 1.54 / 1.55, of 4: 2.29 / 2.24 / 2.24 / 2.33 / 2.34 /

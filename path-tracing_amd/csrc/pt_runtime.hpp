@@ -26,6 +26,7 @@
 #include "pt_post.hpp"
 #include "pt_present.hpp"
 #include "pt_shard_layout.hpp"
+#include "pt_stream_plan.hpp"
 #include "pt_temporal.hpp"
 
 // =====================================================================================
@@ -117,6 +118,9 @@ struct EnvSwitches
     bool firstBounce = true;     // PTX_FIRST_BOUNCE=0: k_generate hands the primary rays over through memory (rounds 1-6) instead of the first
                                  // bounce's kernels computing them (pt_wavefront.hpp, FirstClosestIO)
     bool streamLevelwise = false; // PTX_STREAM_LEVELWISE=1: ptx_texture_upload builds every chain level by level (k_blit_level) instead of k_stream_chain
+    bool streamPlan = true;      // PTX_STREAM_PLAN=0: two streams per handle whatever the queues granted (rounds 1-9) instead of the plan of
+                                 // pt_stream_plan.hpp
+    bool copyRuntime = false;    // PTX_COPY_RUNTIME=1: the read-back's copy to the host by hipMemcpyAsync instead of a kernel (measured, not kept)
     static EnvSwitches read()
     {
         EnvSwitches e;
@@ -126,6 +130,9 @@ struct EnvSwitches
             e.pairLeaves = std::strcmp(v, "0") != 0;
         if (const char *v = getenv("PTX_FIRST_BOUNCE"))
             e.firstBounce = std::strcmp(v, "0") != 0;
+        if (const char *v = getenv("PTX_STREAM_PLAN"))
+            e.streamPlan = std::strcmp(v, "0") != 0;
+        e.copyRuntime = getenv("PTX_COPY_RUNTIME") != nullptr && std::strcmp(getenv("PTX_COPY_RUNTIME"), "0") != 0;
         if (const char *v = getenv("PTX_COPY_GROUPS"))
             e.copyGroups = (uint32_t)strtoul(v, nullptr, 10);
         e.snapshotMemcpy = getenv("PTX_SNAPSHOT_MEMCPY") != nullptr && std::strcmp(getenv("PTX_SNAPSHOT_MEMCPY"), "0") != 0;
@@ -417,9 +424,13 @@ struct PtxRenderer
 
     hipEvent_t evA = nullptr, evB = nullptr, evT0 = nullptr, evT1 = nullptr; // render / build span; ptx_trace_rays kernel span
 
-    // bounce schedule of the wavefront backend (pt_render_host.hpp): closest + shade on `stream`, shadow + tail on `auxStream`
+    // bounce schedule of the wavefront backend (pt_render_host.hpp): closest + shade on `stream`, shadow + tail on `auxStream` or,
+    // where the launch's plan says so (pt_stream_plan.hpp, planFor), on `stream` too.  auxStream is made by the first launch whose
+    // plan wants it and stays.
     hipStream_t auxStream = nullptr;
     bool auxIsMain = false; // single-stream handle: auxStream is `stream` itself
+    StreamPlan plan = { false, false, 1u }; // of the last launch or read-back (what a change is logged against)
+    bool planSeen = false;
     bool singleStream = false; // PtxDeviceDesc.flags & PTX_DEVICE_SINGLE_STREAM
     uint32_t handleSeq = 0, mainXcds = 0xffu, auxXcds = 0xffu; // PTX_CU_PARTITION: the XCDs this handle's streams may use
     DevBuf<uint32_t> spillAux; // traversal-stack overflow region of the kernels on auxStream
@@ -596,8 +607,12 @@ static LaunchParams makeParams(const PtxRenderer *r, const PtxRaygenUniformData 
 // - / 1.73 / 1.68 / 1.54.  The variable is read when the runtime initialises (the first HIP call of the process) and is
 // the HOST's to set (the Python package and bench.py set it at import): a library that edits its host's
 // environment at load time races with getenv in the host's other threads and cannot know whether HIP is up already.  What
-// the library does instead is REPORT: PtxStats::hardwareQueues says how many queues the environment grants, and the
-// handle whose streams no longer fit says so once (ptx_last_error after a successful ptx_create, stderr under PTX_VERBOSE).
+// the library does instead is REPORT and ADAPT: PtxStats::hardwareQueues says how many queues the environment grants, the
+// handle whose streams no longer fit says so once (ptx_last_error after a successful ptx_create, stderr under PTX_VERBOSE),
+// and every launch takes the schedule that fits what is granted (planFor, pt_stream_plan.hpp): while the two streams of every
+// live handle have a queue each, the two-stream schedule measured above; once they do not, the frame's auxiliary kernels and
+// its read-back ride the main stream -- a stream that waits for another stream's event, or runs a one-workgroup copy for
+// milliseconds, holds a queue that another frame's stream shares (docs/EXPERIMENTS.md, "Stream plan").
 static uint32_t hardwareQueuesGranted()
 {
     const char *e = getenv("GPU_MAX_HW_QUEUES");
@@ -605,6 +620,20 @@ static uint32_t hardwareQueuesGranted()
     return v ? (uint32_t)v : 4u; // the runtime's default
 }
 static std::atomic<bool> g_queueWarningGiven{false};
+
+// The plan of the launch (or read-back) being enqueued now: handles come and go, so it is evaluated every time.  A change is logged
+// under PTX_VERBOSE; nothing else happens on one -- the streams a plan no longer uses stay.
+static StreamPlan planFor(PtxRenderer *r)
+{
+    const StreamPlan now = streamPlanFor({ (uint32_t)r->stats.hardwareQueues, g_liveHandles.load(std::memory_order_relaxed),
+                                           r->env.singleStream || r->singleStream, r->env.streamPlan });
+    if (r->env.verbose && (!r->planSeen || now != r->plan))
+        fprintf(stderr, "[ptx] handle %u: stream plan %s: %s (%u live handles, %u hardware queues)\n", r->handleSeq, r->planSeen ? "changes to" : "is",
+                streamPlanName(now), g_liveHandles.load(std::memory_order_relaxed), (uint32_t)r->stats.hardwareQueues);
+    r->plan = now;
+    r->planSeen = true;
+    return now;
+}
 
 static void destroyRenderer(PtxRenderer *r);
 
@@ -724,9 +753,11 @@ static int createRenderer(const PtxDeviceDesc *desc, PtxRenderer **out)
     const uint32_t streamsPerHandle = (r->singleStream || r->env.singleStream) ? 1u : 2u;
     if (streamsPerHandle * live > r->stats.hardwareQueues && live > 1 && !g_queueWarningGiven.exchange(true))
     {
-        // not an error: the handle works, its frames just run behind the other handles' instead of beside them
-        fail(r, PTX_OK, "%u handles (%u stream(s) each) share %u hardware queues: frames in flight will serialise; export GPU_MAX_HW_QUEUES=16 "
-                        "(24 for a process that also gathers) before the process first uses HIP", live, streamsPerHandle, (uint32_t)r->stats.hardwareQueues);
+        // not an error: the handle works, and the note says which schedule its launches take from here on (planFor)
+        const StreamPlan plan = streamPlanFor({ (uint32_t)r->stats.hardwareQueues, live, streamsPerHandle == 1u, r->env.streamPlan });
+        fail(r, PTX_OK, "%u handles (%u stream(s) each) share %u hardware queues; stream plan: %s; export GPU_MAX_HW_QUEUES=16 "
+                        "(24 for a process that also gathers) before the process first uses HIP to give every stream a queue", live, streamsPerHandle,
+             (uint32_t)r->stats.hardwareQueues, streamPlanName(plan));
         if (r->env.verbose)
             fprintf(stderr, "[ptx] %s\n", r->error.c_str());
     }
