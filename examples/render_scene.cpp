@@ -11,6 +11,7 @@
 //   examples/render_scene default 640 360 16 4 screen.png --present 1280x720          (the screen path: the frame as an SDR window of that size shows it)
 //   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
+//   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
 #include <filesystem>
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <string>
 
+#include "../include/ptx_host.h"
 #include "ExampleScenes.h"
 #include "RendererHip.h"
 
@@ -74,6 +76,16 @@ int main(int argc, char **argv)
             argc -= drop;
             break;
         }
+    bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--native-bc")
+        {
+            nativeBc = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     const std::string name = argc > 1 ? argv[1] : "default";
     const uint32_t width = argc > 2 ? std::atoi(argv[2]) : 640, height = argc > 3 ? std::atoi(argv[3]) : 360;
     const uint32_t spp = argc > 4 ? std::atoi(argv[4]) : 16, bounces = argc > 5 ? std::atoi(argv[5]) : 4;
@@ -82,7 +94,7 @@ int main(int argc, char **argv)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
-        std::shared_ptr<Scene> scene = ExampleScenes::CreateScene(name, 0.25f, 0);
+        std::shared_ptr<Scene> scene = ExampleScenes::CreateScene(name, 0.25f, 0, nativeBc ? static_cast<uint32_t>(PTH_SCENE_NATIVE_BC) : 0u);
         RendererHip::Init(0);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);

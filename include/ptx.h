@@ -239,7 +239,46 @@ typedef struct PtxModelInstance {
 typedef enum PtxTextureFormat {
     PTX_TEXTURE_RGBA8_UNORM = 0,
     PTX_TEXTURE_RGBA8_SRGB = 1,
-    PTX_TEXTURE_RGBA32F = 2
+    PTX_TEXTURE_RGBA32F = 2,
+    /* Block-compressed scene textures, uploaded as blocks and decoded on the device (docs/NEXT_ROWS.md section 15).  The format
+     * follows TextureUploader::GetImageFormat in full (TextureUploader.cpp:586-591): BC3 is always sRGB, BC5 always UNORM, BC1 is
+     * sRGB or UNORM by the texture type.  Skybox images in these formats are refused.
+     *
+     * Layout of PtxTextureDesc.data: `levels` levels back to back, level 0 first (the order of a DDS file).  Level l has the
+     * extent w_l x h_l = max(w >> l, 1) x max(h >> l, 1) and is ceil(w_l / 4) * ceil(h_l / 4) blocks, row-major (block (bx, by)
+     * covers the texels 4 bx .. 4 bx + 3, 4 by .. 4 by + 3; texels of a partial block beyond the extent do not exist).  A block is
+     * 8 bytes for BC1 and 16 bytes for BC3 / BC5, little-endian.  Texel (x, y) of a block has the number i = 4 (y & 3) + (x & 3).
+     *
+     * Colour block (8 bytes; all of BC1, bytes 8 .. 15 of BC3): c0 = bytes 0-1 and c1 = bytes 2-3 as 16-bit RGB565 (R in bits
+     * 11-15, G in 5-10, B in 0-4), then 32 bits of codes, 2 bits per texel, texel i in bits 2i, 2i + 1 of the dword of bytes 4-7.
+     * An end point expands to 8 bits by bit replication: R8 = R5 << 3 | R5 >> 2, G8 = G6 << 2 | G6 >> 4, B8 = B5 << 3 | B5 >> 2.
+     * Per channel, with p0 / p1 the expanded end points and integer arithmetic with floor division:
+     *   four-colour mode:  code 0: p0, 1: p1, 2: (2 p0 + p1) / 3, 3: (p0 + 2 p1) / 3; alpha 255
+     *   three-colour mode: code 0: p0, 1: p1, 2: (p0 + p1) / 2, alpha 255;  code 3: R = G = B = 0 and alpha 0
+     * BC1 is the RGBA variant: four-colour mode iff c0 > c1 (compared as 16-bit integers), three-colour mode otherwise.  The colour
+     * block of BC3 is always in four-colour mode and its alpha comes from the alpha block.
+     * Alpha block (8 bytes, the "BC4" block; bytes 0 .. 7 of BC3, both halves of BC5): a0 = byte 0, a1 = byte 1, then 48 bits of
+     * codes, 3 bits per texel, texel i in bits 3i .. 3i + 2 of the little-endian integer of bytes 2-7.  Integer, floor division:
+     *   a0 > a1:  code 0: a0, 1: a1, c = 2 .. 7: ((8 - c) a0 + (c - 1) a1) / 7
+     *   a0 <= a1: code 0: a0, 1: a1, c = 2 .. 5: ((6 - c) a0 + (c - 1) a1) / 5, 6: 0, 7: 255
+     * BC3: RGB from the colour block, A from the alpha block.  BC5: R from bytes 0-7, G from bytes 8-15, B = 0, A = 255.
+     * The 8-bit RGBA result becomes four floats exactly as an RGBA8 texel of PTX_TEXTURE_RGBA8_SRGB (the _SRGB formats) or
+     * PTX_TEXTURE_RGBA8_UNORM (the _UNORM formats) does: the same blocks decoded by the caller and uploaded as RGBA8 sample the
+     * same bits.
+     *
+     * Upload rules (TextureUploader::UploadTexture for a format that cannot be blitted, TextureUploader.cpp:401-503).  The budget
+     * prices a texture in block bytes: the largest square extent whose full chain, sum over its levels of
+     * ceil(w_l / 4) ceil(h_l / 4) block bytes, fits textureMemoryBudget / textureCount (BC1 keeps 8x, BC3 / BC5 4x the texels of
+     * RGBA8).  Scale and budgeted extent w' x h' as for the other formats.  At scale 1: a full chain is used as it is; levels <= 1
+     * gives a ONE-level image at the full extent (no levels are generated); any other count is REJECTED.  At scale > 1: levels <= 1
+     * is rejected; otherwise with skip = levels - fullLevels(w', h'), the image is the file's levels from `skip` on iff skip >= 0
+     * and file level `skip` has exactly the extent w' x h', and rejected otherwise.  A rejected texture (the reference's
+     * m_RejectedCount) does not fail the upload: it is replaced by the 1 x 1 one-level opaque-white RGBA8 texel and reported by
+     * ptx_textures_rejected. */
+    PTX_TEXTURE_BC1_UNORM = 3,
+    PTX_TEXTURE_BC1_SRGB = 4,
+    PTX_TEXTURE_BC3_SRGB = 5,
+    PTX_TEXTURE_BC5_UNORM = 6
 } PtxTextureFormat;
 
 /* ShaderTypes.incl:50-59 (scalar block layout), the input of skinning.comp */
@@ -443,6 +482,13 @@ PTX_API int ptx_textures_commit(PtxRenderer *r, uint32_t *committed);
 /* Counts over the scene's textures (of the owner's scene on a borrower): resident = uploaded with the scene or committed,
  * pending = everything else.  After a plain ptx_scene_upload every texture is resident. */
 PTX_API int ptx_texture_residency(PtxRenderer *r, uint32_t *resident, uint32_t *pending);
+/* TextureUploader's m_RejectedCount: the block-compressed scene textures the last ptx_scene_upload / ptx_scene_upload_streamed
+ * on this handle (on the owner, for a borrower) could not take by the upload rules of PtxTextureFormat and replaced by the white
+ * texel.  Returns their count and writes the first min(count, capacity) scene texture indices, ascending, into `indices` (may be
+ * NULL with capacity 0).  0 for a scene without block-compressed textures, without a scene, and for a NULL handle.  In a
+ * streamed upload a rejected texture is resident at once, never pending, and ptx_texture_upload for it is refused with
+ * PTX_ERROR_INVALID_ARGUMENT. */
+PTX_API uint32_t ptx_textures_rejected(PtxRenderer *r, uint32_t *indices, uint32_t capacity);
 /* AccelerationStructure::Build (AccelerationStructure.cpp:26-46; BLAS :64-247, TLAS
  * :250-301), replaced by a software LBVH over the flattened world-space triangles.
  * The reference asks its driver for ePreferFastTrace (AccelerationStructure.cpp:319-324); this build spends time the same way:

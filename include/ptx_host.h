@@ -24,9 +24,15 @@ PTX_API const char *pth_scene_names(void);
  *                            one-component file scenes, ExampleScenes.cpp:41-66)
  *   "description:<json>"     a SceneDescription (host/SceneDescription.h; the aggregates of ExampleScenes.cpp:87-236):
  *   "description:@<file>"    {"components": [...], "skybox": "x.hdr", "mapping": "orca" | "none",
- *                            "dxNormalTextures": bool, "forceFullTextureSize": bool}; components and skybox that do not
+ *                            "dxNormalTextures": bool, "forceFullTextureSize": bool, "nativeBlockCompression": bool}; components and skybox that do not
  *                            exist are dropped (the reference warns and carries on, SceneManager.cpp:66-94), none left = error */
 PTX_API PthScene *pth_scene_create(const char *name, float detail, uint32_t seed);
+/* The same with flags (pth_scene_create has no room for them).  PTH_SCENE_NATIVE_BC: the .dds textures of an imported scene keep
+ * their BC1 / BC3 / BC5 blocks -- PTX_TEXTURE_BC* descs with the file's own levels, hasTransparency for every .dds, no
+ * premultiply -- instead of being decoded to RGBA8 (TextureImporter::Options; a description's "nativeBlockCompression": true
+ * does the same).  Off by default: the RGBA8 decode stays until the oracle reads the block formats.  Unknown bits: NULL. */
+enum { PTH_SCENE_NATIVE_BC = 1u };
+PTX_API PthScene *pth_scene_create_ex(const char *name, float detail, uint32_t seed, uint32_t flags);
 PTX_API void pth_scene_destroy(PthScene *s);
 PTX_API const char *pth_last_error(void);
 

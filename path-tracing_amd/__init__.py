@@ -60,7 +60,7 @@ PTX_SYMBOLS = [
     "ptx_shard_bytes", "ptx_pack_shard", "ptx_unpack_shard", "ptx_unpack_shard_host", "ptx_unpack_shards", "ptx_bind_shard_accumulation", "ptx_get_stats", "ptx_bind_accumulation",
     "ptx_trace_rays", "ptx_test_input_stride", "ptx_test_output_stride", "ptx_test_eval", "ptx_test_texture",
     "ptx_postprocess", "ptx_read_output", "ptx_write_accumulation", "ptx_update_animation",
-    "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency",
+    "ptx_scene_upload_streamed", "ptx_texture_upload", "ptx_textures_commit", "ptx_texture_residency", "ptx_textures_rejected",
     "ptx_render_debug", "ptx_test_debug_eval",
     "ptx_present", "ptx_read_present", "ptx_device_present_ptr", "ptx_present_bytes",
     "ptx_render_guides", "ptx_read_guide", "ptx_device_guide_ptr", "ptx_denoise", "ptx_read_denoised", "ptx_device_denoised_ptr",
@@ -68,10 +68,12 @@ PTX_SYMBOLS = [
     "ptx_temporal_accumulate", "ptx_read_temporal", "ptx_device_temporal_ptr", "ptx_denoise_temporal",
 ]
 PTH_SYMBOLS = [
-    "pth_scene_names", "pth_scene_create", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
+    "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
     "pth_scene_lights", "pth_scene_triangle_count", "pth_scene_raygen_uniform", "pth_scene_camera_matrices", "pth_scene_set_active_camera",
     "pth_scene_set_camera_pose", "pth_scene_update", "pth_scene_bone_count", "pth_scene_animation_state", "pth_decode_image", "pth_decode_image_levels", "pth_write_image", "pth_save_checkpoint", "pth_load_checkpoint",
 ]
+
+SCENE_NATIVE_BC = 1  # PTH_SCENE_NATIVE_BC
 
 BACKEND_WAVEFRONT = 0
 BACKEND_MEGAKERNEL = 1
@@ -106,6 +108,8 @@ class TextureDesc(C.Structure):
 
 
 TEXTURE_RGBA8_UNORM, TEXTURE_RGBA8_SRGB, TEXTURE_RGBA32F = 0, 1, 2
+# block-compressed scene textures, uploaded as blocks (include/ptx.h, PtxTextureFormat; docs/NEXT_ROWS.md section 15)
+TEXTURE_BC1_UNORM, TEXTURE_BC1_SRGB, TEXTURE_BC3_SRGB, TEXTURE_BC5_UNORM = 3, 4, 5, 6
 PLACEHOLDER_TEXTURE_INDEX = 8  # PTX_PLACEHOLDER_TEXTURE_INDEX
 
 
@@ -282,6 +286,8 @@ def load_host() -> C.CDLL:
         lib.pth_last_error.restype = C.c_char_p
         lib.pth_scene_create.restype = C.c_void_p
         lib.pth_scene_create.argtypes = [C.c_char_p, C.c_float, C.c_uint32]
+        lib.pth_scene_create_ex.restype = C.c_void_p
+        lib.pth_scene_create_ex.argtypes = [C.c_char_p, C.c_float, C.c_uint32, C.c_uint32]
         lib.pth_scene_destroy.argtypes = [C.c_void_p]
         lib.pth_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
         lib.pth_scene_lights.argtypes = [C.c_void_p, C.POINTER(LightsUbo)]
@@ -373,6 +379,8 @@ def load_hip() -> C.CDLL:
         lib.ptx_texture_upload.argtypes = [P, C.c_uint32, C.POINTER(TextureDesc)]
         lib.ptx_textures_commit.argtypes = [P, C.POINTER(C.c_uint32)]
         lib.ptx_texture_residency.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.ptx_textures_rejected.argtypes = [P, P, C.c_uint32]
+        lib.ptx_textures_rejected.restype = C.c_uint32
         lib.ptx_render_debug.argtypes = [P, C.POINTER(RaygenUniformData), C.POINTER(LightsUbo), C.POINTER(DebugViewDesc)]
         lib.ptx_test_debug_eval.argtypes = [P, C.c_uint32, P, P, C.c_uint32]
         lib.ptx_present.argtypes = [P, C.POINTER(PresentDesc)]
@@ -409,10 +417,14 @@ class PtxError(RuntimeError):
 class Scene:
     """A host-side scene (PathTracing::Scene built by ExampleScenes::CreateScene)."""
 
-    def __init__(self, name: str = "default", detail: float = 1.0, seed: int = 0):
+    def __init__(self, name: str = "default", detail: float = 1.0, seed: int = 0, native_bc: bool = False):
+        """native_bc: the .dds textures of an imported scene keep their BC1 / BC3 / BC5 blocks (PTH_SCENE_NATIVE_BC)."""
         self.lib = load_host()
         self.name = name
-        self.handle = self.lib.pth_scene_create(name.encode(), float(detail), int(seed))
+        if native_bc:
+            self.handle = self.lib.pth_scene_create_ex(name.encode(), float(detail), int(seed), SCENE_NATIVE_BC)
+        else:
+            self.handle = self.lib.pth_scene_create(name.encode(), float(detail), int(seed))
         if not self.handle:
             raise PtxError(self.lib.pth_last_error().decode())
 
@@ -559,6 +571,14 @@ class Renderer:
         a, b = C.c_uint32(), C.c_uint32()
         self._check(self.lib.ptx_texture_residency(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def textures_rejected(self):
+        """ptx_textures_rejected: the scene texture indices of the block-compressed files the last upload could not take by the
+        upload rules (they sample the white texel); empty for a scene without block-compressed textures."""
+        n = int(self.lib.ptx_textures_rejected(self.handle, None, 0))
+        idx = np.zeros(max(n, 1), np.uint32)
+        n = min(n, int(self.lib.ptx_textures_rejected(self.handle, idx.ctypes.data, n)))
+        return [int(i) for i in idx[:n]]
 
     def share_scene(self, owner: "Renderer"):
         """Render `owner`'s scene and tree instead of holding copies (ptx_share_scene): frames in flight share one scene."""

@@ -1139,7 +1139,9 @@ PT_DEV f4 trilinearSample(const TextureView &tv, const DevTexture &t, float lod,
 
 PT_DEV f4 textureGradSample(const TextureView &tv, const DevTexture &t, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
 {
-    if (t.levels <= 1)
+    // A 1 x 1 texture is its texel.  (Until the block-compressed formats, one level meant 1 x 1: a one-level image of any other
+    // extent -- a BC file with a single level -- is filtered like level 0 of a chain, anisotropic taps included.)
+    if (t.levels <= 1 && t.width == 1 && t.height == 1)
         return sampleLevel(tv, t, 0, u, v);
     const float mux = dudx * (float)t.width, mvx = dvdx * (float)t.height;
     const float muy = dudy * (float)t.width, mvy = dvdy * (float)t.height;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "pt_aux_kernels.hpp"
+#include "pt_bc.hpp"
 #include "pt_bvh_build.hpp"
 #include "pt_debug_view.hpp"
 #include "pt_denoise.hpp"
@@ -120,6 +121,7 @@ struct EnvSwitches
     bool streamLevelwise = false; // PTX_STREAM_LEVELWISE=1: ptx_texture_upload builds every chain level by level (k_blit_level) instead of k_stream_chain
     bool streamPlan = true;      // PTX_STREAM_PLAN=0: two streams per handle whatever the queues granted (rounds 1-9) instead of the plan of
                                  // pt_stream_plan.hpp
+    bool bcRowMapping = false;   // PTX_BC_MAPPING=rows: k_decode_bc with one thread per block row and four stores (measured, not kept) instead of one per texel
     bool copyRuntime = false;    // PTX_COPY_RUNTIME=1: the read-back's copy to the host by hipMemcpyAsync instead of a kernel (measured, not kept)
     static EnvSwitches read()
     {
@@ -132,6 +134,7 @@ struct EnvSwitches
             e.firstBounce = std::strcmp(v, "0") != 0;
         if (const char *v = getenv("PTX_STREAM_PLAN"))
             e.streamPlan = std::strcmp(v, "0") != 0;
+        e.bcRowMapping = getenv("PTX_BC_MAPPING") != nullptr && std::strcmp(getenv("PTX_BC_MAPPING"), "rows") == 0;
         e.copyRuntime = getenv("PTX_COPY_RUNTIME") != nullptr && std::strcmp(getenv("PTX_COPY_RUNTIME"), "0") != 0;
         if (const char *v = getenv("PTX_COPY_GROUPS"))
             e.copyGroups = (uint32_t)strtoul(v, nullptr, 10);
@@ -195,6 +198,7 @@ struct SceneData
     uint32_t textureCount = 0;
     uint32_t skyKind = PTX_SKYBOX_CLEAR_COLOR; // its images follow the scene textures in `renderTextures`
     bool samplerNeeded = false; // some uploaded texture is not a 1x1 white placeholder
+    std::vector<uint32_t> rejectedTextures; // block-compressed files the upload rules could not take (ptx_textures_rejected)
     // animation (row N3)
     std::vector<DevPair> hostPairs;            // to recompose pair transforms when instances move
     std::vector<uint32_t> pairInstance;        // pair -> instance

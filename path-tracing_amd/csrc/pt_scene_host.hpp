@@ -211,6 +211,8 @@ struct Placement
     bool useFileChain;    // every level comes from the file (TextureUploader.cpp:440,492-501)
     uint32_t halvings;    // blits from the file's level 0 down towards the budgeted extent (:479-490)
     int temp;             // table entry of the scratch chain, or -1
+    bool rejected = false; // a block-compressed file the upload rules cannot take: planned as the 1 x 1 white texel
+    size_t bcOffset = 0;   // block-compressed: first byte of the kept levels in the block pool (a multiple of 16)
 };
 
 struct TexturePlan
@@ -222,6 +224,8 @@ struct TexturePlan
     std::vector<DevTexture> renderTable; // [total]: offsets into the decoded pool, the RGBA32F textures first
     size_t n8 = 0, nf = 0;               // texels of the two format pools ...
     size_t scratch8 = 0, scratchF = 0;   // ... and of the scratch region behind each, used by one scaled texture after the other
+    size_t nbc = 0, bcBytes = 0;         // block-compressed textures: their decoded texels (behind nf + n8 in the decoded pool), their blocks
+    std::vector<uint32_t> rejected;      // scene textures planned as the white texel (ptx_textures_rejected)
     bool samplerNeeded = false;
     std::vector<AlphaTex> alphaTex; // any-hit data: the alpha footprints of every texture some material names as its colour texture
     std::vector<uint32_t> alphaTexOf;
@@ -252,19 +256,74 @@ static size_t placeLevels(DevTexture &t, size_t first)
     return first + chainTexels(t.width, t.height, t.levels);
 }
 
+// ---- block-compressed formats (pt_bc.hpp; the layout is the text of include/ptx.h) ----
+constexpr uint32_t kTextureFormats = PTX_TEXTURE_BC5_UNORM + 1u;
+static const uint32_t kWhiteTexel8 = 0xffffffffu; // what a rejected texture holds
+static bool isBcFormat(uint32_t f) { return f >= PTX_TEXTURE_BC1_UNORM && f <= PTX_TEXTURE_BC5_UNORM; }
+static uint32_t bcBlockBytes(uint32_t f) { return f == PTX_TEXTURE_BC1_UNORM || f == PTX_TEXTURE_BC1_SRGB ? 8u : 16u; }
+// bytes of the levels [first, first + levels) of a w x h image: ceil(w_l / 4) * ceil(h_l / 4) blocks each
+static size_t bcChainBytes(uint32_t w, uint32_t h, uint32_t first, uint32_t levels, uint32_t format)
+{
+    size_t blocks = 0;
+    for (uint32_t l = first; l < first + levels; l++)
+        blocks += (size_t)((mipDim(w, l) + 3u) / 4u) * ((mipDim(h, l) + 3u) / 4u);
+    return blocks * bcBlockBytes(format);
+}
+// the texel data a texture is uploaded from: the caller's, or the white texel of a rejected one
+static const void *textureData(const PtxTextureDesc &d, const Placement &pl) { return pl.rejected ? &kWhiteTexel8 : d.data; }
+
 // TextureUploader::DetermineMaxTextureSizes (TextureUploader.cpp:551-569): the largest square extent whose full chain
 // fits the per-texture share of the budget (Config.h:63-64,162-163: min(80 % of the device memory, 1 GiB)), per format;
-// forceFullTextureSize keeps MaxTextureDataSize = 4096 (TextureUploader.h:74).  Block-compressed files arrive decoded
-// to RGBA8 and are budgeted as that.
-static void maxTextureExtents(const PtxSceneDesc *s, uint32_t textureCount, uint64_t deviceTotalBytes, uint32_t maxExtent[3])
+// forceFullTextureSize keeps MaxTextureDataSize = 4096 (TextureUploader.h:74).  A block-compressed format is priced in
+// block bytes with the 4 x 4 rounding of every level.
+static void maxTextureExtents(const PtxSceneDesc *s, uint32_t textureCount, uint64_t deviceTotalBytes, uint32_t maxExtent[kTextureFormats])
 {
-    maxExtent[0] = maxExtent[1] = maxExtent[2] = 4096u;
+    for (uint32_t f = 0; f < kTextureFormats; f++)
+        maxExtent[f] = 4096u;
     if (s->forceFullTextureSize || !textureCount || s->textureMemoryBudget == ~0ull)
         return;
     const uint64_t budget = s->textureMemoryBudget ? s->textureMemoryBudget : std::min<uint64_t>(deviceTotalBytes / 100u * 80u, 1024ull << 20);
     for (uint32_t f = 0; f <= PTX_TEXTURE_RGBA32F; f++)
         for (uint32_t &m = maxExtent[f]; m > 1u && chainTexels(m, m, fullLevels(m, m)) * (f == PTX_TEXTURE_RGBA32F ? 16u : 4u) > budget / textureCount;)
             m >>= 1;
+    for (uint32_t f = PTX_TEXTURE_BC1_UNORM; f < kTextureFormats; f++)
+        for (uint32_t &m = maxExtent[f]; m > 1u && bcChainBytes(m, m, 0, fullLevels(m, m), f) > budget / textureCount;)
+            m >>= 1;
+}
+
+// The same for a block-compressed file, whose levels can be neither generated nor rescaled (TextureUploader.cpp:401-503 for a
+// format outside ScalingFormats): the file's chain, a one-level image, the file's levels from the budgeted extent on, or rejected.
+static int placeBcTexture(PtxRenderer *r, uint32_t i, uint32_t mx, DevTexture &t, Placement &pl)
+{
+    const uint32_t scale = std::max((pl.srcW + mx - 1) / mx, (pl.srcH + mx - 1) / mx);
+    const uint32_t full = fullLevels(pl.srcW, pl.srcH);
+    if (pl.fileLevels > full)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture %u: %u levels for a %u x %u image", i, pl.fileLevels, pl.srcW, pl.srcH);
+    t.width = std::max(pl.srcW / scale, 1u);
+    t.height = std::max(pl.srcH / scale, 1u);
+    pl.useFileChain = true;
+    if (scale == 1)
+    {
+        t.levels = pl.fileLevels == full ? full : 1u; // :423-437: a single-level file stays a single-level image
+        pl.rejected = pl.fileLevels != full && pl.fileLevels > 1u; // :444-453
+    }
+    else
+    {
+        // :462-476, :492-501; a level `skip` of another extent is rejected here, where the reference would copy mismatching data
+        t.levels = fullLevels(t.width, t.height);
+        pl.rejected = pl.fileLevels <= 1u || pl.fileLevels < t.levels;
+        if (!pl.rejected)
+        {
+            pl.firstFile = pl.fileLevels - t.levels;
+            pl.rejected = mipDim(pl.srcW, pl.firstFile) != t.width || mipDim(pl.srcH, pl.firstFile) != t.height;
+        }
+    }
+    if (pl.rejected)
+    {
+        pl = { 1u, 1u, 1u, 0u, false, 0u, -1, true };
+        t = { 1u, 1u, 1u, PTX_TEXTURE_RGBA8_UNORM, {} };
+    }
+    return PTX_OK;
 }
 
 // One scene texture of at most `mx` texels across (TextureUploader::UploadTexture): its extent and levels into `t`, the way
@@ -338,7 +397,7 @@ static int planTextures(PtxRenderer *r, const PtxSceneDesc *s, uint64_t deviceTo
         for (uint32_t f = 0; f < 6; f++)
             if (s->skybox[f].width != s->skybox[0].width || s->skybox[f].height != s->skybox[0].width || s->skybox[f].format != s->skybox[0].format)
                 return fail(r, PTX_ERROR_INVALID_ARGUMENT, "cube skybox: the six faces must be equal squares of one format");
-    uint32_t maxExtent[3];
+    uint32_t maxExtent[kTextureFormats];
     maxTextureExtents(s, plan.textureCount, deviceTotalBytes, maxExtent);
     plan.place.resize(plan.total);
     plan.table.resize(plan.total);
@@ -348,11 +407,29 @@ static int planTextures(PtxRenderer *r, const PtxSceneDesc *s, uint64_t deviceTo
         const PtxTextureDesc &d = textureDescOf(s, plan.textureCount, i);
         DevTexture &t = plan.table[i];
         Placement &pl = plan.place[i];
-        if (d.format > PTX_TEXTURE_RGBA32F)
+        if (d.format >= kTextureFormats)
             return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture %u: unknown format %u", i, d.format);
+        if (isBcFormat(d.format) && i >= plan.textureCount) // the reference loads its skyboxes through stb only
+            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "skybox image %u: block-compressed format %u", i - plan.textureCount, d.format);
         pl = { d.width ? d.width : 1, d.height ? d.height : 1, d.levels ? d.levels : 1u, 0u, false, 0u, -1 };
         t = { pl.srcW, pl.srcH, 1u, d.format, {} };
-        if (i < plan.textureCount)
+        if (isBcFormat(d.format))
+        {
+            if ((rc = placeBcTexture(r, i, maxExtent[d.format], t, pl)) != PTX_OK) return rc;
+            if (pl.rejected)
+                plan.rejected.push_back(i); // (the white texel: no sampler needed on its account)
+            else
+            {
+                plan.samplerNeeded = true;
+                pl.bcOffset = plan.bcBytes;
+                plan.bcBytes += (bcChainBytes(t.width, t.height, 0, t.levels, t.format) + 15u) & ~(size_t)15u;
+                plan.nbc = placeLevels(t, plan.nbc);
+                if (plan.nbc > 0xffffffffull)
+                    return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture pool exceeds 2^32 texels");
+                continue;
+            }
+        }
+        else if (i < plan.textureCount)
         {
             if ((rc = placeSceneTexture(r, i, maxExtent[d.format], plan.total + scaled, t, pl, plan)) != PTX_OK) return rc;
             scaled += pl.temp >= 0 ? 1u : 0u;
@@ -375,11 +452,13 @@ static int planTextures(PtxRenderer *r, const PtxSceneDesc *s, uint64_t deviceTo
             placeLevels(t, t.format == PTX_TEXTURE_RGBA32F ? plan.nf : plan.n8);
         }
     // (the second sum is the pool the render kernels sample, uploadTextures)
-    if (plan.n8 + plan.scratch8 > 0xffffffffull || plan.nf + plan.scratchF > 0xffffffffull || (uint64_t)plan.nf + plan.n8 > 0xffffffffull)
+    if (plan.n8 + plan.scratch8 > 0xffffffffull || plan.nf + plan.scratchF > 0xffffffffull || (uint64_t)plan.nf + plan.n8 + plan.nbc > 0xffffffffull)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "texture pool exceeds 2^32 texels");
     plan.renderTable.assign(plan.table.begin(), plan.table.begin() + plan.total);
     for (DevTexture &t : plan.renderTable)
-        if (t.format != PTX_TEXTURE_RGBA32F)
+        if (isBcFormat(t.format))
+            placeLevels(t, plan.nf + plan.n8 + t.levelOffset[0]);
+        else if (t.format != PTX_TEXTURE_RGBA32F)
             placeLevels(t, plan.nf + t.levelOffset[0]);
     plan.alphaTexOf.assign(plan.textureCount ? plan.textureCount : 1u, kNoAlphaTex);
     return anyNonOpaque ? planAlphaFootprints(r, s, plan) : PTX_OK;
@@ -423,6 +502,40 @@ static int uploadGeometry(PtxRenderer *r, const PtxSceneDesc *s, FlatScene &flat
     return upload(r, sc.pairFirst, flat.pairFirst.data(), flat.pairFirst.size());
 }
 
+// k_decode_bc for texture `t` (the plan's entry; `rt` its entry of the render table): every level in one launch, from the kept
+// levels' blocks at `blocks` into the texture's region of the decoded pool.  rows: the one-thread-per-block-row mapping.
+static void decodeBcTexture(const DevTexture &t, const DevTexture &rt, const uint8_t *blocks, const float *srgbLut, float4 *decoded, bool rows, hipStream_t stream)
+{
+    BcDecodeArgs a = {};
+    a.width = t.width; a.height = t.height; a.levels = t.levels;
+    for (uint32_t l = 0; l < 16u; l++)
+    {
+        a.itemFirst[l] = 0xffffffffu;
+        if (l >= t.levels)
+            continue;
+        const uint32_t w = mipDim(t.width, l), h = mipDim(t.height, l);
+        a.itemFirst[l] = a.items;
+        a.items += (rows ? (w + 3u) / 4u : w) * h;
+        a.blockFirst[l] = (uint32_t)bcChainBytes(t.width, t.height, 0, l, t.format);
+        a.decodedFirst[l] = rt.levelOffset[l];
+    }
+    const uint32_t grid = (a.items + 255u) / 256u;
+#define PT_BC_LAUNCH(F)                                                                        \
+    case F:                                                                                    \
+        if (rows) k_decode_bc<F, true><<<grid, 256, 0, stream>>>(a, blocks, srgbLut, decoded); \
+        else k_decode_bc<F, false><<<grid, 256, 0, stream>>>(a, blocks, srgbLut, decoded);     \
+        break;
+    switch (t.format)
+    {
+        PT_BC_LAUNCH(PTX_TEXTURE_BC1_UNORM)
+        PT_BC_LAUNCH(PTX_TEXTURE_BC1_SRGB)
+        PT_BC_LAUNCH(PTX_TEXTURE_BC3_SRGB)
+        PT_BC_LAUNCH(PTX_TEXTURE_BC5_UNORM)
+    default: break;
+    }
+#undef PT_BC_LAUNCH
+}
+
 // Stage 5 (row N1): every texture into the pools of the upload formats -- the file's own chain, or its level 0 (scaled through the
 // scratch chain where the plan says so) and the mip chain below it level by level on the device --, then decoded into the pool the
 // render kernels sample.  The upload-format pools are this stage's own: freed when it returns, whichever way (hipFree waits).
@@ -434,8 +547,10 @@ static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePl
     DevBuf<uint32_t> texels8;    // the sRGB byte -> linear table
     DevBuf<float4> texelsF;
     DevBuf<float> srgbLut;
+    DevBuf<uint8_t> bcBlocks;    // the kept levels of the block-compressed textures, as the files hold them
     HIP_TRY(r, srgbLut.alloc(256));
     k_build_srgb_lut<<<1, 256, 0, r->stream>>>(srgbLut.p);
+    sc.rejectedTextures = plan.rejected;
     sc.textureCount = plan.textureCount; sc.skyKind = plan.skyKind; sc.samplerNeeded = plan.samplerNeeded;
     HIP_TRY(r, textures.alloc(plan.table.size()));
     HIP_TRY(r, texels8.alloc(plan.n8 + plan.scratch8));
@@ -454,6 +569,9 @@ static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePl
         const Placement &pl = plan.place[i];
         const bool isFloat = t.format == PTX_TEXTURE_RGBA32F;
         const size_t texel = isFloat ? 16 : 4;
+        if (isBcFormat(t.format)) // never in the 8-bit pool: decoded below, straight from its blocks
+            continue;
+        const void *data = textureData(d, pl); // (a rejected texture: its one white texel, whatever the caller passed)
         auto poolAt = [&](uint32_t offset) -> void * { return isFloat ? (void *)(texelsF.p + offset) : (void *)(texels8.p + offset); };
         auto blit = [&](uint32_t src, uint32_t srcLevel, uint32_t dst, uint32_t dstLevel) {
             const uint32_t dw = mipDim(plan.table[dst].width, dstLevel), dh = mipDim(plan.table[dst].height, dstLevel);
@@ -481,26 +599,48 @@ static int uploadTextures(PtxRenderer *r, const PtxSceneDesc *s, const TexturePl
             else
                 blit((uint32_t)pl.temp, pl.halvings, i, 0);
         }
-        else if (d.data)
-            HIP_TRY(r, hipMemcpyAsync(poolAt(t.levelOffset[0]), d.data, (size_t)t.width * t.height * texel, hipMemcpyHostToDevice, r->stream));
+        else if (data)
+            HIP_TRY(r, hipMemcpyAsync(poolAt(t.levelOffset[0]), data, (size_t)t.width * t.height * texel, hipMemcpyHostToDevice, r->stream));
         for (uint32_t l = 1; l < t.levels; l++)
             blit(i, l - 1, i, l);
     }
     // The pool the render kernels sample (pt_device.hpp, fetchTexel): every level of every texture decoded to four floats,
     // the RGBA32F pool first, the 8-bit textures behind it; `renderTextures` is the table with offsets into that pool.
-    HIP_TRY(r, sc.renderTexels.alloc(plan.nf + plan.n8 + extraTexels));
+    // the block-compressed textures behind both, decoded by k_decode_bc from the block pool
+    HIP_TRY(r, sc.renderTexels.alloc(plan.nf + plan.n8 + plan.nbc + extraTexels));
     HIP_TRY(r, sc.renderTextures.alloc(plan.total));
     if (plan.nf)
         HIP_TRY(r, hipMemcpyAsync(sc.renderTexels.p, texelsF.p, plan.nf * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
     for (uint32_t i = 0; i < plan.total; i++)
     {
         const DevTexture &t = plan.table[i];
-        if (t.format == PTX_TEXTURE_RGBA32F)
+        if (t.format == PTX_TEXTURE_RGBA32F || isBcFormat(t.format))
             continue;
         const size_t count = chainTexels(t.width, t.height, t.levels);
         const uint32_t first = t.levelOffset[0];
         k_decode_texels<<<(uint32_t)((count + 255) / 256), 256, 0, r->stream>>>(texels8.p, srgbLut.p, first, (uint32_t)count, t.format,
                                                                               sc.renderTexels.p + plan.nf + first);
+    }
+    if (plan.nbc)
+    {
+        // only the levels that are kept, straight from the caller's data; one launch per texture
+        HIP_TRY(r, bcBlocks.alloc(plan.bcBytes));
+        for (uint32_t i = 0; i < plan.textureCount; i++)
+        {
+            const DevTexture &t = plan.table[i], &rt = plan.renderTable[i];
+            const Placement &pl = plan.place[i];
+            if (!isBcFormat(t.format))
+                continue;
+            const size_t count = chainTexels(t.width, t.height, t.levels);
+            if (!s->textures[i].data) // a texture without data reads as zeros (a pending one: until its upload)
+            {
+                HIP_TRY(r, hipMemsetAsync(sc.renderTexels.p + rt.levelOffset[0], 0, count * sizeof(float4), r->stream));
+                continue;
+            }
+            const uint8_t *src = static_cast<const uint8_t *>(s->textures[i].data) + bcChainBytes(pl.srcW, pl.srcH, 0, pl.firstFile, t.format);
+            HIP_TRY(r, hipMemcpyAsync(bcBlocks.p + pl.bcOffset, src, bcChainBytes(t.width, t.height, 0, t.levels, t.format), hipMemcpyHostToDevice, r->stream));
+            decodeBcTexture(t, rt, bcBlocks.p + pl.bcOffset, srgbLut.p, sc.renderTexels.p, r->env.bcRowMapping, r->stream);
+        }
     }
     if (plan.total)
         HIP_TRY(r, hipMemcpyAsync(sc.renderTextures.p, plan.renderTable.data(), plan.total * sizeof(DevTexture), hipMemcpyHostToDevice, r->stream));
@@ -602,7 +742,7 @@ static int beginStreaming(PtxRenderer *r, const PtxSceneDesc *s, std::shared_ptr
     const TexturePlan &plan = st->plan;
     int rc;
     st->device = r->device;
-    st->standInTexel = (uint32_t)(plan.nf + plan.n8);
+    st->standInTexel = (uint32_t)(plan.nf + plan.n8 + plan.nbc);
     st->standInQuad = (uint32_t)plan.alphaQuads;
     HIP_TRY(r, st->srgbLut.alloc(256));
     k_build_srgb_lut<<<1, 256, 0, r->stream>>>(st->srgbLut.p);
@@ -662,13 +802,13 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s, bool streamed = fa
         {
             if (standIn && standIn[i] >= PTX_SCENE_TEXTURE_OFFSET)
                 return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: stand-in %u of texture %u is not one of the nine fixed textures", who, standIn[i], i);
-            if (!s->textures[i].data)
+            if (!s->textures[i].data && !plan.place[i].rejected) // (a rejected texture is its white texel: resident at once)
             {
                 st->state[i] = kTexPending;
                 st->pendingCount++;
             }
         }
-        if ((uint64_t)plan.nf + plan.n8 + PTX_SCENE_TEXTURE_OFFSET > 0xffffffffull || (uint64_t)plan.alphaQuads + PTX_SCENE_TEXTURE_OFFSET >= 0xffffffffull)
+        if ((uint64_t)plan.nf + plan.n8 + plan.nbc + PTX_SCENE_TEXTURE_OFFSET > 0xffffffffull || (uint64_t)plan.alphaQuads + PTX_SCENE_TEXTURE_OFFSET >= 0xffffffffull)
             return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture pool exceeds 2^32 texels", who);
     }
 
@@ -776,6 +916,8 @@ static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d
                     decl.levels);
     if (!d->data)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u: null data", who, index);
+    if (plan.place[index].rejected)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u was rejected by the upload rules of its block-compressed format (ptx_textures_rejected)", who, index);
     if (st->state[index] != kTexPending)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: texture %u is not pending (already uploaded or resident)", who, index);
     HIP_TRY(r, hipSetDevice(r->device));
@@ -784,7 +926,7 @@ static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d
 
     const DevTexture &t = plan.table[index];
     const Placement &pl = plan.place[index];
-    const bool isFloat = t.format == PTX_TEXTURE_RGBA32F;
+    const bool isFloat = t.format == PTX_TEXTURE_RGBA32F, isBc = isBcFormat(t.format);
     const size_t texel = isFloat ? 16 : 4;
     // the slot's one-texture pool: the chain at its head, the scratch chain of a scaled texture behind it
     DevTexture tab[2];
@@ -796,8 +938,11 @@ static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d
         tab[1] = plan.table[(size_t)pl.temp];
         poolTexels = placeLevels(tab[1], poolTexels);
     }
-    const uint8_t *src = static_cast<const uint8_t *>(d->data) + (pl.useFileChain ? chainTexels(pl.srcW, pl.srcH, pl.firstFile) * texel : 0);
-    const size_t srcBytes = (pl.useFileChain ? chainTexels(t.width, t.height, t.levels) : (size_t)pl.srcW * pl.srcH) * texel;
+    // (a block-compressed texture: the slot's pool holds the kept levels' blocks and nothing else)
+    const uint8_t *src = static_cast<const uint8_t *>(d->data) +
+                         (isBc ? bcChainBytes(pl.srcW, pl.srcH, 0, pl.firstFile, t.format) : pl.useFileChain ? chainTexels(pl.srcW, pl.srcH, pl.firstFile) * texel : 0);
+    const size_t srcBytes = isBc ? bcChainBytes(t.width, t.height, 0, t.levels, t.format)
+                                 : (pl.useFileChain ? chainTexels(t.width, t.height, t.levels) : (size_t)pl.srcW * pl.srcH) * texel;
     const size_t header = 256; // the table, and the texels 16-byte aligned behind it
 
     // a free slot: the reference's free-buffer semaphore
@@ -818,7 +963,7 @@ static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d
         HIP_TRY(r, hipHostMalloc(&sl.host, header + srcBytes, hipHostMallocDefault));
         sl.hostBytes = header + srcBytes;
     }
-    HIP_TRY(r, sl.pool.alloc(poolTexels * texel));
+    HIP_TRY(r, sl.pool.alloc(isBc ? srcBytes : poolTexels * texel));
     HIP_TRY(r, sl.table.alloc(2));
     st->nextSlot = (st->nextSlot + 1) % kStreamRing;
     std::memcpy(sl.host, tab, sizeof(tab));
@@ -835,7 +980,13 @@ static int textureUpload(PtxRenderer *r, uint32_t index, const PtxTextureDesc *d
         const uint32_t dw = mipDim(tab[d0].width, dstLevel), dh = mipDim(tab[d0].height, dstLevel);
         k_blit_level<<<(dw * dh + 255) / 256, 256, 0, S>>>(tv, s0, srcLevel, d0, dstLevel, reinterpret_cast<uint32_t *>(sl.pool.p), reinterpret_cast<float4 *>(sl.pool.p));
     };
-    if (pl.useFileChain)
+    if (isBc)
+    {
+        // the kept levels' blocks: one copy, one launch into the texture's own region
+        HIP_TRY(r, hipMemcpyAsync(sl.pool.p, staged, srcBytes, hipMemcpyHostToDevice, S));
+        decodeBcTexture(t, rt, sl.pool.p, st->srgbLut.p, decoded, r->env.bcRowMapping, S);
+    }
+    else if (pl.useFileChain)
     {
         // the file's own levels from the one that has the budgeted extent: one copy, then decoded as they are
         const size_t count = chainTexels(t.width, t.height, t.levels);
@@ -932,4 +1083,18 @@ static int textureResidency(PtxRenderer *r, uint32_t *resident, uint32_t *pendin
     if (resident) *resident = s->scene.textureCount - notResident;
     if (pending) *pending = notResident;
     return PTX_OK;
+}
+
+// TextureUploader's m_RejectedCount, with the indices.
+static uint32_t texturesRejected(PtxRenderer *r, uint32_t *indices, uint32_t capacity)
+{
+    if (!r)
+        return 0;
+    const PtxRenderer *s = sceneOf(r);
+    if (!s->sceneReady)
+        return 0;
+    const std::vector<uint32_t> &rej = s->scene.rejectedTextures;
+    for (uint32_t k = 0; indices && k < capacity && k < rej.size(); k++)
+        indices[k] = rej[k];
+    return (uint32_t)rej.size();
 }

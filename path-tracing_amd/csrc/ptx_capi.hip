@@ -75,6 +75,11 @@ int ptx_texture_residency(PtxRenderer *r, uint32_t *resident, uint32_t *pending)
     return textureResidency(r, resident, pending);
 }
 
+uint32_t ptx_textures_rejected(PtxRenderer *r, uint32_t *indices, uint32_t capacity)
+{
+    return texturesRejected(r, indices, capacity);
+}
+
 int ptx_build_accel(PtxRenderer *r)
 {
     return buildBestTree(r);

@@ -12,6 +12,8 @@
 #include "ExampleScenes.h"
 #include "SceneImporter.h"
 #include "SceneDescription.h"
+#include "TextureImporter.h"
+#include "../../include/ptx_host.h"
 
 #include <fstream>
 #include <sstream>
@@ -1609,9 +1611,12 @@ const char *GetSceneNames()
     return kSceneNames;
 }
 
-std::shared_ptr<Scene> CreateScene(const std::string &name, float detail, uint32_t seed)
+std::shared_ptr<Scene> CreateScene(const std::string &name, float detail, uint32_t seed, uint32_t flags)
 {
     SceneBuilder sb;
+    TextureImporter::Options options;
+    options.NativeBlockCompression = (flags & PTH_SCENE_NATIVE_BC) != 0;
+    const TextureImporter::ScopedOptions scoped(options);
     bool useSceneCamera = true;
     if (name.rfind("file:", 0) == 0) // a glTF 2.0 asset through the importer (the registry's file scenes, ExampleScenes.cpp:41-66)
         SceneImporter::AddFile(sb, name.substr(5));

@@ -24,6 +24,7 @@ void CreateTextureTestScene(SceneBuilder &sceneBuilder, uint32_t seed); // sampl
 void CreateMaterialsTestScene(SceneBuilder &sceneBuilder, float detail, uint32_t seed);
 
 const char *GetSceneNames();
-std::shared_ptr<Scene> CreateScene(const std::string &name, float detail, uint32_t seed);
+// flags: PTH_SCENE_* of include/ptx_host.h
+std::shared_ptr<Scene> CreateScene(const std::string &name, float detail, uint32_t seed, uint32_t flags = 0);
 
 }

@@ -186,6 +186,13 @@ PtxSceneDesc Scene::GetDesc() const
         rec.width = t.Width;
         rec.height = t.Height;
         rec.format = t.Format == TextureFormat::RGBAF32 ? PTX_TEXTURE_RGBA32F : (isColor ? PTX_TEXTURE_RGBA8_SRGB : PTX_TEXTURE_RGBA8_UNORM);
+        // :586-591: BC3 is always sRGB and BC5 always UNORM, whatever the type (a quirk of the reference, reproduced)
+        if (t.Format == TextureFormat::BC1)
+            rec.format = isColor ? PTX_TEXTURE_BC1_SRGB : PTX_TEXTURE_BC1_UNORM;
+        else if (t.Format == TextureFormat::BC3)
+            rec.format = PTX_TEXTURE_BC3_SRGB;
+        else if (t.Format == TextureFormat::BC5)
+            rec.format = PTX_TEXTURE_BC5_UNORM;
         rec.levels = t.Pixels.empty() ? 1u : t.Levels;
         rec.data = t.Pixels.empty() ? nullptr : t.Pixels.data();
         if (t.Pixels.empty()) // no data: a 1x1 white placeholder

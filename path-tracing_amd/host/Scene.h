@@ -67,11 +67,14 @@ enum class TextureType : uint8_t
     Skybox,
 };
 
-// Scene.h:35-42 (the block-compressed formats arrive with the importer, row N2)
+// Scene.h:35-42.  BC1 / BC3 / BC5: the blocks of a .dds file as it holds them (TextureImporter's NativeBlockCompression option)
 enum class TextureFormat : uint8_t
 {
     RGBAU8,
     RGBAF32,
+    BC1,
+    BC3,
+    BC5,
 };
 
 // Scene.h:48-59.  The reference keeps a file / memory source and decodes on a loader thread
@@ -84,7 +87,7 @@ struct TextureInfo
     uint32_t Width = 1, Height = 1;
     std::string Name;
     TextureFormat Format = TextureFormat::RGBAU8;
-    std::vector<uint8_t> Pixels; // RGBAU8: 4 bytes per texel; RGBAF32: 16 bytes per texel
+    std::vector<uint8_t> Pixels; // RGBAU8: 4 bytes per texel; RGBAF32: 16 bytes per texel; BC1 / BC3 / BC5: the file's blocks, 8 / 16 / 16 bytes each
     uint32_t Levels = 1;         // mip levels in Pixels (a DDS file's own chain), level 0 first, tightly packed
 };
 

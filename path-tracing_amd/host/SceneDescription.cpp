@@ -35,6 +35,7 @@ SceneDescription SceneDescription::Parse(const std::string &json, const std::fil
     }
     d.DxNormalTextures = flag("dxNormalTextures");
     d.FullSizeTextures = flag("forceFullTextureSize");
+    d.NativeBlockCompression = flag("nativeBlockCompression");
     return d;
 }
 
@@ -42,6 +43,10 @@ std::vector<std::filesystem::path> SceneDescription::Build(SceneBuilder &builder
 {
     std::vector<std::filesystem::path> missing;
     size_t found = 0;
+    // the key switches the native route on; without it the caller's setting stands (pth_scene_create_ex's flag)
+    TextureImporter::Options options = TextureImporter::CurrentOptions();
+    options.NativeBlockCompression |= NativeBlockCompression;
+    const TextureImporter::ScopedOptions scoped(options);
     for (const std::filesystem::path &file : Components)
     {
         if (!std::filesystem::exists(file))

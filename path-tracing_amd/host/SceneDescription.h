@@ -26,9 +26,10 @@ struct SceneDescription
     TextureMapping Mapping;                        // which imported texture slot feeds which material slot
     bool DxNormalTextures = false;                 // normal maps in the DirectX convention (green flipped)
     bool FullSizeTextures = false;                 // exempt the scene from the texture memory budget
+    bool NativeBlockCompression = false;           // .dds textures keep their BC1 / BC3 / BC5 blocks (TextureImporter::Options)
 
     // {"components": ["a.gltf", ...], "skybox": "sky.hdr", "mapping": "orca" | "none", "dxNormalTextures": true,
-    //  "forceFullTextureSize": true}; relative paths are taken from `base`.
+    //  "forceFullTextureSize": true, "nativeBlockCompression": true}; relative paths are taken from `base`.
     static SceneDescription Parse(const std::string &json, const std::filesystem::path &base = {});
 
     // Imports what exists on disk into `builder` and returns the paths that did not (the reference warns and carries on;

@@ -590,28 +590,38 @@ void DecodeBc4Channel(const uint8_t *b, uint8_t out[16]) // the alpha block of B
 
 }
 
-DecodedImage TextureImporter::DecodeDds(std::span<const uint8_t> f)
+namespace
+{
+enum class DdsFormat { BC1, BC3, BC5 };
+struct DdsHeader
+{
+    DdsFormat Format;
+    uint32_t Width, Height, Levels;
+    size_t Offset; // of level 0's blocks
+};
+
+DdsHeader ParseDdsHeader(std::span<const uint8_t> f)
 {
     if (f.size() < 128 || std::memcmp(f.data(), "DDS ", 4) != 0)
         throw error("Not a DDS texture");
     auto le32 = [&](size_t o) { return uint32_t(f[o]) | (uint32_t(f[o + 1]) << 8) | (uint32_t(f[o + 2]) << 16) | (uint32_t(f[o + 3]) << 24); };
     const uint32_t h = le32(12), w = le32(16), pfFlags = le32(80), fourCC = le32(84);
     size_t offset = 128;
-    enum { BC1, BC3, BC5 } fmt;
+    DdsFormat fmt;
     auto cc = [](const char *s) { return uint32_t(s[0]) | (uint32_t(s[1]) << 8) | (uint32_t(s[2]) << 16) | (uint32_t(s[3]) << 24); };
     if (!(pfFlags & 4))
         throw error("Unsupported texture format");
-    if (fourCC == cc("DXT1")) fmt = BC1;
-    else if (fourCC == cc("DXT5")) fmt = BC3;
-    else if (fourCC == cc("ATI2") || fourCC == cc("BC5U")) fmt = BC5;
+    if (fourCC == cc("DXT1")) fmt = DdsFormat::BC1;
+    else if (fourCC == cc("DXT5")) fmt = DdsFormat::BC3;
+    else if (fourCC == cc("ATI2") || fourCC == cc("BC5U")) fmt = DdsFormat::BC5;
     else if (fourCC == cc("DX10"))
     {
         if (f.size() < 148) throw error("DDS: truncated DX10 header");
         const uint32_t dxgi = le32(128);
         offset = 148;
-        if (dxgi == 71 || dxgi == 72) fmt = BC1;
-        else if (dxgi == 77 || dxgi == 78) fmt = BC3;
-        else if (dxgi == 83) fmt = BC5;
+        if (dxgi == 71 || dxgi == 72) fmt = DdsFormat::BC1;
+        else if (dxgi == 77 || dxgi == 78) fmt = DdsFormat::BC3;
+        else if (dxgi == 83) fmt = DdsFormat::BC5;
         else throw error("Unsupported texture format");
     }
     else
@@ -631,12 +641,23 @@ DecodedImage TextureImporter::DecodeDds(std::span<const uint8_t> f)
         if (levels > full)
             throw error("DDS: more mip levels than the image has");
     }
+    return { fmt, w, h, levels, offset };
+}
+}
+
+DecodedImage TextureImporter::DecodeDds(std::span<const uint8_t> f)
+{
+    const DdsHeader hd = ParseDdsHeader(f);
+    constexpr DdsFormat BC1 = DdsFormat::BC1, BC3 = DdsFormat::BC3;
+    const DdsFormat fmt = hd.Format;
+    const uint32_t w = hd.Width, h = hd.Height, levels = hd.Levels;
+    size_t offset = hd.Offset;
     const size_t blockBytes = fmt == BC1 ? 8 : 16;
     DecodedImage img;
     img.Width = w;
     img.Height = h;
     img.Levels = levels;
-    img.Channels = fmt == BC5 ? 2 : 4;
+    img.Channels = fmt == DdsFormat::BC5 ? 2 : 4;
     size_t texels = 0;
     for (uint32_t l = 0; l < levels; l++)
         texels += static_cast<size_t>(std::max(w >> l, 1u)) * std::max(h >> l, 1u);
@@ -721,14 +742,46 @@ TextureInfo ToTextureInfo(DecodedImage &&img, TextureType type, std::string &&na
 }
 }
 
+TextureImporter::Options &TextureImporter::CurrentOptions()
+{
+    static thread_local Options options;
+    return options;
+}
+
+// The native route (TextureImporter.cpp:53-66, :262-343): the file's blocks as they are, every level the file holds.
+TextureInfo TextureImporter::GetBlockTextureInfo(std::span<const uint8_t> f, TextureType type, std::string &&name, bool *hasTransparency)
+{
+    const DdsHeader hd = ParseDdsHeader(f);
+    const size_t blockBytes = hd.Format == DdsFormat::BC1 ? 8 : 16;
+    size_t bytes = 0;
+    for (uint32_t l = 0; l < hd.Levels; l++)
+        bytes += static_cast<size_t>((std::max(hd.Width >> l, 1u) + 3) / 4) * ((std::max(hd.Height >> l, 1u) + 3) / 4) * blockBytes;
+    if (hd.Offset + bytes > f.size())
+        throw error("DDS: truncated data");
+    if (hasTransparency)
+        *hasTransparency = true; // :267-268: every .dds, whatever its channels
+    TextureInfo info;
+    info.Type = type;
+    info.Width = hd.Width;
+    info.Height = hd.Height;
+    info.Name = std::move(name);
+    info.Format = hd.Format == DdsFormat::BC1 ? TextureFormat::BC1 : hd.Format == DdsFormat::BC3 ? TextureFormat::BC3 : TextureFormat::BC5;
+    info.Levels = hd.Levels;
+    info.Pixels.assign(f.begin() + hd.Offset, f.begin() + hd.Offset + bytes); // not premultiplied: :386-387 runs on stb data only
+    return info;
+}
+
 TextureInfo TextureImporter::GetTextureInfo(const std::filesystem::path &path, TextureType type, std::string &&name, bool *hasTransparency)
 {
     const std::vector<uint8_t> bytes = ReadFileBytes(path);
-    return ToTextureInfo(Decode(bytes), type, std::move(name), hasTransparency);
+    return GetTextureInfo(std::span<const uint8_t>(bytes), type, std::move(name), hasTransparency);
 }
 
 TextureInfo TextureImporter::GetTextureInfo(std::span<const uint8_t> memory, TextureType type, std::string &&name, bool *hasTransparency)
 {
+    // (a skybox never takes the native route: the reference loads its skyboxes through stb only)
+    if (CurrentOptions().NativeBlockCompression && type != TextureType::Skybox && memory.size() >= 4 && !std::memcmp(memory.data(), "DDS ", 4))
+        return GetBlockTextureInfo(memory, type, std::move(name), hasTransparency);
     return ToTextureInfo(Decode(memory), type, std::move(name), hasTransparency);
 }
 

@@ -46,6 +46,28 @@ public:
     static TextureInfo GetTextureInfo(const std::filesystem::path &path, TextureType type, std::string &&name, bool *hasTransparency = nullptr);
     static TextureInfo GetTextureInfo(std::span<const uint8_t> memory, TextureType type, std::string &&name, bool *hasTransparency = nullptr);
 
+    // NativeBlockCompression: a .dds file keeps its BC1 / BC3 / BC5 blocks (TextureFormat::BC1 / BC3 / BC5, every level the
+    // file holds) instead of being decoded to RGBA8; it then reports hasTransparency = true (TextureImporter.cpp:267-268) and
+    // is not premultiplied (:386-387).  Off by default: the RGBA8 decode stays until the oracle reads the block formats
+    // (docs/NEXT_ROWS.md section 15).  Per thread; ScopedOptions sets it for the import of one scene.
+    struct Options
+    {
+        bool NativeBlockCompression = false;
+    };
+    static Options &CurrentOptions();
+    struct ScopedOptions
+    {
+        explicit ScopedOptions(const Options &o) : m_Saved(CurrentOptions()) { CurrentOptions() = o; }
+        ~ScopedOptions() { CurrentOptions() = m_Saved; }
+        ScopedOptions(const ScopedOptions &) = delete;
+        ScopedOptions &operator=(const ScopedOptions &) = delete;
+
+    private:
+        Options m_Saved;
+    };
+    // the blocks of a DDS file as a TextureInfo (what GetTextureInfo returns for a .dds with the option on)
+    static TextureInfo GetBlockTextureInfo(std::span<const uint8_t> file, TextureType type, std::string &&name, bool *hasTransparency = nullptr);
+
     // format sniffing + decode; throws PathTracing::error
     static DecodedImage Decode(std::span<const uint8_t> file);
 

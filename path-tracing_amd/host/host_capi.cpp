@@ -30,12 +30,19 @@ const char *pth_last_error(void)
 
 PthScene *pth_scene_create(const char *name, float detail, uint32_t seed)
 {
+    return pth_scene_create_ex(name, detail, seed, 0);
+}
+
+PthScene *pth_scene_create_ex(const char *name, float detail, uint32_t seed, uint32_t flags)
+{
     try
     {
+        if (flags & ~static_cast<uint32_t>(PTH_SCENE_NATIVE_BC))
+            throw error("pth_scene_create_ex: unknown flag bits");
         if (!(detail > 0.0f))
             detail = 1.0f;
         auto *s = new PthScene;
-        s->scene = ExampleScenes::CreateScene(name ? name : "default", detail, seed);
+        s->scene = ExampleScenes::CreateScene(name ? name : "default", detail, seed, flags);
         return s;
     }
     catch (const std::exception &e)
