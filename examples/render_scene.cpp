@@ -11,6 +11,7 @@
 //   examples/render_scene default 640 360 16 4 screen.png --present 1280x720          (the screen path: the frame as an SDR window of that size shows it)
 //   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
+//   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3   (guides + temporal moments + the variance-guided filter)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -76,6 +77,22 @@ int main(int argc, char **argv)
             argc -= drop;
             break;
         }
+    // --denoise-variance [iterations]: the denoiser, the temporal accumulation and, in the fixed-sigma filter's place, the variance-guided one
+    RendererHip::TemporalSettings temporal;
+    RendererHip::VarianceSettings variance;
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--denoise-variance")
+        {
+            denoiser.Enabled = temporal.Enabled = variance.Enabled = true;
+            const bool counted = i + 1 < argc && std::strlen(argv[i + 1]) == 1 && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '6';
+            if (counted)
+                variance.Iterations = static_cast<uint32_t>(argv[i + 1][0] - '0');
+            const int drop = counted ? 2 : 1;
+            for (int k = i; k + drop < argc; k++)
+                argv[k] = argv[k + drop];
+            argc -= drop;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -103,6 +120,8 @@ int main(int argc, char **argv)
         settings.BounceCount = bounces;
         RendererHip::SetSettings(settings);
         RendererHip::SetSettings(denoiser);
+        RendererHip::SetSettings(temporal);
+        RendererHip::SetSettings(variance);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

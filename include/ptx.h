@@ -932,6 +932,66 @@ PTX_API void *ptx_device_temporal_ptr(PtxRenderer *r);
  * ptx_temporal_accumulate since the last ptx_resize. */
 PTX_API int ptx_denoise_temporal(PtxRenderer *r, const PtxDenoiseDesc *desc);
 
+/* ------------------------------------------------------------------------- */
+/* Variance-guided denoising (docs/NEXT_ROWS.md section 16): the first two     */
+/* luminance moments accumulated beside the colour history, a per-pixel        */
+/* variance from them, and a filter whose colour weight is measured in it.     */
+/* ------------------------------------------------------------------------- */
+
+/* ptx_temporal_accumulate, and beside it the MOMENT HISTORY.  T, the colour history and the refusals are the plain call's, bit for
+ * bit.  In addition, per valid pixel p with this frame's demodulated mean c = c(p):
+ *     l = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z,   mu = (l, l l).
+ * The moment history M' = (mu1', mu2', L_M') of the previous moments call is gathered at the same texels with the same bilinear
+ * weights as the colour.  A tap q counts for the moments iff it counted for the colour, L_M'(q) > 0 and both of its moments are
+ * finite.  With sum w_M >= 1/64 over those taps:
+ *     M_h = sum w mu'(q) / sum w_M,   L_M = min(sum w L_M'(q) / sum w_M + 1, maxHistory),   M = M_h + (mu - M_h) / L_M;
+ * otherwise M = mu and L_M = 1 -- also without a history and with PTX_TEMPORAL_RESET.  If either component of M is not finite,
+ * (0, 0, 0, 0) is stored: the pixel's moments are UNKNOWN (L_M = 0) and no later tap takes them.  A pixel that is not valid stores
+ * zeros.  float32 throughout.
+ * The moment history is one more RGBA32F image, (mu1, mu2, L_M, 0), kept twice, ping-ponging with the colour history: 32 more bytes
+ * per pixel.  A plain ptx_temporal_accumulate DROPS the moment history: the next moments call restarts M (M = mu, L_M = 1) on the
+ * colour history as it stands.  ptx_resize drops everything; a refused call leaves everything intact.  One launch, asynchronous on
+ * the render stream; a caller that never makes this call allocates nothing for it. */
+PTX_API int ptx_temporal_accumulate_moments(PtxRenderer *r, const PtxTemporalDesc *desc);
+/* The moment history of the last moments call, device -> host, width*height*16 bytes: (mu1, mu2, L_M, 0) per pixel; synchronous.
+ * PTX_ERROR_INVALID_ARGUMENT: a buffer of another size; PTX_ERROR_NOT_READY: the last accepted accumulate call since ptx_resize was
+ * not ptx_temporal_accumulate_moments. */
+PTX_API int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes);
+
+/* The variance-guided filter.  Input: T, the moment history and the three guides; output: D where ptx_denoise leaves it (alpha 1),
+ * so ptx_read_denoised, ptx_postprocess_denoised and ptx_present follow unchanged, and V_0 for ptx_read_variance.  No input is
+ * written.  The desc is read as: iterations 1 .. 6; sigmaColor as sigmaLuminance, > 0 here; sigmaNormal, sigmaPosition > 0;
+ * totalSamples ignored (T is a mean); flags 0, reserved 0.  Validity, a_p and h are the denoiser's with m(p) = T(p).rgb;
+ * lum(c) = (0.2126 c.x + 0.7152 c.y) + 0.0722 c.z; c_0(p) = m(p) / a_p on valid pixels and m(p) elsewhere.
+ *
+ * 1. ESTIMATE (the first launch).  V_0(p) = 0 on a pixel that is not valid.  On a valid p with the moments (mu1, mu2, L_M):
+ *    where L_M(p) >= 4, v = mu2 - mu1 mu1.  Otherwise a 7 x 7 window around p: a tap q counts iff it is inside the image, valid and
+ *    L_M(q) > 0, with
+ *        w = exp(-(|n_p - n_q|^2 / sigmaNormal^2 + (dot(n_p, x_q - x_p) / (sigmaPosition t_p))^2)),
+ *    the centre with w = 1 iff its moments are known (L_M(p) > 0);
+ *        m1 = sum w mu1(q) / sum w,  m2 = sum w mu2(q) / sum w,  v = m2 - m1 m1;   sum w = 0 gives v = 0.
+ *    V_0 = v where v is finite and > 0, else 0.  There is no boost for a short history.
+ * 2. FILTER.  For i = 0 .. iterations-1 and s = 2^i, on a valid p:
+ *    PREFILTER: vt(p) = the 3 x 3 mean of V_i around p (not dilated) with the weights 1/4 (centre), 1/8 (edges), 1/16 (corners) over
+ *    the taps inside the image and valid, divided by the sum of the weights that count.
+ *    TAPS: the denoiser's -- q = p + s (dx, dy), dx, dy in -2 .. 2, the centre with w = h[2] h[2] by rule, any other tap only if q is
+ *    inside the image and valid, c_i(q) is finite and e >= 0 -- with the colour term replaced:
+ *        d = |lum(c_i(p)) - lum(c_i(q))|;  e_l = 0 if d = 0;  the tap does NOT count if d > 0 and vt(p) = 0;  otherwise
+ *        e_l = d^2 / (sigmaLuminance^2 vt(p)),
+ *        e = e_l + |n_p - n_q|^2 / sigmaNormal^2 + (dot(n_p, x_q - x_p) / (sigmaPosition t_p))^2,   w = h[dx+2] h[dy+2] exp(-e),
+ *        c_{i+1}(p) = sum w c_i(q) / sum w,   V_{i+1}(p) = sum w^2 V_i(q) / (sum w)^2.
+ *    sigmaLuminance is NOT halved per iteration: the variance shrinks by itself.  On any other p, c_{i+1}(p) = c_i(p).
+ *    D(p).rgb = c_N(p) a_p on valid pixels and m(p) elsewhere, as in ptx_denoise.
+ * The formulas hold no epsilon and no square root: a sum scaled by 2^k gives D scaled by 2^k.  float32 throughout; 1 + iterations
+ * launches, asynchronous on the render stream; V_0 is one float per pixel the renderer keeps.
+ * PTX_ERROR_INVALID_ARGUMENT: iterations outside 1 .. 6, a sigma that is <= 0 or not finite, unknown flags, reserved != 0.
+ * PTX_ERROR_NOT_READY: whatever ptx_denoise_temporal answers so, and unless the last accepted accumulate call since ptx_resize
+ * was ptx_temporal_accumulate_moments.  A refused call leaves D, V_0, T and both histories intact. */
+PTX_API int ptx_denoise_variance(PtxRenderer *r, const PtxDenoiseDesc *desc);
+/* V_0 of the last ptx_denoise_variance, device -> host, width*height*4 bytes: one float per pixel; synchronous.
+ * PTX_ERROR_INVALID_ARGUMENT: a buffer of another size; PTX_ERROR_NOT_READY: no ptx_denoise_variance since the last ptx_resize. */
+PTX_API int ptx_read_variance(PtxRenderer *r, void *host, size_t bytes);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

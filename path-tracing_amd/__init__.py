@@ -66,6 +66,7 @@ PTX_SYMBOLS = [
     "ptx_render_guides", "ptx_read_guide", "ptx_device_guide_ptr", "ptx_denoise", "ptx_read_denoised", "ptx_device_denoised_ptr",
     "ptx_postprocess_denoised",
     "ptx_temporal_accumulate", "ptx_read_temporal", "ptx_device_temporal_ptr", "ptx_denoise_temporal",
+    "ptx_temporal_accumulate_moments", "ptx_read_moments", "ptx_denoise_variance", "ptx_read_variance",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -186,6 +187,9 @@ TEMPORAL_RESET = 1  # PTX_TEMPORAL_RESET
 # filter behind it come first in the sweep of tools/temporal_quality.py (docs/NEXT_ROWS.md section 14)
 TEMPORAL_DEFAULTS = dict(max_history=32.0, normal_threshold=0.3, position_threshold=0.03)
 TEMPORAL_DENOISE_DEFAULTS = dict(iterations=2, sigma_color=0.5, sigma_normal=0.3, sigma_position=0.03)
+# The defaults of Renderer.denoise_variance: the best geometric mean over two scenes at 8 frames of history in the sweep of
+# tools/temporal_quality.py (docs/NEXT_ROWS.md section 16); sigma_luminance is in standard deviations of the pixel's luminance
+VARIANCE_DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=0.75, sigma_normal=0.3, sigma_position=0.03)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -403,6 +407,10 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_temporal_ptr.argtypes = [P]
         lib.ptx_device_temporal_ptr.restype = P
         lib.ptx_denoise_temporal.argtypes = [P, C.POINTER(DenoiseDesc)]
+        lib.ptx_temporal_accumulate_moments.argtypes = [P, C.POINTER(TemporalDesc)]
+        lib.ptx_read_moments.argtypes = [P, P, C.c_size_t]
+        lib.ptx_denoise_variance.argtypes = [P, C.POINTER(DenoiseDesc)]
+        lib.ptx_read_variance.argtypes = [P, P, C.c_size_t]
         _hip = lib
     return _hip
 
@@ -728,11 +736,16 @@ class Renderer:
         """ptx_temporal_accumulate: blend the demodulated mean of the accumulation image with the history of the previous calls,
         reprojected through the position guide.  view, proj: the forward matrices of the camera render_guides() was given
         (Scene.camera_matrices)."""
+        d = self._temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags)
+        self._check(self.lib.ptx_temporal_accumulate(self.handle, C.byref(d)))
+
+    @staticmethod
+    def _temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags):
         d = TemporalDesc()
         d.View[:] = [float(v) for v in np.asarray(view, np.float32).reshape(16)]
         d.Proj[:] = [float(v) for v in np.asarray(proj, np.float32).reshape(16)]
         d.totalSamples, d.maxHistory, d.normalThreshold, d.positionThreshold, d.flags = total_samples, max_history, normal_threshold, position_threshold, flags
-        self._check(self.lib.ptx_temporal_accumulate(self.handle, C.byref(d)))
+        return d
 
     def read_temporal(self) -> np.ndarray:
         """T of the last temporal_accumulate(): the accumulated MEAN, H x W x 4 float32, alpha = the history length (0: not valid)."""
@@ -748,6 +761,33 @@ class Renderer:
         """ptx_denoise_temporal: denoise() on T, which holds the mean; the result is read with read_denoised()."""
         d = DenoiseDesc(1, iterations, sigma_color, sigma_normal, sigma_position, 0, 0)
         self._check(self.lib.ptx_denoise_temporal(self.handle, C.byref(d)))
+
+    def temporal_accumulate_moments(self, total_samples: int, view, proj, max_history: float = TEMPORAL_DEFAULTS["max_history"],
+                                    normal_threshold: float = TEMPORAL_DEFAULTS["normal_threshold"],
+                                    position_threshold: float = TEMPORAL_DEFAULTS["position_threshold"], flags: int = 0):
+        """ptx_temporal_accumulate_moments: temporal_accumulate() that also accumulates the first two luminance moments, which
+        denoise_variance() needs."""
+        d = self._temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags)
+        self._check(self.lib.ptx_temporal_accumulate_moments(self.handle, C.byref(d)))
+
+    def read_moments(self) -> np.ndarray:
+        """The moment history of the last temporal_accumulate_moments(): H x W x 4 float32, (mu1, mu2, L_M, 0); L_M = 0: unknown."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.ptx_read_moments(self.handle, img.ctypes.data, img.nbytes))
+        return img
+
+    def denoise_variance(self, iterations: int = VARIANCE_DENOISE_DEFAULTS["iterations"], sigma_luminance: float = VARIANCE_DENOISE_DEFAULTS["sigma_luminance"],
+                         sigma_normal: float = VARIANCE_DENOISE_DEFAULTS["sigma_normal"], sigma_position: float = VARIANCE_DENOISE_DEFAULTS["sigma_position"]):
+        """ptx_denoise_variance: the filter on T with the colour weight in units of the pixel's own standard deviation, estimated from
+        the moments; the result is read with read_denoised(), V_0 with read_variance()."""
+        d = DenoiseDesc(1, iterations, sigma_luminance, sigma_normal, sigma_position, 0, 0)
+        self._check(self.lib.ptx_denoise_variance(self.handle, C.byref(d)))
+
+    def read_variance(self) -> np.ndarray:
+        """V_0 of the last denoise_variance(): H x W float32, 0 on pixels that are not valid."""
+        img = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self.lib.ptx_read_variance(self.handle, img.ctypes.data, img.nbytes))
+        return img
 
     def stats(self) -> Stats:
         s = Stats()

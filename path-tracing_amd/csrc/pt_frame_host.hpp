@@ -28,6 +28,8 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->denoisedIn = -1;
     r->temporalReady = false; // ... and so do T and the history
     r->temporalHistoryIn = -1;
+    r->momentsLive = false; // ... and the moments and V_0
+    r->varianceReady = false;
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     return resetAccumulation(r);
 }

@@ -4,8 +4,9 @@
 // order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp),
 // the render launches with the bounce schedule of the wavefront backend (pt_render_host.hpp), the frame's hand-over -- accumulation
 // image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the denoiser
-// (pt_denoise_host.hpp), the temporal accumulation ahead of it (pt_temporal_host.hpp).  Their functions take a valid or null handle;
-// include/ptx.h's entry points (ptx_capi.hip) are one-line wrappers around them.
+// (pt_denoise_host.hpp), the temporal accumulation ahead of it (pt_temporal_host.hpp), the variance-guided filter on its result
+// (pt_variance_host.hpp).  Their functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line
+// wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
@@ -29,6 +30,7 @@
 #include "pt_shard_layout.hpp"
 #include "pt_stream_plan.hpp"
 #include "pt_temporal.hpp"
+#include "pt_variance.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -417,6 +419,13 @@ struct PtxRenderer
     bool temporalReady = false;
     int temporalHistoryIn = -1;
     float temporalView[16] = {}, temporalProj[16] = {};
+    // variance-guided denoising (pt_variance_host.hpp): the two copies of the moment history, which ping-pong with temporalHistory
+    // (live: the last accepted accumulate call since ptx_resize was a moments call, so momentHistory[temporalHistoryIn] is current),
+    // and V_0 of the last ptx_denoise_variance
+    DevBuf<float4> momentHistory[2];
+    bool momentsLive = false;
+    DevBuf<float> varianceImage;
+    bool varianceReady = false;
 
     // wavefront state
     PathState paths;
@@ -898,6 +907,7 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
 #include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
 #include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
 #include "pt_temporal_host.hpp" // ptx_temporal_accumulate, ptx_denoise_temporal and the read-back of T
+#include "pt_variance_host.hpp" // ptx_temporal_accumulate_moments, ptx_denoise_variance and the read-backs of the moments and V_0
 
 static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
 {

@@ -1,6 +1,7 @@
 // pt_temporal.hpp -- temporal accumulation (docs/NEXT_ROWS.md section 14; semantics: include/ptx.h ptx_temporal_accumulate): the
 // history of the previous frames, found by projecting the position guide into the previous camera, blended with the current
-// frame's demodulated mean ahead of the filter.  One kernel, host side in pt_temporal_host.hpp:
+// frame's demodulated mean ahead of the filter.  One kernel, host side in pt_temporal_host.hpp; its per-pixel body, temporalPixel, is
+// also k_temporal_moments' (pt_variance.hpp), which carries the luminance moments along the same taps:
 //
 //   k_temporal<SAME_CAMERA>  one thread per pixel; reads the sum and the three guides of its pixel and up to four taps of the three
 //                            history images (one tap, at the pixel itself, when the camera did not move); writes T and the three
@@ -40,25 +41,36 @@ PT_DEV void temporalMul(const float *m, float x, float y, float z, float w, floa
     ow = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * w;
 }
 
-// One tap inside the image with the bilinear weight w: its share of the sums if it counts
-PT_DEV void temporalTap(const TemporalArgs &a, uint32_t q, float w, f3 nP, f3 xP, float planeBound, f3 &acc, float &lacc, float &wsum)
+// One tap inside the image with the bilinear weight w: its share of the sums if it counts, and whether it did
+PT_DEV bool temporalTap(const TemporalArgs &a, uint32_t q, float w, f3 nP, f3 xP, float planeBound, f3 &acc, float &lacc, float &wsum)
 {
     const float4 h = a.histIn[q];
     if (!(h.w > 0.0f) || !finite3_(F3(h.x, h.y, h.z)))
-        return;
+        return false;
     const float4 nq = a.histIn[(size_t)a.pixels + q];
     const float4 xq = a.histIn[2 * (size_t)a.pixels + q];
     const f3 dn = nP - F3(nq.x, nq.y, nq.z);
     const float plane = dot(nP, F3(xq.x, xq.y, xq.z) - xP);
     if (!(dot(dn, dn) <= a.normalThreshold2) || !(abs_(plane) <= planeBound)) // a NaN fails either
-        return;
+        return false;
     acc = acc + F3(h.x, h.y, h.z) * w;
     lacc = lacc + h.w * w;
     wsum = wsum + w;
+    return true;
 }
 
-template <bool SAME_CAMERA>
-__global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(TemporalArgs a)
+// What a kernel carries along the colour's taps: tap(q, w) after every tap that counted for the colour, then exactly one of
+// store(p, c) on a valid pixel (c: this frame's demodulated mean) and storeNotValid(p).  k_temporal carries nothing;
+// k_temporal_moments (pt_variance.hpp) the luminance moments.
+struct TemporalColourOnly
+{
+    PT_DEV void tap(uint32_t, float) {}
+    PT_DEV void store(uint32_t, f3) {}
+    PT_DEV void storeNotValid(uint32_t) {}
+};
+
+template <bool SAME_CAMERA, class Extra>
+PT_DEV void temporalPixel(const TemporalArgs &a, Extra &extra)
 {
     const int x = (int)(blockIdx.x * kDenoiseTileX + threadIdx.x), y = (int)(blockIdx.y * kDenoiseTileY + threadIdx.y);
     if (x >= (int)a.width || y >= (int)a.height)
@@ -75,6 +87,7 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(Tempo
         a.histOut[p] = zero; // L = 0: no tap of the next call
         a.histOut[(size_t)a.pixels + p] = zero;
         a.histOut[2 * (size_t)a.pixels + p] = zero;
+        extra.storeNotValid(p);
         return;
     }
     const f3 al = albedoFloor(a.albedo[p]);
@@ -88,7 +101,10 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(Tempo
         f3 acc = F3s(0.0f);
         float lacc = 0.0f, wsum = 0.0f;
         if (SAME_CAMERA)
-            temporalTap(a, p, 1.0f, nP, xP, planeBound, acc, lacc, wsum);
+        {
+            if (temporalTap(a, p, 1.0f, nP, xP, planeBound, acc, lacc, wsum))
+                extra.tap(p, 1.0f);
+        }
         else
         {
             float vx, vy, vz, vw, cx, cy, cz, cw;
@@ -118,7 +134,9 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(Tempo
                             if (qx < 0 || qx >= (int)a.width)
                                 continue;
                             const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
-                            temporalTap(a, (uint32_t)qy * a.width + (uint32_t)qx, w, nP, xP, planeBound, acc, lacc, wsum);
+                            const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
+                            if (temporalTap(a, q, w, nP, xP, planeBound, acc, lacc, wsum))
+                                extra.tap(q, w);
                         }
                     }
                 }
@@ -137,4 +155,12 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(Tempo
     a.histOut[p] = make_float4(cAcc.x, cAcc.y, cAcc.z, L);
     a.histOut[(size_t)a.pixels + p] = make_float4(nP.x, nP.y, nP.z, 0.0f);
     a.histOut[2 * (size_t)a.pixels + p] = xp;
+    extra.store(p, c);
+}
+
+template <bool SAME_CAMERA>
+__global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(TemporalArgs a)
+{
+    TemporalColourOnly none;
+    temporalPixel<SAME_CAMERA>(a, none);
 }

@@ -3,30 +3,37 @@
 // the filter, its read-back, and the filter on its result.
 #pragma once
 
-static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d)
+// `moments`: ptx_temporal_accumulate_moments (pt_variance_host.hpp) -- the same stage with k_temporal_moments, which carries the
+// moment history along; a plain call drops that history.
+static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool moments = false, const char *who = "ptx_temporal_accumulate")
 {
     if (!r || !d)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate: null argument");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
     const auto positive = [](float v) { return v > 0.0f && v <= 3.402823466e38f; }; // finite and above zero (a NaN fails both)
     if (d->totalSamples == 0u || !(d->maxHistory >= 1.0f) || !positive(d->maxHistory) || !positive(d->normalThreshold) || !positive(d->positionThreshold) ||
         (d->flags & ~(uint32_t)PTX_TEMPORAL_RESET) != 0u || d->reserved != 0u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate: need totalSamples > 0 (%u), maxHistory >= 1 (%g), normalThreshold > 0 (%g), "
-                    "positionThreshold > 0 (%g), all finite, flags 0 or PTX_TEMPORAL_RESET (0x%x) and reserved 0 (%u)", d->totalSamples, (double)d->maxHistory,
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need totalSamples > 0 (%u), maxHistory >= 1 (%g), normalThreshold > 0 (%g), "
+                    "positionThreshold > 0 (%g), all finite, flags 0 or PTX_TEMPORAL_RESET (0x%x) and reserved 0 (%u)", who, d->totalSamples, (double)d->maxHistory,
                     (double)d->normalThreshold, (double)d->positionThreshold, d->flags, d->reserved);
     if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: no accumulation image (call ptx_resize)");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
     if (r->frame.boundShard)
-        return frameIsElsewhere(r, "ptx_temporal_accumulate");
+        return frameIsElsewhere(r, who);
     if (!r->guidesReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: no guides for this extent (call ptx_render_guides)");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no guides for this extent (call ptx_render_guides)", who);
     if (r->frame.shard.worldSize > 1u)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_temporal_accumulate: this renderer holds one tile shard of %u; the history's taps cross tiles",
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; the history's taps cross tiles", who,
                     r->frame.shard.worldSize);
     HIP_TRY(r, hipSetDevice(r->device));
     const size_t n = r->frame.pixels();
     HIP_TRY(r, r->temporalImage.alloc(n));
     HIP_TRY(r, r->temporalHistory[0].alloc(n * kTemporalHistoryImages));
     HIP_TRY(r, r->temporalHistory[1].alloc(n * kTemporalHistoryImages));
+    if (moments)
+    {
+        HIP_TRY(r, r->momentHistory[0].alloc(n));
+        HIP_TRY(r, r->momentHistory[1].alloc(n));
+    }
     const bool useHistory = r->temporalHistoryIn >= 0 && !(d->flags & PTX_TEMPORAL_RESET);
     const int dst = r->temporalHistoryIn == 0 ? 1 : 0; // the history ping-pongs: a thread reads q while its neighbour writes it
     TemporalArgs a;
@@ -48,9 +55,17 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d)
     memcpy(a.proj, r->temporalProj, sizeof a.proj);
     const bool sameCamera = useHistory && !memcmp(d->View, r->temporalView, sizeof d->View) && !memcmp(d->Proj, r->temporalProj, sizeof d->Proj);
     const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->frame.width + kDenoiseTileX - 1) / kDenoiseTileX, (r->frame.height + kDenoiseTileY - 1) / kDenoiseTileY);
-    if (sameCamera) k_temporal<true><<<grid, block, 0, r->stream>>>(a);
+    if (moments)
+    {
+        // the moment history ping-pongs with the colour's; without a live one the moments restart on the colour history as it stands
+        const float4 *momentsIn = useHistory && r->momentsLive ? r->momentHistory[r->temporalHistoryIn].p : nullptr;
+        if (sameCamera) k_temporal_moments<true><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p);
+        else k_temporal_moments<false><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p);
+    }
+    else if (sameCamera) k_temporal<true><<<grid, block, 0, r->stream>>>(a);
     else k_temporal<false><<<grid, block, 0, r->stream>>>(a);
     HIP_TRY(r, hipGetLastError());
+    r->momentsLive = moments;
     r->temporalHistoryIn = dst;
     r->temporalReady = true;
     memcpy(r->temporalView, d->View, sizeof d->View);

@@ -1,8 +1,8 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
 // Renderer member it replaces in include/ptx.h; here each is ONE line (ptx_set_backend, ptx_synchronize and the trivial getters
 // apart) that calls the implementation in pt_runtime.hpp or one of the host files it includes (pt_scene_host.hpp, pt_bvh_host.hpp,
-// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp, pt_temporal_host.hpp); device side:
-// pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
+// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp, pt_temporal_host.hpp, pt_variance_host.hpp);
+// device side: pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
 extern "C" {
@@ -278,6 +278,26 @@ void *ptx_device_temporal_ptr(PtxRenderer *r)
 int ptx_denoise_temporal(PtxRenderer *r, const PtxDenoiseDesc *desc)
 {
     return denoiseTemporal(r, desc);
+}
+
+int ptx_temporal_accumulate_moments(PtxRenderer *r, const PtxTemporalDesc *desc)
+{
+    return temporalAccumulate(r, desc, true, "ptx_temporal_accumulate_moments");
+}
+
+int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readMoments(r, host, bytes);
+}
+
+int ptx_denoise_variance(PtxRenderer *r, const PtxDenoiseDesc *desc)
+{
+    return denoiseVariance(r, desc);
+}
+
+int ptx_read_variance(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readVariance(r, host, bytes);
 }
 
 int ptx_write_accumulation(PtxRenderer *r, const float *rgba, size_t bytes)

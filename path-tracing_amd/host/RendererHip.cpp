@@ -162,9 +162,17 @@ void RendererHip::SetSettings(const TemporalSettings &settings)
     s_TemporalSettings = settings;
 }
 
+static RendererHip::VarianceSettings s_VarianceSettings;
+
+void RendererHip::SetSettings(const VarianceSettings &settings)
+{
+    s_VarianceSettings = settings;
+}
+
 // The post-processing chain on the current frame: on the running sum, or -- with the denoiser enabled and the path-tracing pipeline
 // bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser"); with the temporal accumulation enabled as well
-// the filter runs on its result (ptx.h, "Temporal accumulation").
+// the filter runs on its result (ptx.h, "Temporal accumulation"), and with the variance settings enabled on top the moments are
+// accumulated beside it and the variance-guided filter takes the fixed-sigma one's place (ptx.h, "Variance-guided denoising").
 static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode)
 {
     if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
@@ -182,10 +190,17 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         const Camera &camera = s_Scene->GetActiveCamera(); // FillRaygenUniform brought it to the extent
         ToColumnMajor(camera.GetViewMatrix(), temporal.View);
         ToColumnMajor(camera.GetProjectionMatrix(), temporal.Proj);
-        if (const int rc = ptx_temporal_accumulate(s_Renderer, &temporal))
+        if (const int rc = s_VarianceSettings.Enabled ? ptx_temporal_accumulate_moments(s_Renderer, &temporal) : ptx_temporal_accumulate(s_Renderer, &temporal))
             return rc;
         s_AccumulationRestarted = false;
-        if (const int rc = ptx_denoise_temporal(s_Renderer, &desc))
+        if (s_VarianceSettings.Enabled)
+        {
+            const PtxDenoiseDesc variance = { 1u, s_VarianceSettings.Iterations, s_VarianceSettings.SigmaLuminance, s_DenoiserSettings.SigmaNormal,
+                                              s_DenoiserSettings.SigmaPosition, 0u, 0u };
+            if (const int rc = ptx_denoise_variance(s_Renderer, &variance))
+                return rc;
+        }
+        else if (const int rc = ptx_denoise_temporal(s_Renderer, &desc))
             return rc;
         return ptx_postprocess_denoised(s_Renderer, &u, mode);
     }

@@ -80,6 +80,17 @@ public:
         float PositionThreshold = 0.03f;
     };
     static void SetSettings(const TemporalSettings &settings);
+    // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
+    // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
+    // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either
+    // of the two: everything does exactly what it did without it.  The defaults are the measured ones of docs/NEXT_ROWS.md section 16.
+    struct VarianceSettings
+    {
+        bool Enabled = false;
+        float SigmaLuminance = 0.75f;
+        uint32_t Iterations = 3;
+    };
+    static void SetSettings(const VarianceSettings &settings);
     // RecordPostProcessCommands + RecordSaveOutputCommands on the current running sum, then OutputSaver::WriteImage
     static void SaveOutput(const OutputInfo &info);
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Times the calls between ptx_render and the window (docs/NEXT_ROWS.md sections 12, 13 and 14): ptx_postprocess, ptx_present,
-ptx_render_guides, ptx_temporal_accumulate (both variants), ptx_denoise and ptx_postprocess_denoised at 1920 x 1080 and
-3840 x 2160, beside one 8-spp step of chess_like.
+"""Times the calls between ptx_render and the window (docs/NEXT_ROWS.md sections 12, 13, 14 and 16): ptx_postprocess, ptx_present,
+ptx_render_guides, ptx_temporal_accumulate and ptx_temporal_accumulate_moments (both variants each), ptx_denoise, ptx_denoise_temporal,
+ptx_denoise_variance and ptx_postprocess_denoised at 1920 x 1080 and 3840 x 2160, beside one 8-spp step of chess_like.
 
 Every figure is a device-synchronised wall-clock time: synchronise, enqueue the call `repeat` times, synchronise; `repeat` is chosen
 per shape so that a window lasts about five milliseconds, every shape is warmed up first, and the figure is the median of 20
@@ -9,6 +9,9 @@ windows divided by `repeat`.  ptx_denoise is also given as a rate against its al
 (16 B in, 16 B out, 48 B of guides) -- a rate, not a measured bandwidth: the 25 taps are served by the caches.
 ptx_temporal_accumulate likewise against 176 bytes per pixel (64 B of sum and guides and 48 B of history in, T and 48 B of history
 out); its projected variant is called with two cameras a fraction of a pixel apart in turn, so that every call gathers four taps.
+ptx_temporal_accumulate_moments adds 16 B of moment history in and out: 208 bytes per pixel.  ptx_denoise_variance is timed on a
+history at its cap (every pixel takes mu2 - mu1^2) and, as `_restarted`, right after a PTX_TEMPORAL_RESET (every valid pixel takes
+the 7 x 7 window); ptx_denoise_temporal at the same iteration counts stands beside it.
 
 Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D]"""
 import json
@@ -28,6 +31,7 @@ WINDOWS, WINDOW_MS, STEP_SPP, STEP_DEPTH = 20, 5.0, 8, 8
 POST = dict(exposure=1.0, bloom_threshold=0.8, bloom_intensity=0.35)
 DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
 TEMPORAL_BYTES_PER_PIXEL = 176
+MOMENTS_BYTES_PER_PIXEL = 208
 
 
 def timed(r, call):
@@ -84,6 +88,20 @@ def main():
             t = timed(r, lambda: accumulate(moving))
             t["algorithmic_GB_per_s"] = w * h * TEMPORAL_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
             rec[key] = t
+
+        def accumulate_moments(moving):
+            calls[0] += 1
+            r.temporal_accumulate_moments(STEP_SPP, *cams[calls[0] % 2 if moving else 0])
+        for key, moving in (("temporal_accumulate_moments_projected", True), ("temporal_accumulate_moments_same_camera", False)):
+            t = timed(r, lambda: accumulate_moments(moving))
+            t["algorithmic_GB_per_s"] = w * h * MOMENTS_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
+            rec[key] = t
+        for it in (1, 3, 5):  # the history stands at its cap after the windows above
+            rec[f"denoise_temporal_{it}_iterations"] = timed(r, lambda: r.denoise_temporal(iterations=it))
+            rec[f"denoise_variance_{it}_iterations"] = timed(r, lambda: r.denoise_variance(iterations=it))
+        r.temporal_accumulate_moments(STEP_SPP, *cams[0], flags=pkg.TEMPORAL_RESET)
+        for it in (1, 3, 5):
+            rec[f"denoise_variance_{it}_iterations_restarted"] = timed(r, lambda: r.denoise_variance(iterations=it))
         for it in (1, 3, 5):
             t = timed(r, lambda: r.denoise(STEP_SPP, iterations=it))
             t["algorithmic_GB_per_s"] = w * h * DENOISE_BYTES_PER_PIXEL_AND_PASS * it / (t["median_ms"] * 1e-3) / 1e9

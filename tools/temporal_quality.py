@@ -5,7 +5,9 @@ first-hit guides from tests/debug_view_ref.py, the accumulation of tests/tempora
 last frame is compared with a 192-spp render at its pose.
 
     python tools/temporal_quality.py            the relative L2 error of the last frame: raw, spatial filter, temporal, both
-    python tools/temporal_quality.py --sweep    the chained filter over maxHistory x iterations x sigmaColor, best geometric mean first
+    python tools/temporal_quality.py --sweep    the chained filter over maxHistory x iterations x sigmaColor, best geometric mean first,
+                                                then the variance-guided filter (section 16, tests/variance_ref.py) over iterations x
+                                                sigmaLuminance at 8, 4, 2 and 1 frames of history
     python tools/temporal_quality.py --write    (re)writes tests/golden/temporal_truth.npz, the 192-spp means as binary16
 
 tests/test_temporal.py's quality test reads that file and recomputes the sequence; the file holds the two scenes that test uses
@@ -26,6 +28,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 import __graft_entry__ as graft  # noqa: E402
 import denoise_ref as R  # noqa: E402
 import temporal_ref as TR  # noqa: E402
+import variance_ref as VR  # noqa: E402
 
 SCENES = ("default", "texture_test", "alpha_test")
 GOLDEN_SCENES = ("default", "texture_test")
@@ -39,6 +42,23 @@ def temporal(frames, max_history, t):
 
 def filtered(image, frame, samples, p):
     return R.denoise(image, frame[1], frame[2], frame[3], samples, p["iterations"], p["sigma_color"], p["sigma_normal"], p["sigma_position"], np.float32)
+
+
+HISTORIES = (8, 4, 2, 1)  # frames of history: the last k frames of the sequence, so the pose and the truth stay
+VARIANCE_ITERATIONS, VARIANCE_SIGMAS = (2, 3, 4, 5), (0.35, 0.5, 0.75, 1.0, 1.5, 2.0)
+
+
+def moments(frames, t):
+    """(T, moments, V_0) of the last frame after ptx_temporal_accumulate_moments over `frames`"""
+    Ts, Ms, _ = VR.run_sequence(frames, t["max_history"], t["normal_threshold"], t["position_threshold"], np.float32)
+    last = frames[-1]
+    return Ts[-1], Ms[-1], VR.estimate(Ts[-1], last[1], last[2], last[3], Ms[-1], 0.3, 0.03, np.float32)[0]
+
+
+def variance_guided(T, V0, frame, p, iterations=None):
+    """D per iteration count up to p['iterations'] (or `iterations`)"""
+    return VR.filter_all(T, frame[1], frame[2], frame[3], V0, iterations or p["iterations"], p["sigma_luminance"], p["sigma_normal"], p["sigma_position"],
+                         np.float32)[0]
 
 
 def main():
@@ -62,7 +82,7 @@ def main():
         print(f"wrote {TRUTH} ({os.path.getsize(TRUTH)} bytes)")
     truth.update(np.load(TRUTH).items())
     truth = {k: v.astype(np.float32) for k, v in truth.items()}
-    td, dd, cd = pkg.TEMPORAL_DEFAULTS, pkg.DENOISE_DEFAULTS, pkg.TEMPORAL_DENOISE_DEFAULTS
+    td, dd, cd, vd = pkg.TEMPORAL_DEFAULTS, pkg.DENOISE_DEFAULTS, pkg.TEMPORAL_DENOISE_DEFAULTS, pkg.VARIANCE_DENOISE_DEFAULTS
     if not args.sweep:
         print(f"{TR.QUALITY_W} x {TR.QUALITY_H}, {TR.QUALITY_FRAMES} frames of {TR.QUALITY_SPP} spp against {TR.QUALITY_TRUTH_SPP} spp at the last pose")
         print(f"temporal {td}\nspatial alone {dd}\nchained {cd}")
@@ -75,6 +95,15 @@ def main():
                  R.relative_l2(T, truth[name]), R.relative_l2(filtered(T, last, 1, cd), truth[name]), R.relative_l2(filtered(T, last, 1, dd), truth[name])]
             print(f"  {name:14s}({TR.QUALITY_STEPS[name]:4.2f})  {e[0]:.4f}  {e[1]:.4f}   {e[2]:.4f}    {e[3]:.4f}   {e[4]:.4f}"
                   f"                            {T[..., 3][valid].mean():.2f}     {100.0 * (T[..., 3][valid] == 1).mean():.2f} %")
+        print(f"variance-guided {vd}\nscene           frames of history   temporal  chained  variance-guided   pixels on the 7 x 7 window")
+        for name in SCENES:
+            for k in HISTORIES:
+                frames = seqs[name][-k:]
+                T, M, V0 = moments(frames, td)
+                e = [R.relative_l2(T, truth[name]), R.relative_l2(filtered(T, frames[-1], 1, cd), truth[name]),
+                     R.relative_l2(variance_guided(T, V0, frames[-1], vd)[-1], truth[name])]
+                valid = R.valid_mask(T, frames[-1][1], frames[-1][2], 1, np.float32)
+                print(f"  {name:14s}  {k}                 {e[0]:.4f}    {e[1]:.4f}   {e[2]:.4f}            {100.0 * (M.L[valid] < VR.LONG_HISTORY).mean():.1f} %")
         return
     rows = []
     for mh in (8.0, 16.0, 32.0, 64.0):
@@ -87,6 +116,19 @@ def main():
     print("geometric mean  maxHistory  iterations  sigmaColor   " + "  ".join(SCENES))
     for score, mh, it, sc, e in rows:
         print(f"{score:.4f}          {mh:4.0f}        {it}           {sc:4.2f}         " + "  ".join(f"{v:.4f}" for v in e))
+    for k in HISTORIES:
+        rows = []
+        est = {n: moments(seqs[n][-k:], td) for n in SCENES}
+        for sl in VARIANCE_SIGMAS:
+            p = dict(sigma_luminance=sl, sigma_normal=vd["sigma_normal"], sigma_position=vd["sigma_position"])
+            D = {n: variance_guided(est[n][0], est[n][2], seqs[n][-1], p, max(VARIANCE_ITERATIONS)) for n in SCENES}
+            for it in VARIANCE_ITERATIONS:
+                e = [R.relative_l2(D[n][it - 1], truth[n]) for n in SCENES]
+                rows.append((float(np.exp(np.mean(np.log(e)))), it, sl, e))
+        rows.sort(key=lambda r: r[0])
+        print(f"variance-guided, {k} frames of history\ngeometric mean  iterations  sigmaLuminance   " + "  ".join(SCENES))
+        for score, it, sl, e in rows:
+            print(f"{score:.4f}          {it}           {sl:4.2f}             " + "  ".join(f"{v:.4f}" for v in e))
 
 
 if __name__ == "__main__":
