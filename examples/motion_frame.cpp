@@ -1,0 +1,100 @@
+// motion_frame.cpp -- two frames of an animated scene through RendererHip with TemporalSettings::MotionVectors on (ptx.h "Motion
+// guides", docs/NEXT_ROWS.md section 17), dumped raw so that a test can hold them against the same ptx_* calls made by hand
+// (tests/test_motion.py).  RendererHip has no animation path of its own: the pose is moved with ptx_update_animation on its handle,
+// as a host with animated scenes does today.
+//
+//   g++ -std=c++20 -O2 examples/motion_frame.cpp path-tracing_amd/host/{Scene,Camera,ExampleScenes,OutputSaver,TextureImporter,JpegDecoder,SceneImporter,SceneDescription,FbxReader,ObjReader,RendererHip}.cpp \
+//       -Ipath-tracing_amd/host -Lpath-tracing_amd -lptx_hip -Wl,-rpath,'$ORIGIN/../path-tracing_amd' -o examples/motion_frame
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin     (scene, extent, spp, depth, time step, variance 0 / 1, file)
+//
+// The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
+// height x 16 bytes.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ExampleScenes.h"
+#include "RendererHip.h"
+
+using namespace PathTracing;
+
+static void Check(int status, const char *what)
+{
+    if (status != PTX_OK)
+        throw error(std::string(what) + ": " + ptx_last_error(RendererHip::GetHandle()));
+}
+
+int main(int argc, char **argv)
+{
+    if (argc != 9)
+    {
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin\n");
+        return 1;
+    }
+    const std::string name = argv[1];
+    const uint32_t width = std::atoi(argv[2]), height = std::atoi(argv[3]), spp = std::atoi(argv[4]), bounces = std::atoi(argv[5]);
+    const float timeStep = static_cast<float>(std::atof(argv[6]));
+    const bool useVariance = std::atoi(argv[7]) != 0;
+    setenv("GPU_MAX_HW_QUEUES", "16", 0);
+    try
+    {
+        std::shared_ptr<Scene> scene = ExampleScenes::CreateScene(name, 0.25f, 0, 0u);
+        RendererHip::Init(0);
+        // the settings first: the upload below turns the scene's tracking off, and UpdateSceneData has to turn it on again
+        RendererHip::DenoiserSettings denoiser;
+        denoiser.Enabled = true;
+        RendererHip::TemporalSettings temporal;
+        temporal.Enabled = temporal.MotionVectors = true;
+        RendererHip::VarianceSettings variance;
+        variance.Enabled = useVariance;
+        RendererHip::SetSettings(denoiser);
+        RendererHip::SetSettings(temporal);
+        RendererHip::SetSettings(variance);
+        scene->Update(0.0f);
+        RendererHip::UpdateSceneData(scene, true);
+        RendererHip::OnResize(width, height);
+        RendererHip::PathTracingSettings settings;
+        settings.BounceCount = bounces;
+        RendererHip::SetSettings(settings);
+        const size_t bytes = static_cast<size_t>(width) * height * 16;
+        std::vector<char> file(6 * bytes);
+        const std::string scratch = std::string(argv[8]) + ".png";
+        for (int frame = 0; frame < 2; frame++)
+        {
+            // every frame is posed explicitly, the first one as Scene::Update(0) left it (the uploaded description is the bind pose)
+            {
+                if (frame)
+                    scene->Update(timeStep);
+                const auto instances = scene->GetModelInstances();
+                const auto bones = scene->GetBoneTransforms();
+                std::vector<PtxTransform> it(instances.size());
+                for (size_t i = 0; i < instances.size(); i++)
+                    std::memcpy(it[i].m, &instances[i].Transform.m[0][0], sizeof(float) * 12);
+                Check(ptx_update_animation(RendererHip::GetHandle(), it.data(), static_cast<uint32_t>(it.size()), bones.empty() ? nullptr : bones.data(),
+                                           static_cast<uint32_t>(bones.size()), PTX_ACCEL_REFIT), "ptx_update_animation");
+                RendererHip::UpdateSceneData(scene, true); // the same scene, moved: the accumulation restarts, the history stays
+            }
+            for (uint32_t i = 0; i < spp; i++)
+                RendererHip::Render();
+            const std::vector<float> sum = RendererHip::ReadAccumulationImage();
+            std::memcpy(&file[(3 * frame) * bytes], sum.data(), bytes);
+            RendererHip::SaveOutput({ scratch, { width, height }, 0, OutputFormat::Png });
+            Check(ptx_read_temporal(RendererHip::GetHandle(), &file[(3 * frame + 1) * bytes], bytes), "ptx_read_temporal");
+            Check(ptx_read_output(RendererHip::GetHandle(), PTX_OUTPUT_RGBA32F, &file[(3 * frame + 2) * bytes], bytes), "ptx_read_output");
+        }
+        FILE *f = std::fopen(argv[8], "wb");
+        if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size())
+            throw error(std::string("cannot write ") + argv[8]);
+        std::fclose(f);
+        std::printf("scene %s %ux%u %u spp depth %u, two frames %g apart -> %s\n", name.c_str(), width, height, spp, bounces, (double)timeStep, argv[8]);
+        RendererHip::Shutdown();
+    }
+    catch (const std::exception &e)
+    {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

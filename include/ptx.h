@@ -992,6 +992,73 @@ PTX_API int ptx_denoise_variance(PtxRenderer *r, const PtxDenoiseDesc *desc);
  * PTX_ERROR_INVALID_ARGUMENT: a buffer of another size; PTX_ERROR_NOT_READY: no ptx_denoise_variance since the last ptx_resize. */
 PTX_API int ptx_read_variance(PtxRenderer *r, void *host, size_t bytes);
 
+/* ------------------------------------------------------------------------- */
+/* Motion guides (docs/NEXT_ROWS.md section 17): where every first hit was in  */
+/* the pose the temporal history was made from, so that animated geometry      */
+/* keeps its history.  An addition: a host that never calls ptx_track_motion   */
+/* pays nothing, and every call above computes what it computed before.        */
+/* ------------------------------------------------------------------------- */
+
+enum {
+    PTX_MOTION_POSITION = 0, /* X_prev: (Position_prev, 1) known, (x_p, 0) unknown, (0, 0, 0, 0) miss */
+    PTX_MOTION_NORMAL = 1,   /* N_prev: (Normal_prev, 1) known,   (n_p, 0) unknown, (0, 0, 0, 0) miss */
+    PTX_MOTION_COUNT = 2
+};
+
+/* POSE BOOKKEEPING, kept with the scene, so the borrowers of a shared scene see it.  The POSE SERIAL S counts the accepted
+ * ptx_update_animation calls, tracking or not.  Every guide pass (ptx_render_guides, ptx_render_guides_motion) records the serial
+ * it rendered at; every accepted accumulate call (plain, moments or motion) tags its history with the serial of the guides it
+ * consumed.  While tracking is on, ptx_update_animation first SNAPSHOTS the pose it is about to replace: the device pair-transform
+ * table and the skinned part of the vertex buffer (whole PtxVertex records), device to device on the render stream ahead of its
+ * uploads and the skinning; the snapshot is valid for serial S - 1.  The buffers come with the first such update (the table plus
+ * 56 bytes per skinned vertex); turning tracking off releases them; with tracking off the update enqueues exactly what it always
+ * did.  ptx_scene_upload and its streamed form reset everything: tracking off, no snapshot, and a serial no earlier history
+ * leads back to.
+ * Owner only: PTX_ERROR_INVALID_ARGUMENT on a renderer that borrows its scene (like ptx_update_animation), PTX_ERROR_NOT_READY
+ * without a scene. */
+PTX_API int ptx_track_motion(PtxRenderer *r, int enable);
+
+/* ptx_render_guides plus two more RGBA32F images from the same single traversal.  The three guides it stores are those of
+ * ptx_render_guides bit for bit.  Let h be the pose serial of this renderer's current temporal history and S the scene's:
+ *     h == S                                  the previous pose is the current one;
+ *     h == S - 1 and the snapshot is valid    the previous pose is the snapshot;
+ *     anything else (no history, several updates since, tracking enabled after the update)   the motion is UNKNOWN.
+ * At a pixel whose primary ray hit (pair, prim) with the barycentrics b = (1 - u - v, u, v), with a known previous pose:
+ *   1. the triangle's three vertices of the previous pose are vertices[pair.vertexOffset + indices[pair.indexOffset + 3 prim + k]],
+ *      k = 0, 1, 2 -- a vertex from the snapshot when its index lies in the skinned block, from the vertex buffer otherwise;
+ *   2. Position, Normal, Tangent and Bitangent are interpolated as (a b.x + b b.y) + c b.z;
+ *   3. the previous pose's pair transform is applied as the guide pass applies the current one: the position by the 3 x 4 matrix,
+ *      tangent and bitangent by its linear part and normalised, the normal by the inverse transpose and normalised;
+ *   4. X_prev = (Position_prev, 1) and N_prev = (normalize(Normal_prev + TBN_prev material.Normal), 1), where material.Normal is
+ *      the tangent-space normal the guide pass sampled at this hit (of the CURRENT frame; it is not sampled again).
+ * Unknown motion stores (x_p, 0) and (n_p, 0), the position and normal guides with w = 0; a miss stores zeros.  Where neither the
+ * pair's transform nor the triangle's vertices changed, X_prev.xyz and N_prev.xyz equal the guides bit for bit (the same
+ * operations on the same operands).  The previous pose is found through (pair, prim), never through the triangle's place in the
+ * tree: the result does not depend on PTX_ACCEL_REFIT versus PTX_ACCEL_REBUILD.
+ * Refusals as ptx_render_guides', and PTX_ERROR_NOT_READY while the scene's owner does not track motion.  Works on a borrower and
+ * with pending streamed textures.  ptx_resize drops the motion images; a later plain ptx_render_guides makes them stale.  Known
+ * limits: two updates between temporal frames make the motion unknown; first hit only; a moving light still lags; several
+ * borrowers at different histories share the one snapshot, which the serial rule keeps correct, not optimal. */
+PTX_API int ptx_render_guides_motion(PtxRenderer *r, const PtxRaygenUniformData *uniform);
+/* One motion image, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_INVALID_ARGUMENT: an unknown image or a buffer
+ * of another size; PTX_ERROR_NOT_READY: the last guide pass since ptx_resize was not ptx_render_guides_motion. */
+PTX_API int ptx_read_motion(PtxRenderer *r, uint32_t which, void *host, size_t bytes);
+/* ... or its device address (NULL without one). */
+PTX_API void *ptx_device_motion_ptr(PtxRenderer *r, uint32_t which);
+
+/* ptx_temporal_accumulate (withMoments = 0) or ptx_temporal_accumulate_moments (withMoments = 1) with steps 1 and 2 of
+ * ptx_temporal_accumulate run on (x~, n~) = (X_prev.xyz, N_prev.xyz) of the last ptx_render_guides_motion in place of (x_p, n_p):
+ * x~ is projected, and a tap q counts only if |n~ - N'(q)|^2 <= normalThreshold^2 and |dot(n~, X'(q) - x~)| <= positionThreshold t_p
+ * (the other conditions as they were).  SAME-CAMERA RULE: one tap of weight 1 at p itself requires equal matrices AND x~ bit-equal to
+ * x_p; under equal matrices a pixel whose x~ differs is projected through them like any other.  A pixel whose motion is unknown
+ * takes no history: c_acc = c(p), L = 1 (and M = mu, L_M = 1).  Everything else is the plain call's: the blend, what is stored for
+ * the next call (the CURRENT n_p and (x_p, t_p)), the moments' taps, the treatment of pixels that are not valid, the refusals.
+ * Consequence: after a ptx_render_guides_motion with no update since the history's pose, the call is the plain one bit for bit.
+ * PTX_ERROR_INVALID_ARGUMENT: withMoments above 1.  PTX_ERROR_NOT_READY: the motion guides are stale -- a plain ptx_render_guides
+ * came after them, or an accumulate call moved the history to another pose.  ptx_denoise_temporal, ptx_denoise_variance and the
+ * output stage follow unchanged. */
+PTX_API int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, uint32_t withMoments);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

@@ -67,6 +67,7 @@ PTX_SYMBOLS = [
     "ptx_postprocess_denoised",
     "ptx_temporal_accumulate", "ptx_read_temporal", "ptx_device_temporal_ptr", "ptx_denoise_temporal",
     "ptx_temporal_accumulate_moments", "ptx_read_moments", "ptx_denoise_variance", "ptx_read_variance",
+    "ptx_track_motion", "ptx_render_guides_motion", "ptx_read_motion", "ptx_device_motion_ptr", "ptx_temporal_accumulate_motion",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -172,6 +173,7 @@ class DenoiseDesc(C.Structure):
 
 
 GUIDE_NORMAL, GUIDE_POSITION, GUIDE_ALBEDO = range(3)  # PTX_GUIDE_* of include/ptx.h
+MOTION_POSITION, MOTION_NORMAL = range(2)  # PTX_MOTION_* of include/ptx.h
 # The defaults of Renderer.denoise, chosen on 4-spp frames of three scenes against 512 spp (docs/NEXT_ROWS.md section 13)
 DENOISE_DEFAULTS = dict(iterations=3, sigma_color=1.5, sigma_normal=0.3, sigma_position=0.03)
 
@@ -411,6 +413,12 @@ def load_hip() -> C.CDLL:
         lib.ptx_read_moments.argtypes = [P, P, C.c_size_t]
         lib.ptx_denoise_variance.argtypes = [P, C.POINTER(DenoiseDesc)]
         lib.ptx_read_variance.argtypes = [P, P, C.c_size_t]
+        lib.ptx_track_motion.argtypes = [P, C.c_int]
+        lib.ptx_render_guides_motion.argtypes = [P, C.POINTER(RaygenUniformData)]
+        lib.ptx_read_motion.argtypes = [P, C.c_uint32, P, C.c_size_t]
+        lib.ptx_device_motion_ptr.argtypes = [P, C.c_uint32]
+        lib.ptx_device_motion_ptr.restype = P
+        lib.ptx_temporal_accumulate_motion.argtypes = [P, C.POINTER(TemporalDesc), C.c_uint32]
         _hip = lib
     return _hip
 
@@ -788,6 +796,32 @@ class Renderer:
         img = np.empty((self.height, self.width), dtype=np.float32)
         self._check(self.lib.ptx_read_variance(self.handle, img.ctypes.data, img.nbytes))
         return img
+
+    def track_motion(self, enable: bool = True):
+        """ptx_track_motion: update_animation() keeps the pose it replaces, for render_guides_motion().  Owner only."""
+        self._check(self.lib.ptx_track_motion(self.handle, 1 if enable else 0))
+
+    def render_guides_motion(self, uniform: RaygenUniformData):
+        """ptx_render_guides_motion: render_guides() plus where every hit was, and which way its normal pointed, in the pose the
+        temporal history was made from."""
+        self._check(self.lib.ptx_render_guides_motion(self.handle, C.byref(uniform)))
+
+    def read_motion(self, which: int) -> np.ndarray:
+        """One motion image (MOTION_POSITION / MOTION_NORMAL), H x W x 4 float32; w = 1: known, 0: unknown (xyz = the guide) or a miss."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.lib.ptx_read_motion(self.handle, which, img.ctypes.data, img.nbytes))
+        return img
+
+    def motion_ptr(self, which: int) -> int:
+        return int(self.lib.ptx_device_motion_ptr(self.handle, which) or 0)
+
+    def temporal_accumulate_motion(self, total_samples: int, view, proj, max_history: float = TEMPORAL_DEFAULTS["max_history"],
+                                   normal_threshold: float = TEMPORAL_DEFAULTS["normal_threshold"],
+                                   position_threshold: float = TEMPORAL_DEFAULTS["position_threshold"], flags: int = 0, moments: bool = False):
+        """ptx_temporal_accumulate_motion: temporal_accumulate() (moments: temporal_accumulate_moments()) that looks the history up
+        through the motion guides of render_guides_motion(), so that animated geometry keeps it."""
+        d = self._temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags)
+        self._check(self.lib.ptx_temporal_accumulate_motion(self.handle, C.byref(d), int(moments)))
 
     def stats(self) -> Stats:
         s = Stats()

@@ -2,7 +2,9 @@
 // DESIGN.md section 9 names this exception).  Two kernels, host side in pt_denoise_host.hpp:
 //
 //   k_render_guides  one primary ray through the centre of every owned pixel, exactly the debug view's (debugViewBody,
-//                    pt_debug_view.hpp), storing the first hit's shading normal, world position + hit distance and base colour
+//                    pt_debug_view.hpp), storing the first hit's shading normal, world position + hit distance and base colour;
+//                    <MODE, true> (ptx_render_guides_motion, docs/NEXT_ROWS.md section 17) also where the hit was, and which way its
+//                    normal pointed, in the pose the temporal history was made from
 //   k_denoise        one iteration of the edge-avoiding a-trous filter (a 5 x 5 B3-spline stencil dilated by `step`) over the
 //                    demodulated mean, guided by those three images; the first launch demodulates, the last remodulates
 //
@@ -14,12 +16,61 @@
 
 // ---- the guide pass ----------------------------------------------------------------------------------------
 
+// What k_render_guides<MODE, true> gets beside the scene: the pose the renderer's temporal history was made from, and the two images
+// it writes.  A kernel argument of its own -- SceneView and TraceScene do not grow for a pass most launches never run.
+struct PrevPose
+{
+    const DevPair *pairs;      // the DevPair table of that pose: the scene's own, or the snapshot ptx_update_animation kept
+    const PtxVertex *skinned;  // vertices[firstSkinned ...] of that pose; nullptr: the vertex buffer itself holds them
+    uint32_t firstSkinned;     // the first index of the vertex buffer that k_skin writes
+    uint32_t known;            // 0: the pose is not known; the images hold (x_p, 0) and (n_p, 0) on hits
+    float4 *position, *normal; // PTX_MOTION_POSITION, PTX_MOTION_NORMAL
+};
+
+// The hit's surface point and shading normal in the previous pose.  The triangle is found through (pair, prim), never through the
+// slot: a rebuild between the two poses reorders slots.  Vertices as writeShadeTri fetches them, then renderGuidesBody's own
+// expressions in its order -- where neither the pair's transform nor its vertices changed, the same operations on the same bits.
+PT_DEV void motionGuides(const SceneView &sv, const PrevPose &prev, const Hit &h, f3 bary, f3 materialNormal, float4 gp, float4 gn, float4 &mx,
+                         float4 &mn)
+{
+    if (!prev.known)
+    {
+        mx = make_float4(gp.x, gp.y, gp.z, 0.0f);
+        mn = make_float4(gn.x, gn.y, gn.z, 0.0f);
+        return;
+    }
+    const DevPair pr = prev.pairs[h.pair];
+    Vtx o[3];
+    for (int k = 0; k < 3; k++)
+    {
+        const uint32_t vi = pr.vertexOffset + sv.indices[pr.indexOffset + h.prim * 3 + k];
+        o[k] = loadVertex(prev.skinned && vi >= prev.firstSkinned ? &prev.skinned[vi - prev.firstSkinned] : &sv.vertices[vi]);
+    }
+    Vtx ov;
+    ov.Position = interp3(o[0].Position, o[1].Position, o[2].Position, bary);
+    ov.Normal = interp3(o[0].Normal, o[1].Normal, o[2].Normal, bary);
+    ov.Tangent = interp3(o[0].Tangent, o[1].Tangent, o[2].Tangent, bary);
+    ov.Bitangent = interp3(o[0].Bitangent, o[1].Bitangent, o[2].Bitangent, bary);
+    const Vtx vertex = transformVertex(pr, ov);
+    mat3 TBN;
+    TBN.c0 = vertex.Tangent;
+    TBN.c1 = vertex.Bitangent;
+    TBN.c2 = vertex.Normal;
+    const f3 N = normalize(vertex.Normal + mul(TBN, materialNormal));
+    mx = make_float4(vertex.Position.x, vertex.Position.y, vertex.Position.z, 1.0f);
+    mn = make_float4(N.x, N.y, N.z, 1.0f);
+}
+
 // debugRaygen.rgen:22-40 + debugClosestHit.rchit:164-202 without flags: the values of the debug view's Normal and WorldPosition
 // modes and the material's colour after the decal mix, from ONE traversal.  Every expression is the debug view's, in its order:
 // the normal and position images are the same bits as ptx_render_debug's.
-template <int MODE>
+//
+// MOTION (ptx_render_guides_motion, docs/NEXT_ROWS.md section 17): two more images from the same traversal -- where the hit's
+// surface point was and which way its normal pointed in the pose `prev` describes (motionGuides above).
+template <int MODE, bool MOTION = false>
 PT_DEV void renderGuidesBody(const LaunchParams &p, const SceneView &sv, const TraceScene &sc, float4 *__restrict__ gNormal,
-                             float4 *__restrict__ gPosition, float4 *__restrict__ gAlbedo, uint32_t *__restrict__ counters, uint32_t *spill)
+                             float4 *__restrict__ gPosition, float4 *__restrict__ gAlbedo, uint32_t *__restrict__ counters, uint32_t *spill,
+                             const PrevPose *prev = nullptr)
 {
     constexpr bool TEX = MODE >= 1, ALPHA = MODE == 2;
     PT_DECLARE_STACK(st, PT_TAIL_LDS, spill)
@@ -36,6 +87,7 @@ PT_DEV void renderGuidesBody(const LaunchParams &p, const SceneView &sv, const T
         nPix++;
         const bool hit = traceRay<false, false, ALPHA>(sc, ro, rd, 0.00001f, 10000.0f, st, h, nullptr, nullptr, ALPHA ? &decal : nullptr);
         float4 gn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), gp = gn, ga = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        float4 mx = gn, mn = gn; // MOTION: a miss stores zeros
         if (hit)
         {
             const f3 bary = F3(1.0f - h.u - h.v, h.u, h.v);
@@ -70,10 +122,17 @@ PT_DEV void renderGuidesBody(const LaunchParams &p, const SceneView &sv, const T
             gn = make_float4(N.x, N.y, N.z, 1.0f);
             gp = make_float4(vertex.Position.x, vertex.Position.y, vertex.Position.z, h.t);
             ga = make_float4(material.Color.x, material.Color.y, material.Color.z, 1.0f);
+            if constexpr (MOTION)
+                motionGuides(sv, *prev, h, bary, material.Normal, gp, gn, mx, mn);
         }
         gNormal[pixel] = gn;
         gPosition[pixel] = gp;
         gAlbedo[pixel] = ga;
+        if constexpr (MOTION)
+        {
+            prev->position[pixel] = mx;
+            prev->normal[pixel] = mn;
+        }
     }
     if (st.overflow)
         atomicAdd(&counters[C_OVERFLOW], 1u);
@@ -86,9 +145,10 @@ PT_DEV void renderGuidesBody(const LaunchParams &p, const SceneView &sv, const T
 #ifndef PT_GUIDES_ATTR
 #define PT_GUIDES_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
-template <int MODE>
+// MOTION adds one trailing argument, the PrevPose: the pack is empty for the plain pass, whose argument list stays what it was.
+template <int MODE, bool MOTION = false, class... Prev>
 __global__ void __launch_bounds__(kBlock) k_render_guides(LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, float4 *gPosition,
-                                                           float4 *gAlbedo, uint32_t *counters, uint32_t *spill);
+                                                           float4 *gAlbedo, uint32_t *counters, uint32_t *spill, Prev... prev);
 #define PT_GUIDES_KERNEL(MODE)                                                                                                          \
     template <>                                                                                                                         \
     __global__ void __launch_bounds__(kBlock) PT_GUIDES_ATTR k_render_guides<MODE>(LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, \
@@ -96,6 +156,13 @@ __global__ void __launch_bounds__(kBlock) k_render_guides(LaunchParams p, SceneV
                                                                                    uint32_t *spill)                                      \
     {                                                                                                                                   \
         renderGuidesBody<MODE>(p, sv, sc, gNormal, gPosition, gAlbedo, counters, spill);                                                \
+    }                                                                                                                                   \
+    template <>                                                                                                                         \
+    __global__ void __launch_bounds__(kBlock) PT_GUIDES_ATTR k_render_guides<MODE, true>(LaunchParams p, SceneView sv, TraceScene sc,      \
+                                                                                         float4 *gNormal, float4 *gPosition, float4 *gAlbedo, \
+                                                                                         uint32_t *counters, uint32_t *spill, PrevPose prev) \
+    {                                                                                                                                   \
+        renderGuidesBody<MODE, true>(p, sv, sc, gNormal, gPosition, gAlbedo, counters, spill, &prev);                                   \
     }
 PT_GUIDES_KERNEL(0)
 PT_GUIDES_KERNEL(1)

@@ -7,39 +7,73 @@ static float4 *guidePtr(PtxRenderer *r, uint32_t which)
     return r->guides.p + which * r->frame.pixels();
 }
 
+static float4 *motionPtr(PtxRenderer *r, uint32_t which)
+{
+    return r->motion.p + which * r->frame.pixels();
+}
+
 // ptx_render_guides: one launch, enqueued like ptx_render_debug's -- the counter block comes back with collectRender, which is
-// where a traversal-stack overflow fails the stream.
-static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform)
+// where a traversal-stack overflow fails the stream.  `motion`: ptx_render_guides_motion -- the same launch of k_render_guides<MODE,
+// true>, which also writes where every hit was in the pose the temporal history was made from (docs/NEXT_ROWS.md section 17).
+static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, bool motion = false, const char *who = "ptx_render_guides")
 {
     if (!r || !uniform)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render_guides: null argument");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
     if (!sceneUsable(r) || !imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_render_guides: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: need ptx_scene_upload (or ptx_share_scene), ptx_build_accel and ptx_resize first", who);
     if (r->frame.boundShard)
-        return frameIsElsewhere(r, "ptx_render_guides");
+        return frameIsElsewhere(r, who);
+    const SceneData &scene = sceneOf(r)->scene;
+    if (motion && !scene.pose.enabled)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: the scene's owner does not track motion (ptx_track_motion)", who);
     HIP_TRY(r, hipSetDevice(r->device));
     const size_t n = r->frame.pixels();
     HIP_TRY(r, r->guides.alloc(n * PTX_GUIDE_COUNT));
+    if (motion)
+        HIP_TRY(r, r->motion.alloc(n * PTX_MOTION_COUNT));
     static const PtxLightsUbo noLights = {}; // the pass reads no light
     const LaunchParams p = makeParams(r, uniform, 0, 1);
     if (const int rc = beginLaunch(r, &noLights, p, 0))
         return rc;
     if (!r->guidesReady) // pixels of other ranks' tiles read as misses that were not hit: all zeros
         HIP_TRY(r, hipMemsetAsync(r->guides.p, 0, n * PTX_GUIDE_COUNT * sizeof(float4), r->stream));
+    if (motion && !r->motionReady)
+        HIP_TRY(r, hipMemsetAsync(r->motion.p, 0, n * PTX_MOTION_COUNT * sizeof(float4), r->stream));
+    // the pose the history was made from: the current one, the one the last update replaced, or one nobody kept
+    const uint64_t serial = scene.pose.serial, from = r->temporalHistoryIn >= 0 ? r->temporalPose : PtxRenderer::kNoPose;
     if (p.slotsPerFrame)
     {
         const SceneView sv = makeSceneView(r);
         const TraceScene sc = makeTraceScene(r);
         // at most kMaxPersistentThreads threads: the global part of the traversal stack is sized for that many
         const dim3 grid(gridFor(p.slotsPerFrame, kBlock, kMaxPersistentThreads / kBlock));
-        withMode(kernelMode(r), [&](auto M) {
-            k_render_guides<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, guidePtr(r, PTX_GUIDE_NORMAL), guidePtr(r, PTX_GUIDE_POSITION),
-                                                                                guidePtr(r, PTX_GUIDE_ALBEDO), r->counters.p, r->spill.p);
-        });
+        if (motion)
+        {
+            PrevPose prev = {};
+            const bool same = from == serial, snapshot = !same && scene.pose.snapshotValid && from != PtxRenderer::kNoPose && from + 1u == serial;
+            prev.known = same || snapshot;
+            prev.pairs = snapshot ? scene.pose.prevPairs.p : scene.pairs.p;
+            prev.skinned = snapshot && scene.skinnedCount ? scene.pose.prevSkinned.p : nullptr;
+            prev.firstSkinned = (uint32_t)std::min<uint64_t>(scene.staticVertexCount, 0xffffffffull);
+            prev.position = motionPtr(r, PTX_MOTION_POSITION);
+            prev.normal = motionPtr(r, PTX_MOTION_NORMAL);
+            withMode(kernelMode(r), [&](auto M) {
+                k_render_guides<decltype(M)::value, true><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, guidePtr(r, PTX_GUIDE_NORMAL), guidePtr(r, PTX_GUIDE_POSITION),
+                                                                                          guidePtr(r, PTX_GUIDE_ALBEDO), r->counters.p, r->spill.p, prev);
+            });
+        }
+        else
+            withMode(kernelMode(r), [&](auto M) {
+                k_render_guides<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, guidePtr(r, PTX_GUIDE_NORMAL), guidePtr(r, PTX_GUIDE_POSITION),
+                                                                                    guidePtr(r, PTX_GUIDE_ALBEDO), r->counters.p, r->spill.p);
+            });
     }
     if (const int rc = endLaunch(r, { PendingLaunch::kDebugView })) // the counters are the kernel's own, as the debug view's
         return rc;
     r->guidesReady = true;
+    r->guidesPose = serial;
+    r->motionReady = motion; // a plain pass leaves the motion images behind the guides: stale
+    r->motionFromPose = from;
     return PTX_OK;
 }
 
@@ -61,6 +95,15 @@ static int readGuide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
     if (!r->guidesReady)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_read_guide: call ptx_render_guides first");
     return readFrameImage(r, guidePtr(r, which), host, bytes, "ptx_read_guide");
+}
+
+static int readMotion(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    if (!r || !host || which >= PTX_MOTION_COUNT)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_motion: null argument or unknown image %u", which);
+    if (!r->motionReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_motion: call ptx_render_guides_motion first");
+    return readFrameImage(r, motionPtr(r, which), host, bytes, "ptx_read_motion");
 }
 
 // The filter over the mean `source` / `totalSamples`: ptx_denoise passes the accumulation image and the desc's count (source null:

@@ -30,6 +30,7 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->temporalHistoryIn = -1;
     r->momentsLive = false; // ... and the moments and V_0
     r->varianceReady = false;
+    r->motionReady = false; // ... and the motion guides
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     return resetAccumulation(r);
 }

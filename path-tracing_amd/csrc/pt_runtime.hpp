@@ -215,6 +215,21 @@ struct SceneData
     bool mixedMaterialTypes = false; // the instanced meshes use more than one material type (ShaderTypes.incl:143-145): k_shade sorts its queue
     bool mixedTextured = false;      // ... or materials with and without scene textures: the sampler runs for waves of textured hits only
     uint32_t pairCount = 0, triCount = 0, dxNormalTextures = 0;
+    // pose bookkeeping of the motion guides (docs/NEXT_ROWS.md section 17): here, so that the borrowers of a shared scene see it
+    struct PoseTracking
+    {
+        uint64_t serial = 0;        // accepted ptx_update_animation calls; an upload moves it past every history made before it
+        bool enabled = false;       // ptx_track_motion
+        bool snapshotValid = false; // prevPairs / prevSkinned hold the pose of serial - 1
+        DevBuf<DevPair> prevPairs;        // the DevPair table ...
+        DevBuf<PtxVertex> prevSkinned;    // ... and vertices[staticVertexCount ...] of the pose the last update replaced
+        void release()
+        {
+            snapshotValid = false;
+            prevPairs.release();
+            prevSkinned.release();
+        }
+    } pose;
     // ptx_scene_upload_streamed: the plan, the texture states and the upload stream (pt_scene_host.hpp); null after a plain upload.
     // The last member: it goes first, and its destructor waits for the uploads that still write into the buffers above.
     std::shared_ptr<struct TextureStreaming> streaming;
@@ -426,6 +441,14 @@ struct PtxRenderer
     bool momentsLive = false;
     DevBuf<float> varianceImage;
     bool varianceReady = false;
+    // motion guides (pt_denoise_host.hpp, pt_temporal_host.hpp): the pose serial (SceneData::PoseTracking) the guides were rendered
+    // at and the one the history was made from, the two images of the last ptx_render_guides_motion, whether they belong to the
+    // current guides, and the history pose they lead back to (kNoPose: there was no history)
+    static constexpr uint64_t kNoPose = ~0ull;
+    uint64_t guidesPose = kNoPose, temporalPose = kNoPose;
+    DevBuf<float4> motion;
+    bool motionReady = false;
+    uint64_t motionFromPose = kNoPose;
 
     // wavefront state
     PathState paths;
@@ -858,6 +881,51 @@ static bool transformMirrors(const float *m)
 
 #include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
 
+// ptx_track_motion: whether ptx_update_animation keeps the pose it replaces (snapshotPose).  Owner only, like the update itself.
+static int trackMotion(PtxRenderer *r, int enable)
+{
+    if (!r)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    if (r->sceneOwner)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_track_motion: this renderer shares another renderer's scene (ptx_share_scene)");
+    if (!r->sceneReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_track_motion: no scene uploaded");
+    SceneData::PoseTracking &pose = r->scene.pose;
+    if (!enable && pose.enabled)
+    {
+        // a guide pass in flight may still read the snapshot
+        HIP_TRY(r, hipSetDevice(r->device));
+        quiesceSharers(r);
+        HIP_TRY(r, hipStreamSynchronize(r->stream));
+        pose.release();
+    }
+    pose.enabled = enable != 0;
+    return PTX_OK;
+}
+
+// The first step of ptx_update_animation behind its checks: with tracking on the pose about to be replaced is kept -- the DevPair
+// table and the skinned part of the vertex buffer, device to device on the render stream ahead of the uploads and k_skin.  With
+// tracking off nothing is enqueued.  The snapshot counts, and the pose serial moves on, only once the update has succeeded
+// (updateAnimation): a failed one leaves no snapshot, and the serial where it was.
+static int snapshotPose(PtxRenderer *r)
+{
+    SceneData &sc = r->scene;
+    sc.pose.snapshotValid = false;
+    if (sc.pose.enabled)
+    {
+        HIP_TRY(r, sc.pose.prevPairs.alloc(sc.pairCount));
+        HIP_TRY(r, sc.pose.prevSkinned.alloc(sc.skinnedCount));
+        if (sc.pairCount)
+            HIP_TRY(r, hipMemcpyAsync(sc.pose.prevPairs.p, sc.pairs.p, (size_t)sc.pairCount * sizeof(DevPair), hipMemcpyDeviceToDevice, r->stream));
+        if (sc.skinnedCount)
+            HIP_TRY(r, hipMemcpyAsync(sc.pose.prevSkinned.p, sc.vertices.p + sc.staticVertexCount, (size_t)sc.skinnedCount * sizeof(PtxVertex),
+                                      hipMemcpyDeviceToDevice, r->stream));
+    }
+    return PTX_OK;
+}
+
+static int applyAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate);
+
 // Renderer.cpp:1750-1754 (+ RecordSkinningCommands :854-890, AccelerationStructure::Update :48-57)
 static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, uint32_t instanceCount, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate)
 {
@@ -872,6 +940,20 @@ static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransform
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_update_animation: %u instance transforms for a scene of %u instances", instanceCount,
                     r->scene.instanceCount);
     HIP_TRY(r, hipSetDevice(r->device));
+    if (const int rc = snapshotPose(r))
+        return rc;
+    const int rc = applyAnimation(r, instanceTransforms, boneTransforms, boneCount, accelUpdate);
+    if (rc == PTX_OK) // accepted: the serial moves on, and what snapshotPose kept is the pose of the serial before
+    {
+        r->scene.pose.serial++;
+        r->scene.pose.snapshotValid = r->scene.pose.enabled;
+    }
+    return rc;
+}
+
+// the update itself, behind ptx_update_animation's checks and the snapshot
+static int applyAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate)
+{
     if (instanceTransforms)
     {
         for (size_t p = 0; p < r->scene.hostPairs.size(); p++)

@@ -6,6 +6,9 @@
 //   k_temporal<SAME_CAMERA>  one thread per pixel; reads the sum and the three guides of its pixel and up to four taps of the three
 //                            history images (one tap, at the pixel itself, when the camera did not move); writes T and the three
 //                            images of the next history
+//   k_temporal_motion<SAME_CAMERA>  the same pixel looking its history up through the motion guides (docs/NEXT_ROWS.md section 17):
+//                            two more float4 reads, and under the same camera a per-pixel choice between the tap at the pixel
+//                            itself and the projected four
 //
 // Every access is a 16-byte float4 and nothing is staged in LDS: the four taps of neighbouring lanes overlap in L1 / L2.  The
 // arithmetic is float32 in the order the header states; nothing here is compared with a reference bit for bit.
@@ -69,8 +72,17 @@ struct TemporalColourOnly
     PT_DEV void storeNotValid(uint32_t) {}
 };
 
-template <bool SAME_CAMERA, class Extra>
-PT_DEV void temporalPixel(const TemporalArgs &a, Extra &extra)
+// The motion guides of ptx_temporal_accumulate_motion (docs/NEXT_ROWS.md section 17): (x~, known) and (n~, known) per pixel, the
+// surface point and its normal in the pose of the history.  A kernel argument of its own: TemporalArgs does not grow.
+struct TemporalMotion
+{
+    const float4 *position, *normal;
+};
+
+// MOTION: the history is looked up with (x~, n~) in place of (x_p, n_p) -- projected, and tested against the taps -- and a pixel
+// whose motion is not known takes none.  What is blended and what is stored for the next call stay the current pixel's.
+template <bool SAME_CAMERA, class Extra, bool MOTION = false>
+PT_DEV void temporalPixel(const TemporalArgs &a, Extra &extra, const TemporalMotion *motion = nullptr)
 {
     const int x = (int)(blockIdx.x * kDenoiseTileX + threadIdx.x), y = (int)(blockIdx.y * kDenoiseTileY + threadIdx.y);
     if (x >= (int)a.width || y >= (int)a.height)
@@ -95,20 +107,36 @@ PT_DEV void temporalPixel(const TemporalArgs &a, Extra &extra)
     const f3 nP = F3(np.x, np.y, np.z), xP = F3(xp.x, xp.y, xp.z);
     f3 cAcc = c;
     float L = 1.0f;
-    if (a.histIn)
+    // where the history is looked up, and with which normal; under the same camera, whether at the pixel itself
+    f3 nH = nP, xH = xP;
+    bool look = a.histIn != nullptr, atPixel = SAME_CAMERA;
+    if constexpr (MOTION)
+    {
+        if (look)
+        {
+            const float4 mx = motion->position[p], mn = motion->normal[p];
+            look = mx.w == 1.0f;
+            xH = F3(mx.x, mx.y, mx.z);
+            nH = F3(mn.x, mn.y, mn.z);
+            // the same-camera rule asks for x~ bit-equal to x_p as well: a point that moved is projected like any other
+            atPixel = SAME_CAMERA && __float_as_uint(mx.x) == __float_as_uint(xp.x) && __float_as_uint(mx.y) == __float_as_uint(xp.y) &&
+                      __float_as_uint(mx.z) == __float_as_uint(xp.z);
+        }
+    }
+    if (look)
     {
         const float planeBound = a.positionThreshold * xp.w;
         f3 acc = F3s(0.0f);
         float lacc = 0.0f, wsum = 0.0f;
-        if (SAME_CAMERA)
+        if (atPixel)
         {
-            if (temporalTap(a, p, 1.0f, nP, xP, planeBound, acc, lacc, wsum))
+            if (temporalTap(a, p, 1.0f, nH, xH, planeBound, acc, lacc, wsum))
                 extra.tap(p, 1.0f);
         }
         else
         {
             float vx, vy, vz, vw, cx, cy, cz, cw;
-            temporalMul(a.view, xP.x, xP.y, xP.z, 1.0f, vx, vy, vz, vw);
+            temporalMul(a.view, xH.x, xH.y, xH.z, 1.0f, vx, vy, vz, vw);
             temporalMul(a.proj, vx, vy, vz, vw, cx, cy, cz, cw);
             if (cw > 0.0f)
             {
@@ -135,7 +163,7 @@ PT_DEV void temporalPixel(const TemporalArgs &a, Extra &extra)
                                 continue;
                             const float w = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
                             const uint32_t q = (uint32_t)qy * a.width + (uint32_t)qx;
-                            if (temporalTap(a, q, w, nP, xP, planeBound, acc, lacc, wsum))
+                            if (temporalTap(a, q, w, nH, xH, planeBound, acc, lacc, wsum))
                                 extra.tap(q, w);
                         }
                     }
@@ -163,4 +191,11 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal(Tempo
 {
     TemporalColourOnly none;
     temporalPixel<SAME_CAMERA>(a, none);
+}
+
+template <bool SAME_CAMERA>
+__global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal_motion(TemporalArgs a, TemporalMotion motion)
+{
+    TemporalColourOnly none;
+    temporalPixel<SAME_CAMERA, TemporalColourOnly, true>(a, none, &motion);
 }

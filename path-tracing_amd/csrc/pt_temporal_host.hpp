@@ -5,7 +5,9 @@
 
 // `moments`: ptx_temporal_accumulate_moments (pt_variance_host.hpp) -- the same stage with k_temporal_moments, which carries the
 // moment history along; a plain call drops that history.
-static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool moments = false, const char *who = "ptx_temporal_accumulate")
+// `motion`: ptx_temporal_accumulate_motion -- the same stage with k_temporal_motion / k_temporal_moments_motion, which look the
+// history up through the motion guides of the last ptx_render_guides_motion (docs/NEXT_ROWS.md section 17).
+static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool moments = false, const char *who = "ptx_temporal_accumulate", bool motion = false)
 {
     if (!r || !d)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
@@ -21,6 +23,10 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
         return frameIsElsewhere(r, who);
     if (!r->guidesReady)
         return fail(r, PTX_ERROR_NOT_READY, "%s: no guides for this extent (call ptx_render_guides)", who);
+    // the motion images belong to the guides they were rendered with and lead back to the history as it stood then
+    if (motion && (!r->motionReady || r->motionFromPose != (r->temporalHistoryIn >= 0 ? r->temporalPose : PtxRenderer::kNoPose)))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: the motion guides are stale: a ptx_render_guides or an accumulate call came after the last "
+                    "ptx_render_guides_motion", who);
     if (r->frame.shard.worldSize > 1u)
         return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; the history's taps cross tiles", who,
                     r->frame.shard.worldSize);
@@ -55,22 +61,35 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
     memcpy(a.proj, r->temporalProj, sizeof a.proj);
     const bool sameCamera = useHistory && !memcmp(d->View, r->temporalView, sizeof d->View) && !memcmp(d->Proj, r->temporalProj, sizeof d->Proj);
     const dim3 block(kDenoiseTileX, kDenoiseTileY), grid((r->frame.width + kDenoiseTileX - 1) / kDenoiseTileX, (r->frame.height + kDenoiseTileY - 1) / kDenoiseTileY);
+    const TemporalMotion mo = { motion ? motionPtr(r, PTX_MOTION_POSITION) : nullptr, motion ? motionPtr(r, PTX_MOTION_NORMAL) : nullptr };
     if (moments)
     {
         // the moment history ping-pongs with the colour's; without a live one the moments restart on the colour history as it stands
         const float4 *momentsIn = useHistory && r->momentsLive ? r->momentHistory[r->temporalHistoryIn].p : nullptr;
-        if (sameCamera) k_temporal_moments<true><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p);
+        if (motion && sameCamera) k_temporal_moments_motion<true><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p, mo);
+        else if (motion) k_temporal_moments_motion<false><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p, mo);
+        else if (sameCamera) k_temporal_moments<true><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p);
         else k_temporal_moments<false><<<grid, block, 0, r->stream>>>(a, momentsIn, r->momentHistory[dst].p);
     }
+    else if (motion && sameCamera) k_temporal_motion<true><<<grid, block, 0, r->stream>>>(a, mo);
+    else if (motion) k_temporal_motion<false><<<grid, block, 0, r->stream>>>(a, mo);
     else if (sameCamera) k_temporal<true><<<grid, block, 0, r->stream>>>(a);
     else k_temporal<false><<<grid, block, 0, r->stream>>>(a);
     HIP_TRY(r, hipGetLastError());
     r->momentsLive = moments;
     r->temporalHistoryIn = dst;
     r->temporalReady = true;
+    r->temporalPose = r->guidesPose; // the history now leads back to the pose its guides were rendered at
     memcpy(r->temporalView, d->View, sizeof d->View);
     memcpy(r->temporalProj, d->Proj, sizeof d->Proj);
     return PTX_OK;
+}
+
+static int temporalAccumulateMotion(PtxRenderer *r, const PtxTemporalDesc *d, uint32_t withMoments)
+{
+    if (withMoments > 1u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate_motion: withMoments is 0 or 1 (%u)", withMoments);
+    return temporalAccumulate(r, d, withMoments != 0u, "ptx_temporal_accumulate_motion", true);
 }
 
 static int readTemporal(PtxRenderer *r, void *host, size_t bytes)

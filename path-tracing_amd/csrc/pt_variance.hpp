@@ -70,6 +70,18 @@ __global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal_momen
     temporalPixel<SAME_CAMERA>(a, m);
 }
 
+// ... through the motion guides (ptx_temporal_accumulate_motion with withMoments = 1)
+template <bool SAME_CAMERA>
+__global__ void __launch_bounds__(kDenoiseTileX *kDenoiseTileY) k_temporal_moments_motion(TemporalArgs a, const float4 *momentsIn, float4 *momentsOut,
+                                                                                          TemporalMotion motion)
+{
+    MomentHistory m;
+    m.in = momentsIn;
+    m.out = momentsOut;
+    m.maxHistory = a.maxHistory;
+    temporalPixel<SAME_CAMERA, MomentHistory, true>(a, m, &motion);
+}
+
 // ---- the estimate and the filter ----------------------------------------------------------------------------------------------------
 
 struct VarianceArgs

@@ -285,6 +285,31 @@ int ptx_temporal_accumulate_moments(PtxRenderer *r, const PtxTemporalDesc *desc)
     return temporalAccumulate(r, desc, true, "ptx_temporal_accumulate_moments");
 }
 
+int ptx_track_motion(PtxRenderer *r, int enable)
+{
+    return trackMotion(r, enable);
+}
+
+int ptx_render_guides_motion(PtxRenderer *r, const PtxRaygenUniformData *uniform)
+{
+    return renderGuides(r, uniform, true, "ptx_render_guides_motion");
+}
+
+int ptx_read_motion(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    return readMotion(r, which, host, bytes);
+}
+
+void *ptx_device_motion_ptr(PtxRenderer *r, uint32_t which)
+{
+    return r && r->motionReady && which < PTX_MOTION_COUNT ? motionPtr(r, which) : nullptr;
+}
+
+int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, uint32_t withMoments)
+{
+    return temporalAccumulateMotion(r, desc, withMoments);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

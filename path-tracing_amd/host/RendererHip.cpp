@@ -14,6 +14,7 @@ uint32_t s_Width = 0, s_Height = 0;
 bool s_DebugPipeline = false; // s_ActiveRaytracingPipeline == the debug pipeline (Renderer.cpp:579-610)
 PtxDebugViewDesc s_DebugView = { PTX_DEBUG_MODE_COLOR, 0u, 0u, 0u };
 bool s_AccumulationRestarted = true; // since the last temporal accumulation: the sum holds samples of a frame the history has not seen
+bool s_MotionVectors = false; // denoiser, temporal accumulation and TemporalSettings.MotionVectors are all on (UpdateMotionVectors)
 }
 
 void RendererHip::Check(int status)
@@ -52,6 +53,8 @@ void RendererHip::UpdateSceneData(const std::shared_ptr<Scene> &scene, bool upda
     const PtxSceneDesc desc = scene->GetDesc();
     Check(ptx_scene_upload(s_Renderer, &desc));
     Check(ptx_build_accel(s_Renderer));
+    if (s_MotionVectors) // the upload turned tracking off
+        Check(ptx_track_motion(s_Renderer, 1));
     ResetAccumulationImage();
 }
 
@@ -150,16 +153,28 @@ void RendererHip::SetPostProcessSettings(const PostProcessSettings &settings)
 
 static RendererHip::DenoiserSettings s_DenoiserSettings;
 
+static RendererHip::TemporalSettings s_TemporalSettings;
+
+// Motion guides are used when all three are on; the scene's pose tracking follows (ptx_track_motion), and a host that never asks
+// for them makes no call it did not make before.
+static int UpdateMotionVectors()
+{
+    const bool want = s_DenoiserSettings.Enabled && s_TemporalSettings.Enabled && s_TemporalSettings.MotionVectors;
+    const bool change = want != s_MotionVectors && s_Renderer && s_Scene;
+    s_MotionVectors = want;
+    return change ? ptx_track_motion(s_Renderer, want ? 1 : 0) : (int)PTX_OK;
+}
+
 void RendererHip::SetSettings(const DenoiserSettings &settings)
 {
     s_DenoiserSettings = settings;
+    Check(UpdateMotionVectors());
 }
-
-static RendererHip::TemporalSettings s_TemporalSettings;
 
 void RendererHip::SetSettings(const TemporalSettings &settings)
 {
     s_TemporalSettings = settings;
+    Check(UpdateMotionVectors());
 }
 
 static RendererHip::VarianceSettings s_VarianceSettings;
@@ -178,7 +193,8 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
     if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
         return ptx_postprocess(s_Renderer, &u, mode);
     const PtxRaygenUniformData rgenData = FillRaygenUniform();
-    if (const int rc = ptx_render_guides(s_Renderer, &rgenData))
+    const bool motion = s_MotionVectors && s_TemporalSettings.Enabled;
+    if (const int rc = motion ? ptx_render_guides_motion(s_Renderer, &rgenData) : ptx_render_guides(s_Renderer, &rgenData))
         return rc;
     const PtxDenoiseDesc desc = { u.TotalSamples, s_DenoiserSettings.Iterations, s_DenoiserSettings.SigmaColor, s_DenoiserSettings.SigmaNormal,
                                   s_DenoiserSettings.SigmaPosition, 0u, 0u };
@@ -190,7 +206,9 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         const Camera &camera = s_Scene->GetActiveCamera(); // FillRaygenUniform brought it to the extent
         ToColumnMajor(camera.GetViewMatrix(), temporal.View);
         ToColumnMajor(camera.GetProjectionMatrix(), temporal.Proj);
-        if (const int rc = s_VarianceSettings.Enabled ? ptx_temporal_accumulate_moments(s_Renderer, &temporal) : ptx_temporal_accumulate(s_Renderer, &temporal))
+        if (const int rc = motion                     ? ptx_temporal_accumulate_motion(s_Renderer, &temporal, s_VarianceSettings.Enabled ? 1u : 0u)
+                           : s_VarianceSettings.Enabled ? ptx_temporal_accumulate_moments(s_Renderer, &temporal)
+                                                        : ptx_temporal_accumulate(s_Renderer, &temporal))
             return rc;
         s_AccumulationRestarted = false;
         if (s_VarianceSettings.Enabled)

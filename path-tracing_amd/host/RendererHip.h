@@ -72,12 +72,19 @@ public:
     // the active camera; a frame whose accumulation continued from the previous one (nothing moved: the sum already holds every
     // sample) passes PTX_TEMPORAL_RESET.  Disabled (the default), or without the denoiser: everything does exactly what it did
     // without it.  The thresholds are the filter's sigmas; nobody has tuned them (docs/NEXT_ROWS.md section 14).
+    // MotionVectors (ptx.h "Motion guides", docs/NEXT_ROWS.md section 17), together with the denoiser and Enabled: UpdateSceneData
+    // turns ptx_track_motion on, and SaveOutput and Present call ptx_render_guides_motion and ptx_temporal_accumulate_motion (with
+    // the VarianceSettings its moments form) in the plain pair's place, so that animated geometry keeps its history.  Off (the
+    // default): nothing changes.  RendererHip itself never moves a pose: the switch pays off for a host that calls
+    // ptx_update_animation on GetHandle() between frames (examples/motion_frame.cpp); without that every frame finds the previous
+    // pose equal to the current one, at the motion variants' cost.
     struct TemporalSettings
     {
         bool Enabled = false;
         float MaxHistory = 32.0f;
         float NormalThreshold = 0.3f;
         float PositionThreshold = 0.03f;
+        bool MotionVectors = false;
     };
     static void SetSettings(const TemporalSettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
