@@ -704,15 +704,19 @@ class Renderer:
     def present_bytes(self) -> int:
         return int(self.lib.ptx_present_bytes(self.handle))
 
+    def _read_image(self, read, *which) -> np.ndarray:
+        """One RGBA32F image of the render extent through a ptx_read_* entry point (`which`: the image's index, where it takes one)."""
+        img = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(read(self.handle, *which, img.ctypes.data, img.nbytes))
+        return img
+
     def render_guides(self, uniform: RaygenUniformData):
         """ptx_render_guides: the first hit's normal, position and base colour of every owned pixel, kept for denoise()."""
         self._check(self.lib.ptx_render_guides(self.handle, C.byref(uniform)))
 
     def read_guide(self, which: int) -> np.ndarray:
         """One guide image (GUIDE_NORMAL / GUIDE_POSITION / GUIDE_ALBEDO), H x W x 4 float32."""
-        img = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self.lib.ptx_read_guide(self.handle, which, img.ctypes.data, img.nbytes))
-        return img
+        return self._read_image(self.lib.ptx_read_guide, which)
 
     def guide_ptr(self, which: int) -> int:
         return int(self.lib.ptx_device_guide_ptr(self.handle, which) or 0)
@@ -725,9 +729,7 @@ class Renderer:
 
     def read_denoised(self) -> np.ndarray:
         """The denoised MEAN of the last denoise(), H x W x 4 float32, alpha 1."""
-        img = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self.lib.ptx_read_denoised(self.handle, img.ctypes.data, img.nbytes))
-        return img
+        return self._read_image(self.lib.ptx_read_denoised)
 
     def denoised_ptr(self) -> int:
         return int(self.lib.ptx_device_denoised_ptr(self.handle) or 0)
@@ -757,9 +759,7 @@ class Renderer:
 
     def read_temporal(self) -> np.ndarray:
         """T of the last temporal_accumulate(): the accumulated MEAN, H x W x 4 float32, alpha = the history length (0: not valid)."""
-        img = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self.lib.ptx_read_temporal(self.handle, img.ctypes.data, img.nbytes))
-        return img
+        return self._read_image(self.lib.ptx_read_temporal)
 
     def temporal_ptr(self) -> int:
         return int(self.lib.ptx_device_temporal_ptr(self.handle) or 0)
@@ -780,9 +780,7 @@ class Renderer:
 
     def read_moments(self) -> np.ndarray:
         """The moment history of the last temporal_accumulate_moments(): H x W x 4 float32, (mu1, mu2, L_M, 0); L_M = 0: unknown."""
-        img = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self.lib.ptx_read_moments(self.handle, img.ctypes.data, img.nbytes))
-        return img
+        return self._read_image(self.lib.ptx_read_moments)
 
     def denoise_variance(self, iterations: int = VARIANCE_DENOISE_DEFAULTS["iterations"], sigma_luminance: float = VARIANCE_DENOISE_DEFAULTS["sigma_luminance"],
                          sigma_normal: float = VARIANCE_DENOISE_DEFAULTS["sigma_normal"], sigma_position: float = VARIANCE_DENOISE_DEFAULTS["sigma_position"]):
@@ -808,9 +806,7 @@ class Renderer:
 
     def read_motion(self, which: int) -> np.ndarray:
         """One motion image (MOTION_POSITION / MOTION_NORMAL), H x W x 4 float32; w = 1: known, 0: unknown (xyz = the guide) or a miss."""
-        img = np.empty((self.height, self.width, 4), dtype=np.float32)
-        self._check(self.lib.ptx_read_motion(self.handle, which, img.ctypes.data, img.nbytes))
-        return img
+        return self._read_image(self.lib.ptx_read_motion, which)
 
     def motion_ptr(self, which: int) -> int:
         return int(self.lib.ptx_device_motion_ptr(self.handle, which) or 0)

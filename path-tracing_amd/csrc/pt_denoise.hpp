@@ -1,5 +1,5 @@
 // pt_denoise.hpp -- the denoiser (docs/NEXT_ROWS.md section 13): the one stage the reference does not have (it relies on accumulation;
-// DESIGN.md section 9 names this exception).  Two kernels, host side in pt_denoise_host.hpp:
+// DESIGN.md section 9 names this exception).  Two kernels, host side in pt_chain_host.hpp:
 //
 //   k_render_guides  one primary ray through the centre of every owned pixel, exactly the debug view's (debugViewBody,
 //                    pt_debug_view.hpp), storing the first hit's shading normal, world position + hit distance and base colour;

@@ -24,13 +24,7 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->frame.height = height;
     r->frame.unbind();
     r->output.invalidate();
-    r->guidesReady = false; // the guides and the denoised image belong to the extent they were made for
-    r->denoisedIn = -1;
-    r->temporalReady = false; // ... and so do T and the history
-    r->temporalHistoryIn = -1;
-    r->momentsLive = false; // ... and the moments and V_0
-    r->varianceReady = false;
-    r->motionReady = false; // ... and the motion guides
+    r->chain.invalidate(); // guides, D, T, the histories, V_0 and the motion guides belong to the extent they were made for
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     return resetAccumulation(r);
 }

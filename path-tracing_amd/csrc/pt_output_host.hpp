@@ -1,6 +1,6 @@
 // pt_output_host.hpp -- the output stage (ptx_postprocess, ptx_read_output: row N4) and the screen path (ptx_present, ptx_read_present:
 // row D15; docs/NEXT_ROWS.md section 12).  Kernels: pt_post.hpp, pt_present.hpp; state: OutputState, the member `output` of the handle.
-// Included by pt_runtime.hpp ahead of pt_denoise_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
+// Included by pt_runtime.hpp ahead of pt_chain_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
 #pragma once
 
 // Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)

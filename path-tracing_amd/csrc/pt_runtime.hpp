@@ -3,10 +3,9 @@
 // ptx_get_stats and the ptx_test_* / ptx_trace_rays entry points.  The stages are host files of their own, included below in the
 // order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp),
 // the render launches with the bounce schedule of the wavefront backend (pt_render_host.hpp), the frame's hand-over -- accumulation
-// image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the denoiser
-// (pt_denoise_host.hpp), the temporal accumulation ahead of it (pt_temporal_host.hpp), the variance-guided filter on its result
-// (pt_variance_host.hpp).  Their functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line
-// wrappers around them.
+// image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the interactive
+// chain -- guide pass, temporal accumulation, the filters -- (pt_chain_host.hpp; its bookkeeping: pt_chain_state.hpp).  Their
+// functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line wrappers around them.
 // No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
@@ -23,6 +22,7 @@
 #include "pt_aux_kernels.hpp"
 #include "pt_bc.hpp"
 #include "pt_bvh_build.hpp"
+#include "pt_chain_state.hpp"
 #include "pt_debug_view.hpp"
 #include "pt_denoise.hpp"
 #include "pt_post.hpp"
@@ -359,6 +359,25 @@ struct OutputState
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
 };
 
+// The interactive chain behind ptx_render (pt_chain_host.hpp): the images of the guide pass, the temporal accumulation and the
+// filters, all of the render extent and allocated by the first call that needs them, and the bookkeeping over them.
+struct ChainState
+{
+    DevBuf<float4> guides;                            // the PTX_GUIDE_COUNT images of the last guide pass
+    DevBuf<float4> motion;                            // the PTX_MOTION_COUNT images of the last ptx_render_guides_motion
+    DevBuf<float4> denoisePing[2];                    // the filters' iterations alternate between them: D is [status.denoisedIn]
+    DevBuf<float4> temporalImage, temporalHistory[2]; // T, and the two copies of the three history images the calls alternate between
+    DevBuf<float4> momentHistory[2];                  // the moment history ping-pongs with temporalHistory
+    DevBuf<float> varianceImage;                      // V_0 of the last ptx_denoise_variance
+    float temporalView[16] = {}, temporalProj[16] = {}; // the matrices the last accepted accumulate call was given
+    ChainStatus status;
+
+    float4 *guidePtr(uint32_t which, size_t pixels) const { return guides.p + which * pixels; }
+    float4 *motionPtr(uint32_t which, size_t pixels) const { return motion.p + which * pixels; }
+    float4 *denoised() const { return status.denoisedIn >= 0 ? denoisePing[status.denoisedIn].p : nullptr; }
+    void invalidate() { status.resize(); } // the images stay allocated: the next calls of the new extent grow them if they must
+};
+
 struct PtxRenderer
 {
     EnvSwitches env;
@@ -423,32 +442,7 @@ struct PtxRenderer
 
     FrameState frame;
     OutputState output;
-    // denoiser (pt_denoise_host.hpp): the three guide images of the last ptx_render_guides, the two images the filter's iterations
-    // alternate between, and which of them holds the result of the last ptx_denoise
-    DevBuf<float4> guides, denoisePing[2];
-    bool guidesReady = false;
-    int denoisedIn = -1; // -1: nothing denoised since the last ptx_resize
-    // temporal accumulation (pt_temporal_host.hpp): T, the two copies of the three history images the calls alternate between, which
-    // of them the last accepted call wrote (-1: no history since the last ptx_resize) and the matrices it was given
-    DevBuf<float4> temporalImage, temporalHistory[2];
-    bool temporalReady = false;
-    int temporalHistoryIn = -1;
-    float temporalView[16] = {}, temporalProj[16] = {};
-    // variance-guided denoising (pt_variance_host.hpp): the two copies of the moment history, which ping-pong with temporalHistory
-    // (live: the last accepted accumulate call since ptx_resize was a moments call, so momentHistory[temporalHistoryIn] is current),
-    // and V_0 of the last ptx_denoise_variance
-    DevBuf<float4> momentHistory[2];
-    bool momentsLive = false;
-    DevBuf<float> varianceImage;
-    bool varianceReady = false;
-    // motion guides (pt_denoise_host.hpp, pt_temporal_host.hpp): the pose serial (SceneData::PoseTracking) the guides were rendered
-    // at and the one the history was made from, the two images of the last ptx_render_guides_motion, whether they belong to the
-    // current guides, and the history pose they lead back to (kNoPose: there was no history)
-    static constexpr uint64_t kNoPose = ~0ull;
-    uint64_t guidesPose = kNoPose, temporalPose = kNoPose;
-    DevBuf<float4> motion;
-    bool motionReady = false;
-    uint64_t motionFromPose = kNoPose;
+    ChainState chain;
 
     // wavefront state
     PathState paths;
@@ -987,9 +981,7 @@ static int applyAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms
 #include "pt_render_host.hpp" // ptx_render, ptx_render_debug: renderImpl and its stages, collectRender, renderDebug
 #include "pt_frame_host.hpp" // accumulation image and its bindings, tile shards, read-back: resizeFrame ... unpackShards
 #include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
-#include "pt_denoise_host.hpp" // ptx_render_guides, ptx_denoise, ptx_postprocess_denoised and their read-backs
-#include "pt_temporal_host.hpp" // ptx_temporal_accumulate, ptx_denoise_temporal and the read-back of T
-#include "pt_variance_host.hpp" // ptx_temporal_accumulate_moments, ptx_denoise_variance and the read-backs of the moments and V_0
+#include "pt_chain_host.hpp" // the guide pass, the temporal accumulation, the three filters and their read-backs
 
 static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
 {

@@ -91,8 +91,7 @@ static int shareScene(PtxRenderer *r, PtxRenderer *owner)
     owner->sceneSharers.push_back(r);
     r->accelReady = true;
     r->hint.forget(); // whatever this handle had learnt, it had learnt on another scene
-    r->guidesPose = r->temporalPose = PtxRenderer::kNoPose; // ... and its guides and history lead back to no pose of this one
-    r->motionReady = false;
+    r->chain.status.sceneChanged(); // ... and its guides and history lead back to no pose of this one
     r->stats.triangles = owner->stats.triangles;
     r->stats.bvhNodes = owner->stats.bvhNodes;
     r->stats.treeTriangles = owner->stats.treeTriangles;
@@ -826,8 +825,7 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s, bool streamed = fa
     r->scene.pose.enabled = false;
     r->scene.pose.serial += 2;
     // ... and this handle's own guides and history (made on the old scene, or on an owner's with serials of its own) to no pose at all
-    r->guidesPose = r->temporalPose = PtxRenderer::kNoPose;
-    r->motionReady = false;
+    r->chain.status.sceneChanged();
     if ((rc = uploadGeometry(r, s, flat)) != PTX_OK) return rc;
     if ((rc = uploadTextures(r, s, plan, streamed ? PTX_SCENE_TEXTURE_OFFSET : 0)) != PTX_OK) return rc;
     if ((rc = alphaFootprints(r, plan, streamed ? &st->state : nullptr, streamed ? PTX_SCENE_TEXTURE_OFFSET : 0)) != PTX_OK) return rc;

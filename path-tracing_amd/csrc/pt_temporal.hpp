@@ -1,6 +1,6 @@
 // pt_temporal.hpp -- temporal accumulation (docs/NEXT_ROWS.md section 14; semantics: include/ptx.h ptx_temporal_accumulate): the
 // history of the previous frames, found by projecting the position guide into the previous camera, blended with the current
-// frame's demodulated mean ahead of the filter.  One kernel, host side in pt_temporal_host.hpp; its per-pixel body, temporalPixel, is
+// frame's demodulated mean ahead of the filter.  One kernel, host side in pt_chain_host.hpp; its per-pixel body, temporalPixel, is
 // also k_temporal_moments' (pt_variance.hpp), which carries the luminance moments along the same taps:
 //
 //   k_temporal<SAME_CAMERA>  one thread per pixel; reads the sum and the three guides of its pixel and up to four taps of the three

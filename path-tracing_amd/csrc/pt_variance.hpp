@@ -1,6 +1,6 @@
 // pt_variance.hpp -- variance-guided denoising (docs/NEXT_ROWS.md section 16; semantics: include/ptx.h ptx_temporal_accumulate_moments
 // and ptx_denoise_variance): the first two luminance moments accumulated beside the colour history, a per-pixel variance from them,
-// and an a-trous filter whose colour weight is measured in that variance.  Three kernels, host side in pt_variance_host.hpp, all on
+// and an a-trous filter whose colour weight is measured in that variance.  Three kernels, host side in pt_chain_host.hpp, all on
 // k_denoise's 32 x 8 tiles with one thread per pixel:
 //
 //   k_temporal_moments<SAME_CAMERA>  k_temporal's pixel (temporalPixel, pt_temporal.hpp: the same expressions, so T and the colour

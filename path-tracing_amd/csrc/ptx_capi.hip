@@ -1,7 +1,7 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
 // Renderer member it replaces in include/ptx.h; here each is ONE line (ptx_set_backend, ptx_synchronize and the trivial getters
 // apart) that calls the implementation in pt_runtime.hpp or one of the host files it includes (pt_scene_host.hpp, pt_bvh_host.hpp,
-// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_denoise_host.hpp, pt_temporal_host.hpp, pt_variance_host.hpp);
+// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_chain_host.hpp);
 // device side: pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
@@ -237,7 +237,7 @@ int ptx_read_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
 
 void *ptx_device_guide_ptr(PtxRenderer *r, uint32_t which)
 {
-    return r && r->guidesReady && which < PTX_GUIDE_COUNT ? guidePtr(r, which) : nullptr;
+    return r && r->chain.status.guidesReady && which < PTX_GUIDE_COUNT ? r->chain.guidePtr(which, r->frame.pixels()) : nullptr;
 }
 
 int ptx_denoise(PtxRenderer *r, const PtxDenoiseDesc *desc)
@@ -252,7 +252,7 @@ int ptx_read_denoised(PtxRenderer *r, void *host, size_t bytes)
 
 void *ptx_device_denoised_ptr(PtxRenderer *r)
 {
-    return r && r->denoisedIn >= 0 ? r->denoisePing[r->denoisedIn].p : nullptr;
+    return r ? r->chain.denoised() : nullptr;
 }
 
 int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
@@ -272,7 +272,7 @@ int ptx_read_temporal(PtxRenderer *r, void *host, size_t bytes)
 
 void *ptx_device_temporal_ptr(PtxRenderer *r)
 {
-    return r && r->temporalReady ? r->temporalImage.p : nullptr;
+    return r && r->chain.status.temporalReady ? r->chain.temporalImage.p : nullptr;
 }
 
 int ptx_denoise_temporal(PtxRenderer *r, const PtxDenoiseDesc *desc)
@@ -302,7 +302,7 @@ int ptx_read_motion(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
 
 void *ptx_device_motion_ptr(PtxRenderer *r, uint32_t which)
 {
-    return r && r->motionReady && which < PTX_MOTION_COUNT ? motionPtr(r, which) : nullptr;
+    return r && r->chain.status.motionReady && which < PTX_MOTION_COUNT ? r->chain.motionPtr(which, r->frame.pixels()) : nullptr;
 }
 
 int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, uint32_t withMoments)
