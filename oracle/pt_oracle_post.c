@@ -10,9 +10,13 @@
  * The reference's intermediate images are rgba16f: every store below rounds to binary16.
  *
  * PARITY PIN: the per-pixel arithmetic of postprocess.comp / composition.comp / toneMapping.comp is
- * pinned by golden vectors made from those shader lines (tools/gen_golden.py); the bloom taps and the
- * sRGB8 encode go through fixed-function hardware in the reference (sampler filtering, format
- * conversion in vkCmdBlitImage) and are restated from the Vulkan spec: unpinned.
+ * pinned by golden vectors made from those shader lines (tools/gen_golden.py).  The bloom taps go through
+ * fixed-function hardware in the reference (sampler filtering); bloomTap, the two bloom passes and the level
+ * plan of pto_postprocess are pinned by tests/bloom_ref.py, a numpy restatement written from the shader text
+ * and the Vulkan spec on its own: its float32 instance must give this file's bits at every shape of
+ * tests/test_bloom.py, and its tap weights, level counts and extents are checked there against tables derived
+ * by hand.  The sRGB8 encode (format conversion in vkCmdBlitImage) is restated from the Vulkan spec and swept
+ * over every binary16 value by tests/test_transcendentals.py.
  */
 #include <math.h>
 #include <stdint.h>

@@ -12,6 +12,10 @@
 // The reference's intermediate images are rgba16f; here they are float arrays whose values are rounded to
 // binary16 at every store (f16Round), which keeps the arithmetic identical and the code free of half types.
 // All of it is HBM-streaming work: one launch per pass, coalesced float4 / float3 rows.
+//
+// The bloom taps go through the sampler's fixed-function filter in the reference; bloomTap, the two bloom kernels and the level plan
+// of postprocessImage are pinned by tests/bloom_ref.py, a float64 restatement written from the shader text and the Vulkan
+// specification on its own, and by the hand-derived tap tables of tests/test_bloom.py.
 #pragma once
 
 #include "pt_device.hpp"

@@ -1,7 +1,8 @@
 """Row N4: the output stage -- postprocess.comp -> bloom chain -> composition.comp -> toneMapping.comp ->
 sRGB8 / RGBA32F output image -> PNG / TGA / HDR files, plus checkpoint / resume of the running sum.
 The per-pixel shader arithmetic is pinned by golden vectors (test_oracle_golden.py / test_gpu_parity.py
-pick the three functions up automatically); here: properties of the oracle, HIP == oracle, file round trips."""
+pick the three functions up automatically); the bloom chain -- taps, weights, level plan -- is pinned by test_bloom.py against
+bloom_ref.py, a restatement of its own, and hand-derived tables; here: properties of the oracle, HIP == oracle, file round trips."""
 import struct
 import zlib
 
