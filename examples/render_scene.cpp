@@ -12,6 +12,7 @@
 //   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3   (guides + temporal moments + the variance-guided filter)
+//   examples/render_scene default 640 360 4 4 denoised.png --denoise 3 --specular-guides 4   (... whose guides follow mirrors and glass)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -87,6 +88,18 @@ int main(int argc, char **argv)
             const bool counted = i + 1 < argc && std::strlen(argv[i + 1]) == 1 && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '6';
             if (counted)
                 variance.Iterations = static_cast<uint32_t>(argv[i + 1][0] - '0');
+            const int drop = counted ? 2 : 1;
+            for (int k = i; k + drop < argc; k++)
+                argv[k] = argv[k + drop];
+            argc -= drop;
+            break;
+        }
+    // --specular-guides [bounces]: with a denoiser, the guide pass follows mirrors and glass (1 .. 8 continuation rays, 1 without a count)
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--specular-guides")
+        {
+            const bool counted = i + 1 < argc && std::strlen(argv[i + 1]) == 1 && argv[i + 1][0] >= '1' && argv[i + 1][0] <= '8';
+            denoiser.SpecularBounces = counted ? static_cast<uint32_t>(argv[i + 1][0] - '0') : 1u;
             const int drop = counted ? 2 : 1;
             for (int k = i; k + drop < argc; k++)
                 argv[k] = argv[k + drop];

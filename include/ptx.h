@@ -1059,6 +1059,81 @@ PTX_API void *ptx_device_motion_ptr(PtxRenderer *r, uint32_t which);
  * output stage follow unchanged. */
 PTX_API int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, uint32_t withMoments);
 
+/* ------------------------------------------------------------------------- */
+/* Specular-chain guides (docs/NEXT_ROWS.md section 18): the guide pass that   */
+/* follows mirrors and glass to the first surface that is neither, so that the */
+/* filters and the temporal stage see what a mirror shows, not the mirror.  An */
+/* addition: every call above computes what it computed before.                */
+/* ------------------------------------------------------------------------- */
+
+typedef struct PtxSpecularGuidesDesc {
+    uint32_t maxBounces;   /* 0 ... 8 continuation rays per pixel; 0 = the plain pass */
+    float    roughnessMax; /* a surface is followed only if material.Roughness <= roughnessMax; >= 0, finite */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved;     /* 0 */
+} PtxSpecularGuidesDesc;
+
+enum {
+    PTX_SPECULAR_SURFACE = 0, /* (first-hit Position, float(bounces) + 16 class); primary miss: (0, 0, 0, 0) */
+    PTX_SPECULAR_COUNT = 1
+};
+
+/* ptx_render_guides that follows near-delta surfaces.  Writes PTX_GUIDE_NORMAL, PTX_GUIDE_POSITION, PTX_GUIDE_ALBEDO and
+ * PTX_SPECULAR_SURFACE for the owned pixels of the current tile shard, in one launch.
+ * PRIMARY RAY AND FIRST HIT are ptx_render_guides': the ray through (0.5, 0.5) of the pixel with its two offset rays (which start at
+ * the primary's origin), traced over 1e-5 ... 1e4 with the any-hit stage where the scene has non-opaque geometry, an ignored
+ * candidate in front of the hit tinting its colour (the decal mix).
+ * THE CHAIN.  Let d be the current ray's direction, T = 0, M = the identity, tint = (1, 1, 1), bounces = 0.  At the current hit, at
+ * distance t:
+ *   1. The vertex is interpolated and transformed, the texture footprint taken from the offset rays and the material sampled: at
+ *      the first hit with the expressions of ptx_render_guides, at later hits with those of the path tracer's closest-hit stage.
+ *      isHitFromInside = dot(geometricNormal, d) > 0; the material is sampled with it, so that Eta is the path tracer's (Ior from
+ *      inside, 1 / Ior from outside); the decal mix follows as above.
+ *   2. N = normalize(vertex.Normal + TBN material.Normal).  N_guide takes the vertex frame as interpolated (nothing flipped, as
+ *      ptx_render_guides); N_cont takes the frame with Normal, Tangent and Bitangent negated where the hit is from inside, and is
+ *      the only one the continuation uses.
+ *   3. The chain STOPS here if bounces == maxBounces, or material.Roughness > roughnessMax, or neither class of 4 applies.
+ *   4. Otherwise it continues along the zero-roughness limit of the BSDF sample (the half vector is the shading normal):
+ *        MIRROR, Metalness >= 0.5: d' = normalize(reflect(d, N_cont)); the origin is the closest-hit stage's shadow-terminator
+ *          offset for a reflected ray; tint *= material.Color; M = M (I - 2 N_cont N_cont^T).
+ *        GLASS, else Transmission >= 0.5: r = refract(d, N_cont, material.Eta).  r = 0 (total internal reflection): as MIRROR, but
+ *          tint stays.  Otherwise d' = normalize(r), the origin is the closest-hit stage's self-intersection offset along
+ *          -geometricNormal (flipped where the hit is from inside), tint *= material.Color, M stays.
+ *      The offset rays follow as the closest-hit stage propagates them (reflected or refracted differentials, vertex.Normal flipped
+ *      where from inside).  T += t, bounces += 1, and d' is traced like the primary ray (interval, any-hit stage, decal).  A miss
+ *      ends the chain as ESCAPED.
+ * STORED, with T including the last segment, ro and rd0 the primary ray's origin and direction (t is the ray parameter of the
+ * traced direction: later directions are normalised, rd0 is the primary ray's as it is, unit to float32 rounding):
+ *                   chain ends on a surface                         escaped (miss after >= 1 bounce)   primary miss
+ *     NORMAL        (M N_guide, 1)                                  (0, 0, 0, 0)                       (0, 0, 0, 0)
+ *     POSITION      (ro + normalize(rd0) T, T)                      (0, 0, 0, 0)                       (0, 0, 0, 0)
+ *     ALBEDO        (tint material.Color, 1)                        (1, 1, 1, 1)                       (1, 1, 1, 1)
+ *     SURFACE       (first-hit Position, bounces + 16 class)        the same with class 2              (0, 0, 0, 0)
+ *   class 0: ended on a surface that is not followed; 1: stopped at maxBounces; 2: escaped.  For a planar mirror the stored position
+ *   is the mirror image of the reflected surface point, a fixed world point: it reprojects into the previous camera, and the
+ *   unfolded normal M N passes the plane tests of the filters and of ptx_temporal_accumulate.  An escaped pixel is "not hit" to every
+ *   consumer and passes through unfiltered, as sky does.
+ * BIT-EXACTNESS.  A pixel with bounces == 0 holds exactly the bits ptx_render_guides stores in all three guides, whatever the desc
+ * says -- (N_guide, 1), (vertex.Position, t) and (material.Color, 1), never M N or ro + rd T; maxBounces == 0 reproduces
+ * ptx_render_guides entirely.
+ * CONTRACT: ptx_render_guides'.  Asynchronous on the render stream; works on a borrower and with pending streamed textures; uploads
+ * the empty light block; a traversal-stack overflow fails the stream through the counter block; the accumulation is untouched.
+ * ptx_get_stats: pathSamples = owned pixels, segments = rays traced (primary + continuation), shadowRays = retries = 0.  To the
+ * chain the call is a plain guide pass: the motion images go stale.  ptx_resize drops the fourth image with the guides.
+ * A later ptx_render_guides or ptx_render_guides_motion rewrites the three guides and leaves the fourth image as it was: it then
+ * belongs to older guides and stays readable until the next ptx_resize.
+ * PTX_ERROR_NOT_READY: as ptx_render_guides.  PTX_ERROR_INVALID_ARGUMENT: a NULL argument, maxBounces > 8, roughnessMax negative or
+ * not finite, flags or reserved not 0.  A refused call leaves all four images and the chain's state intact.
+ * Known limits: refraction does not unfold the normal and the virtual point is exact for planar mirrors only (curved mirrors and
+ * glass are an approximation the plane test may reject: the pixel restarts); Fresnel reflection on glass is not followed; there is
+ * no motion variant; surfaces rougher than roughnessMax stay first-hit. */
+PTX_API int ptx_render_guides_specular(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxSpecularGuidesDesc *desc);
+/* The fourth image, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_INVALID_ARGUMENT: an unknown image or a buffer of
+ * another size; PTX_ERROR_NOT_READY: no ptx_render_guides_specular since the last ptx_resize. */
+PTX_API int ptx_read_specular_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes);
+/* ... or its device address (NULL without one). */
+PTX_API void *ptx_device_specular_guide_ptr(PtxRenderer *r, uint32_t which);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

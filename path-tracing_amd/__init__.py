@@ -68,6 +68,7 @@ PTX_SYMBOLS = [
     "ptx_temporal_accumulate", "ptx_read_temporal", "ptx_device_temporal_ptr", "ptx_denoise_temporal",
     "ptx_temporal_accumulate_moments", "ptx_read_moments", "ptx_denoise_variance", "ptx_read_variance",
     "ptx_track_motion", "ptx_render_guides_motion", "ptx_read_motion", "ptx_device_motion_ptr", "ptx_temporal_accumulate_motion",
+    "ptx_render_guides_specular", "ptx_read_specular_guide", "ptx_device_specular_guide_ptr",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -192,6 +193,16 @@ TEMPORAL_DENOISE_DEFAULTS = dict(iterations=2, sigma_color=0.5, sigma_normal=0.3
 # The defaults of Renderer.denoise_variance: the best geometric mean over two scenes at 8 frames of history in the sweep of
 # tools/temporal_quality.py (docs/NEXT_ROWS.md section 16); sigma_luminance is in standard deviations of the pixel's luminance
 VARIANCE_DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=0.75, sigma_normal=0.3, sigma_position=0.03)
+
+
+class SpecularGuidesDesc(C.Structure):
+    _fields_ = [("maxBounces", C.c_uint32), ("roughnessMax", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SPECULAR_SURFACE = 0  # PTX_SPECULAR_SURFACE of include/ptx.h
+SPECULAR_CLASS_SURFACE, SPECULAR_CLASS_CAPPED, SPECULAR_CLASS_ESCAPED = range(3)  # the class in SURFACE.w = bounces + 16 * class
+# The defaults of Renderer.render_guides_specular: first in the sweep of tools/specular_guides_quality.py (docs/NEXT_ROWS.md section 18)
+SPECULAR_GUIDES_DEFAULTS = dict(max_bounces=1, roughness_max=0.2)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -419,6 +430,10 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_motion_ptr.argtypes = [P, C.c_uint32]
         lib.ptx_device_motion_ptr.restype = P
         lib.ptx_temporal_accumulate_motion.argtypes = [P, C.POINTER(TemporalDesc), C.c_uint32]
+        lib.ptx_render_guides_specular.argtypes = [P, C.POINTER(RaygenUniformData), C.POINTER(SpecularGuidesDesc)]
+        lib.ptx_read_specular_guide.argtypes = [P, C.c_uint32, P, C.c_size_t]
+        lib.ptx_device_specular_guide_ptr.argtypes = [P, C.c_uint32]
+        lib.ptx_device_specular_guide_ptr.restype = P
         _hip = lib
     return _hip
 
@@ -818,6 +833,21 @@ class Renderer:
         through the motion guides of render_guides_motion(), so that animated geometry keeps it."""
         d = self._temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags)
         self._check(self.lib.ptx_temporal_accumulate_motion(self.handle, C.byref(d), int(moments)))
+
+    def render_guides_specular(self, uniform: RaygenUniformData, max_bounces: int = None, roughness_max: float = None):
+        """ptx_render_guides_specular: render_guides() that follows mirrors and glass (Roughness <= roughness_max) for up to
+        max_bounces continuation rays and stores the guides of the surface the chain ends on; max_bounces 0 is render_guides()."""
+        d = SpecularGuidesDesc(SPECULAR_GUIDES_DEFAULTS["max_bounces"] if max_bounces is None else max_bounces,
+                               SPECULAR_GUIDES_DEFAULTS["roughness_max"] if roughness_max is None else roughness_max, 0, 0)
+        self._check(self.lib.ptx_render_guides_specular(self.handle, C.byref(uniform), C.byref(d)))
+
+    def read_specular_guide(self, which: int = 0) -> np.ndarray:
+        """The fourth image of render_guides_specular() (SPECULAR_SURFACE), H x W x 4 float32: the first hit's position, and
+        w = bounces + 16 * class (0: ended on a surface that is not followed, 1: stopped at max_bounces, 2: escaped)."""
+        return self._read_image(self.lib.ptx_read_specular_guide, which)
+
+    def specular_guide_ptr(self, which: int = 0) -> int:
+        return int(self.lib.ptx_device_specular_guide_ptr(self.handle, which) or 0)
 
     def stats(self) -> Stats:
         s = Stats()

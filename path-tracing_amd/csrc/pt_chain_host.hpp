@@ -1,7 +1,7 @@
 // pt_chain_host.hpp -- host side of the interactive chain, the stages on the render stream between ptx_render and the output stage:
-// the guide pass (plain and with motion guides), the temporal accumulation (plain, with moments, through the motion guides), the three
-// filters (on the accumulation image, on T, variance-guided on T) and their read-backs.  Kernels: pt_denoise.hpp, pt_temporal.hpp,
-// pt_variance.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14, 16 and 17; state: ChainState, the member `chain` of
+// the guide pass (plain, with motion guides, following specular chains), the temporal accumulation (plain, with moments, through the
+// motion guides), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs.  Kernels: pt_denoise.hpp, pt_temporal.hpp,
+// pt_variance.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 18; state: ChainState, the member `chain` of
 // the handle, whose bookkeeping (pt_chain_state.hpp) is told of every accepted call.  Included by pt_runtime.hpp after
 // pt_output_host.hpp (postprocessImage); every function takes a valid or null handle and returns a PTX_* code.
 #pragma once
@@ -44,7 +44,10 @@ template <class Args> static void setGuides(const PtxRenderer *r, Args &a)
 // ptx_render_guides: one launch, enqueued like ptx_render_debug's -- the counter block comes back with collectRender, which is
 // where a traversal-stack overflow fails the stream.  `motion`: ptx_render_guides_motion -- the same launch of k_render_guides<MODE,
 // true>, which also writes where every hit was in the pose the temporal history was made from (docs/NEXT_ROWS.md section 17).
-static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, bool motion = false, const char *who = "ptx_render_guides")
+// `specular`: ptx_render_guides_specular's checked desc -- the same ladder and launch with k_render_guides_specular<MODE>, which follows
+// near-delta surfaces and writes a fourth image (section 18); to the chain it is a plain guide pass.
+static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, bool motion = false, const char *who = "ptx_render_guides",
+                        const PtxSpecularGuidesDesc *specular = nullptr)
 {
     if (!r || !uniform)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
@@ -61,6 +64,8 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, boo
     HIP_TRY(r, c.guides.alloc(n * PTX_GUIDE_COUNT));
     if (motion)
         HIP_TRY(r, c.motion.alloc(n * PTX_MOTION_COUNT));
+    if (specular)
+        HIP_TRY(r, c.specular.alloc(n * PTX_SPECULAR_COUNT));
     static const PtxLightsUbo noLights = {}; // the pass reads no light
     const LaunchParams p = makeParams(r, uniform, 0, 1);
     if (const int rc = beginLaunch(r, &noLights, p, 0))
@@ -69,6 +74,8 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, boo
         HIP_TRY(r, hipMemsetAsync(c.guides.p, 0, n * PTX_GUIDE_COUNT * sizeof(float4), r->stream));
     if (motion && !c.status.motionReady)
         HIP_TRY(r, hipMemsetAsync(c.motion.p, 0, n * PTX_MOTION_COUNT * sizeof(float4), r->stream));
+    if (specular && !c.status.specularReady)
+        HIP_TRY(r, hipMemsetAsync(c.specular.p, 0, n * PTX_SPECULAR_COUNT * sizeof(float4), r->stream));
     const uint64_t serial = scene.pose.serial;
     if (p.slotsPerFrame)
     {
@@ -82,7 +89,13 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, boo
                     p, sv, sc, c.guidePtr(PTX_GUIDE_NORMAL, n), c.guidePtr(PTX_GUIDE_POSITION, n), c.guidePtr(PTX_GUIDE_ALBEDO, n), r->counters.p, r->spill.p, prev...);
             });
         };
-        if (motion)
+        if (specular)
+            withMode(kernelMode(r), [&](auto M) {
+                k_render_guides_specular<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(
+                    p, sv, sc, c.guidePtr(PTX_GUIDE_NORMAL, n), c.guidePtr(PTX_GUIDE_POSITION, n), c.guidePtr(PTX_GUIDE_ALBEDO, n),
+                    c.specularPtr(PTX_SPECULAR_SURFACE, n), specular->maxBounces, specular->roughnessMax, r->counters.p, r->spill.p);
+            });
+        else if (motion)
         {
             // the pose the history was made from: the current one, the one the last update replaced, or one nobody kept
             const PrevPoseSource from = ChainStatus::prevPoseSource(c.status.historyPose(), serial, scene.pose.snapshotValid);
@@ -102,7 +115,21 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, boo
     if (const int rc = endLaunch(r, { PendingLaunch::kDebugView })) // the counters are the kernel's own, as the debug view's
         return rc;
     c.status.guidesRendered(serial, motion);
+    if (specular)
+        c.status.specularRendered();
     return PTX_OK;
+}
+
+// ptx_render_guides_specular (docs/NEXT_ROWS.md section 18): the desc is checked first, the rest is renderGuides' own ladder and launch
+static int renderGuidesSpecular(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxSpecularGuidesDesc *d)
+{
+    const char *who = "ptx_render_guides_specular";
+    if (!r || !uniform || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (d->maxBounces > 8u || !(d->roughnessMax >= 0.0f && d->roughnessMax <= 3.402823466e38f) || d->flags != 0u || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need maxBounces <= 8 (%u), roughnessMax >= 0 and finite (%g), flags 0 (0x%x) and reserved 0 (%u)", who,
+                    d->maxBounces, (double)d->roughnessMax, d->flags, d->reserved);
+    return renderGuides(r, uniform, false, who, d);
 }
 
 // device -> host copy of one renderer-owned image of the render extent with `texel` bytes per pixel, synchronous
@@ -132,6 +159,15 @@ static int readMotion(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
     if (!r->chain.status.motionReady)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_read_motion: call ptx_render_guides_motion first");
     return readFrameImage(r, r->chain.motionPtr(which, r->frame.pixels()), host, bytes, sizeof(float4), "ptx_read_motion");
+}
+
+static int readSpecularGuide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    if (!r || !host || which >= PTX_SPECULAR_COUNT)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_specular_guide: null argument or unknown image %u", which);
+    if (!r->chain.status.specularReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_specular_guide: call ptx_render_guides_specular first");
+    return readFrameImage(r, r->chain.specularPtr(which, r->frame.pixels()), host, bytes, sizeof(float4), "ptx_read_specular_guide");
 }
 
 // ---- the temporal accumulation -----------------------------------------------------------------------------

@@ -19,6 +19,7 @@ struct ChainStatus
     bool momentsLive = false;   // that call was a moments call: copy `historyIn` of the moment history is current
     bool varianceReady = false; // V_0 of a ptx_denoise_variance
     bool motionReady = false;   // the motion images belong to the current guides
+    bool specularReady = false; // a ptx_render_guides_specular since the last ptx_resize: the fourth image exists
     // pose serials (SceneData::PoseTracking): the one the guides were rendered at, the one the history was made from, and the history
     // pose the motion images lead back to (kNoPose: there was no history)
     uint64_t guidesPose = kNoPose, temporalPose = kNoPose, motionFromPose = kNoPose;
@@ -38,7 +39,7 @@ struct ChainStatus
     // ptx_resize: everything belongs to the extent it was made for (the serials stay: nothing is left that they describe)
     void resize()
     {
-        guidesReady = temporalReady = momentsLive = varianceReady = motionReady = false;
+        guidesReady = temporalReady = momentsLive = varianceReady = motionReady = specularReady = false;
         denoisedIn = historyIn = -1;
     }
     // ptx_scene_upload, its streamed form, ptx_share_scene: guides and history lead back to no pose of the new scene, the motion images are stale
@@ -55,6 +56,8 @@ struct ChainStatus
         guidesPose = serial;
         motionReady = motion;
     }
+    // an accepted ptx_render_guides_specular, beside its guidesRendered(serial, false)
+    void specularRendered() { specularReady = true; }
     // An accepted accumulate call.  The history ping-pongs (a thread reads q while its neighbour writes it) and the moment history with
     // it: `src` is read where there is a history and the call did not ask for PTX_TEMPORAL_RESET (useHistory), its moments where they are
     // live too (useMoments: without, they restart on the colour history as it stands); `dst` is written.  A plain call drops the moments.

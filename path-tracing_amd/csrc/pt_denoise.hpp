@@ -1,10 +1,13 @@
 // pt_denoise.hpp -- the denoiser (docs/NEXT_ROWS.md section 13): the one stage the reference does not have (it relies on accumulation;
-// DESIGN.md section 9 names this exception).  Two kernels, host side in pt_chain_host.hpp:
+// DESIGN.md section 9 names this exception).  Three kernels, host side in pt_chain_host.hpp:
 //
 //   k_render_guides  one primary ray through the centre of every owned pixel, exactly the debug view's (debugViewBody,
 //                    pt_debug_view.hpp), storing the first hit's shading normal, world position + hit distance and base colour;
 //                    <MODE, true> (ptx_render_guides_motion, docs/NEXT_ROWS.md section 17) also where the hit was, and which way its
 //                    normal pointed, in the pose the temporal history was made from
+//   k_render_guides_specular  the same pass following mirrors and glass to the first surface that is neither, storing that surface's
+//                    guides and, in a fourth image, the first hit and the chain's length and class (ptx_render_guides_specular,
+//                    docs/NEXT_ROWS.md section 18)
 //   k_denoise        one iteration of the edge-avoiding a-trous filter (a 5 x 5 B3-spline stencil dilated by `step`) over the
 //                    demodulated mean, guided by those three images; the first launch demodulates, the last remodulates
 //
@@ -168,6 +171,226 @@ PT_GUIDES_KERNEL(0)
 PT_GUIDES_KERNEL(1)
 PT_GUIDES_KERNEL(2)
 #undef PT_GUIDES_KERNEL
+
+// ---- the specular-chain guide pass (ptx_render_guides_specular, docs/NEXT_ROWS.md section 18) ---------------
+
+// What one lane carries from hit to hit: the ray, its offset rays (TEX variants), the summed length, the product of the mirrors'
+// reflections (rows: (M v)_i = dot(m_i, v)), the product of the followed surfaces' colours.
+struct SpecularChain
+{
+    f3 o, d;
+    DiffRays diff;
+    float T;
+    f3 m0, m1, m2;
+    f3 tint;
+    uint32_t bounces;
+};
+
+// The hit as steps 1 and 2 of the header text shade it.  bounces == 0: renderGuidesBody's expressions in its order (the footprint from
+// the unflipped frame and the primary's offset rays); later: closestHit's (pt_device.hpp), which flips the frame first where the
+// hit is from inside.  `vertex` comes back unflipped; nGuide, nCont and the footprint's by-products go to the continuation.
+struct SpecularHit
+{
+    Vtx vertex;
+    TriVertices tri;
+    f3 bary, geometricNormal; // the normal facing the ray
+    bool inside;
+    MaterialSample material;
+    f4 derivatives;
+    f3 dndu, dndv;
+    f3 nGuide, nCont;
+};
+
+template <bool TEX, bool ALPHA>
+PT_DEV void specularShadeHit(const SceneView &sv, const SpecularChain &c, const Hit &h, const Decal &decal, SpecularHit &s)
+{
+    s.bary = F3(1.0f - h.u - h.v, h.u, h.v);
+    const DevPair pr = sv.pairs[h.pair];
+    s.tri = loadTriangle(&sv.shadeTris[h.slot]);
+    const TriVertices &tv3 = s.tri;
+    Vtx ov;
+    ov.Position = interp3(tv3.o[0].Position, tv3.o[1].Position, tv3.o[2].Position, s.bary);
+    ov.Normal = interp3(tv3.o[0].Normal, tv3.o[1].Normal, tv3.o[2].Normal, s.bary);
+    ov.Tangent = interp3(tv3.o[0].Tangent, tv3.o[1].Tangent, tv3.o[2].Tangent, s.bary);
+    ov.Bitangent = interp3(tv3.o[0].Bitangent, tv3.o[1].Bitangent, tv3.o[2].Bitangent, s.bary);
+    s.vertex = transformVertex(pr, ov);
+    s.inside = dot(tv3.geometricNormal, c.d) > 0.0f;
+    s.geometricNormal = s.inside ? -tv3.geometricNormal : tv3.geometricNormal;
+    Vtx flipped = s.vertex; // the continuation's frame
+    if (s.inside)
+    {
+        flipped.Normal = -flipped.Normal;
+        flipped.Tangent = -flipped.Tangent;
+        flipped.Bitangent = -flipped.Bitangent;
+    }
+    const Vtx &fp = c.bounces ? flipped : s.vertex; // the footprint's frame: the plain pass flips nothing
+    const f2 uv0 = tv3.uv[0], uv1 = tv3.uv[1], uv2 = tv3.uv[2];
+    const f2 texCoords = F2((uv0.x * s.bary.x + uv1.x * s.bary.y) + uv2.x * s.bary.z, (uv0.y * s.bary.x + uv1.y * s.bary.y) + uv2.y * s.bary.z);
+    const f3 P3[3] = { tv3.worldPosition[0], tv3.worldPosition[1], tv3.worldPosition[2] };
+    const f3 N3[3] = { tv3.worldNormal[0], tv3.worldNormal[1], tv3.worldNormal[2] };
+    const f2 UV3[3] = { uv0, uv1, uv2 };
+    f3 dpdu, dpdv, dpdx, dpdy;
+    computeDpnDuv(P3, N3, UV3, fp.Tangent, fp.Bitangent, dpdu, dpdv, s.dndu, s.dndv);
+    computeDpDxy(s.vertex.Position, c.diff.rxOrigin, c.diff.rxDirection, c.diff.ryOrigin, c.diff.ryDirection, fp.Normal, dpdx, dpdy);
+    s.derivatives = computeDerivatives(dpdx, dpdy, dpdu, dpdv);
+    s.material = sampleMaterial<TEX>(sv, pr.materialId, texCoords, s.derivatives, s.inside, false, false);
+    if (ALPHA && decal.dist != -1.0f && h.t > decal.dist)
+    {
+        const f4 dc = hitBaseColor(sv, decal.pair, decal.slot, decal.u, decal.v);
+        s.material.Color = mix(s.material.Color, rgb(dc), dc.w);
+    }
+    mat3 TBN;
+    TBN.c0 = s.vertex.Tangent;
+    TBN.c1 = s.vertex.Bitangent;
+    TBN.c2 = s.vertex.Normal;
+    s.nGuide = normalize(s.vertex.Normal + mul(TBN, s.material.Normal));
+    s.nCont = s.inside ? -s.nGuide : s.nGuide; // the flipped frame negates every term of the sum: the same bits, negated
+}
+
+// Step 4 of the header text: the continuation ray of a hit that is followed -- mirror, refraction, or total internal reflection (a
+// mirror that leaves the tint alone).  The offset rays follow as closestHit propagates them.
+template <bool TEX>
+PT_DEV void specularContinue(SpecularChain &c, const SpecularHit &s, float t)
+{
+    const TriVertices &tv3 = s.tri;
+    const f3 flippedNormal = s.inside ? -s.vertex.Normal : s.vertex.Normal;
+    f3 r = F3s(0.0f);
+    const bool glass = !(s.material.Metalness >= 0.5f);
+    if (glass)
+        r = refract(c.d, s.nCont, s.material.Eta);
+    const bool refracted = glass && !(r.x == 0.0f && r.y == 0.0f && r.z == 0.0f);
+    const f3 rayOrigin = offsetRayOriginShadowTerminator(s.vertex.Position, tv3.worldPosition[0], tv3.worldNormal[0], tv3.worldPosition[1], tv3.worldNormal[1],
+                                                         tv3.worldPosition[2], tv3.worldNormal[2], s.bary, refracted);
+    f3 dir, origin;
+    if (refracted)
+    {
+        dir = normalize(r);
+        origin = offsetRayOriginSelfIntersection(s.vertex.Position, -s.geometricNormal);
+        c.tint = c.tint * s.material.Color;
+    }
+    else
+    {
+        dir = normalize(reflect(c.d, s.nCont));
+        origin = rayOrigin;
+        if (!glass)
+            c.tint = c.tint * s.material.Color;
+        const f3 n = s.nCont; // M <- M (I - 2 n n^T)
+        const float a0 = 2.0f * dot(c.m0, n), a1 = 2.0f * dot(c.m1, n), a2 = 2.0f * dot(c.m2, n);
+        c.m0 = c.m0 - n * a0;
+        c.m1 = c.m1 - n * a1;
+        c.m2 = c.m2 - n * a2;
+    }
+    if constexpr (TEX)
+    {
+        if (refracted)
+            computeRefractedDifferentialRays(s.derivatives, flippedNormal, rayOrigin, -c.d, dir, s.dndu, s.dndv, s.material.Eta, c.diff);
+        else
+            computeReflectedDifferentialRays(s.derivatives, flippedNormal, rayOrigin, -c.d, dir, s.dndu, s.dndv, c.diff);
+    }
+    c.o = origin;
+    c.d = dir;
+    c.T = c.T + t;
+    c.bounces++;
+}
+
+// One traversal and one shading site, run once per segment: the primary ray enters the loop like every continuation ray, so a lane
+// whose chain ended waits, results in registers, until the wave's longest chain is done, and stores once.
+template <int MODE>
+PT_DEV void renderGuidesSpecularBody(const LaunchParams &p, const SceneView &sv, const TraceScene &sc, float4 *__restrict__ gNormal,
+                                     float4 *__restrict__ gPosition, float4 *__restrict__ gAlbedo, float4 *__restrict__ gSurface, uint32_t maxBounces,
+                                     float roughnessMax, uint32_t *__restrict__ counters, uint32_t *spill)
+{
+    constexpr bool TEX = MODE >= 1, ALPHA = MODE == 2;
+    PT_DECLARE_STACK(st, PT_TAIL_LDS, spill)
+    uint32_t nPix = 0, nRays = 0;
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < p.slotsPerFrame; slot += gridDim.x * blockDim.x)
+    {
+        const uint32_t pixel = slotPixel(p, slot);
+        if (pixel == kNoPixel)
+            continue;
+        f3 ro, rd, rx, ry;
+        constructPrimaryRay<true>(pixel % p.width, pixel / p.width, p.width, p.height, p.u.ViewInverse, p.u.ProjInverse, F2(0.5f, 0.5f), ro, rd, rx, ry);
+        SpecularChain c;
+        c.o = ro;
+        c.d = rd;
+        c.diff.rxOrigin = ro;
+        c.diff.rxDirection = rx;
+        c.diff.ryOrigin = ro;
+        c.diff.ryDirection = ry;
+        c.T = 0.0f;
+        c.m0 = F3(1.0f, 0.0f, 0.0f);
+        c.m1 = F3(0.0f, 1.0f, 0.0f);
+        c.m2 = F3(0.0f, 0.0f, 1.0f);
+        c.tint = F3s(1.0f);
+        c.bounces = 0u;
+        nPix++;
+        float4 gn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), gp = gn, gs = gn, ga = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        for (;;)
+        {
+            Hit h;
+            Decal decal = noDecal();
+            nRays++;
+            if (!traceRay<false, false, ALPHA>(sc, c.o, c.d, 0.00001f, 10000.0f, st, h, nullptr, nullptr, ALPHA ? &decal : nullptr))
+            {
+                if (c.bounces) // escaped: a miss to every consumer
+                    gs.w = (float)c.bounces + 32.0f;
+                break;
+            }
+            SpecularHit s;
+            specularShadeHit<TEX, ALPHA>(sv, c, h, decal, s);
+            if (c.bounces == 0u)
+                gs = make_float4(s.vertex.Position.x, s.vertex.Position.y, s.vertex.Position.z, 0.0f);
+            const bool followed = s.material.Roughness <= roughnessMax && (s.material.Metalness >= 0.5f || s.material.Transmission >= 0.5f);
+            if (c.bounces == maxBounces || !followed)
+            {
+                if (c.bounces == 0u) // the plain pass's values, bit for bit
+                {
+                    gn = make_float4(s.nGuide.x, s.nGuide.y, s.nGuide.z, 1.0f);
+                    gp = make_float4(s.vertex.Position.x, s.vertex.Position.y, s.vertex.Position.z, h.t);
+                    ga = make_float4(s.material.Color.x, s.material.Color.y, s.material.Color.z, 1.0f);
+                }
+                else
+                {
+                    const float T = c.T + h.t;
+                    const f3 x = ro + normalize(rd) * T;
+                    const f3 al = c.tint * s.material.Color;
+                    gn = make_float4(dot(c.m0, s.nGuide), dot(c.m1, s.nGuide), dot(c.m2, s.nGuide), 1.0f);
+                    gp = make_float4(x.x, x.y, x.z, T);
+                    ga = make_float4(al.x, al.y, al.z, 1.0f);
+                }
+                gs.w = (float)c.bounces + (followed ? 16.0f : 0.0f);
+                break;
+            }
+            specularContinue<TEX>(c, s, h.t);
+        }
+        gNormal[pixel] = gn;
+        gPosition[pixel] = gp;
+        gAlbedo[pixel] = ga;
+        gSurface[pixel] = gs;
+    }
+    if (st.overflow)
+        atomicAdd(&counters[C_OVERFLOW], 1u);
+    waveAddCounter(&counters[C_SEGMENTS], nRays);
+    waveAddCounter(&counters[C_SAMPLES], nPix);
+}
+
+// The plain pass's class of kernel and its occupancy attribute; register and scratch figures: docs/NEXT_ROWS.md section 18.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_render_guides_specular(LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, float4 *gPosition,
+                                                                    float4 *gAlbedo, float4 *gSurface, uint32_t maxBounces, float roughnessMax,
+                                                                    uint32_t *counters, uint32_t *spill);
+#define PT_GUIDES_SPECULAR_KERNEL(MODE)                                                                                                 \
+    template <>                                                                                                                         \
+    __global__ void __launch_bounds__(kBlock) PT_GUIDES_ATTR k_render_guides_specular<MODE>(                                            \
+        LaunchParams p, SceneView sv, TraceScene sc, float4 *gNormal, float4 *gPosition, float4 *gAlbedo, float4 *gSurface, uint32_t maxBounces, \
+        float roughnessMax, uint32_t *counters, uint32_t *spill)                                                                         \
+    {                                                                                                                                   \
+        renderGuidesSpecularBody<MODE>(p, sv, sc, gNormal, gPosition, gAlbedo, gSurface, maxBounces, roughnessMax, counters, spill);     \
+    }
+PT_GUIDES_SPECULAR_KERNEL(0)
+PT_GUIDES_SPECULAR_KERNEL(1)
+PT_GUIDES_SPECULAR_KERNEL(2)
+#undef PT_GUIDES_SPECULAR_KERNEL
 
 // ---- the filter --------------------------------------------------------------------------------------------
 

@@ -365,6 +365,7 @@ struct ChainState
 {
     DevBuf<float4> guides;                            // the PTX_GUIDE_COUNT images of the last guide pass
     DevBuf<float4> motion;                            // the PTX_MOTION_COUNT images of the last ptx_render_guides_motion
+    DevBuf<float4> specular;                          // the PTX_SPECULAR_COUNT images of the last ptx_render_guides_specular
     DevBuf<float4> denoisePing[2];                    // the filters' iterations alternate between them: D is [status.denoisedIn]
     DevBuf<float4> temporalImage, temporalHistory[2]; // T, and the two copies of the three history images the calls alternate between
     DevBuf<float4> momentHistory[2];                  // the moment history ping-pongs with temporalHistory
@@ -374,6 +375,7 @@ struct ChainState
 
     float4 *guidePtr(uint32_t which, size_t pixels) const { return guides.p + which * pixels; }
     float4 *motionPtr(uint32_t which, size_t pixels) const { return motion.p + which * pixels; }
+    float4 *specularPtr(uint32_t which, size_t pixels) const { return specular.p + which * pixels; }
     float4 *denoised() const { return status.denoisedIn >= 0 ? denoisePing[status.denoisedIn].p : nullptr; }
     void invalidate() { status.resize(); } // the images stay allocated: the next calls of the new extent grow them if they must
 };

@@ -305,6 +305,21 @@ void *ptx_device_motion_ptr(PtxRenderer *r, uint32_t which)
     return r && r->chain.status.motionReady && which < PTX_MOTION_COUNT ? r->chain.motionPtr(which, r->frame.pixels()) : nullptr;
 }
 
+int ptx_render_guides_specular(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxSpecularGuidesDesc *desc)
+{
+    return renderGuidesSpecular(r, uniform, desc);
+}
+
+int ptx_read_specular_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes)
+{
+    return readSpecularGuide(r, which, host, bytes);
+}
+
+void *ptx_device_specular_guide_ptr(PtxRenderer *r, uint32_t which)
+{
+    return r && r->chain.status.specularReady && which < PTX_SPECULAR_COUNT ? r->chain.specularPtr(which, r->frame.pixels()) : nullptr;
+}
+
 int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, uint32_t withMoments)
 {
     return temporalAccumulateMotion(r, desc, withMoments);

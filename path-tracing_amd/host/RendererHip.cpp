@@ -194,7 +194,10 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         return ptx_postprocess(s_Renderer, &u, mode);
     const PtxRaygenUniformData rgenData = FillRaygenUniform();
     const bool motion = s_MotionVectors && s_TemporalSettings.Enabled;
-    if (const int rc = motion ? ptx_render_guides_motion(s_Renderer, &rgenData) : ptx_render_guides(s_Renderer, &rgenData))
+    const PtxSpecularGuidesDesc specular = { s_DenoiserSettings.SpecularBounces, s_DenoiserSettings.SpecularRoughnessMax, 0u, 0u };
+    if (const int rc = motion                                 ? ptx_render_guides_motion(s_Renderer, &rgenData)
+                       : s_DenoiserSettings.SpecularBounces ? ptx_render_guides_specular(s_Renderer, &rgenData, &specular)
+                                                            : ptx_render_guides(s_Renderer, &rgenData))
         return rc;
     const PtxDenoiseDesc desc = { u.TotalSamples, s_DenoiserSettings.Iterations, s_DenoiserSettings.SigmaColor, s_DenoiserSettings.SigmaNormal,
                                   s_DenoiserSettings.SigmaPosition, 0u, 0u };

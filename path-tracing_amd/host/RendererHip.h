@@ -58,6 +58,10 @@ public:
     // -> ptx_postprocess_denoised on the current running sum instead of ptx_postprocess; a debug-view frame is shown as it is.
     // Disabled (the default): both do exactly what they did without it.  The defaults are the measured ones of
     // docs/NEXT_ROWS.md section 13.
+    // SpecularBounces (ptx.h "Specular-chain guides", docs/NEXT_ROWS.md section 18): 0 (the default) calls exactly what it called
+    // before; above 0 ptx_render_guides_specular(SpecularBounces, SpecularRoughnessMax) takes ptx_render_guides' place, so that the
+    // filter and the temporal stage see what mirrors and glass show.  The pass has no motion variant: with TemporalSettings'
+    // MotionVectors in use the motion pass runs instead.
     struct DenoiserSettings
     {
         bool Enabled = false;
@@ -65,6 +69,8 @@ public:
         float SigmaColor = 1.5f;
         float SigmaNormal = 0.3f;
         float SigmaPosition = 0.03f;
+        uint32_t SpecularBounces = 0;
+        float SpecularRoughnessMax = 0.2f;
     };
     static void SetSettings(const DenoiserSettings &settings);
     // Temporal accumulation (ptx.h "Temporal accumulation").  Enabled together with the denoiser: SaveOutput and Present run

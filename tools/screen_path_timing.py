@@ -13,7 +13,10 @@ ptx_temporal_accumulate_moments adds 16 B of moment history in and out: 208 byte
 history at its cap (every pixel takes mu2 - mu1^2) and, as `_restarted`, right after a PTX_TEMPORAL_RESET (every valid pixel takes
 the 7 x 7 window); ptx_denoise_temporal at the same iteration counts stands beside it.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D]"""
+ptx_render_guides_specular (section 18) at the package's defaults stands beside ptx_render_guides of the same run on chess_like and on
+`default`; --guides-only times nothing but the two guide passes.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only]"""
 import json
 import math
 import os
@@ -53,7 +56,8 @@ def main():
     pkg = graft.load_package()
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
-    scenes = {name: pkg.Scene(name, detail) for name in ("chess_like", "atrium_like")}
+    guides_only = "--guides-only" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like", "default") if guides_only else ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
         renderers[name] = pkg.Renderer()
@@ -63,6 +67,26 @@ def main():
         scene, r = scenes["chess_like"], renderers["chess_like"]
         r.resize(w, h)
         u = scene.uniform(w, h, bounces=STEP_DEPTH)
+
+        def specular_row(name, rg, ug):  # right behind the plain pass of the same scene
+            t = timed(rg, lambda: rg.render_guides_specular(ug))
+            t["ratio_to_render_guides"] = t["median_ms"] / rec[f"render_guides_{name}"]["median_ms"]
+            rec[f"render_guides_specular_{name}"] = t
+
+        def default_rows():
+            sd, rd = scenes["default"], renderers["default"]
+            rd.resize(w, h)
+            ud = sd.uniform(w, h, bounces=STEP_DEPTH)
+            rec["render_guides_default"] = timed(rd, lambda: rd.render_guides(ud))
+            specular_row("default", rd, ud)
+        if guides_only:
+            rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
+            specular_row("chess_like", r, u)
+            default_rows()
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
         rec["render_8spp_step_chess_like"] = timed(r, lambda: r.render_frames(u, scene.lights, 0, STEP_SPP))
         r.reset()
         r.render_frames(u, scene.lights, 0, STEP_SPP)
@@ -74,6 +98,8 @@ def main():
             r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_HDR, **POST)
             rec[f"present_to_{sw}x{sh}_hdr10"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_A2B10G10R10_UNORM, pkg.TONE_MAPPING_HDR))
         rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
+        specular_row("chess_like", r, u)
+        r.render_guides(u)  # what follows is timed on first-hit guides, as it always was
         cams = [scene.camera_matrices(w, h)]
         pos, fwd, right = (np.frombuffer(u.ViewInverse, np.float32).reshape(4, 4).T[0:3, k].astype(np.float64) for k in (3, 2, 0))
         scene.set_camera_pose(pos + right * 0.002, fwd)
@@ -115,6 +141,7 @@ def main():
         ra.resize(w, h)
         ua = a.uniform(w, h, bounces=STEP_DEPTH)
         rec["render_guides_atrium_like"] = timed(ra, lambda: ra.render_guides(ua))
+        default_rows()
         out[f"{w}x{h}"] = rec
         for k, v in rec.items():
             print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
