@@ -6,6 +6,8 @@
 //   g++ -std=c++20 -O2 examples/motion_frame.cpp path-tracing_amd/host/{Scene,Camera,ExampleScenes,OutputSaver,TextureImporter,JpegDecoder,SceneImporter,SceneDescription,FbxReader,ObjReader,RendererHip}.cpp \
 //       -Ipath-tracing_amd/host -Lpath-tracing_amd -lptx_hip -Wl,-rpath,'$ORIGIN/../path-tracing_amd' -o examples/motion_frame
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin     (scene, extent, spp, depth, time step, variance 0 / 1, file)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 1   (... with TemporalSettings::Responsive on: section 19,
+//                                                                        tests/test_responsive.py)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
 // height x 16 bytes.
@@ -28,15 +30,15 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc != 9)
+    if (argc != 9 && argc != 10)
     {
-        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin\n");
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1)]\n");
         return 1;
     }
     const std::string name = argv[1];
     const uint32_t width = std::atoi(argv[2]), height = std::atoi(argv[3]), spp = std::atoi(argv[4]), bounces = std::atoi(argv[5]);
     const float timeStep = static_cast<float>(std::atof(argv[6]));
-    const bool useVariance = std::atoi(argv[7]) != 0;
+    const bool useVariance = std::atoi(argv[7]) != 0, useResponsive = argc == 10 && std::atoi(argv[9]) != 0;
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
@@ -47,6 +49,7 @@ int main(int argc, char **argv)
         denoiser.Enabled = true;
         RendererHip::TemporalSettings temporal;
         temporal.Enabled = temporal.MotionVectors = true;
+        temporal.Responsive = useResponsive;
         RendererHip::VarianceSettings variance;
         variance.Enabled = useVariance;
         RendererHip::SetSettings(denoiser);

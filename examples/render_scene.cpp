@@ -13,6 +13,7 @@
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3   (guides + temporal moments + the variance-guided filter)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3 --specular-guides 4   (... whose guides follow mirrors and glass)
+//   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3 --responsive   (... whose history follows a change of lighting)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -104,6 +105,16 @@ int main(int argc, char **argv)
             for (int k = i; k + drop < argc; k++)
                 argv[k] = argv[k + drop];
             argc -= drop;
+            break;
+        }
+    // --responsive: with a temporal accumulation, the accumulate call keeps a fast history and clamps the long one into its box
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--responsive")
+        {
+            temporal.Responsive = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
             break;
         }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks

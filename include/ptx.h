@@ -1037,7 +1037,8 @@ PTX_API int ptx_track_motion(PtxRenderer *r, int enable);
  * tree: the result does not depend on PTX_ACCEL_REFIT versus PTX_ACCEL_REBUILD.
  * Refusals as ptx_render_guides', and PTX_ERROR_NOT_READY while the scene's owner does not track motion.  Works on a borrower and
  * with pending streamed textures.  ptx_resize drops the motion images; a later plain ptx_render_guides makes them stale.  Known
- * limits: two updates between temporal frames make the motion unknown; first hit only; a moving light still lags; several
+ * limits: two updates between temporal frames make the motion unknown; first hit only; a moving light lags unless the
+ * accumulate call is ptx_temporal_accumulate_responsive (docs/NEXT_ROWS.md section 19); several
  * borrowers at different histories share the one snapshot, which the serial rule keeps correct, not optimal. */
 PTX_API int ptx_render_guides_motion(PtxRenderer *r, const PtxRaygenUniformData *uniform);
 /* One motion image, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_INVALID_ARGUMENT: an unknown image or a buffer
@@ -1133,6 +1134,74 @@ PTX_API int ptx_render_guides_specular(PtxRenderer *r, const PtxRaygenUniformDat
 PTX_API int ptx_read_specular_guide(PtxRenderer *r, uint32_t which, void *host, size_t bytes);
 /* ... or its device address (NULL without one). */
 PTX_API void *ptx_device_specular_guide_ptr(PtxRenderer *r, uint32_t which);
+
+/* ------------------------------------------------------------------------- */
+/* Responsive temporal history (docs/NEXT_ROWS.md section 19): a second, short */
+/* history beside the long one follows a change of lighting within a few       */
+/* frames; the long history is clamped into the box the short one spans around */
+/* the pixel and shortened where the clamp bit.  An addition: every call above */
+/* computes what it computed before, and a host that never makes this call     */
+/* allocates nothing for it.                                                   */
+/* ------------------------------------------------------------------------- */
+
+enum { PTX_RESPONSIVE_MOMENTS = 1, PTX_RESPONSIVE_MOTION = 2 };   /* PtxResponsiveDesc.flags */
+
+typedef struct PtxResponsiveDesc {
+    float fastHistory;   /* >= 1, finite, <= the temporal desc's maxHistory: cap of the fast history's length L_F */
+    float clampSigma;    /* > 0, finite: half-width of the clamp box in standard deviations */
+    uint32_t flags;      /* which accumulate call this one extends */
+    uint32_t reserved;   /* 0 */
+} PtxResponsiveDesc;
+
+/* Two launches on the render stream: pass A accumulates, pass B clamps.
+ *
+ * PASS A is the BASE CALL chosen by responsive->flags, bit for bit in T, the colour history, the moment history and every tap
+ * decision:
+ *     0                                                ptx_temporal_accumulate
+ *     PTX_RESPONSIVE_MOMENTS                           ptx_temporal_accumulate_moments
+ *     PTX_RESPONSIVE_MOTION                            ptx_temporal_accumulate_motion(.., 0)
+ *     PTX_RESPONSIVE_MOTION | PTX_RESPONSIVE_MOMENTS   ptx_temporal_accumulate_motion(.., 1)
+ * Beside the colour history it carries the FAST HISTORY F' = (F.rgb, L_F) of the previous responsive call along the same taps with
+ * the same bilinear weights, as the moments are carried.  With c = c(p), this frame's demodulated mean: a tap q counts for F iff it
+ * counted for the colour, L_F'(q) > 0 and F'(q).rgb is finite.  With sum w_F >= 1/64 over those taps:
+ *     F_h = sum w F'(q) / sum w_F,   L_F = min(sum w L_F'(q) / sum w_F + 1, fastHistory),   F = F_h + (c - F_h) / L_F
+ * (the colour's own operations in the colour's own order); otherwise F = c and L_F = 1 -- also without a history, with
+ * PTX_TEMPORAL_RESET and on a pixel whose motion is unknown.  If F is not finite, (0, 0, 0, 0) is stored: F is UNKNOWN (L_F = 0) and
+ * no later tap takes it.  A pixel that is not valid stores zeros.  F is one more RGBA32F image, (F.rgb demodulated, L_F), kept twice,
+ * ping-ponging with the colour history: 32 more bytes per pixel, allocated by the first responsive call.  An accumulate call that is
+ * not responsive DROPS the fast history, as a plain call drops the moments: the next responsive call restarts F (F = c, L_F = 1) on
+ * the colour history as it stands.
+ *
+ * PASS B acts on a valid pixel p only if pass A found a history for it (L > 1), L_F(p) > 0 and c_acc(p) is finite; everywhere else
+ * it is the identity.  The window is the 5 x 5 texels around p (not dilated) of THIS call's F; a tap q counts iff it is inside the
+ * image and L_F(q) > 0, so the centre always counts and n >= 1.  There is no normal or position term: a window that straddles an
+ * edge only widens the box.  Per channel, in two passes over the window, row by row from (-2, -2) to (2, 2):
+ *     mu = sum F(q) / n,   var = sum (F(q) - mu)^2 / n,   sigma = sqrt(var),
+ *     lo = mu - clampSigma sigma,   hi = mu + clampSigma sigma,   c' = min(max(c_acc, lo), hi),
+ * min and max taken as comparisons (c' = lo where c_acc < lo, hi where c_acc > hi, else c_acc: a bound that is not a number leaves
+ * c_acc as it is).  The pixel is CLAMPED iff c_acc < lo or c_acc > hi in some channel.  On a clamped pixel L_out = min(L, L_F(p)),
+ * and with PTX_RESPONSIVE_MOMENTS and L_M(p) > 0, L_M becomes min(L_M, L_F(p)); the moments themselves are kept.  Elsewhere
+ * L_out = L.  Pass B rewrites T(p) = (c' a_p, L_out), the pixel's own entry (c', L_out) of the colour history pass A just wrote, and
+ * L_M of its own entry of the moment history; it touches nothing of any other pixel, so both passes work on the same ping-pong copy.
+ * float32 throughout; n is a float; a division is the project's a * rcp(b); the square root is sqrt_ of csrc/pt_device.hpp, the
+ * correctly rounded IEEE square root PTX_FN_SQRT exposes.
+ *
+ * Consequences: (a) a first call, a PTX_TEMPORAL_RESET call and a maxHistory 1 call are the base call bit for bit (no pixel has
+ * L > 1); (b) with fastHistory == maxHistory, from a common start and while nothing is clamped, F equals the colour history bit for
+ * bit; (c) where F is constant over the window (sigma = 0), c' = F(p).
+ *
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL argument, fastHistory below 1, not finite or above desc->maxHistory, clampSigma <= 0 or not
+ * finite, unknown flags, reserved != 0, and whatever the base call answers so.  PTX_ERROR_NOT_READY: whatever the base call answers
+ * so, stale motion guides under PTX_RESPONSIVE_MOTION included.  A refused call leaves T, all three histories and D intact;
+ * ptx_resize drops everything.  Works on a borrower; ptx_denoise_temporal, ptx_denoise_variance and the output stage follow
+ * unchanged. */
+PTX_API int ptx_temporal_accumulate_responsive(PtxRenderer *r, const PtxTemporalDesc *desc, const PtxResponsiveDesc *responsive);
+/* The fast history of the last responsive call, device -> host, width*height*16 bytes: (F.rgb demodulated, L_F) per pixel;
+ * synchronous.  PTX_ERROR_INVALID_ARGUMENT: a buffer of another size; PTX_ERROR_NOT_READY: the last accepted accumulate call since
+ * ptx_resize was not ptx_temporal_accumulate_responsive. */
+PTX_API int ptx_read_fast_history(PtxRenderer *r, void *host, size_t bytes);   /* (F.rgb demodulated, L_F), width*height*16 */
+/* ... or its device address (NULL without one). */
+PTX_API void *ptx_device_fast_history_ptr(PtxRenderer *r);
 
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);

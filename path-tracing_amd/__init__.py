@@ -69,6 +69,7 @@ PTX_SYMBOLS = [
     "ptx_temporal_accumulate_moments", "ptx_read_moments", "ptx_denoise_variance", "ptx_read_variance",
     "ptx_track_motion", "ptx_render_guides_motion", "ptx_read_motion", "ptx_device_motion_ptr", "ptx_temporal_accumulate_motion",
     "ptx_render_guides_specular", "ptx_read_specular_guide", "ptx_device_specular_guide_ptr",
+    "ptx_temporal_accumulate_responsive", "ptx_read_fast_history", "ptx_device_fast_history_ptr",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -203,6 +204,16 @@ SPECULAR_SURFACE = 0  # PTX_SPECULAR_SURFACE of include/ptx.h
 SPECULAR_CLASS_SURFACE, SPECULAR_CLASS_CAPPED, SPECULAR_CLASS_ESCAPED = range(3)  # the class in SURFACE.w = bounces + 16 * class
 # The defaults of Renderer.render_guides_specular: first in the sweep of tools/specular_guides_quality.py (docs/NEXT_ROWS.md section 18)
 SPECULAR_GUIDES_DEFAULTS = dict(max_bounces=1, roughness_max=0.2)
+
+
+class ResponsiveDesc(C.Structure):
+    _fields_ = [("fastHistory", C.c_float), ("clampSigma", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RESPONSIVE_MOMENTS, RESPONSIVE_MOTION = 1, 2  # PTX_RESPONSIVE_* of include/ptx.h
+# The defaults of Renderer.temporal_accumulate_responsive: first in the sweep of tools/temporal_quality.py --responsive
+# (docs/NEXT_ROWS.md section 19)
+RESPONSIVE_DEFAULTS = dict(fast_history=2.0, clamp_sigma=1.0)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -434,6 +445,10 @@ def load_hip() -> C.CDLL:
         lib.ptx_read_specular_guide.argtypes = [P, C.c_uint32, P, C.c_size_t]
         lib.ptx_device_specular_guide_ptr.argtypes = [P, C.c_uint32]
         lib.ptx_device_specular_guide_ptr.restype = P
+        lib.ptx_temporal_accumulate_responsive.argtypes = [P, C.POINTER(TemporalDesc), C.POINTER(ResponsiveDesc)]
+        lib.ptx_read_fast_history.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_fast_history_ptr.argtypes = [P]
+        lib.ptx_device_fast_history_ptr.restype = P
         _hip = lib
     return _hip
 
@@ -848,6 +863,26 @@ class Renderer:
 
     def specular_guide_ptr(self, which: int = 0) -> int:
         return int(self.lib.ptx_device_specular_guide_ptr(self.handle, which) or 0)
+
+    def temporal_accumulate_responsive(self, total_samples: int, view, proj, max_history: float = TEMPORAL_DEFAULTS["max_history"],
+                                       normal_threshold: float = TEMPORAL_DEFAULTS["normal_threshold"],
+                                       position_threshold: float = TEMPORAL_DEFAULTS["position_threshold"], flags: int = 0,
+                                       fast_history: float = RESPONSIVE_DEFAULTS["fast_history"], clamp_sigma: float = RESPONSIVE_DEFAULTS["clamp_sigma"],
+                                       responsive_flags: int = 0):
+        """ptx_temporal_accumulate_responsive: the accumulate call responsive_flags names (0: temporal_accumulate, RESPONSIVE_MOMENTS:
+        temporal_accumulate_moments, RESPONSIVE_MOTION: temporal_accumulate_motion) carrying a fast history of at most fast_history
+        frames, followed by a clamp of the long history into mean +- clamp_sigma standard deviations of the fast one's 5 x 5
+        neighbourhood; a clamped pixel's history length drops to the fast one's, so a change of lighting shows within a few frames."""
+        d = self._temporal_desc(total_samples, view, proj, max_history, normal_threshold, position_threshold, flags)
+        rd = ResponsiveDesc(fast_history, clamp_sigma, responsive_flags, 0)
+        self._check(self.lib.ptx_temporal_accumulate_responsive(self.handle, C.byref(d), C.byref(rd)))
+
+    def read_fast_history(self) -> np.ndarray:
+        """The fast history of the last temporal_accumulate_responsive(): H x W x 4 float32, (F.rgb demodulated, L_F); L_F = 0: unknown."""
+        return self._read_image(self.lib.ptx_read_fast_history)
+
+    def fast_history_ptr(self) -> int:
+        return int(self.lib.ptx_device_fast_history_ptr(self.handle) or 0)
 
     def stats(self) -> Stats:
         s = Stats()

@@ -1,7 +1,7 @@
 // pt_chain_host.hpp -- host side of the interactive chain, the stages on the render stream between ptx_render and the output stage:
 // the guide pass (plain, with motion guides, following specular chains), the temporal accumulation (plain, with moments, through the
-// motion guides), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs.  Kernels: pt_denoise.hpp, pt_temporal.hpp,
-// pt_variance.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 18; state: ChainState, the member `chain` of
+// motion guides, responsive), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs.  Kernels: pt_denoise.hpp, pt_temporal.hpp,
+// pt_variance.hpp, pt_responsive.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 19; state: ChainState, the member `chain` of
 // the handle, whose bookkeeping (pt_chain_state.hpp) is told of every accepted call.  Included by pt_runtime.hpp after
 // pt_output_host.hpp (postprocessImage); every function takes a valid or null handle and returns a PTX_* code.
 #pragma once
@@ -176,7 +176,11 @@ static int readSpecularGuide(PtxRenderer *r, uint32_t which, void *host, size_t 
 // k_temporal_moments, which carries the moment history along; a plain call drops that history.
 // `motion`: ptx_temporal_accumulate_motion -- the same stage with k_temporal_motion / k_temporal_moments_motion, which look the
 // history up through the motion guides of the last ptx_render_guides_motion (docs/NEXT_ROWS.md section 17).
-static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool moments = false, const char *who = "ptx_temporal_accumulate", bool motion = false)
+// `responsive`: ptx_temporal_accumulate_responsive's desc, checked here behind the base call's -- the same stage with
+// k_temporal_responsive, which carries the fast history along, and k_responsive_clamp behind it (docs/NEXT_ROWS.md section 19); a
+// call without it drops the fast history.
+static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool moments = false, const char *who = "ptx_temporal_accumulate", bool motion = false,
+                              const PtxResponsiveDesc *responsive = nullptr)
 {
     if (!r || !d)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
@@ -186,6 +190,10 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need totalSamples > 0 (%u), maxHistory >= 1 (%g), normalThreshold > 0 (%g), "
                     "positionThreshold > 0 (%g), all finite, flags 0 or PTX_TEMPORAL_RESET (0x%x) and reserved 0 (%u)", who, d->totalSamples, (double)d->maxHistory,
                     (double)d->normalThreshold, (double)d->positionThreshold, d->flags, d->reserved);
+    if (responsive && (!(responsive->fastHistory >= 1.0f) || !(responsive->fastHistory <= d->maxHistory) || !positive(responsive->clampSigma) ||
+                       responsive->reserved != 0u)) // the flags chose `moments` and `motion`: temporalAccumulateResponsive
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need 1 <= fastHistory <= maxHistory (%g, %g), clampSigma > 0 and finite (%g) and reserved 0 (%u)", who,
+                    (double)responsive->fastHistory, (double)d->maxHistory, (double)responsive->clampSigma, responsive->reserved);
     if (const int rc = chainRefusal(r, who, "history", motion))
         return rc;
     HIP_TRY(r, hipSetDevice(r->device));
@@ -197,9 +205,11 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
         HIP_TRY(r, c.temporalHistory[i].alloc(n * kTemporalHistoryImages));
         if (moments)
             HIP_TRY(r, c.momentHistory[i].alloc(n));
+        if (responsive)
+            HIP_TRY(r, c.fastHistory[i].alloc(n));
     }
     ChainStatus next = c.status; // the call counts once its launch is accepted
-    const ChainStatus::Accumulate h = next.accumulate(moments, (d->flags & PTX_TEMPORAL_RESET) != 0u);
+    const ChainStatus::Accumulate h = next.accumulate(moments, (d->flags & PTX_TEMPORAL_RESET) != 0u, responsive != nullptr);
     TemporalArgs a;
     a.sum = imagePtr(r);
     setGuides(r, a);
@@ -220,13 +230,34 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
     float4 *momentsOut = c.momentHistory[h.dst].p;
     const TemporalMotion mo = { motion ? c.motionPtr(PTX_MOTION_POSITION, n) : nullptr, motion ? c.motionPtr(PTX_MOTION_NORMAL, n) : nullptr };
     const dim3 grid = tileGrid(r);
-    withFlag(moments, [&](auto Moments) { withFlag(motion, [&](auto Motion) { withFlag(sameCamera, [&](auto Same) {
-        constexpr bool mm = decltype(Moments)::value, mv = decltype(Motion)::value, same = decltype(Same)::value;
-        if constexpr (mm && mv) k_temporal_moments_motion<same><<<grid, kTileBlock, 0, r->stream>>>(a, momentsIn, momentsOut, mo);
-        else if constexpr (mm) k_temporal_moments<same><<<grid, kTileBlock, 0, r->stream>>>(a, momentsIn, momentsOut);
-        else if constexpr (mv) k_temporal_motion<same><<<grid, kTileBlock, 0, r->stream>>>(a, mo);
-        else k_temporal<same><<<grid, kTileBlock, 0, r->stream>>>(a);
-    }); }); });
+    if (responsive)
+    {
+        const ResponsiveHistories rh = { h.useFast ? c.fastHistory[h.src].p : nullptr, c.fastHistory[h.dst].p, momentsIn, momentsOut, responsive->fastHistory };
+        ResponsiveClampArgs b;
+        b.fast = c.fastHistory[h.dst].p;
+        b.temporal = c.temporalImage.p;
+        b.history = c.temporalHistory[h.dst].p;
+        b.moments = momentsOut;
+        b.albedo = a.albedo;
+        b.width = a.width;
+        b.height = a.height;
+        b.clampSigma = responsive->clampSigma;
+        withFlag(moments, [&](auto Moments) {
+            constexpr bool mm = decltype(Moments)::value;
+            withFlag(motion, [&](auto Motion) { withFlag(sameCamera, [&](auto Same) {
+                k_temporal_responsive<decltype(Same)::value, mm, decltype(Motion)::value><<<grid, kTileBlock, 0, r->stream>>>(a, rh, mo);
+            }); });
+            k_responsive_clamp<mm><<<grid, kTileBlock, 0, r->stream>>>(b);
+        });
+    }
+    else
+        withFlag(moments, [&](auto Moments) { withFlag(motion, [&](auto Motion) { withFlag(sameCamera, [&](auto Same) {
+            constexpr bool mm = decltype(Moments)::value, mv = decltype(Motion)::value, same = decltype(Same)::value;
+            if constexpr (mm && mv) k_temporal_moments_motion<same><<<grid, kTileBlock, 0, r->stream>>>(a, momentsIn, momentsOut, mo);
+            else if constexpr (mm) k_temporal_moments<same><<<grid, kTileBlock, 0, r->stream>>>(a, momentsIn, momentsOut);
+            else if constexpr (mv) k_temporal_motion<same><<<grid, kTileBlock, 0, r->stream>>>(a, mo);
+            else k_temporal<same><<<grid, kTileBlock, 0, r->stream>>>(a);
+        }); }); });
     HIP_TRY(r, hipGetLastError());
     c.status = next;
     memcpy(c.temporalView, d->View, sizeof d->View);
@@ -239,6 +270,26 @@ static int temporalAccumulateMotion(PtxRenderer *r, const PtxTemporalDesc *d, ui
     if (withMoments > 1u)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_temporal_accumulate_motion: withMoments is 0 or 1 (%u)", withMoments);
     return temporalAccumulate(r, d, withMoments != 0u, "ptx_temporal_accumulate_motion", true);
+}
+
+// ptx_temporal_accumulate_responsive: the flags choose the base call, whose name the refusals keep apart from the plain calls'
+static int temporalAccumulateResponsive(PtxRenderer *r, const PtxTemporalDesc *d, const PtxResponsiveDesc *responsive)
+{
+    const char *who = "ptx_temporal_accumulate_responsive";
+    if (!r || !d || !responsive)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    if ((responsive->flags & ~(uint32_t)(PTX_RESPONSIVE_MOMENTS | PTX_RESPONSIVE_MOTION)) != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: flags are PTX_RESPONSIVE_MOMENTS and PTX_RESPONSIVE_MOTION (0x%x)", who, responsive->flags);
+    return temporalAccumulate(r, d, (responsive->flags & PTX_RESPONSIVE_MOMENTS) != 0u, who, (responsive->flags & PTX_RESPONSIVE_MOTION) != 0u, responsive);
+}
+
+static int readFastHistory(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_fast_history: null argument");
+    if (!r->chain.status.fastCurrent())
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_fast_history: the last accumulate call was not ptx_temporal_accumulate_responsive");
+    return readFrameImage(r, r->chain.fastHistory[r->chain.status.historyIn].p, host, bytes, sizeof(float4), "ptx_read_fast_history");
 }
 
 static int readTemporal(PtxRenderer *r, void *host, size_t bytes)

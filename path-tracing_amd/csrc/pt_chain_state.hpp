@@ -1,5 +1,5 @@
 // pt_chain_state.hpp -- the bookkeeping of the interactive chain (guide pass, temporal accumulation, the filters; semantics:
-// include/ptx.h, docs/NEXT_ROWS.md sections 13-17): what is ready, which ping-pong copy is current, whether the moments are live and
+// include/ptx.h, docs/NEXT_ROWS.md sections 13-19): what is ready, which ping-pong copy is current, whether the moments are live and
 // which pose a history leads back to, with every event that changes them as one member function.  No buffers, no matrices and no HIP
 // in here (tests/test_chain_state.py compiles it alone); ChainState (pt_runtime.hpp) holds one beside the images, and
 // pt_chain_host.hpp, pt_frame_host.hpp and pt_scene_host.hpp report the events.
@@ -17,6 +17,7 @@ struct ChainStatus
     bool temporalReady = false; // T holds the result of an accumulate call
     int historyIn = -1;         // which copy of the history the last accepted accumulate call wrote (-1: none since the last ptx_resize)
     bool momentsLive = false;   // that call was a moments call: copy `historyIn` of the moment history is current
+    bool fastLive = false;      // that call was a responsive call: copy `historyIn` of the fast history is current
     bool varianceReady = false; // V_0 of a ptx_denoise_variance
     bool motionReady = false;   // the motion images belong to the current guides
     bool specularReady = false; // a ptx_render_guides_specular since the last ptx_resize: the fourth image exists
@@ -28,6 +29,7 @@ struct ChainStatus
     // the motion images belong to the guides they were rendered with and lead back to the history as it stood then
     bool motionFresh() const { return motionReady && motionFromPose == historyPose(); }
     bool momentsCurrent() const { return temporalReady && momentsLive; }
+    bool fastCurrent() const { return temporalReady && fastLive; }
     // `from`: the history's pose; `serial`: the scene's; a valid snapshot holds the pose of serial - 1
     static PrevPoseSource prevPoseSource(uint64_t from, uint64_t serial, bool snapshotValid)
     {
@@ -39,7 +41,7 @@ struct ChainStatus
     // ptx_resize: everything belongs to the extent it was made for (the serials stay: nothing is left that they describe)
     void resize()
     {
-        guidesReady = temporalReady = momentsLive = varianceReady = motionReady = specularReady = false;
+        guidesReady = temporalReady = momentsLive = fastLive = varianceReady = motionReady = specularReady = false;
         denoisedIn = historyIn = -1;
     }
     // ptx_scene_upload, its streamed form, ptx_share_scene: guides and history lead back to no pose of the new scene, the motion images are stale
@@ -61,13 +63,15 @@ struct ChainStatus
     // An accepted accumulate call.  The history ping-pongs (a thread reads q while its neighbour writes it) and the moment history with
     // it: `src` is read where there is a history and the call did not ask for PTX_TEMPORAL_RESET (useHistory), its moments where they are
     // live too (useMoments: without, they restart on the colour history as it stands); `dst` is written.  A plain call drops the moments.
-    struct Accumulate { int src, dst; bool useHistory, useMoments; };
-    Accumulate accumulate(bool moments, bool reset)
+    // The fast history of a responsive call (`fast`, docs/NEXT_ROWS.md section 19) ping-pongs and is dropped in the same way (useFast).
+    struct Accumulate { int src, dst; bool useHistory, useMoments, useFast; };
+    Accumulate accumulate(bool moments, bool reset, bool fast = false)
     {
         const bool useHistory = historyIn >= 0 && !reset;
-        const Accumulate a = { historyIn, historyIn == 0 ? 1 : 0, useHistory, useHistory && momentsLive };
+        const Accumulate a = { historyIn, historyIn == 0 ? 1 : 0, useHistory, useHistory && momentsLive, useHistory && fastLive };
         historyIn = a.dst;
         momentsLive = moments;
+        fastLive = fast;
         temporalReady = true;
         temporalPose = guidesPose; // the history now leads back to the pose its guides were rendered at
         return a;

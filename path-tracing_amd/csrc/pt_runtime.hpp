@@ -31,6 +31,7 @@
 #include "pt_stream_plan.hpp"
 #include "pt_temporal.hpp"
 #include "pt_variance.hpp"
+#include "pt_responsive.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -369,6 +370,7 @@ struct ChainState
     DevBuf<float4> denoisePing[2];                    // the filters' iterations alternate between them: D is [status.denoisedIn]
     DevBuf<float4> temporalImage, temporalHistory[2]; // T, and the two copies of the three history images the calls alternate between
     DevBuf<float4> momentHistory[2];                  // the moment history ping-pongs with temporalHistory
+    DevBuf<float4> fastHistory[2];                    // ... and so does the fast history of ptx_temporal_accumulate_responsive
     DevBuf<float> varianceImage;                      // V_0 of the last ptx_denoise_variance
     float temporalView[16] = {}, temporalProj[16] = {}; // the matrices the last accepted accumulate call was given
     ChainStatus status;

@@ -325,6 +325,21 @@ int ptx_temporal_accumulate_motion(PtxRenderer *r, const PtxTemporalDesc *desc, 
     return temporalAccumulateMotion(r, desc, withMoments);
 }
 
+int ptx_temporal_accumulate_responsive(PtxRenderer *r, const PtxTemporalDesc *desc, const PtxResponsiveDesc *responsive)
+{
+    return temporalAccumulateResponsive(r, desc, responsive);
+}
+
+int ptx_read_fast_history(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readFastHistory(r, host, bytes);
+}
+
+void *ptx_device_fast_history_ptr(PtxRenderer *r)
+{
+    return r && r->chain.status.fastCurrent() ? r->chain.fastHistory[r->chain.status.historyIn].p : nullptr;
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

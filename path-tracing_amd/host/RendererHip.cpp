@@ -209,7 +209,10 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         const Camera &camera = s_Scene->GetActiveCamera(); // FillRaygenUniform brought it to the extent
         ToColumnMajor(camera.GetViewMatrix(), temporal.View);
         ToColumnMajor(camera.GetProjectionMatrix(), temporal.Proj);
-        if (const int rc = motion                     ? ptx_temporal_accumulate_motion(s_Renderer, &temporal, s_VarianceSettings.Enabled ? 1u : 0u)
+        const PtxResponsiveDesc responsive = { s_TemporalSettings.FastHistory, s_TemporalSettings.ClampSigma,
+                                               (motion ? (uint32_t)PTX_RESPONSIVE_MOTION : 0u) | (s_VarianceSettings.Enabled ? (uint32_t)PTX_RESPONSIVE_MOMENTS : 0u), 0u };
+        if (const int rc = s_TemporalSettings.Responsive ? ptx_temporal_accumulate_responsive(s_Renderer, &temporal, &responsive)
+                           : motion                     ? ptx_temporal_accumulate_motion(s_Renderer, &temporal, s_VarianceSettings.Enabled ? 1u : 0u)
                            : s_VarianceSettings.Enabled ? ptx_temporal_accumulate_moments(s_Renderer, &temporal)
                                                         : ptx_temporal_accumulate(s_Renderer, &temporal))
             return rc;

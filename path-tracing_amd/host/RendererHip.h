@@ -84,6 +84,12 @@ public:
     // default): nothing changes.  RendererHip itself never moves a pose: the switch pays off for a host that calls
     // ptx_update_animation on GetHandle() between frames (examples/motion_frame.cpp); without that every frame finds the previous
     // pose equal to the current one, at the motion variants' cost.
+    // Responsive (ptx.h "Responsive temporal history", docs/NEXT_ROWS.md section 19), together with the denoiser and Enabled: the
+    // accumulate call, whichever of the four the other switches choose, is made through ptx_temporal_accumulate_responsive with
+    // FastHistory and ClampSigma, so that a change of lighting shows within a few frames.  Off (the default): SaveOutput and Present
+    // enqueue exactly what they did without it.  The defaults are the measured ones of section 19.  A frame whose accumulation
+    // continued from the previous one passes PTX_TEMPORAL_RESET as always, and on such a frame the responsive call is the base call:
+    // the switch pays off while something moves and every frame's sum starts anew.
     struct TemporalSettings
     {
         bool Enabled = false;
@@ -91,6 +97,9 @@ public:
         float NormalThreshold = 0.3f;
         float PositionThreshold = 0.03f;
         bool MotionVectors = false;
+        bool Responsive = false;
+        float FastHistory = 2.0f;
+        float ClampSigma = 1.0f;
     };
     static void SetSettings(const TemporalSettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal

@@ -13,10 +13,17 @@ ptx_temporal_accumulate_moments adds 16 B of moment history in and out: 208 byte
 history at its cap (every pixel takes mu2 - mu1^2) and, as `_restarted`, right after a PTX_TEMPORAL_RESET (every valid pixel takes
 the 7 x 7 window); ptx_denoise_temporal at the same iteration counts stands beside it.
 
+ptx_temporal_accumulate_responsive (section 19) is one call of two launches, accumulate and clamp; it stands right behind the plain call
+of the same run, with the difference between the two, and against 240 bytes per pixel: the plain call's 176, 16 B of fast history in and
+out, and the clamp's 16 B of fast history and 16 B of colour history in (a clamped pixel reads 16 B of albedo and writes 32 B more,
+which the figure leaves out).  --temporal-only times nothing but the accumulate calls; --extent W H takes one extent in place of the
+two.  The wall clock cannot take the call's two launches apart: a kernel trace of `--temporal-only --extent W H` (rocprofv3
+--kernel-trace --stats, in a run of its own) gives k_responsive_clamp's and k_temporal_responsive's device times per extent.
+
 ptx_render_guides_specular (section 18) at the package's defaults stands beside ptx_render_guides of the same run on chess_like and on
 `default`; --guides-only times nothing but the two guide passes.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only]"""
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--extent W H]"""
 import json
 import math
 import os
@@ -35,6 +42,7 @@ POST = dict(exposure=1.0, bloom_threshold=0.8, bloom_intensity=0.35)
 DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
 TEMPORAL_BYTES_PER_PIXEL = 176
 MOMENTS_BYTES_PER_PIXEL = 208
+RESPONSIVE_BYTES_PER_PIXEL = 240
 
 
 def timed(r, call):
@@ -56,13 +64,17 @@ def main():
     pkg = graft.load_package()
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
-    guides_only = "--guides-only" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like", "default") if guides_only else ("chess_like", "atrium_like", "default"))}
+    guides_only, temporal_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only else ("chess_like", "default") if guides_only else
+                                                          ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
         renderers[name] = pkg.Renderer()
         renderers[name].upload(scene)
-    for w, h in ((1920, 1080), (3840, 2160)):
+    extents = ((1920, 1080), (3840, 2160))
+    if "--extent" in sys.argv:
+        extents = ((int(sys.argv[sys.argv.index("--extent") + 1]), int(sys.argv[sys.argv.index("--extent") + 2])),)
+    for w, h in extents:
         rec = {}
         scene, r = scenes["chess_like"], renderers["chess_like"]
         r.resize(w, h)
@@ -87,18 +99,21 @@ def main():
             for k, v in rec.items():
                 print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
             continue
-        rec["render_8spp_step_chess_like"] = timed(r, lambda: r.render_frames(u, scene.lights, 0, STEP_SPP))
+        if not temporal_only:
+            rec["render_8spp_step_chess_like"] = timed(r, lambda: r.render_frames(u, scene.lights, 0, STEP_SPP))
         r.reset()
         r.render_frames(u, scene.lights, 0, STEP_SPP)
-        rec["postprocess"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
+        if not temporal_only:
+            rec["postprocess"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
         screens = [(w, h)] + ([(3840, 2160)] if (w, h) == (1920, 1080) else [])
-        for sw, sh in screens:
+        for sw, sh in ([] if temporal_only else screens):
             r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_SDR, **POST)
             rec[f"present_to_{sw}x{sh}_sdr_srgb8"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_R8G8B8A8_SRGB, pkg.TONE_MAPPING_SDR))
             r.postprocess(STEP_SPP, tone_mapping=pkg.TONE_MAPPING_HDR, **POST)
             rec[f"present_to_{sw}x{sh}_hdr10"] = timed(r, lambda: r.present(sw, sh, pkg.PRESENT_A2B10G10R10_UNORM, pkg.TONE_MAPPING_HDR))
-        rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
-        specular_row("chess_like", r, u)
+        if not temporal_only:
+            rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
+            specular_row("chess_like", r, u)
         r.render_guides(u)  # what follows is timed on first-hit guides, as it always was
         cams = [scene.camera_matrices(w, h)]
         pos, fwd, right = (np.frombuffer(u.ViewInverse, np.float32).reshape(4, 4).T[0:3, k].astype(np.float64) for k in (3, 2, 0))
@@ -114,6 +129,25 @@ def main():
             t = timed(r, lambda: accumulate(moving))
             t["algorithmic_GB_per_s"] = w * h * TEMPORAL_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
             rec[key] = t
+
+        def accumulate_responsive(moving, flags):
+            calls[0] += 1
+            r.temporal_accumulate_responsive(STEP_SPP, *cams[calls[0] % 2 if moving else 0], responsive_flags=flags)
+        for key, moving, flags, base in (("temporal_accumulate_responsive_same_camera", False, 0, "temporal_accumulate_same_camera"),
+                                         ("temporal_accumulate_responsive_projected", True, 0, "temporal_accumulate_projected"),
+                                         ("temporal_accumulate_responsive_moments_projected", True, pkg.RESPONSIVE_MOMENTS, None)):
+            t = timed(r, lambda: accumulate_responsive(moving, flags))
+            t["algorithmic_GB_per_s"] = w * h * (RESPONSIVE_BYTES_PER_PIXEL + (32 if flags else 0)) / (t["median_ms"] * 1e-3) / 1e9
+            if base:
+                t["minus_plain_call_ms"] = t["median_ms"] - rec[base]["median_ms"]
+            T = r.read_temporal()
+            t["share_of_valid_pixels_below_max_history"] = float((T[..., 3][T[..., 3] > 0] < pkg.TEMPORAL_DEFAULTS["max_history"]).mean())
+            rec[key] = t
+        if temporal_only:
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
 
         def accumulate_moments(moving):
             calls[0] += 1

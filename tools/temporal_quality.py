@@ -9,6 +9,10 @@ last frame is compared with a 192-spp render at its pose.
                                                 then the variance-guided filter (section 16, tests/variance_ref.py) over iterations x
                                                 sigmaLuminance at 8, 4, 2 and 1 frames of history
     python tools/temporal_quality.py --write    (re)writes tests/golden/temporal_truth.npz, the 192-spp means as binary16
+    python tools/temporal_quality.py --responsive   the responsive history (section 19, tests/responsive_ref.py): two sequences with a
+                                                moving light on animated_test and the three sliding-camera sequences as controls; the
+                                                sweep fastHistory x clampSigma, best geometric mean first, and the table at
+                                                RESPONSIVE_DEFAULTS; with --write also tests/golden/responsive_truth.npz
 
 tests/test_temporal.py's quality test reads that file and recomputes the sequence; the file holds the two scenes that test uses
 (a committed file stays below 100 KB), the truth of the third is rendered on every run of this tool.
@@ -29,10 +33,13 @@ import __graft_entry__ as graft  # noqa: E402
 import denoise_ref as R  # noqa: E402
 import temporal_ref as TR  # noqa: E402
 import variance_ref as VR  # noqa: E402
+import responsive_ref as RR  # noqa: E402
 
 SCENES = ("default", "texture_test", "alpha_test")
 GOLDEN_SCENES = ("default", "texture_test")
 TRUTH = os.path.join(REPO, "tests", "golden", "temporal_truth.npz")
+RESPONSIVE_TRUTH = os.path.join(REPO, "tests", "golden", "responsive_truth.npz")
+FAST_HISTORIES, CLAMP_SIGMAS = (2.0, 4.0, 8.0), (1.0, 1.5, 2.0, 3.0, 4.0)
 
 
 def temporal(frames, max_history, t):
@@ -61,13 +68,74 @@ def variance_guided(T, V0, frame, p, iterations=None):
                          np.float32)[0]
 
 
+def responsive(frames, t, fast_history, clamp_sigma):
+    """(T of the last frame, share of the valid pixels clamped per frame) of ptx_temporal_accumulate_responsive over `frames`"""
+    T, _, _, _, dec = RR.run_sequence(frames, t["max_history"], t["normal_threshold"], t["position_threshold"], fast_history, clamp_sigma, np.float32)
+    return T[-1], [float(d["clamped"].sum()) / max(1, int(d["valid"].sum())) for d in dec]
+
+
+def responsive_main(pkg, orc, write):
+    t0 = time.time()
+    td, dd, cd = pkg.TEMPORAL_DEFAULTS, pkg.DENOISE_DEFAULTS, pkg.TEMPORAL_DENOISE_DEFAULTS
+    shared = RR.light_scene(pkg, orc)
+    seqs = {kind: RR.light_sequence(shared, pkg, kind) for kind in RR.LIGHT_SEQUENCES}
+    truth = {}
+    if write or not os.path.exists(RESPONSIVE_TRUTH):
+        lit = RR.render_lit(shared, pkg, RR.LIGHT_X_TO, TR.QUALITY_TRUTH_SPP, TR.QUALITY_TRUTH_FIRST_SAMPLE)
+        np.savez_compressed(RESPONSIVE_TRUTH, light=(lit[..., 0:3] / TR.QUALITY_TRUTH_SPP).astype(np.float16))
+        print(f"wrote {RESPONSIVE_TRUTH} ({os.path.getsize(RESPONSIVE_TRUTH)} bytes)")
+    light = np.load(RESPONSIVE_TRUTH)["light"].astype(np.float32)
+    for kind in RR.LIGHT_SEQUENCES:
+        truth[kind] = light
+    # how much the two end positions differ: the 192-spp means with the light at either end
+    start = RR.render_lit(shared, pkg, RR.LIGHT_X_FROM, TR.QUALITY_TRUTH_SPP, 2 * TR.QUALITY_TRUTH_FIRST_SAMPLE)[..., 0:3] / TR.QUALITY_TRUTH_SPP
+    valid = shared[2][0][..., 3] == 1
+    la, lb = VR.lum(start, np.float32)[valid], VR.lum(light, np.float32)[valid]
+    with np.errstate(all="ignore"):
+        ratio = np.maximum(la, lb) / np.minimum(la, lb)
+    print(f"light at x = {RR.LIGHT_X_FROM} and at x = {RR.LIGHT_X_TO}: the luminance differs by more than a factor of 2 on {100.0 * (ratio > 2).mean():.1f} % of the "
+          f"{int(valid.sum())} valid pixels")
+    controls = np.load(TRUTH)
+    for name in SCENES:
+        scene, seqs[name] = TR.quality_sequence(pkg, orc, name)
+        if name in controls:
+            truth[name] = controls[name].astype(np.float32)
+        else:
+            S = TR.render_oracle_sum(orc, scene, TR.QUALITY_W, TR.QUALITY_H, TR.QUALITY_TRUTH_SPP, TR.QUALITY_TRUTH_FIRST_SAMPLE)
+            truth[name] = (S[..., 0:3] / TR.QUALITY_TRUTH_SPP).astype(np.float16).astype(np.float32)
+    names = list(RR.LIGHT_SEQUENCES) + list(SCENES)
+    print(f"sequences rendered in {time.time() - t0:.0f} s")
+    rows = []
+    for fh, cs in itertools.product(FAST_HISTORIES, CLAMP_SIGMAS):
+        e = [R.relative_l2(responsive(seqs[n], td, fh, cs)[0], truth[n]) for n in names]
+        rows.append((float(np.exp(np.mean(np.log(e)))), fh, cs, e))
+    rows.sort(key=lambda r: r[0])
+    print(f"temporal {td}\ngeometric mean  fastHistory  clampSigma   " + "  ".join(names))
+    for score, fh, cs, e in rows:
+        print(f"{score:.4f}          {fh:4.0f}         {cs:4.2f}         " + "  ".join(f"{v:.4f}" for v in e))
+    rd = pkg.RESPONSIVE_DEFAULTS
+    print(f"head of the list: fast_history {rows[0][1]}, clamp_sigma {rows[0][2]}; RESPONSIVE_DEFAULTS {rd}\nchained {cd}, spatial alone {dd}")
+    print("sequence        raw     spatial  temporal  chained  responsive  responsive chained   clamped, mean over the frames / last frame")
+    for n in names:
+        last = seqs[n][-1]
+        spp = last[4]
+        T = temporal(seqs[n], td["max_history"], td)[0]
+        Tr, share = responsive(seqs[n], td, rd["fast_history"], rd["clamp_sigma"])
+        e = [R.relative_l2(last[0][..., 0:3] / spp, truth[n]), R.relative_l2(filtered(last[0], last, spp, dd), truth[n]), R.relative_l2(T, truth[n]),
+             R.relative_l2(filtered(T, last, 1, cd), truth[n]), R.relative_l2(Tr, truth[n]), R.relative_l2(filtered(Tr, last, 1, cd), truth[n])]
+        print(f"  {n:14s}{e[0]:.4f}  {e[1]:.4f}   {e[2]:.4f}    {e[3]:.4f}   {e[4]:.4f}      {e[5]:.4f}               {100.0 * np.mean(share):.1f} % / {100.0 * share[-1]:.1f} %")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--write", action="store_true")
+    ap.add_argument("--responsive", action="store_true")
     args = ap.parse_args()
     pkg, orc = graft.load_package(), graft.load_oracle()
     orc.build()
+    if args.responsive:
+        return responsive_main(pkg, orc, args.write)
     t0 = time.time()
     seqs, truth = {}, {}
     write = args.write or not os.path.exists(TRUTH)
