@@ -812,9 +812,7 @@ __global__ void k_karras(int n, const uint64_t *__restrict__ keys, int2 *__restr
 // 32, 64} x shape {0, 0.25, 1} moves by 5-10 % per scene with no setting best everywhere (temple_like: 2.86 M at (64, 1), 3.18 M at
 // (16, 0); street_like: 3.96 M at (8, 0), 4.75 M at (64, 0), 3.78 M at (8, 1) over a Morton curve with cubic cells, which costs
 // chess_like and atrium_like 3-5 %).  So ptx_build_accel builds a few candidates and keeps the tree that costs the sampled rays
-// least (kTreeCandidates).  These constants are the parameters of builds that skip the comparison.
-constexpr int kPlocRadius = 16;
-constexpr float kPlocShape = 0.0f;
+// least (kTreeCandidates).  kPlocRadius / kPlocShape (pt_env.hpp, beside TreeParams) are the parameters of builds that skip the comparison.
 
 __global__ void k_ploc_init(uint32_t n, const uint32_t *__restrict__ vals, const float4 *__restrict__ boxLo, const float4 *__restrict__ boxHi,
                             int *__restrict__ cluster, float4 *__restrict__ cLo, float4 *__restrict__ cHi)

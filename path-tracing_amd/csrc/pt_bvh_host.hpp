@@ -1,6 +1,8 @@
 // pt_bvh_host.hpp -- host side of the tree build (kernels: pt_bvh_build.hpp): the scan and sort helpers, the level lists, the
 // stages of one build, buildAccel that strings them together, and buildBestTree that prices a few trees and keeps the cheapest.
-// Included by pt_runtime.hpp below the renderer object (PtxRenderer, DevBuf, HIP_TRY, fail); a stage returns a PTX_* code.
+// Included by pt_runtime.hpp below the renderer object (PtxRenderer, DevBuf, HIP_TRY, fail); a stage returns a PTX_* code.  The state
+// is AccelState, the member `accel` of the handle: the Tree in use (its four buffers and the three numbers that describe them move
+// together), the BuildState a refit reuses, the TreeParams.
 #pragma once
 
 // Exclusive scan in place of `count` 32-bit counts; blockSums holds one word per kScan32Block counts (unused for one block).
@@ -43,7 +45,7 @@ struct RefSet
 // kernels.  Scratch: B.keys0 / keys1 (the Morton keys are done with), B.hist / histSums.
 static int treeLevels(PtxRenderer *r, uint32_t nv)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     B.levelsValid = false;
     if (nv < 2)
         return PTX_OK;
@@ -104,7 +106,7 @@ static int treeLevels(PtxRenderer *r, uint32_t nv)
 // arrival flags, only for a tree the lists cannot take or with PTX_FENCE_REFIT.
 static int bottomUpPass(PtxRenderer *r, const RefSet &refs, uint32_t nv, bool price, bool askForLists)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     int rc;
     if (askForLists && !r->env.fenceRefit && (rc = treeLevels(r, nv)) != PTX_OK)
         return rc;
@@ -135,7 +137,7 @@ static int bottomUpPass(PtxRenderer *r, const RefSet &refs, uint32_t nv, bool pr
 // no tree: it invalidates the kept state (the buffers stay for reuse).
 static int triangleRecords(PtxRenderer *r, bool refit)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t nTri = r->scene.triCount;
     if (!refit)
     {
@@ -152,7 +154,7 @@ static int triangleRecords(PtxRenderer *r, bool refit)
     // [0..5] centroid bounds (ordered floats), [6] references in the tree (k_count_valid), [7] a refit found a revived triangle
     const uint32_t initBounds[8] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u };
     HIP_TRY(r, hipMemcpyAsync(B.sceneBounds.p, initBounds, sizeof(initBounds), hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evA, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evA.get(), r->stream));
     k_tri_setup<<<(nTri + 255) / 256, 256, 0, r->stream>>>(nTri, r->scene.pairCount, r->scene.pairFirst.p, r->scene.pairs.p, r->scene.vertices.p, r->scene.indices.p, B.triTmp.p,
                                                           B.boxLo.p, B.boxHi.p, B.sceneBounds.p, B.inert.p, refit ? 1 : 0);
     return PTX_OK;
@@ -162,20 +164,20 @@ static int triangleRecords(PtxRenderer *r, bool refit)
 // of references made; left alone if the budget buys none.
 static int splitReferences(PtxRenderer *r, uint32_t *n)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t nTri = r->scene.triCount, tb = (nTri + 255) / 256;
     DevBuf<float> priority;
     DevBuf<uint32_t> count, sums;
     DevBuf<unsigned long long> sum;
     HIP_TRY(r, priority.alloc(nTri)); HIP_TRY(r, count.alloc((size_t)nTri + 1)); HIP_TRY(r, sums.alloc((nTri + 1 + kScan32Block - 1) / kScan32Block));
     HIP_TRY(r, sum.alloc(1)); HIP_TRY(r, hipMemsetAsync(sum.p, 0, sizeof(unsigned long long), r->stream));
-    k_split_priority<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p, r->tree.mortonCubic ? 1 : 0, priority.p, sum.p);
+    k_split_priority<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p, r->accel.params.mortonCubic ? 1 : 0, priority.p, sum.p);
     unsigned long long total = 0;
     HIP_TRY(r, hipMemcpyAsync(&total, sum.p, sizeof(total), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     if (!total)
         return PTX_OK;
-    const float perPriority = (float)((double)r->tree.splitBudget * nTri / ((double)total / kSplitPriorityScale));
+    const float perPriority = (float)((double)r->accel.params.splitBudget * nTri / ((double)total / kSplitPriorityScale));
     HIP_TRY(r, hipMemsetAsync(count.p + nTri, 0, sizeof(uint32_t), r->stream));
     k_split_count<<<tb, 256, 0, r->stream>>>(nTri, priority.p, perPriority, count.p);
     scanExclusive32(r->stream, nTri + 1, count.p, sums.p);
@@ -185,7 +187,7 @@ static int splitReferences(PtxRenderer *r, uint32_t *n)
     if (refs <= nTri || refs > kMaxTriangles)
         return PTX_OK;
     HIP_TRY(r, B.refLo.alloc(refs)); HIP_TRY(r, B.refHi.alloc(refs)); HIP_TRY(r, B.refTri.alloc(refs)); HIP_TRY(r, B.refInert.alloc(refs));
-    k_split_write<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p, r->tree.mortonCubic ? 1 : 0, count.p, refs,
+    k_split_write<<<tb, 256, 0, r->stream>>>(nTri, B.triTmp.p, B.boxLo.p, B.boxHi.p, B.inert.p, B.sceneBounds.p, r->accel.params.mortonCubic ? 1 : 0, count.p, refs,
                                             B.refLo.p, B.refHi.p, B.refTri.p, B.refInert.p);
     HIP_TRY(r, hipStreamSynchronize(r->stream)); // (count and priority go out of scope)
     *n = refs;
@@ -196,7 +198,7 @@ static int splitReferences(PtxRenderer *r, uint32_t *n)
 // write.  *n is the number of references made; left alone if no two triangles pair.
 static int pairReferences(PtxRenderer *r, uint32_t *n)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t nTri = r->scene.triCount, tb = (nTri + 255) / 256;
     DevBuf<uint8_t> link;
     DevBuf<uint32_t> s0, s1, head, sums;
@@ -230,15 +232,15 @@ static int pairReferences(PtxRenderer *r, uint32_t *n)
 // A refit keeps the references of the last full build, and recomputes the union boxes of the pairs like a full build does.
 static int leafReferences(PtxRenderer *r, bool refit, bool keepState, RefSet *refs)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t nTri = r->scene.triCount;
     uint32_t n = refit ? B.refCount : nTri;
     int rc;
     if (!refit)
     {
-        if (!keepState && r->tree.splitBudget > 0.0f && nTri > 1 && (rc = splitReferences(r, &n)) != PTX_OK)
+        if (!keepState && r->accel.params.splitBudget > 0.0f && nTri > 1 && (rc = splitReferences(r, &n)) != PTX_OK)
             return rc;
-        if (r->env.pairLeaves && r->tree.splitBudget <= 0.0f && nTri > 1 && (rc = pairReferences(r, &n)) != PTX_OK)
+        if (r->env.pairLeaves && r->accel.params.splitBudget <= 0.0f && nTri > 1 && (rc = pairReferences(r, &n)) != PTX_OK)
             return rc;
         B.pairRefs = n < nTri;
         B.refCount = n;
@@ -264,16 +266,16 @@ struct PlocScratch
 // What a full build needs per reference, the tree's own arrays included (a refit reuses all of it).
 static int referenceBuffers(PtxRenderer *r, uint32_t n, uint32_t slotCap, PlocScratch &ploc)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t histCount = 256 * ((n + kSortTile - 1) / kSortTile);
-    HIP_TRY(r, r->nodes.alloc(n)); // (as many as the emitted array: the two change places in the depth-first relayout)
-    HIP_TRY(r, r->tris.alloc(slotCap)); HIP_TRY(r, r->shadeTris.alloc(slotCap));
+    HIP_TRY(r, r->accel.tree.nodes.alloc(n)); // (as many as the emitted array: the two change places in the depth-first relayout)
+    HIP_TRY(r, r->accel.tree.tris.alloc(slotCap)); HIP_TRY(r, r->accel.tree.shadeTris.alloc(slotCap));
     HIP_TRY(r, B.nodeLo.alloc(n)); HIP_TRY(r, B.nodeHi.alloc(n)); HIP_TRY(r, B.vals0.alloc(n)); HIP_TRY(r, B.vals1.alloc(n));
     HIP_TRY(r, B.hist.alloc(histCount)); HIP_TRY(r, B.histSums.alloc((histCount + kScan32Block - 1) / kScan32Block)); HIP_TRY(r, B.flags.alloc(n));
     HIP_TRY(r, B.keys0.alloc(n)); HIP_TRY(r, B.keys1.alloc(n));
     HIP_TRY(r, B.children.alloc(n)); HIP_TRY(r, B.parentOfNode.alloc(n)); HIP_TRY(r, B.parentOfLeaf.alloc(n));
     HIP_TRY(r, B.rawNodes.alloc(n)); HIP_TRY(r, B.oldOf.alloc((size_t)n + 1)); HIP_TRY(r, B.collapseCost.alloc(n)); HIP_TRY(r, B.collapseDecide.alloc(n));
-    if (r->usePloc && n > 1)
+    if (r->accel.usePloc && n > 1)
     {
         HIP_TRY(r, ploc.cl0.alloc(n)); HIP_TRY(r, ploc.cl1.alloc(n)); HIP_TRY(r, ploc.lo0.alloc(n)); HIP_TRY(r, ploc.hi0.alloc(n)); HIP_TRY(r, ploc.lo1.alloc(n));
         HIP_TRY(r, ploc.hi1.alloc(n)); HIP_TRY(r, ploc.nn.alloc(n)); HIP_TRY(r, ploc.flags.alloc(n)); HIP_TRY(r, ploc.sums.alloc((n + kScanBlock - 1) / kScanBlock));
@@ -286,8 +288,8 @@ static int referenceBuffers(PtxRenderer *r, uint32_t n, uint32_t slotCap, PlocSc
 // zero-area ones, which sort to the end), B.slotOf for pair leaves.  Kept for refits.
 static int sortReferences(PtxRenderer *r, const RefSet &refs)
 {
-    PtxRenderer::BuildState &B = r->build;
-    k_morton<<<(refs.n + 255) / 256, 256, 0, r->stream>>>(refs.n, refs.lo, refs.hi, B.sceneBounds.p, refs.inert, B.keys0.p, B.vals0.p, r->tree.mortonCubic ? 1 : 0);
+    BuildState &B = r->accel.build;
+    k_morton<<<(refs.n + 255) / 256, 256, 0, r->stream>>>(refs.n, refs.lo, refs.hi, B.sceneBounds.p, refs.inert, B.keys0.p, B.vals0.p, r->accel.params.mortonCubic ? 1 : 0);
     // 63-bit keys + the all-ones sentinel of inert triangles: 8 passes, which ping-pong the buffers an even number of times
     for (uint32_t shift = 0; shift < 64; shift += 16)
     {
@@ -313,8 +315,8 @@ static int sortReferences(PtxRenderer *r, const RefSet &refs)
 // Binary topology over the nv sorted references, with its boxes: PLOC (which computes them as it merges), or Karras.
 static int binaryTopology(PtxRenderer *r, const RefSet &refs, uint32_t nv, PlocScratch &ploc)
 {
-    PtxRenderer::BuildState &B = r->build;
-    if (!r->usePloc)
+    BuildState &B = r->accel.build;
+    if (!r->accel.usePloc)
     {
         k_karras<<<(nv + 255) / 256, 256, 0, r->stream>>>((int)nv, B.keys0.p, B.children.p, B.parentOfNode.p, B.parentOfLeaf.p);
         return bottomUpPass(r, refs, nv, false, true);
@@ -328,7 +330,7 @@ static int binaryTopology(PtxRenderer *r, const RefSet &refs, uint32_t nv, PlocS
     while (count > 1)
     {
         const uint32_t cb = (count + 255) / 256, sb = (count + kScanBlock - 1) / kScanBlock;
-        k_ploc_nearest<<<cb, 256, 0, r->stream>>>(count, r->tree.plocRadius, r->tree.plocShape, lIn, hIn, ploc.nn.p);
+        k_ploc_nearest<<<cb, 256, 0, r->stream>>>(count, r->accel.params.plocRadius, r->accel.params.plocShape, lIn, hIn, ploc.nn.p);
         k_ploc_flags<<<cb, 256, 0, r->stream>>>(count, ploc.nn.p, ploc.flags.p);
         k_scan64_sums<<<sb, 256, 0, r->stream>>>(count, ploc.flags.p, ploc.sums.p);
         k_scan64_top<<<1, 1024, 0, r->stream>>>(sb, ploc.sums.p, ploc.total.p);
@@ -357,7 +359,7 @@ static int binaryTopology(PtxRenderer *r, const RefSet &refs, uint32_t nv, PlocS
 // *broken: a pass left something that is not a tree; the caller starts the build again (this handle reinserts no more).
 static int reinsertionPasses(PtxRenderer *r, const RefSet &refs, uint32_t nv, uint32_t passes, bool *broken)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t slots = 2 * nv - 1, sblocks = (slots + 255) / 256;
     DevBuf<int> target, top;
     DevBuf<float> gain;
@@ -388,7 +390,7 @@ static int reinsertionPasses(PtxRenderer *r, const RefSet &refs, uint32_t nv, ui
         {
             // Not a tree any more (never seen since the path locks were completed, but the moves of a pass race by design):
             // this handle builds without reinsertion from now on, starting with this tree again.
-            r->reinsertBroken = true;
+            r->accel.reinsertBroken = true;
             fail(r, PTX_OK, "ptx_build_accel: reinsertion pass %u left %u bad parent links, %u leaves off the root: rebuilt without reinsertion",
                  pass, check[0], check[1]);
             if (r->env.verbose)
@@ -407,7 +409,7 @@ static int reinsertionPasses(PtxRenderer *r, const RefSet &refs, uint32_t nv, ui
 // each launch), then depth-first order if the tree asks for it.  stats.bvhNodes = the nodes that are live.
 static int relayoutNodes(PtxRenderer *r, uint32_t n, uint32_t nv)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     uint32_t *nextFree = B.oldOf.p + n;
     const uint32_t first[1] = { 0u }, one = 1u;
     HIP_TRY(r, hipMemcpyAsync(B.oldOf.p, first, sizeof(first), hipMemcpyHostToDevice, r->stream)); // the root stays node 0
@@ -417,7 +419,7 @@ static int relayoutNodes(PtxRenderer *r, uint32_t n, uint32_t nv)
     while (lo < hi)
     {
         levelStart.push_back(lo);
-        k_relayout_level<<<(hi - lo + 255) / 256, 256, 0, r->stream>>>(lo, hi, B.rawNodes.p, B.oldOf.p, nextFree, r->nodes.p);
+        k_relayout_level<<<(hi - lo + 255) / 256, 256, 0, r->stream>>>(lo, hi, B.rawNodes.p, B.oldOf.p, nextFree, r->accel.tree.nodes.p);
         uint32_t end = 0;
         HIP_TRY(r, hipMemcpyAsync(&end, nextFree, sizeof(end), hipMemcpyDeviceToHost, r->stream));
         HIP_TRY(r, hipStreamSynchronize(r->stream));
@@ -427,18 +429,18 @@ static int relayoutNodes(PtxRenderer *r, uint32_t n, uint32_t nv)
         hi = end;
         levels++;
     }
-    r->stats.bvhNodes = hi;
-    if (r->tree.layout == 1 && hi > 1)
+    r->stats.bvhNodes = r->accel.tree.nodeCount = hi;
+    if (r->accel.params.layout == 1 && hi > 1)
     {
         // depth-first order (k_subtree_size / _pos / k_place_nodes); scratch: the build's flags and the sort's second value array are done with
         levelStart.push_back(hi);
         uint32_t *size = B.flags.p, *pos = B.vals1.p;
         for (uint32_t l = levels; l-- > 0;)
-            k_subtree_size<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->nodes.p, size);
+            k_subtree_size<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->accel.tree.nodes.p, size);
         for (uint32_t l = 0; l < levels; l++)
-            k_subtree_pos<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->nodes.p, size, pos);
-        k_place_nodes<<<(hi + 255) / 256, 256, 0, r->stream>>>(hi, r->nodes.p, pos, B.rawNodes.p);
-        r->nodes.swap(B.rawNodes); // the emitted nodes are not needed again before the next k_emit, which rewrites them all
+            k_subtree_pos<<<(levelStart[l + 1] - levelStart[l] + 255) / 256, 256, 0, r->stream>>>(levelStart[l], levelStart[l + 1], r->accel.tree.nodes.p, size, pos);
+        k_place_nodes<<<(hi + 255) / 256, 256, 0, r->stream>>>(hi, r->accel.tree.nodes.p, pos, B.rawNodes.p);
+        r->accel.tree.nodes.swap(B.rawNodes); // the emitted nodes are not needed again before the next k_emit, which rewrites them all
     }
     if (r->env.verbose)
         std::fprintf(stderr, "[ptx] relayout: %u of %u emitted nodes are live, %u levels\n", hi, nv - 1, levels);
@@ -451,7 +453,7 @@ static int relayoutNodes(PtxRenderer *r, uint32_t n, uint32_t nv)
 // builds in full instead -- reinsertion left something that is not a tree, or a refit found a revived triangle.
 static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver)
 {
-    PtxRenderer::BuildState &B = r->build;
+    BuildState &B = r->accel.build;
     const uint32_t nTri = r->scene.triCount;
     int rc;
     RefSet refs;
@@ -464,41 +466,41 @@ static int buildOnce(PtxRenderer *r, bool refit, bool keepState, bool *startOver
         return rc;
     // triangle slots in the tree: the references', plus the second triangle of every pair (pairs are live: all in the tree)
     const uint32_t nv = B.treeTris, pairLeaves = B.pairRefs ? nTri - refs.n : 0u, slots = nv + pairLeaves;
-    r->treeTris = slots;
-    r->stats.bvhNodes = nv > 1 ? nv - 1 : (nv ? 1 : 0);
-    r->stats.treeReferences = slots;
+    r->accel.tree.slots = slots;
+    r->stats.bvhNodes = r->accel.tree.nodeCount = nv > 1 ? nv - 1 : (nv ? 1 : 0);
+    r->stats.treeReferences = r->accel.tree.references = slots;
     r->stats.treeTriangles = nTri - (refs.n - nv); // a zero-area triangle has exactly one reference, and they are the ones left out
     if (r->env.verbose && !refit && B.pairRefs)
         std::fprintf(stderr, "[ptx] pair leaves: %u (%u of %u tree triangles paired)\n", pairLeaves, 2 * pairLeaves, slots);
     if (nv == 1)
-        k_single_leaf_root<<<1, 1, 0, r->stream>>>(B.vals0.p, refs.lo, refs.hi, B.triTmp.p, r->nodes.p, r->tris.p, r->scene.pairs.p, r->scene.vertices.p,
-                                                   r->scene.indices.p, r->shadeTris.p, refs.tri, refs.pair);
+        k_single_leaf_root<<<1, 1, 0, r->stream>>>(B.vals0.p, refs.lo, refs.hi, B.triTmp.p, r->accel.tree.nodes.p, r->accel.tree.tris.p, r->scene.pairs.p, r->scene.vertices.p,
+                                                   r->scene.indices.p, r->accel.tree.shadeTris.p, refs.tri, refs.pair);
     else if (nv > 1)
     {
         if (refit)
             rc = bottomUpPass(r, refs, nv, false, false);
-        else if ((rc = binaryTopology(r, refs, nv, ploc)) == PTX_OK && r->tree.reinsertPasses && !r->reinsertBroken && nv > 3)
-            rc = reinsertionPasses(r, refs, nv, r->tree.reinsertPasses, startOver);
+        else if ((rc = binaryTopology(r, refs, nv, ploc)) == PTX_OK && r->accel.params.reinsertPasses && !r->accel.reinsertBroken && nv > 3)
+            rc = reinsertionPasses(r, refs, nv, r->accel.params.reinsertPasses, startOver);
         if (rc != PTX_OK || *startOver)
             return rc;
         // (PLOC computes its boxes itself: in a full build no pass before may have asked for the level lists yet)
-        if (r->tree.collapse && (rc = bottomUpPass(r, refs, nv, true, !refit && !B.levelsValid)) != PTX_OK)
+        if (r->accel.params.collapse && (rc = bottomUpPass(r, refs, nv, true, !refit && !B.levelsValid)) != PTX_OK)
             return rc;
         k_emit<<<(nv + 255) / 256, 256, 0, r->stream>>>((int)nv, B.vals0.p, refs.lo, refs.hi, B.children.p, B.nodeLo.p, B.nodeHi.p, B.triTmp.p,
-                                                       B.rawNodes.p, r->tris.p, r->scene.pairs.p, r->scene.vertices.p, r->scene.indices.p, r->shadeTris.p,
-                                                       r->tree.collapse ? B.collapseDecide.p : nullptr, refs.tri, B.pairRefs ? B.slotOf.p : nullptr, refs.pair);
+                                                       B.rawNodes.p, r->accel.tree.tris.p, r->scene.pairs.p, r->scene.vertices.p, r->scene.indices.p, r->accel.tree.shadeTris.p,
+                                                       r->accel.params.collapse ? B.collapseDecide.p : nullptr, refs.tri, B.pairRefs ? B.slotOf.p : nullptr, refs.pair);
         if ((rc = relayoutNodes(r, refs.n, nv)) != PTX_OK)
             return rc;
     }
     if (r->scene.anyNonOpaque && nv) // the any-hit records of the slots k_emit has just written
     {
-        HIP_TRY(r, r->alphaTris.alloc(slotCap));
-        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->tris.p, r->shadeTris.p, makeSceneView(r), r->scene.alphaTexOf.p, r->scene.alphaTex.p, r->alphaTris.p);
+        HIP_TRY(r, r->accel.tree.alphaTris.alloc(slotCap));
+        k_alpha_tris<<<(slots + 255) / 256, 256, 0, r->stream>>>(slots, r->accel.tree.tris.p, r->accel.tree.shadeTris.p, makeSceneView(r), r->scene.alphaTexOf.p, r->scene.alphaTex.p, r->accel.tree.alphaTris.p);
     }
     uint32_t revived = 0;
     if (refit)
         HIP_TRY(r, hipMemcpyAsync(&revived, &B.sceneBounds.p[7], sizeof(revived), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evB.get(), r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipGetLastError());
     *startOver = revived != 0; // a triangle the last full build left out has an area now: it is not in the kept topology
@@ -514,12 +516,12 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
     {
         if (!refit)
         {
-            HIP_TRY(r, r->nodes.alloc(1)); HIP_TRY(r, r->tris.alloc(1)); HIP_TRY(r, r->shadeTris.alloc(1));
+            HIP_TRY(r, r->accel.tree.nodes.alloc(1)); HIP_TRY(r, r->accel.tree.tris.alloc(1)); HIP_TRY(r, r->accel.tree.shadeTris.alloc(1));
         }
-        r->accelReady = true;
-        r->treeTris = 0;
-        r->stats.bvhNodes = 0;
-        r->stats.treeTriangles = r->stats.treeReferences = 0;
+        r->accel.ready = true;
+        r->accel.tree.slots = 0;
+        r->stats.bvhNodes = r->accel.tree.nodeCount = 0;
+        r->stats.treeTriangles = r->stats.treeReferences = r->accel.tree.references = 0;
         r->stats.lastBuildMs = 0.0;
         return PTX_OK;
     }
@@ -528,15 +530,15 @@ static int buildAccel(PtxRenderer *r, bool refit, bool keepState)
     while (rc == PTX_OK && startOver) // (twice at most: a refit, a full build, a full build without reinsertion)
         rc = buildOnce(r, false, keepState, &startOver);
     if (rc == PTX_OK && keepState)
-        r->build.valid = true;
+        r->accel.build.valid = true;
     else
-        r->build = PtxRenderer::BuildState(); // (a failed build leaves no state behind, a static scene frees its temporaries)
+        r->accel.build = BuildState(); // (a failed build leaves no state behind, a static scene frees its temporaries)
     if (rc != PTX_OK)
         return rc;
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r->evA, r->evB);
+    (void)hipEventElapsedTime(&ms, r->launch.evA.get(), r->launch.evB.get());
     r->stats.lastBuildMs = ms;
-    r->accelReady = true;
+    r->accel.ready = true;
     return PTX_OK;
 }
 
@@ -563,9 +565,9 @@ static int sampleTreeCost(PtxRenderer *r, DevBuf<float4> &segments, bool drawSeg
     if (drawSegments)
         k_sample_segments<<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, kTreeSampleRays, segments.p);
     if (r->scene.anyNonOpaque)
-        k_sample_tree_cost<true><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
+        k_sample_tree_cost<true><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->launch.spill.p, d.p);
     else
-        k_sample_tree_cost<false><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->spill.p, d.p);
+        k_sample_tree_cost<false><<<kTreeSampleRays / kBlock, kBlock, 0, r->stream>>>(sc, segments.p, kTreeSampleRays, r->launch.spill.p, d.p);
     std::vector<uint32_t> h(kTreeSampleRays);
     HIP_TRY(r, hipMemcpyAsync(h.data(), d.p, kTreeSampleRays * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
@@ -585,23 +587,14 @@ static int sampleTreeCost(PtxRenderer *r, DevBuf<float4> &segments, bool drawSeg
 struct TreeCandidate { uint32_t radius; float shape; bool cubic; };
 static TreeParams withCandidate(TreeParams t, const TreeCandidate &c) { t.plocRadius = c.radius; t.plocShape = c.shape; t.mortonCubic = c.cubic; return t; }
 
-// What the renderer says about the size of the tree in its buffers; it travels with a tree that is swapped aside.
-struct TreeSize
-{
-    uint64_t nodes = 0, references = 0;
-    uint32_t treeTris = 0; // (leaf slots: with pre-splitting the candidates can differ -- cubic cells move the cut planes)
-    static TreeSize of(const PtxRenderer *r) { return { r->stats.bvhNodes, r->stats.treeReferences, r->treeTris }; }
-    void restore(PtxRenderer *r) const { r->stats.bvhNodes = nodes; r->stats.treeReferences = references; r->treeTris = treeTris; }
-};
-
 static int buildBestTree(PtxRenderer *r)
 {
-    if (r && r->sceneOwner)
+    if (r && r->link.owner)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_build_accel: this renderer shares another renderer's scene (ptx_share_scene)");
-    if (!r || !r->sceneReady)
+    if (!r || !r->link.ready)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_build_accel: no scene uploaded");
     quiesceSharers(r);
-    r->sceneEpoch++; // schedules learnt on the old tree's scene are not this one's (ptx_scene_upload without a build in between cannot render)
+    r->link.epoch++; // schedules learnt on the old tree's scene are not this one's (ptx_scene_upload without a build in between cannot render)
     // Which tree?  Build a few candidates, price each on the same sampled surface-to-surface segments, keep the cheapest (its
     // buffers are swapped aside while the others are built; lastBuildMs is the time of everything).  Parameters given in the
     // environment, the Karras builder and small scenes skip the comparison; the per-frame rebuilds of an animation use the
@@ -612,39 +605,34 @@ static int buildBestTree(PtxRenderer *r)
     static const TreeCandidate kTreeCandidates[] = { { 8u, 0.0f, false }, { 16u, 0.0f, false }, { 16u, 0.25f, false }, { 32u, 1.0f, false }, { 8u, 1.0f, true },
                                                      { 64u, 0.25f, false }, { 4u, 0.25f, false } };
     constexpr uint32_t kCandidates = sizeof(kTreeCandidates) / sizeof(kTreeCandidates[0]);
-    if (!r->usePloc || r->env.plocFixed || r->scene.triCount < 4096u)
+    if (!r->accel.usePloc || r->env.plocFixed || r->scene.triCount < 4096u)
     {
         // ONE tree: it gets the full number of reinsertion passes at once
-        const TreeParams keep = r->tree;
-        r->tree.reinsertPasses = std::max(keep.reinsertPasses, keep.reinsertFinal);
+        const TreeParams keep = r->accel.params;
+        r->accel.params.reinsertPasses = std::max(keep.reinsertPasses, keep.reinsertFinal);
         const int rc = buildAccel(r, false, false);
-        r->tree = keep;
+        r->accel.params = keep;
         return rc;
     }
-    DevBuf<BvhNode> bestNodes;
-    DevBuf<Tri> bestTris;
-    DevBuf<ShadeTri> bestShadeTris;
-    DevBuf<AlphaTri> bestAlphaTris;
+    AccelState::Tree bestTree; // buffers and size together (leaf slots: with pre-splitting the candidates can differ -- cubic cells move the cut planes)
     DevBuf<float4> segments;
-    auto swapTree = [&]() { r->nodes.swap(bestNodes); r->tris.swap(bestTris); r->shadeTris.swap(bestShadeTris); r->alphaTris.swap(bestAlphaTris); };
     TreeCost cost[kCandidates];
-    TreeSize bestSize;
     double totalMs = 0.0;
     uint32_t best = 0, built = 0;
-    const TreeParams given = r->tree; // what the candidates do not vary (the collapse)
-    // While candidates are built the renderer's buffers hold whichever tree was built last and the best one sits in the locals
+    const TreeParams given = r->accel.params; // what the candidates do not vary (the collapse)
+    // While candidates are built the renderer's tree is whichever was built last and the best one sits in the local
     // above: nothing may render (or borrow the scene) until the final swap.  A candidate that fails (out of memory, a device
     // error) does not take the scene down with it when an earlier one succeeded: that tree, its parameters and its node count
     // are put back and the build succeeds with it.
-    r->accelReady = false;
+    r->accel.ready = false;
     for (uint32_t k = 0; k < kCandidates; k++)
     {
-        r->tree = withCandidate(given, kTreeCandidates[k]);
+        r->accel.params = withCandidate(given, kTreeCandidates[k]);
         int rc = buildAccel(r, false, false);
         totalMs += r->stats.lastBuildMs;
         if (rc != PTX_OK || (rc = sampleTreeCost(r, segments, k == 0, &cost[k])) != PTX_OK)
         {
-            r->accelReady = false;
+            r->accel.ready = false;
             if (k == 0)
                 return rc; // no tree at all: the error stands (ptx_last_error has the text)
             if (r->env.verbose)
@@ -655,8 +643,7 @@ static int buildBestTree(PtxRenderer *r)
         if (k == 0 || cost[k].figure() < cost[best].figure())
         {
             best = k;
-            bestSize = TreeSize::of(r);
-            swapTree(); // the renderer's buffers now hold the previous best (or nothing): the next candidate is built over them
+            r->accel.tree.swap(bestTree); // the renderer's tree is now the previous best (or nothing): the next candidate is built over it
         }
     }
     // The winner once more, with the full number of reinsertion passes (the candidates had a few: the ranking is the same with 2
@@ -666,25 +653,23 @@ static int buildBestTree(PtxRenderer *r)
     bool haveFinal = false;
     if (given.reinsertFinal > given.reinsertPasses && built > 0)
     {
-        r->tree = withCandidate(given, kTreeCandidates[best]);
-        r->tree.reinsertPasses = given.reinsertFinal;
+        r->accel.params = withCandidate(given, kTreeCandidates[best]);
+        r->accel.params.reinsertPasses = given.reinsertFinal;
         int rc = buildAccel(r, false, false);
         totalMs += r->stats.lastBuildMs;
         if (rc == PTX_OK && sampleTreeCost(r, segments, false, &finalCost) == PTX_OK && finalCost.figure() <= cost[best].figure())
-        {
             haveFinal = true;
-            bestSize = TreeSize::of(r);
-        }
         else if (r->env.verbose)
             std::fprintf(stderr, "[ptx] the fully re-optimised tree was not kept (%s)\n", rc == PTX_OK ? "no cheaper" : r->error.c_str());
-        r->accelReady = false;
+        r->accel.ready = false;
     }
     if (!haveFinal)
-        swapTree();
-    bestSize.restore(r);
-    r->tree = withCandidate(given, kTreeCandidates[best]);
+        r->accel.tree.swap(bestTree);
+    r->stats.bvhNodes = r->accel.tree.nodeCount; // the statistics are those of the tree in use
+    r->stats.treeReferences = r->accel.tree.references;
+    r->accel.params = withCandidate(given, kTreeCandidates[best]);
     r->stats.lastBuildMs = totalMs;
-    r->accelReady = true;
+    r->accel.ready = true;
     if (r->env.verbose)
     {
         std::fprintf(stderr, "[ptx] tree cost on %u sampled rays, mean (lowest 99.9 %%) / p99.9 / max visits + tests per ray:", kTreeSampleRays);

@@ -86,14 +86,14 @@ static int renderGuides(PtxRenderer *r, const PtxRaygenUniformData *uniform, boo
         const auto launch = [&](auto... prev) { // nothing, or the PrevPose of a motion pass
             withMode(kernelMode(r), [&](auto M) {
                 k_render_guides<decltype(M)::value, sizeof...(prev) != 0><<<grid, kBlock, 0, r->stream>>>(
-                    p, sv, sc, c.guidePtr(PTX_GUIDE_NORMAL, n), c.guidePtr(PTX_GUIDE_POSITION, n), c.guidePtr(PTX_GUIDE_ALBEDO, n), r->counters.p, r->spill.p, prev...);
+                    p, sv, sc, c.guidePtr(PTX_GUIDE_NORMAL, n), c.guidePtr(PTX_GUIDE_POSITION, n), c.guidePtr(PTX_GUIDE_ALBEDO, n), r->launch.counters.p, r->launch.spill.p, prev...);
             });
         };
         if (specular)
             withMode(kernelMode(r), [&](auto M) {
                 k_render_guides_specular<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(
                     p, sv, sc, c.guidePtr(PTX_GUIDE_NORMAL, n), c.guidePtr(PTX_GUIDE_POSITION, n), c.guidePtr(PTX_GUIDE_ALBEDO, n),
-                    c.specularPtr(PTX_SPECULAR_SURFACE, n), specular->maxBounces, specular->roughnessMax, r->counters.p, r->spill.p);
+                    c.specularPtr(PTX_SPECULAR_SURFACE, n), specular->maxBounces, specular->roughnessMax, r->launch.counters.p, r->launch.spill.p);
             });
         else if (motion)
         {

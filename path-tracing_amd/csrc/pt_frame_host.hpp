@@ -118,10 +118,10 @@ static float4 *hostFrameAlias(PtxRenderer *r, const void *pinnedHost, size_t byt
 // not host-coherent.
 static int ensureCopyEvents(PtxRenderer *r)
 {
-    if (!r->frame.evSnapshot)
+    if (!r->frame.evCopied) // (the second of the two: a call that failed between them makes it again)
     {
-        HIP_TRY(r, hipEventCreateWithFlags(&r->frame.evSnapshot, hipEventDisableTiming));
-        HIP_TRY(r, hipEventCreateWithFlags(&r->frame.evCopied, hipEventDisableTiming | hipEventReleaseToSystem));
+        HIP_TRY(r, createEvent(r->frame.evSnapshot, hipEventDisableTiming));
+        HIP_TRY(r, createEvent(r->frame.evCopied, hipEventDisableTiming | hipEventReleaseToSystem));
     }
     return PTX_OK;
 }
@@ -143,7 +143,7 @@ static int hostTarget(PtxRenderer *r, const void *pinnedHost, size_t bytes, cons
 // everything enqueued before it are released with it.
 static int markHostStoresPending(PtxRenderer *r, hipStream_t stream)
 {
-    HIP_TRY(r, hipEventRecord(r->frame.evCopied, stream));
+    HIP_TRY(r, hipEventRecord(r->frame.evCopied.get(), stream));
     r->frame.copyInFlight = true;
     return PTX_OK;
 }
@@ -200,12 +200,12 @@ static int readbackBegin(PtxRenderer *r, float *pinnedHost, size_t bytes)
     // keeps the handle to ONE stream (pt_stream_plan.hpp: its two do not fit the queues), the copy follows the snapshot on the main
     // stream: a second stream's wait for the snapshot would hold whichever queue that stream shares until this frame is done.
     const StreamPlan plan = planFor(r);
-    if (!plan.copyOnMain && !r->auxStream && !f.copyStream)
-        HIP_TRY(r, hipStreamCreateWithFlags(&f.copyStream, hipStreamNonBlocking));
-    const hipStream_t copyOn = plan.copyOnMain ? r->stream : r->auxStream ? r->auxStream : f.copyStream;
+    if (!plan.copyOnMain && !r->streams.aux && !f.copyStream)
+        HIP_TRY(r, createStreamOn(f.copyStream, 0xffu, r->device)); // (no mask: a plain non-blocking stream)
+    const hipStream_t copyOn = plan.copyOnMain ? r->stream : r->streams.aux.get() ? r->streams.aux.get() : f.copyStream.get();
     HIP_TRY(r, f.staging.alloc(f.pixels()));
     if (f.copyInFlight) // the previous copy still reads the staging image
-        HIP_TRY(r, hipStreamWaitEvent(r->stream, f.evCopied, 0));
+        HIP_TRY(r, hipStreamWaitEvent(r->stream, f.evCopied.get(), 0));
     // the snapshot by a copy KERNEL (33 MB at the memory's rate: ~20 us), not hipMemcpyAsync: the runtime's device-to-device copy
     // took 0.5 ms per 1080p image and the copies of the frames in flight queue behind one another -- a floor of 0.5 ms per step
     // under every renderer that reads back, half the step of a 1 / 8 tile shard (tools/experiments/gather_cost.sh, round 5)
@@ -216,10 +216,10 @@ static int readbackBegin(PtxRenderer *r, float *pinnedHost, size_t bytes)
         k_copy_out<<<1024, kBlock, 0, r->stream>>>(f.accum(), f.staging.p, (uint32_t)(bytes / sizeof(float4)));
         HIP_TRY(r, hipGetLastError()); // (a failed launch would hand the host a stale staging image)
     }
-    if (!plan.copyOnMain || r->auxIsMain) // (a handle that asked for one stream: enqueued exactly as before)
+    if (!plan.copyOnMain || r->streams.auxIsMain()) // (a handle that asked for one stream: enqueued exactly as before)
     {
-        HIP_TRY(r, hipEventRecord(f.evSnapshot, r->stream));
-        HIP_TRY(r, hipStreamWaitEvent(copyOn, f.evSnapshot, 0));
+        HIP_TRY(r, hipEventRecord(f.evSnapshot.get(), r->stream));
+        HIP_TRY(r, hipStreamWaitEvent(copyOn, f.evSnapshot.get(), 0));
     }
     // Host memory the device cannot address (not page-locked) takes the runtime's copy.
     float4 *const hostOnDevice = r->env.copyRuntime ? nullptr : hostFrameAlias(r, pinnedHost, bytes);
@@ -239,7 +239,7 @@ static int readbackEnd(PtxRenderer *r)
         return PTX_ERROR_INVALID_ARGUMENT;
     if (r->frame.copyInFlight)
     {
-        HIP_TRY(r, hipEventSynchronize(r->frame.evCopied));
+        HIP_TRY(r, hipEventSynchronize(r->frame.evCopied.get()));
         r->frame.copyInFlight = false;
     }
     return PTX_OK;

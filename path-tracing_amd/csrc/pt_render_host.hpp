@@ -1,7 +1,9 @@
 // pt_render_host.hpp -- ptx_render / ptx_render_frames / ptx_render_debug: the bounce schedule of the wavefront backend as named
-// stages, the megakernel and zero-bounce launches beside it, and what a launch leaves for the next one (collectRender).
-// Included by pt_runtime.hpp after pt_bvh_host.hpp; the state is three members of the handle: PathState (the per-slot buffers: the
-// list, their growth and the kernels' view of them are that one struct), PendingLaunch, ScheduleHint.
+// stages, the megakernel and zero-bounce launches beside it, what a launch leaves for the next one (collectRender) and for
+// ptx_get_stats (getStats).  Included by pt_runtime.hpp after pt_animation_host.hpp; the state is two members of the handle:
+// PathState (the per-slot buffers: the list, their growth and the kernels' view of them are that one struct) and LaunchState (lights
+// and launch parameters, counter block and its page-locked copy, spill regions, the span and bounce events -- each event an owner
+// that releases itself --, PendingLaunch, ScheduleHint); the streams are StreamSet's.
 #pragma once
 
 #include <type_traits>
@@ -40,28 +42,25 @@ __global__ void k_upload_lights(PtxLightsUbo lights, LaunchParams params, PtxLig
 // (a handle whose streams never fit the queues never makes one) and stays; nothing here runs again in the steady state.
 static int ensureRenderResources(PtxRenderer *r, uint32_t bounces, const StreamPlan &plan)
 {
-    if (!r->auxStream)
+    if (!r->streams.aux)
     {
         // PTX_DEVICE_SINGLE_STREAM (or PTX_SINGLE_STREAM=1 in the environment): the shadow and tail kernels ride on the main stream
         // too -- no overlap inside a frame, one hardware queue per frame in flight instead of two (twice the frames on the same
         // queues; what a rank's thin tile shard of an N-GPU job wants, include/ptx.h)
-        if (r->env.singleStream || r->singleStream)
-        {
-            r->auxStream = r->stream;
-            r->auxIsMain = true;
-        }
+        if (r->env.singleStream || r->streams.singleStream)
+            r->streams.aux.borrow(r->stream);
         else if (!plan.auxOnMain)
-            HIP_TRY(r, createStreamOn(&r->auxStream, r->auxXcds, r->device));
+            HIP_TRY(r, createStreamOn(r->streams.aux, r->streams.auxXcds, r->device));
     }
-    if (!r->spillAux.p)
-        HIP_TRY(r, r->spillAux.alloc((size_t)kGlobalSpill * kMaxPersistentThreads));
+    if (!r->launch.spillAux.p)
+        HIP_TRY(r, r->launch.spillAux.alloc((size_t)kGlobalSpill * kMaxPersistentThreads));
     const size_t want = bounces < (uint32_t)kMaxTimedBounces ? bounces : (uint32_t)kMaxTimedBounces;
-    while (r->bounceEvents.size() < want)
+    while (r->launch.bounceEvents.size() < want)
     {
-        PtxRenderer::BounceEvents e;
-        for (hipEvent_t *ev : { &e.t0, &e.t1, &e.t2, &e.x0, &e.x1, &e.x2 })
-            HIP_TRY(r, hipEventCreate(ev));
-        r->bounceEvents.push_back(e);
+        BounceEvents e; // pushed only when all six exist: a partial one releases itself
+        for (OwnedEvent *ev : { &e.t0, &e.t1, &e.t2, &e.x0, &e.x1, &e.x2 })
+            HIP_TRY(r, createEvent(*ev));
+        r->launch.bounceEvents.push_back(std::move(e));
     }
     return PTX_OK;
 }
@@ -86,7 +85,7 @@ struct RenderPlan
 // The two failures a counter block reports, from the host's copy of it.
 static int counterErrors(PtxRenderer *r)
 {
-    const uint32_t *h = r->hostCounters;
+    const uint32_t *h = r->launch.hostCounters.get();
     if (h[C_OVERFLOW])
         return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
     if (h[C_OVERFLOW + 1])
@@ -98,7 +97,7 @@ static int counterErrors(PtxRenderer *r)
 // first message can fire: C_OVERFLOW + 1 is k_megakernel's and k_finish_restarts', which have not run yet.)
 static int fetchCounters(PtxRenderer *r)
 {
-    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipMemcpyAsync(r->launch.hostCounters.get(), r->launch.counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     return counterErrors(r);
 }
@@ -147,21 +146,21 @@ static void launchTail(PtxRenderer *r, const RenderPlan &pl, int queue, uint32_t
 static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int qin, uint32_t est, int tail, bool fresh)
 {
     hipStream_t S = r->stream, X = pl.aux;
-    PtxRenderer::BounceEvents &ev = r->bounceEvents[(b - 1) % r->bounceEvents.size()];
+    BounceEvents &ev = r->launch.bounceEvents[(b - 1) % r->launch.bounceEvents.size()];
     const BounceCtl ctl = { b, 0u };
     const int qout = qin ^ 1, parity = (int)(b & 1u);
     k_prologue<<<1, 1, 0, S>>>(pl.wf, qin, ctl);
-    HIP_TRY(r, hipEventRecord(ev.t0, S));
+    HIP_TRY(r, hipEventRecord(ev.t0.get(), S));
     withFlag(pl.mode == 2, [&](auto ALPHA) {
-        const dim3 grid(traceGridFor(est, r->residentClosest[decltype(ALPHA)::value])); // (the FIRST variants hold the same occupancy)
+        const dim3 grid(traceGridFor(est, r->accel.residentClosest[decltype(ALPHA)::value])); // (the FIRST variants hold the same occupancy)
         if (fresh)
-            k_trace_closest<FirstBounce, decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, r->launchParams.p, pl.p.numSlots);
+            k_trace_closest<FirstBounce, decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, r->launch.launchParams.p, pl.p.numSlots);
         else
             k_trace_closest<decltype(ALPHA)::value><<<grid, kBlock, 0, S>>>(pl.sc, pl.wf, qin, ctl);
     });
-    HIP_TRY(r, hipEventRecord(ev.t1, S));
+    HIP_TRY(r, hipEventRecord(ev.t1.get(), S));
     if (b > 1 && pl.crossWaits) // shade reads rad[slot] and overwrites rayO[slot]: the previous bounce's shadow adds must have landed, its rays been read
-        HIP_TRY(r, hipStreamWaitEvent(S, r->bounceEvents[(b - 2) % r->bounceEvents.size()].x2, 0));
+        HIP_TRY(r, hipStreamWaitEvent(S, r->launch.bounceEvents[(b - 2) % r->launch.bounceEvents.size()].x2.get(), 0));
     const uint32_t shadeGrid = gridFor((est + kShadeItems - 1) / kShadeItems);
     withFlag(pl.mode >= 1, [&](auto TEXTURED) {
         constexpr bool TEX = decltype(TEXTURED)::value;
@@ -174,15 +173,15 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
         else
             k_shade<TEX><<<shadeGrid, kBlock, 0, S>>>(pl.p, pl.sv, pl.wf, qin, ctl);
     });
-    HIP_TRY(r, hipEventRecord(ev.t2, S));
+    HIP_TRY(r, hipEventRecord(ev.t2.get(), S));
     if (pl.crossWaits)
-        HIP_TRY(r, hipStreamWaitEvent(X, ev.t2, 0));
-    HIP_TRY(r, hipEventRecord(ev.x0, X));
+        HIP_TRY(r, hipStreamWaitEvent(X, ev.t2.get(), 0));
+    HIP_TRY(r, hipEventRecord(ev.x0.get(), X));
     withFlag(pl.mode == 2, [&](auto ALPHA) {
-        k_trace_shadow<decltype(ALPHA)::value><<<traceGridFor(est, r->residentShadow[decltype(ALPHA)::value]), kBlock, 0, X>>>(pl.p, pl.sc, pl.wfAux, qout, parity);
+        k_trace_shadow<decltype(ALPHA)::value><<<traceGridFor(est, r->accel.residentShadow[decltype(ALPHA)::value]), kBlock, 0, X>>>(pl.p, pl.sc, pl.wfAux, qout, parity);
     });
     k_apply_shadow<<<gridFor(est, kBlock, 4096u), kBlock, 0, X>>>(pl.p, pl.wfAux, parity);
-    HIP_TRY(r, hipEventRecord(ev.x1, X));
+    HIP_TRY(r, hipEventRecord(ev.x1.get(), X));
     if (tail)
     {
         // A hinted schedule (tail == 2) hands the tail whatever is left, and the hint is last frame's: a view that keeps four
@@ -191,7 +190,7 @@ static int enqueueBounce(PtxRenderer *r, const RenderPlan &pl, uint32_t b, int q
         const uint32_t room = tail == 2 ? 4u * pl.tailBelow : pl.tailBelow;
         launchTail(r, pl, qout, est < room ? est : room, { b, tail == 2 ? kTailAnyLength : pl.tailBelow });
     }
-    HIP_TRY(r, hipEventRecord(ev.x2, X));
+    HIP_TRY(r, hipEventRecord(ev.x2.get(), X));
     return PTX_OK;
 }
 
@@ -228,8 +227,8 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
     int qin = 0;
     if (hint)
     {
-        hintedSchedule(hint, pl.bounces, pl.tailBelow, upperBound, r->hint.steps);
-        for (const BounceStep &s : r->hint.steps)
+        hintedSchedule(hint, pl.bounces, pl.tailBelow, upperBound, r->launch.hint.steps);
+        for (const BounceStep &s : r->launch.hint.steps)
         {
             if (const int rc = enqueueBounce(r, pl, s.bounce, qin, s.est, s.tail, fresh && s.bounce == 1u))
                 return rc;
@@ -248,7 +247,7 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
             qin ^= 1;
             if (const int rc = fetchCounters(r))
                 return rc;
-            est = r->hostCounters[qin ? C_ACTIVE1 : C_ACTIVE0];
+            est = r->launch.hostCounters.get()[qin ? C_ACTIVE1 : C_ACTIVE0];
             if (est == 0u)
                 break;
             if (b < pl.bounces && est <= pl.tailBelow)
@@ -256,13 +255,13 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
                 // the queue is short: k_tail finishes it, behind the shadow kernel of this bounce on its stream
                 launchTail(r, pl, qin, est, { b, kTailAnyLength });
                 // re-recorded behind the tail: what the stream waits for below
-                HIP_TRY(r, hipEventRecord(r->bounceEvents[(b - 1) % r->bounceEvents.size()].x2, pl.aux));
+                HIP_TRY(r, hipEventRecord(r->launch.bounceEvents[(b - 1) % r->launch.bounceEvents.size()].x2.get(), pl.aux));
                 break;
             }
         }
     }
     if (last && pl.crossWaits)
-        HIP_TRY(r, hipStreamWaitEvent(r->stream, r->bounceEvents[(last - 1) % r->bounceEvents.size()].x2, 0));
+        HIP_TRY(r, hipStreamWaitEvent(r->stream, r->launch.bounceEvents[(last - 1) % r->launch.bounceEvents.size()].x2.get(), 0));
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;
 }
@@ -270,14 +269,14 @@ static int enqueueRound(PtxRenderer *r, const RenderPlan &pl, uint32_t upperBoun
 // Statistics and errors of the last wavefront or debug-view launch, once the device is done with it (blocks until then).
 static int collectRender(PtxRenderer *r)
 {
-    if (r->pending.kind == PendingLaunch::kNone)
+    if (r->launch.pending.kind == PendingLaunch::kNone)
         return PTX_OK;
-    const PendingLaunch pd = r->pending;
-    r->pending = PendingLaunch();
-    HIP_TRY(r, hipEventSynchronize(r->evB));
+    const PendingLaunch pd = r->launch.pending;
+    r->launch.pending = PendingLaunch();
+    HIP_TRY(r, hipEventSynchronize(r->launch.evB.get()));
     if (const int rc = counterErrors(r))
         return rc;
-    const uint32_t *h = r->hostCounters;
+    const uint32_t *h = r->launch.hostCounters.get();
     r->stats.shadowRays = h[C_HITS];
     r->stats.pathSamples = h[C_SAMPLES];
     if (pd.kind == PendingLaunch::kDebugView) // its counters are the kernel's own, no bounce schedule
@@ -296,22 +295,22 @@ static int collectRender(PtxRenderer *r)
     const uint32_t tailPaths = h[C_TAIL_PATHS], tailBounce = h[C_TAIL_PATHS + 1]; // k_tail took the queue shade(tailBounce) filled
     for (uint32_t b = 1; b <= timed; b++)
     {
-        const PtxRenderer::BounceEvents &ev = r->bounceEvents[b - 1];
+        const BounceEvents &ev = r->launch.bounceEvents[b - 1];
         const uint32_t active = h[C_BOUNCE_ACTIVE + b];
         const bool ran = active != 0u && !(tailPaths && b > tailBounce);
         if (!ran)
             continue;
         float closestMs = 0.0f, shadeMs = 0.0f, shadowMs = 0.0f, tailMs = 0.0f;
-        (void)hipEventElapsedTime(&closestMs, ev.t0, ev.t1);
-        (void)hipEventElapsedTime(&shadeMs, ev.t1, ev.t2);
-        (void)hipEventElapsedTime(&shadowMs, ev.x0, ev.x1);
+        (void)hipEventElapsedTime(&closestMs, ev.t0.get(), ev.t1.get());
+        (void)hipEventElapsedTime(&shadeMs, ev.t1.get(), ev.t2.get());
+        (void)hipEventElapsedTime(&shadowMs, ev.x0.get(), ev.x1.get());
         r->stats.lastTraceMs += closestMs;
         r->stats.lastShadeMs += shadeMs;
         r->stats.lastShadowMs += shadowMs;
         r->stats.traceLaunches += 2;
         if (tailPaths && tailBounce == b)
         {
-            (void)hipEventElapsedTime(&tailMs, ev.x1, ev.x2);
+            (void)hipEventElapsedTime(&tailMs, ev.x1.get(), ev.x2.get());
             r->stats.lastTailMs += tailMs;
         }
         if (pd.verbose)
@@ -327,12 +326,27 @@ static int collectRender(PtxRenderer *r)
     // grid / schedule hints for the next launch of this shape.  The queue k_tail took over is part of them (a truncated
     // schedule has no prologue behind its last bounce to record it); a tail that had to take more than its threshold
     // means the hints were off: forget them, the next launch runs the full schedule and learns again.
-    r->hint.active.assign(h + C_BOUNCE_ACTIVE, h + C_BOUNCE_ACTIVE + kMaxTimedBounces + 1);
+    r->launch.hint.active.assign(h + C_BOUNCE_ACTIVE, h + C_BOUNCE_ACTIVE + kMaxTimedBounces + 1);
     if (tailPaths && tailBounce + 1 <= (uint32_t)kMaxTimedBounces)
-        r->hint.active[tailBounce + 1] = tailPaths;
-    r->hint.slots = pd.slots; r->hint.bounces = pd.bounces; r->hint.epoch = pd.epoch;
+        r->launch.hint.active[tailBounce + 1] = tailPaths;
+    r->launch.hint.slots = pd.slots; r->launch.hint.bounces = pd.bounces; r->launch.hint.epoch = pd.epoch;
     if (tailPaths > pd.tailBelow)
-        r->hint.forget();
+        r->launch.hint.forget();
+    return PTX_OK;
+}
+
+// ptx_get_stats: waits for the main stream, collects the last launch, and reads the render / build span off its two events.
+static int getStats(PtxRenderer *r, PtxStats *stats)
+{
+    if (!r || !stats)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    if (const int rc = collectRender(r))
+        return rc;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, r->launch.evA.get(), r->launch.evB.get()) == hipSuccess)
+        r->stats.lastRenderMs = ms;
+    *stats = r->stats;
     return PTX_OK;
 }
 
@@ -349,22 +363,22 @@ static int beginLaunch(PtxRenderer *r, const PtxLightsUbo *lights, const LaunchP
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: too many path slots in one batch");
     if (slots)
         HIP_TRY(r, r->paths.ensure(kernelMode(r), (size_t)slots));
-    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, p, r->lights.p, r->launchParams.p);
-    HIP_TRY(r, hipMemsetAsync(r->counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
+    k_upload_lights<<<1, 256, 0, r->stream>>>(*lights, p, r->launch.lights.p, r->launch.launchParams.p);
+    HIP_TRY(r, hipMemsetAsync(r->launch.counters.p, 0, C_COUNT * sizeof(uint32_t), r->stream));
     r->stats.pathSamples = r->stats.segments = r->stats.shadowRays = r->stats.retries = r->stats.tracedRays = 0;
     r->stats.traceLaunches = 0;
     r->stats.lastTraceMs = r->stats.lastShadeMs = r->stats.lastShadowMs = r->stats.lastTailMs = 0.0;
-    HIP_TRY(r, hipEventRecord(r->evA, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evA.get(), r->stream));
     return PTX_OK;
 }
 
 // ... and close with: the counter block on its way to the host behind the launch, evB, and the record collectRender picks up.
 static int endLaunch(PtxRenderer *r, const PendingLaunch &pd)
 {
-    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+    HIP_TRY(r, hipMemcpyAsync(r->launch.hostCounters.get(), r->launch.counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evB.get(), r->stream));
     HIP_TRY(r, hipGetLastError());
-    r->pending = pd;
+    r->launch.pending = pd;
     return PTX_OK;
 }
 
@@ -374,7 +388,7 @@ static int renderZeroBounces(PtxRenderer *r, const LaunchParams &p, uint32_t sam
 {
     HIP_TRY(r, hipMemsetAsync(r->paths.slotRad.p, 0, (size_t)p.numSlots * sizeof(float4), r->stream));
     launchAccumulate(r, p);
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evB.get(), r->stream));
     HIP_TRY(r, hipGetLastError());
     r->stats.pathSamples = (uint64_t)p.ownedPixels * p.frames * sampleCount;
     return PTX_OK;
@@ -384,20 +398,20 @@ static int renderZeroBounces(PtxRenderer *r, const LaunchParams &p, uint32_t sam
 static int renderMegakernel(PtxRenderer *r, const RenderPlan &pl)
 {
     const dim3 grid((pl.p.numSlots + kBlock - 1) / kBlock);
-    withMode(pl.mode, [&](auto M) { k_megakernel<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(pl.p, pl.sv, pl.sc, r->paths.slotRad.p, r->counters.p); });
+    withMode(pl.mode, [&](auto M) { k_megakernel<decltype(M)::value><<<grid, kBlock, 0, r->stream>>>(pl.p, pl.sv, pl.sc, r->paths.slotRad.p, r->launch.counters.p); });
     launchAccumulate(r, pl.p);
-    HIP_TRY(r, hipMemcpyAsync(r->hostCounters, r->counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+    HIP_TRY(r, hipMemcpyAsync(r->launch.hostCounters.get(), r->launch.counters.p, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipEventRecord(r->launch.evB.get(), r->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipGetLastError());
-    if (r->hostCounters[C_OVERFLOW])
+    if (r->launch.hostCounters.get()[C_OVERFLOW])
         return fail(r, PTX_ERROR_DEVICE, "ptx_render: traversal stack overflow in the megakernel (depth > %d)", kLdsStackMega);
     if (const int rc = counterErrors(r))
         return rc;
-    r->stats.segments = r->hostCounters[C_SEGMENTS];
-    r->stats.shadowRays = r->hostCounters[C_HITS];
-    r->stats.pathSamples = r->hostCounters[C_SAMPLES];
-    r->stats.retries = r->hostCounters[C_RETRIES];
+    r->stats.segments = r->launch.hostCounters.get()[C_SEGMENTS];
+    r->stats.shadowRays = r->launch.hostCounters.get()[C_HITS];
+    r->stats.pathSamples = r->launch.hostCounters.get()[C_SAMPLES];
+    r->stats.retries = r->launch.hostCounters.get()[C_RETRIES];
     return PTX_OK;
 }
 
@@ -417,15 +431,15 @@ static int runSampleRounds(PtxRenderer *r, const RenderPlan &pl, uint32_t sample
     {
         if (const int rc = fetchCounters(r))
             return rc;
-        const uint32_t restarts = r->hostCounters[C_RESTART];
+        const uint32_t restarts = r->launch.hostCounters.get()[C_RESTART];
         if (!restarts)
             return PTX_OK;
         if (round > maxRounds)
             return fail(r, PTX_ERROR_DEVICE, "ptx_render: %u paths still active after %llu rounds", restarts, (unsigned long long)maxRounds);
         k_restart<<<gridFor(restarts), kBlock, 0, r->stream>>>(pl.p, pl.wf, restarts); // next primary ray of every re-queued slot
         HIP_TRY(r, hipMemcpyAsync(pl.wf.queue[0], pl.wf.restartQueue, (size_t)restarts * sizeof(uint32_t), hipMemcpyDeviceToDevice, r->stream));
-        HIP_TRY(r, hipMemsetAsync(&r->counters.p[C_RESTART], 0, sizeof(uint32_t), r->stream));
-        HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)restarts, 1, r->stream));
+        HIP_TRY(r, hipMemsetAsync(&r->launch.counters.p[C_RESTART], 0, sizeof(uint32_t), r->stream));
+        HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->launch.counters.p[C_ACTIVE0]), (int)restarts, 1, r->stream));
         if (const int rc = enqueueRound(r, pl, restarts, nullptr, false))
             return rc;
     }
@@ -450,25 +464,25 @@ static int renderWavefront(PtxRenderer *r, RenderPlan &pl, uint32_t sampleCount)
     const StreamPlan plan = planFor(r);
     if (const int rc = ensureRenderResources(r, pl.bounces, plan))
         return rc;
-    pl.aux = plan.auxOnMain ? r->stream : r->auxStream;
-    pl.crossWaits = !plan.auxOnMain || r->auxIsMain;
+    pl.aux = plan.auxOnMain ? r->stream : r->streams.aux.get();
+    pl.crossWaits = !plan.auxOnMain || r->streams.auxIsMain();
     pl.sortShade = r->env.shadeSort >= 0 ? (uint32_t)r->env.shadeSort : (sceneOf(r)->scene.mixedMaterialTypes || sceneOf(r)->scene.mixedTextured) ? 1u : 0u;
     // measured with 16 hardware queues (chess_like, ms per step at 25 / 50 / 75 / 100 / 200 / 400 K live paths): whole frame 8.04 / 7.82 /
     // 7.85 / 7.80 / 8.14 / 8.13, a rank's tile shard of 8: 1.44 / 1.44 / 1.39 / 1.39 / 1.54 / 1.55, of 4: 2.29 / 2.24 / 2.24 / 2.33 / 2.34 /
     // 2.77, of 2: 3.93 / 3.89 / 3.91 / 3.98 / 4.06 / 4.41; the other scenes are flat from 50 K to 200 K
     pl.tailBelow = r->env.tailThreshold >= 0 ? (uint32_t)r->env.tailThreshold : 75000u;
-    pl.wf = r->paths.view(pl.mode, r->counters.p, r->spill.p);
-    pl.wfAux = r->paths.view(pl.mode, r->counters.p, r->spillAux.p);
+    pl.wf = r->paths.view(pl.mode, r->launch.counters.p, r->launch.spill.p);
+    pl.wfAux = r->paths.view(pl.mode, r->launch.counters.p, r->launch.spillAux.p);
     const bool canonical = sampleCount == 1;
-    const uint64_t epoch = sceneOf(r)->sceneEpoch;
+    const uint64_t epoch = sceneOf(r)->link.epoch;
     // the learnt schedule belongs to (shape of the launch, scene it was learnt on); a camera or light change inside one scene
     // keeps it -- a hint that is off costs time, never results, and the tail's grid leaves room for that (enqueueBounce)
-    const uint32_t *hint = canonical && r->hint.matches(p.numSlots, pl.bounces, epoch) ? r->hint.active.data() : nullptr;
+    const uint32_t *hint = canonical && r->launch.hint.matches(p.numSlots, pl.bounces, epoch) ? r->launch.hint.active.data() : nullptr;
     // the primary rays: computed by the first bounce's kernels, or handed over through memory by k_generate (PTX_FIRST_BOUNCE=0)
     const bool fresh = r->env.firstBounce;
     if (!fresh)
         k_generate<<<gridFor(p.numSlots), kBlock, 0, r->stream>>>(p, pl.wf);
-    HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->counters.p[C_ACTIVE0]), (int)p.numSlots, 1, r->stream));
+    HIP_TRY(r, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&r->launch.counters.p[C_ACTIVE0]), (int)p.numSlots, 1, r->stream));
     if (const int rc = enqueueRound(r, pl, p.numSlots, hint, fresh))
         return rc;
     if (canonical)
@@ -496,7 +510,7 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         return rc;
     if (pl.p.numSlots == 0)
     {
-        HIP_TRY(r, hipEventRecord(r->evB, r->stream));
+        HIP_TRY(r, hipEventRecord(r->launch.evB.get(), r->stream));
         return PTX_OK;
     }
     pl.sv = makeSceneView(r); pl.sc = makeTraceScene(r);
@@ -539,7 +553,7 @@ static int renderDebug(PtxRenderer *r, const PtxRaygenUniformData *uniform, cons
         const dim3 grid(gridFor(p.slotsPerFrame, kBlock, kMaxPersistentThreads / kBlock));
         withMode(kernelMode(r), [&](auto M) {
             withFlag((view->raygenFlags & PTX_DEBUG_RAYGEN_CULL_BACK_FACES) != 0u, [&](auto CULL) {
-                k_debug_view<decltype(M)::value, decltype(CULL)::value><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->counters.p, r->spill.p);
+                k_debug_view<decltype(M)::value, decltype(CULL)::value><<<grid, kBlock, 0, r->stream>>>(p, sv, sc, pairIds, dv, imagePtr(r), r->launch.counters.p, r->launch.spill.p);
             });
         });
     }

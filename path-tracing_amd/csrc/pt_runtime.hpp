@@ -1,12 +1,14 @@
-// pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle (its state one struct per stage),
-// the environment switches, createRenderer / destroyRenderer, the grid helpers, makeParams and the scene views, ptx_update_animation,
-// ptx_get_stats and the ptx_test_* / ptx_trace_rays entry points.  The stages are host files of their own, included below in the
-// order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp; kernels: pt_bvh_build.hpp),
-// the render launches with the bounce schedule of the wavefront backend (pt_render_host.hpp), the frame's hand-over -- accumulation
-// image, tile shards, read-back -- (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the interactive
-// chain -- guide pass, temporal accumulation, the filters -- (pt_chain_host.hpp; its bookkeeping: pt_chain_state.hpp).  Their
-// functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line wrappers around them.
-// No CPU fallback exists: without a HIP device createRenderer fails.
+// pt_runtime.hpp -- host side of the HIP library: the renderer object behind a PtxRenderer handle -- its state one struct per stage,
+// every resource a member that releases itself (device memory: DevBuf; events, streams, page-locked memory: Owned, pt_owned.hpp) --,
+// createRenderer / destroyRenderer, the scene-sharing helpers, the grid helpers, makeParams, the stream plan and the CU masks, and the
+// scene views.  What a handle is created with comes from pt_env.hpp (TreeParams, EnvSwitches).  The stages are host files of their
+// own, included at the end in the order they build on one another: scene upload (pt_scene_host.hpp), the tree build (pt_bvh_host.hpp;
+// kernels: pt_bvh_build.hpp), animation updates (pt_animation_host.hpp), the render launches with the bounce schedule of the wavefront
+// backend and ptx_get_stats (pt_render_host.hpp), the frame's hand-over -- accumulation image, tile shards, read-back --
+// (pt_frame_host.hpp), the output stage and the screen path (pt_output_host.hpp), the interactive chain -- guide pass, temporal
+// accumulation, the filters -- (pt_chain_host.hpp; its bookkeeping: pt_chain_state.hpp), the ptx_test_* / ptx_trace_rays entry
+// points (pt_test_host.hpp).  Their functions take a valid or null handle; include/ptx.h's entry points (ptx_capi.hip) are one-line
+// wrappers around them.  No CPU fallback exists: without a HIP device createRenderer fails.
 #pragma once
 
 #include <algorithm>
@@ -25,6 +27,8 @@
 #include "pt_chain_state.hpp"
 #include "pt_debug_view.hpp"
 #include "pt_denoise.hpp"
+#include "pt_env.hpp"
+#include "pt_owned.hpp"
 #include "pt_post.hpp"
 #include "pt_present.hpp"
 #include "pt_shard_layout.hpp"
@@ -75,110 +79,19 @@ template <typename T> struct DevBuf
     }
 };
 
-// How ptx_build_accel builds the tree (the software stand-in for VkBuildAccelerationStructureFlags: the reference asks its driver
-// for ePreferFastTrace, AccelerationStructure.cpp:319-324).  buildBestTree tries a few settings and keeps the cheapest tree.
-struct TreeParams
+// ... and the same for what is not device memory (pt_owned.hpp): a member that is created late, or not at all, and released by going
+// out of scope.  A stream may also be borrowed: the host's, or the main stream standing in as the auxiliary one.
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+template <typename T> using OwnedPinned = Owned<T *, hipHostFree>; // page-locked host memory (hipHostMalloc)
+static hipError_t createEvent(OwnedEvent &ev, unsigned flags = 0u) // flags: hipEventCreateWithFlags'
 {
-    uint32_t plocRadius = kPlocRadius; // PLOC: clusters look for their merge partner this many positions to either side
-    float plocShape = kPlocShape;      // PLOC: weight of the compactness term in the merge metric
-    bool mortonCubic = false;          // Morton curve with cubic cells (one scale for the three axes)
-    uint32_t collapse = 1;             // 4-wide collapse: 0 greedy by surface area (round 1), 1 cost-driven (k_collapse_cost)
-    uint32_t reinsertPasses = 2;       // passes of parallel reinsertion over the binary tree before the collapse (k_reinsert_*): every
-                                       // candidate tree gets these; a build that keeps its state for refits (animation) at most these
-    uint32_t reinsertFinal = 32;       // ... and the candidate that wins is built once more with this many (15 ms per pass at 2 M triangles)
-    float splitBudget = 0.0f;          // pre-splitting: extra leaf references as a fraction of the triangle count (0: none)
-    uint32_t layout = 0;               // node order: 0 breadth-first levels, 1 depth-first (every subtree one contiguous range; measured flat)
-};
-
-// The environment switches of the library (INTEGRATION.md lists them): experiment and test knobs, read ONCE per handle when it
-// is created -- no entry point calls getenv afterwards, and a handle keeps the values it was created with.
-struct EnvSwitches
-{
-    // Who runs where (round 6; docs/EXPERIMENTS.md): the handle's streams are created with a CU mask (hipExtStreamCreateWithCUMask)
-    //   0 none (any CU)   1 one XCD per handle (handle h -> XCD h % 8)   2 two groups of four XCDs (h % 2)
-    //   3 main stream (closest + shade) on XCDs 0-5, auxiliary stream (shadow, tail) on XCDs 6-7   4 two XCDs per handle (h % 4)
-    //   5 main stream on XCD h % 8, auxiliary stream on XCD (h + 4) % 8
-    // With a mask the library creates the main stream itself even if the host passed one (the host's stream cannot be masked).
-    uint32_t cuPartition = 0;
-    bool singleStream = false; // PTX_SINGLE_STREAM=1: every handle as if created with PTX_DEVICE_SINGLE_STREAM
-    bool verbose = false;        // PTX_VERBOSE: progress and statistics on stderr
-    bool karrasBuilder = false;  // PTX_BUILDER=lbvh: Karras topology instead of PLOC
-    bool plocFixed = false;      // PTX_PLOC_RADIUS / PTX_PLOC_SHAPE given: ONE tree with these parameters, no candidates
-    uint32_t plocRadius = 0;     // PTX_PLOC_RADIUS
-    float plocShape = 0.0f;      // PTX_PLOC_SHAPE
-    int reinsertPasses = -1;     // PTX_REINSERT=N: N reinsertion passes for the winning tree, min(N, 2) for every candidate (-1: not given)
-    float splitBudget = -1.0f;   // PTX_SPLIT_BUDGET: extra leaf references as a fraction of the triangle count (< 0: not given)
-    int layout = -1;             // PTX_NODE_LAYOUT=0 / 1: breadth-first / depth-first node order (-1: not given)
-    int collapse = -1;           // PTX_COLLAPSE=0 / 1: greedy / cost-driven 4-wide collapse (-1: not given; does not fix the other parameters)
-    int shadeSort = -1;          // PTX_SHADE_SORT=0 / 1 overrides the scene's choice (-1: not given)
-    long tailThreshold = -1;     // PTX_TAIL_THRESHOLD: live paths at or below which k_tail takes over (-1: the default)
-    uint32_t framesPerWave = 8;  // PTX_FRAMES_PER_WAVE: samples of one pixel in neighbouring lanes, at most this many
-    uint32_t raysPerThread = 0;  // PTX_RAYS_PER_THREAD (process-wide: the last handle created sets it)
-    long residentCap = -1;       // PTX_RESIDENT_CAP=0: persistent grids are not capped at the resident block count
-    uint32_t copyGroups = 0;     // PTX_COPY_GROUPS: workgroups of the read-back copy kernel (0: one, or 2 per rank of a tile shard, at most 16)
-    bool snapshotMemcpy = false; // PTX_SNAPSHOT_MEMCPY=1: the read-back's device-side snapshot by hipMemcpyAsync (rounds 1-4) instead of a kernel
-    bool fenceRefit = false;     // PTX_FENCE_REFIT=1: the round-4 bottom-up kernels (fence and atomic per node) instead of the level lists
-    bool pairLeaves = true;      // PTX_PAIR_LEAVES=0: single-triangle leaves only (pt_bvh_build.hpp, "pair leaves")
-    bool firstBounce = true;     // PTX_FIRST_BOUNCE=0: k_generate hands the primary rays over through memory (rounds 1-6) instead of the first
-                                 // bounce's kernels computing them (pt_wavefront.hpp, FirstClosestIO)
-    bool streamLevelwise = false; // PTX_STREAM_LEVELWISE=1: ptx_texture_upload builds every chain level by level (k_blit_level) instead of k_stream_chain
-    bool streamPlan = true;      // PTX_STREAM_PLAN=0: two streams per handle whatever the queues granted (rounds 1-9) instead of the plan of
-                                 // pt_stream_plan.hpp
-    bool bcRowMapping = false;   // PTX_BC_MAPPING=rows: k_decode_bc with one thread per block row and four stores (measured, not kept) instead of one per texel
-    bool copyRuntime = false;    // PTX_COPY_RUNTIME=1: the read-back's copy to the host by hipMemcpyAsync instead of a kernel (measured, not kept)
-    static EnvSwitches read()
-    {
-        EnvSwitches e;
-        e.verbose = getenv("PTX_VERBOSE") != nullptr;
-        e.streamLevelwise = getenv("PTX_STREAM_LEVELWISE") != nullptr && std::strcmp(getenv("PTX_STREAM_LEVELWISE"), "0") != 0;
-        if (const char *v = getenv("PTX_PAIR_LEAVES"))
-            e.pairLeaves = std::strcmp(v, "0") != 0;
-        if (const char *v = getenv("PTX_FIRST_BOUNCE"))
-            e.firstBounce = std::strcmp(v, "0") != 0;
-        if (const char *v = getenv("PTX_STREAM_PLAN"))
-            e.streamPlan = std::strcmp(v, "0") != 0;
-        e.bcRowMapping = getenv("PTX_BC_MAPPING") != nullptr && std::strcmp(getenv("PTX_BC_MAPPING"), "rows") == 0;
-        e.copyRuntime = getenv("PTX_COPY_RUNTIME") != nullptr && std::strcmp(getenv("PTX_COPY_RUNTIME"), "0") != 0;
-        if (const char *v = getenv("PTX_COPY_GROUPS"))
-            e.copyGroups = (uint32_t)strtoul(v, nullptr, 10);
-        e.snapshotMemcpy = getenv("PTX_SNAPSHOT_MEMCPY") != nullptr && std::strcmp(getenv("PTX_SNAPSHOT_MEMCPY"), "0") != 0;
-        e.fenceRefit = getenv("PTX_FENCE_REFIT") != nullptr && std::strcmp(getenv("PTX_FENCE_REFIT"), "0") != 0;
-        if (const char *v = getenv("PTX_BUILDER"))
-            e.karrasBuilder = std::strcmp(v, "lbvh") == 0;
-        if (const char *v = getenv("PTX_PLOC_SHAPE"))
-        {
-            e.plocFixed = true;
-            e.plocShape = (float)atof(v);
-        }
-        if (const char *v = getenv("PTX_PLOC_RADIUS"))
-        {
-            e.plocFixed = true;
-            e.plocRadius = std::max(1u, (uint32_t)strtoul(v, nullptr, 10));
-        }
-        if (const char *v = getenv("PTX_REINSERT"))
-            e.reinsertPasses = atoi(v);
-        if (const char *v = getenv("PTX_SPLIT_BUDGET"))
-            e.splitBudget = (float)atof(v);
-        if (const char *v = getenv("PTX_NODE_LAYOUT"))
-            e.layout = atoi(v) ? 1 : 0;
-        if (const char *v = getenv("PTX_COLLAPSE"))
-            e.collapse = atoi(v) ? 1 : 0;
-        if (const char *v = getenv("PTX_SHADE_SORT"))
-            e.shadeSort = atoi(v) ? 1 : 0;
-        if (const char *v = getenv("PTX_TAIL_THRESHOLD"))
-            e.tailThreshold = (long)strtoul(v, nullptr, 10);
-        if (const char *v = getenv("PTX_FRAMES_PER_WAVE"))
-            e.framesPerWave = (uint32_t)atoi(v);
-        if (const char *v = getenv("PTX_RAYS_PER_THREAD"))
-            e.raysPerThread = std::max(1u, (uint32_t)strtoul(v, nullptr, 10));
-        if (const char *v = getenv("PTX_RESIDENT_CAP"))
-            e.residentCap = (long)strtoul(v, nullptr, 10);
-        e.singleStream = getenv("PTX_SINGLE_STREAM") != nullptr && std::strcmp(getenv("PTX_SINGLE_STREAM"), "0") != 0;
-        if (const char *v = getenv("PTX_CU_PARTITION"))
-            e.cuPartition = (uint32_t)strtoul(v, nullptr, 10);
-        return e;
-    }
-};
+    hipEvent_t e = nullptr;
+    const hipError_t rc = flags ? hipEventCreateWithFlags(&e, flags) : hipEventCreate(&e);
+    if (rc == hipSuccess)
+        ev.adopt(e);
+    return rc;
+}
 
 // What ptx_scene_upload produces (pt_scene_host.hpp): HBM copies of the Scene getters, the decoded textures, the any-hit tables,
 // the host's side of the animation.  One member of the handle, so that ptx_share_scene drops a borrower's copy by assignment.
@@ -289,7 +202,7 @@ struct PendingLaunch
     enum Kind { kNone, kWavefront, kDebugView } kind = kNone; // kDebugView: a ptx_render_debug, whose counters are the kernel's own
     uint32_t bounces = 0, tailBelow = 0, slots = 0; // slots: 0 for a launch that is not canonical, it teaches no hint
     uint32_t deadSlots = 0; // slots of ragged edge tiles outside the image: in the first queue, not rays
-    uint64_t epoch = 0;     // sceneEpoch of the scene it rendered
+    uint64_t epoch = 0;     // SceneLink::epoch of the scene it rendered
     bool verbose = false;
 };
 
@@ -300,14 +213,13 @@ struct ScheduleHint
     std::vector<uint32_t> active; // queue length per bounce
     std::vector<BounceStep> steps; // the round laid out for the launch that uses the hint
     uint32_t slots = 0, bounces = 0;
-    uint64_t epoch = 0; // sceneEpoch of the scene the hint was learnt on
+    uint64_t epoch = 0; // SceneLink::epoch of the scene the hint was learnt on
     bool matches(uint32_t s, uint32_t b, uint64_t e) const { return slots == s && bounces == b && epoch == e && !active.empty(); }
     void forget() { slots = 0u; } // (no launch has 0 slots: the next one is driven from the host and learns again)
 };
 
 // The frame between "the samples are accumulated" and "the host has them" (pt_frame_host.hpp): extent and tile shard, the
-// accumulation image and what may stand in for it, and the pipelined copy to the host.  The stream and the events are released by
-// destroyRenderer, not by a destructor.
+// accumulation image and what may stand in for it, and the pipelined copy to the host.
 struct FrameState
 {
     uint32_t width = 0, height = 0;
@@ -322,8 +234,8 @@ struct FrameState
     float4 *hostAlias = nullptr;
     // pipelined read-back (ptx_readback_begin / _end): snapshot of the image, copied out on its own stream
     DevBuf<float4> staging;
-    hipStream_t copyStream = nullptr;
-    hipEvent_t evSnapshot = nullptr, evCopied = nullptr;
+    OwnedStream copyStream; // made by the first read-back whose plan copies on neither the main nor the auxiliary stream
+    OwnedEvent evSnapshot, evCopied;
     bool copyInFlight = false;
 
     size_t pixels() const { return (size_t)width * height; }
@@ -382,104 +294,137 @@ struct ChainState
     void invalidate() { status.resize(); } // the images stay allocated: the next calls of the new extent grow them if they must
 };
 
+// What a refit reuses from the last full build (pt_bvh_host.hpp): sorted order and the binary topology.
+struct BuildState
+{
+    DevBuf<Tri> triTmp;
+    DevBuf<float4> boxLo, boxHi, nodeLo, nodeHi;
+    DevBuf<uint32_t> sceneBounds, vals0, vals1, hist, histSums, flags;
+    DevBuf<uint8_t> inert; // per flattened triangle: left out of the tree (zero area) by the last full build
+    // leaf references of a build that splits triangles (k_split_*): boxes, triangle and zero-area flag per reference
+    DevBuf<float4> refLo, refHi;
+    DevBuf<uint32_t> refTri;
+    DevBuf<uint8_t> refInert;
+    // ... or that pairs them (k_pair_*): refTri names a reference's first triangle, refPair says whether the next one is in it
+    // too, slotOf is the first triangle slot of the reference at each sorted position
+    DevBuf<uint8_t> refPair;
+    DevBuf<uint32_t> slotOf;
+    bool pairRefs = false;
+    uint32_t refCount = 0; // references of the last full build (= triangles unless it split or paired some)
+    uint32_t treeTris = 0; // triangles in the tree = the first treeTris entries of the sorted order
+    DevBuf<uint64_t> keys0, keys1;
+    DevBuf<int2> children;
+    DevBuf<int> parentOfNode, parentOfLeaf;
+    DevBuf<BvhNode> rawNodes; // k_emit's output, one slot per binary node; k_relayout_level compacts it into the tree's `nodes`
+    DevBuf<float4> collapseCost; // k_collapse_cost: T(x, 1..4) per binary node
+    DevBuf<uint8_t> collapseDecide;
+    DevBuf<uint32_t> oldOf;   // [0] onwards: emitted index of every node of the compact array; the last entry is the level counter
+    // level lists of the binary topology (pt_bvh_build.hpp, round 5): the nodes sorted by depth, for the bottom-up passes
+    DevBuf<uint32_t> lvDepth0, lvDepth1, lvVals0, lvVals1, lvStartDev;
+    DevBuf<int> lvAnc0, lvAnc1;
+    const uint32_t *levelOrder = nullptr; // lvVals0 or lvVals1
+    std::vector<uint32_t> levelStart;     // [d] first position of depth d in levelOrder, [maxDepth + 1] = nodes
+    bool levelsValid = false;
+    bool valid = false;
+};
+
+// The tree and how it is built (pt_bvh_host.hpp).  A Tree is the buffers the traversal and shading kernels read and the numbers
+// that describe them: they move together -- buildBestTree swaps whole trees, ptx_share_scene drops a borrower's by assignment.
+struct AccelState
+{
+    struct Tree
+    {
+        DevBuf<BvhNode> nodes;
+        DevBuf<Tri> tris;
+        DevBuf<ShadeTri> shadeTris; // deindexed vertices per triangle slot (leaf order), written by k_emit
+        DevBuf<AlphaTri> alphaTris; // what the any-hit stages read per triangle slot, written behind k_emit
+        uint32_t slots = 0;         // triangle slots in the tree: scene.triCount minus the zero-area triangles, plus the copies of a split
+        uint64_t nodeCount = 0, references = 0; // PtxStats::bvhNodes / treeReferences of this tree
+        void swap(Tree &o) { std::swap(*this, o); } // (by moves: a buffer added above is swapped too)
+    } tree;
+    BuildState build;
+    TreeParams params;           // of the tree in use; the per-frame rebuilds of an animation build with them again
+    bool usePloc = true;         // PLOC topology instead of Karras (PTX_BUILDER=lbvh switches back)
+    bool reinsertBroken = false; // a reinsertion pass once left something that was not a tree (k_tree_check): off for this handle
+    bool ready = false;          // a tree over the uploaded scene (a borrower: ptx_share_scene has been called)
+    uint32_t residentClosest[2] = { 0, 0 }, residentShadow[2] = { 0, 0 }; // blocks the chip holds at once, per [ALPHA] variant
+};
+
+// Whose scene this renderer renders.  ptx_share_scene: it renders the scene and tree of `owner` instead of holding copies (frames in
+// flight share one scene, as the reference's per-frame resources do); the owner knows who borrows from it.  Not in SceneData, which
+// a borrower drops by assignment.
+struct SceneLink
+{
+    bool ready = false; // a scene has been uploaded to THIS handle
+    uint64_t epoch = 1; // bumped by every upload and full build of THIS handle's scene (a refit keeps it: the poses of
+                        // an animation differ little from frame to frame)
+    PtxRenderer *owner = nullptr;
+    std::vector<PtxRenderer *> sharers;
+};
+
+// The streams of the handle and the plan of its launches.  Bounce schedule of the wavefront backend (pt_render_host.hpp): closest +
+// shade on `main`, shadow + tail on `aux` or, where the launch's plan says so (pt_stream_plan.hpp, planFor), on `main` too.  aux is
+// made by the first launch whose plan wants it and stays.
+struct StreamSet
+{
+    OwnedStream main; // the library's own, or the host's of PtxDeviceDesc::stream borrowed; PtxRenderer::stream is the plain view of it
+    OwnedStream aux;  // the library's own, or on a single-stream handle `main` borrowed
+    bool singleStream = false; // PtxDeviceDesc.flags & PTX_DEVICE_SINGLE_STREAM
+    uint32_t handleSeq = 0, mainXcds = 0xffu, auxXcds = 0xffu; // PTX_CU_PARTITION: the XCDs this handle's streams may use
+    StreamPlan plan = { false, false, 1u }; // of the last launch or read-back (what a change is logged against)
+    bool planSeen = false;
+    bool auxIsMain() const { return aux && aux.get() == main.get(); }
+};
+
+// What a render launch needs beside the path state, and what it leaves behind (pt_render_host.hpp).
+struct BounceEvents
+{
+    OwnedEvent t0, t1, t2; // main stream: before closest, after closest, after shade
+    OwnedEvent x0, x1, x2; // auxiliary stream: before shadow, after shadow, after tail
+};
+struct LaunchState
+{
+    DevBuf<PtxLightsUbo> lights;
+    DevBuf<LaunchParams> launchParams; // device copy of the current launch's parameters, written with the lights (k_upload_lights)
+    DevBuf<uint32_t> counters, spill;  // the counter block (enum Counter) and the traversal-stack overflow region of the main stream
+    DevBuf<uint32_t> spillAux;         // traversal-stack overflow region of the kernels on the auxiliary stream
+    OwnedPinned<uint32_t> hostCounters;     // the host's copy of the counter block
+    OwnedEvent evA, evB;                    // render / build span
+    std::vector<BounceEvents> bounceEvents; // [min(BounceCount, kMaxTimedBounces)], reused cyclically beyond
+    PendingLaunch pending;
+    ScheduleHint hint;
+};
+
+// Staging of the ptx_test_* entry points and the kernel span of ptx_trace_rays (pt_test_host.hpp).
+struct TestState
+{
+    DevBuf<float> testIn, testOut;
+    DevBuf<PtxLightsUbo> testUbo;
+    OwnedEvent evT0, evT1;
+};
+
 struct PtxRenderer
 {
     EnvSwitches env;
     int device = 0;
     uint32_t backend = PTX_BACKEND_WAVEFRONT;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
     bool counted = false; // in g_liveHandles
     std::string error;
+    PtxStats stats = {};
 
+    StreamSet streams; // (the first stage member: streams go last, after everything that was ever enqueued on them)
+    hipStream_t stream = nullptr; // streams.main.get()
+    SceneLink link;
     SceneData scene;
-    DevBuf<PtxLightsUbo> lights;
-    DevBuf<LaunchParams> launchParams; // device copy of the current launch's parameters, written with the lights (k_upload_lights)
-    DevBuf<AlphaTri> alphaTris;    // what the any-hit stages read per triangle slot, written behind k_emit
-    struct BuildState // what a refit reuses from the last full build: sorted order and the binary topology
-    {
-        DevBuf<Tri> triTmp;
-        DevBuf<float4> boxLo, boxHi, nodeLo, nodeHi;
-        DevBuf<uint32_t> sceneBounds, vals0, vals1, hist, histSums, flags;
-        DevBuf<uint8_t> inert; // per flattened triangle: left out of the tree (zero area) by the last full build
-        // leaf references of a build that splits triangles (k_split_*): boxes, triangle and zero-area flag per reference
-        DevBuf<float4> refLo, refHi;
-        DevBuf<uint32_t> refTri;
-        DevBuf<uint8_t> refInert;
-        // ... or that pairs them (k_pair_*): refTri names a reference's first triangle, refPair says whether the next one is in it
-        // too, slotOf is the first triangle slot of the reference at each sorted position
-        DevBuf<uint8_t> refPair;
-        DevBuf<uint32_t> slotOf;
-        bool pairRefs = false;
-        uint32_t refCount = 0; // references of the last full build (= triangles unless it split or paired some)
-        uint32_t treeTris = 0; // triangles in the tree = the first treeTris entries of the sorted order
-        DevBuf<uint64_t> keys0, keys1;
-        DevBuf<int2> children;
-        DevBuf<int> parentOfNode, parentOfLeaf;
-        DevBuf<BvhNode> rawNodes; // k_emit's output, one slot per binary node; k_relayout_level compacts it into `nodes`
-        DevBuf<float4> collapseCost; // k_collapse_cost: T(x, 1..4) per binary node
-        DevBuf<uint8_t> collapseDecide;
-        DevBuf<uint32_t> oldOf;   // [0] onwards: emitted index of every node of the compact array; the last entry is the level counter
-        // level lists of the binary topology (pt_bvh_build.hpp, round 5): the nodes sorted by depth, for the bottom-up passes
-        DevBuf<uint32_t> lvDepth0, lvDepth1, lvVals0, lvVals1, lvStartDev;
-        DevBuf<int> lvAnc0, lvAnc1;
-        const uint32_t *levelOrder = nullptr; // lvVals0 or lvVals1
-        std::vector<uint32_t> levelStart;     // [d] first position of depth d in levelOrder, [maxDepth + 1] = nodes
-        bool levelsValid = false;
-        bool valid = false;
-    } build;
-    bool usePloc = true;        // PLOC topology instead of Karras (PTX_BUILDER=lbvh switches back)
-    TreeParams tree;            // of the tree in use; the per-frame rebuilds of an animation build with them again
-    bool reinsertBroken = false; // a reinsertion pass once left something that was not a tree (k_tree_check): off for this handle
-    uint32_t residentClosest[2] = { 0, 0 }, residentShadow[2] = { 0, 0 }; // blocks the chip holds at once, per [ALPHA] variant
-    uint32_t treeTris = 0; // scene.triCount minus the zero-area triangles, which are not in the tree
-    bool sceneReady = false, accelReady = false;
-    // ptx_share_scene: this renderer renders the scene and tree of `sceneOwner` instead of holding copies (frames in flight
-    // share one scene, as the reference's per-frame resources do); the owner knows who borrows from it
-    PtxRenderer *sceneOwner = nullptr;
-    std::vector<PtxRenderer *> sceneSharers;
-
-    // accel
-    DevBuf<BvhNode> nodes;
-    DevBuf<Tri> tris;
-    DevBuf<ShadeTri> shadeTris; // deindexed vertices per triangle slot (leaf order), written by k_emit
-
+    AccelState accel;
+    PathState paths;
+    LaunchState launch;
     FrameState frame;
     OutputState output;
     ChainState chain;
-
-    // wavefront state
-    PathState paths;
-    DevBuf<uint32_t> counters, spill; // the counter block (enum Counter) and the traversal-stack overflow region of the main stream
-    uint32_t *hostCounters = nullptr; // pinned
-
-    DevBuf<float> testIn, testOut;
-    DevBuf<PtxLightsUbo> testUbo;
-
-    hipEvent_t evA = nullptr, evB = nullptr, evT0 = nullptr, evT1 = nullptr; // render / build span; ptx_trace_rays kernel span
-
-    // bounce schedule of the wavefront backend (pt_render_host.hpp): closest + shade on `stream`, shadow + tail on `auxStream` or,
-    // where the launch's plan says so (pt_stream_plan.hpp, planFor), on `stream` too.  auxStream is made by the first launch whose
-    // plan wants it and stays.
-    hipStream_t auxStream = nullptr;
-    bool auxIsMain = false; // single-stream handle: auxStream is `stream` itself
-    StreamPlan plan = { false, false, 1u }; // of the last launch or read-back (what a change is logged against)
-    bool planSeen = false;
-    bool singleStream = false; // PtxDeviceDesc.flags & PTX_DEVICE_SINGLE_STREAM
-    uint32_t handleSeq = 0, mainXcds = 0xffu, auxXcds = 0xffu; // PTX_CU_PARTITION: the XCDs this handle's streams may use
-    DevBuf<uint32_t> spillAux; // traversal-stack overflow region of the kernels on auxStream
-    struct BounceEvents
-    {
-        hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr; // stream: before closest, after closest, after shade
-        hipEvent_t x0 = nullptr, x1 = nullptr, x2 = nullptr; // auxStream: before shadow, after shadow, after tail
-    };
-    std::vector<BounceEvents> bounceEvents; // [min(BounceCount, kMaxTimedBounces)], reused cyclically beyond
-    PendingLaunch pending;
-    ScheduleHint hint;
-    uint64_t sceneEpoch = 1; // bumped by every upload and full build of THIS handle's scene (a refit keeps it: the poses of
-                             // an animation differ little from frame to frame)
-    PtxStats stats = {};
+    TestState test;
 };
+
 
 static int fail(PtxRenderer *r, int code, const char *fmt, ...)
 {
@@ -505,41 +450,38 @@ static int fail(PtxRenderer *r, int code, const char *fmt, ...)
 // the renderer whose scene buffers, tree and scene flags `r` renders with
 static const PtxRenderer *sceneOf(const PtxRenderer *r)
 {
-    return r->sceneOwner ? r->sceneOwner : r;
+    return r->link.owner ? r->link.owner : r;
 }
 
 // May `r` trace and shade right now?  A borrower is only as ready as its owner: between the owner's ptx_scene_upload and
 // its ptx_build_accel the owner's tree describes the OLD triangles while pairs, vertices and textures are the new ones.
 static bool sceneUsable(const PtxRenderer *r)
 {
-    return r->accelReady && (!r->sceneOwner || (r->sceneOwner->sceneReady && r->sceneOwner->accelReady));
+    return r->accel.ready && (!r->link.owner || (r->link.owner->link.ready && r->link.owner->accel.ready));
 }
 
 static void detachSharedScene(PtxRenderer *r)
 {
-    if (!r->sceneOwner)
+    if (!r->link.owner)
         return;
-    std::vector<PtxRenderer *> &v = r->sceneOwner->sceneSharers;
+    std::vector<PtxRenderer *> &v = r->link.owner->link.sharers;
     for (size_t i = 0; i < v.size(); i++)
         if (v[i] == r)
         {
             v.erase(v.begin() + (long)i);
             break;
         }
-    r->sceneOwner = nullptr;
-    r->accelReady = false; // ptx_share_scene released the borrower's own scene: it needs ptx_scene_upload + ptx_build_accel again
+    r->link.owner = nullptr;
+    r->accel.ready = false; // ptx_share_scene released the borrower's own scene: it needs ptx_scene_upload + ptx_build_accel again
 }
 
 // Before the owner of a shared scene changes it (upload, rebuild, animation step): the borrowers' frames in flight end.
 static void quiesceSharers(PtxRenderer *r)
 {
-    for (PtxRenderer *sh : r->sceneSharers)
-    {
-        if (sh->stream)
-            (void)hipStreamSynchronize(sh->stream);
-        if (sh->auxStream)
-            (void)hipStreamSynchronize(sh->auxStream);
-    }
+    for (PtxRenderer *sh : r->link.sharers)
+        for (hipStream_t st : { sh->stream, sh->streams.aux.get() })
+            if (st)
+                (void)hipStreamSynchronize(st);
 }
 
 static float4 *imagePtr(const PtxRenderer *r) { return r->frame.accum(); }
@@ -660,12 +602,12 @@ static std::atomic<bool> g_queueWarningGiven{false};
 static StreamPlan planFor(PtxRenderer *r)
 {
     const StreamPlan now = streamPlanFor({ (uint32_t)r->stats.hardwareQueues, g_liveHandles.load(std::memory_order_relaxed),
-                                           r->env.singleStream || r->singleStream, r->env.streamPlan });
-    if (r->env.verbose && (!r->planSeen || now != r->plan))
-        fprintf(stderr, "[ptx] handle %u: stream plan %s: %s (%u live handles, %u hardware queues)\n", r->handleSeq, r->planSeen ? "changes to" : "is",
+                                           r->env.singleStream || r->streams.singleStream, r->env.streamPlan });
+    if (r->env.verbose && (!r->streams.planSeen || now != r->streams.plan))
+        fprintf(stderr, "[ptx] handle %u: stream plan %s: %s (%u live handles, %u hardware queues)\n", r->streams.handleSeq, r->streams.planSeen ? "changes to" : "is",
                 streamPlanName(now), g_liveHandles.load(std::memory_order_relaxed), (uint32_t)r->stats.hardwareQueues);
-    r->plan = now;
-    r->planSeen = true;
+    r->streams.plan = now;
+    r->streams.planSeen = true;
     return now;
 }
 
@@ -698,14 +640,18 @@ static void partitionOf(uint32_t mode, uint32_t h, uint32_t &mainXcds, uint32_t 
     default: break;
     }
 }
-static hipError_t createStreamOn(hipStream_t *s, uint32_t xcds, int device)
+static hipError_t createStreamOn(OwnedStream &out, uint32_t xcds, int device)
 {
     int cus = 0;
-    if (xcds == 0xffu || xcds == 0x2ffu || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 8)
-        return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+    hipStream_t s = nullptr;
     std::vector<uint32_t> mask;
-    xcdMask(xcds & 0xffu, (uint32_t)cus, mask);
-    return hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
+    const bool plain = xcds == 0xffu || xcds == 0x2ffu || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 8;
+    if (!plain)
+        xcdMask(xcds & 0xffu, (uint32_t)cus, mask);
+    const hipError_t rc = plain ? hipStreamCreateWithFlags(&s, hipStreamNonBlocking) : hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data());
+    if (rc == hipSuccess)
+        out.adopt(s);
+    return rc;
 }
 
 static int createRenderer(const PtxDeviceDesc *desc, PtxRenderer **out)
@@ -719,64 +665,61 @@ static int createRenderer(const PtxDeviceDesc *desc, PtxRenderer **out)
     PtxRenderer *r = new PtxRenderer;
     r->device = desc ? desc->deviceIndex : 0;
     r->backend = desc ? desc->backend : PTX_BACKEND_WAVEFRONT;
-    r->singleStream = desc && (desc->flags & PTX_DEVICE_SINGLE_STREAM) != 0u;
+    r->streams.singleStream = desc && (desc->flags & PTX_DEVICE_SINGLE_STREAM) != 0u;
     if (r->device < 0 || r->device >= n || hipSetDevice(r->device) != hipSuccess)
     {
         delete r;
         return PTX_ERROR_NO_DEVICE;
     }
     r->env = EnvSwitches::read(); // the only place the library reads its switches
-    r->handleSeq = g_handleSeq++;
-    partitionOf(r->env.cuPartition, r->handleSeq, r->mainXcds, r->auxXcds);
-    if (desc && desc->stream && r->mainXcds == 0xffu)
-        r->stream = static_cast<hipStream_t>(desc->stream);
-    else
+    r->streams.handleSeq = g_handleSeq++;
+    partitionOf(r->env.cuPartition, r->streams.handleSeq, r->streams.mainXcds, r->streams.auxXcds);
+    if (desc && desc->stream && r->streams.mainXcds == 0xffu)
+        r->streams.main.borrow(static_cast<hipStream_t>(desc->stream));
+    else if (createStreamOn(r->streams.main, r->streams.mainXcds, r->device) != hipSuccess)
     {
-        if (createStreamOn(&r->stream, r->mainXcds, r->device) != hipSuccess)
-        {
-            delete r;
-            return PTX_ERROR_DEVICE;
-        }
-        r->ownStream = true;
+        delete r;
+        return PTX_ERROR_DEVICE;
     }
-    r->usePloc = !r->env.karrasBuilder;
+    r->stream = r->streams.main.get();
+    r->accel.usePloc = !r->env.karrasBuilder;
     if (r->env.collapse >= 0)
-        r->tree.collapse = (uint32_t)r->env.collapse;
+        r->accel.params.collapse = (uint32_t)r->env.collapse;
     if (r->env.layout >= 0)
-        r->tree.layout = (uint32_t)r->env.layout;
+        r->accel.params.layout = (uint32_t)r->env.layout;
     if (r->env.splitBudget >= 0.0f)
-        r->tree.splitBudget = r->env.splitBudget;
+        r->accel.params.splitBudget = r->env.splitBudget;
     if (r->env.reinsertPasses >= 0)
     {
-        r->tree.reinsertFinal = (uint32_t)r->env.reinsertPasses;
-        r->tree.reinsertPasses = std::min(r->tree.reinsertPasses, r->tree.reinsertFinal);
+        r->accel.params.reinsertFinal = (uint32_t)r->env.reinsertPasses;
+        r->accel.params.reinsertPasses = std::min(r->accel.params.reinsertPasses, r->accel.params.reinsertFinal);
     }
     if (r->env.plocFixed)
     {
-        r->tree.plocShape = r->env.plocShape;
+        r->accel.params.plocShape = r->env.plocShape;
         if (r->env.plocRadius)
-            r->tree.plocRadius = r->env.plocRadius;
+            r->accel.params.plocRadius = r->env.plocRadius;
     }
     if (r->env.raysPerThread)
         g_raysPerThread = r->env.raysPerThread;
     if (r->env.residentCap >= 0)
         g_residentCap = (uint32_t)r->env.residentCap;
     // (a masked stream holds fewer blocks at once: the persistent grids are sized to the XCDs the stream may use)
-    const uint32_t mainShare = (uint32_t)__builtin_popcount(r->mainXcds & 0xffu), auxShare = (uint32_t)__builtin_popcount(r->auxXcds & 0xffu);
-    r->residentClosest[0] = residentBlocksOf(k_trace_closest<false>, r->device) * mainShare / 8u;
-    r->residentClosest[1] = residentBlocksOf(k_trace_closest<true>, r->device) * mainShare / 8u;
-    r->residentShadow[0] = residentBlocksOf(k_trace_shadow<false>, r->device) * auxShare / 8u;
-    r->residentShadow[1] = residentBlocksOf(k_trace_shadow<true>, r->device) * auxShare / 8u;
+    const uint32_t mainShare = (uint32_t)__builtin_popcount(r->streams.mainXcds & 0xffu), auxShare = (uint32_t)__builtin_popcount(r->streams.auxXcds & 0xffu);
+    r->accel.residentClosest[0] = residentBlocksOf(k_trace_closest<false>, r->device) * mainShare / 8u;
+    r->accel.residentClosest[1] = residentBlocksOf(k_trace_closest<true>, r->device) * mainShare / 8u;
+    r->accel.residentShadow[0] = residentBlocksOf(k_trace_shadow<false>, r->device) * auxShare / 8u;
+    r->accel.residentShadow[1] = residentBlocksOf(k_trace_shadow<true>, r->device) * auxShare / 8u;
     if (r->env.verbose)
-        fprintf(stderr, "[ptx] resident blocks: closest %u / %u, shadow %u / %u\n", r->residentClosest[0], r->residentClosest[1], r->residentShadow[0],
-                r->residentShadow[1]);
-    (void)hipEventCreate(&r->evA);
-    (void)hipEventCreate(&r->evB);
-    (void)hipEventCreate(&r->evT0);
-    (void)hipEventCreate(&r->evT1);
-    (void)hipHostMalloc(reinterpret_cast<void **>(&r->hostCounters), C_COUNT * sizeof(uint32_t), hipHostMallocDefault);
-    if (r->counters.alloc(C_COUNT) != hipSuccess || r->lights.alloc(1) != hipSuccess || r->launchParams.alloc(1) != hipSuccess || !r->hostCounters ||
-        r->spill.alloc((size_t)kGlobalSpill * kMaxPersistentThreads) != hipSuccess)
+        fprintf(stderr, "[ptx] resident blocks: closest %u / %u, shadow %u / %u\n", r->accel.residentClosest[0], r->accel.residentClosest[1], r->accel.residentShadow[0],
+                r->accel.residentShadow[1]);
+    LaunchState &L = r->launch;
+    uint32_t *pinned = nullptr; // (an event that cannot be made leaves no counter block, and the handle fails like an allocation)
+    if (createEvent(L.evA) == hipSuccess && createEvent(L.evB) == hipSuccess && createEvent(r->test.evT0) == hipSuccess && createEvent(r->test.evT1) == hipSuccess &&
+        hipHostMalloc(reinterpret_cast<void **>(&pinned), C_COUNT * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess)
+        L.hostCounters.adopt(pinned);
+    if (L.counters.alloc(C_COUNT) != hipSuccess || L.lights.alloc(1) != hipSuccess || L.launchParams.alloc(1) != hipSuccess || !L.hostCounters ||
+        L.spill.alloc((size_t)kGlobalSpill * kMaxPersistentThreads) != hipSuccess)
     {
         destroyRenderer(r);
         return PTX_ERROR_OUT_OF_MEMORY;
@@ -784,7 +727,7 @@ static int createRenderer(const PtxDeviceDesc *desc, PtxRenderer **out)
     r->stats.hardwareQueues = hardwareQueuesGranted();
     r->counted = true;
     const uint32_t live = ++g_liveHandles;
-    const uint32_t streamsPerHandle = (r->singleStream || r->env.singleStream) ? 1u : 2u;
+    const uint32_t streamsPerHandle = (r->streams.singleStream || r->env.singleStream) ? 1u : 2u;
     if (streamsPerHandle * live > r->stats.hardwareQueues && live > 1 && !g_queueWarningGiven.exchange(true))
     {
         // not an error: the handle works, and the note says which schedule its launches take from here on (planFor)
@@ -806,33 +749,18 @@ static void destroyRenderer(PtxRenderer *r)
     (void)hipSetDevice(r->device);
     if (r->counted)
         --g_liveHandles;
-    if (r->stream)
-        (void)hipStreamSynchronize(r->stream);
+    for (hipStream_t st : { r->stream, r->streams.aux.get(), r->frame.copyStream.get() }) // idle before anything is freed
+        if (st)
+            (void)hipStreamSynchronize(st);
     detachSharedScene(r);
     quiesceSharers(r);
-    for (PtxRenderer *sh : r->sceneSharers) // borrowers of this scene: their frames have ended, and now they have no scene
+    for (PtxRenderer *sh : r->link.sharers) // borrowers of this scene: their frames have ended, and now they have no scene
     {
-        sh->sceneOwner = nullptr;
-        sh->accelReady = false;
+        sh->link.owner = nullptr;
+        sh->accel.ready = false;
     }
-    r->sceneSharers.clear();
-    // every DevBuf member (scene, tree, build state, wavefront state, animation, output stage) frees itself in `delete r`
-    if (r->auxStream && !r->auxIsMain) { (void)hipStreamSynchronize(r->auxStream); (void)hipStreamDestroy(r->auxStream); }
-    for (PtxRenderer::BounceEvents &e : r->bounceEvents)
-        for (hipEvent_t ev : { e.t0, e.t1, e.t2, e.x0, e.x1, e.x2 })
-            if (ev)
-                (void)hipEventDestroy(ev);
-    if (r->frame.copyStream) { (void)hipStreamSynchronize(r->frame.copyStream); (void)hipStreamDestroy(r->frame.copyStream); }
-    if (r->frame.evSnapshot) (void)hipEventDestroy(r->frame.evSnapshot);
-    if (r->frame.evCopied) (void)hipEventDestroy(r->frame.evCopied);
-    if (r->hostCounters)
-        (void)hipHostFree(r->hostCounters);
-    if (r->evA) (void)hipEventDestroy(r->evA);
-    if (r->evB) (void)hipEventDestroy(r->evB);
-    if (r->evT0) (void)hipEventDestroy(r->evT0);
-    if (r->evT1) (void)hipEventDestroy(r->evT1);
-    if (r->ownStream && r->stream)
-        (void)hipStreamDestroy(r->stream);
+    r->link.sharers.clear();
+    // every member (scene, tree, build state, wavefront state, events, streams ...) releases itself in `delete r`, the streams last
     delete r;
 }
 
@@ -848,10 +776,10 @@ static SceneView makeSceneView(const PtxRenderer *r)
 {
     const PtxRenderer *s = sceneOf(r);
     SceneView sv;
-    sv.shadeTris = s->shadeTris.p;
+    sv.shadeTris = s->accel.tree.shadeTris.p;
     sv.vertices = s->scene.vertices.p; sv.indices = s->scene.indices.p; sv.mr = s->scene.mr.p; sv.sg = s->scene.sg.p; sv.phong = s->scene.phong.p;
     sv.pairs = s->scene.pairs.p; sv.dxNormalTextures = s->scene.dxNormalTextures;
-    sv.lights = r->lights.p; // the lights come with every launch: each frame in flight has its own
+    sv.lights = r->launch.lights.p; // the lights come with every launch: each frame in flight has its own
     sv.tex.textures = s->scene.renderTextures.p; sv.tex.textureCount = s->scene.textureCount; sv.tex.texels8 = nullptr; sv.tex.texelsF = s->scene.renderTexels.p;
     sv.tex.srgbLut = nullptr;
     sv.skyKind = s->scene.skyKind;
@@ -862,257 +790,18 @@ static TraceScene makeTraceScene(const PtxRenderer *r)
 {
     const PtxRenderer *s = sceneOf(r);
     TraceScene sc;
-    sc.nodes = s->nodes.p; sc.tris = s->tris.p; sc.triCount = s->treeTris;
-    sc.alphaTris = s->alphaTris.p; sc.alphaQuads = s->scene.alphaQuads.p;
+    sc.nodes = s->accel.tree.nodes.p; sc.tris = s->accel.tree.tris.p; sc.triCount = s->accel.tree.slots;
+    sc.alphaTris = s->accel.tree.alphaTris.p; sc.alphaQuads = s->scene.alphaQuads.p;
     return sc;
 }
 
-// Does the linear part of a mat3x4 have a negative determinant (an instance that mirrors its model)?
-static bool transformMirrors(const float *m)
-{
-    const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
-                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
-    return det < 0.0;
-}
+static bool transformMirrors(const float *m); // (pt_animation_host.hpp; the upload asks it about every instance too)
 
 #include "pt_scene_host.hpp" // ptx_share_scene and ptx_scene_upload: shareScene, sceneUpload and its stages
-
 #include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
-
-// ptx_track_motion: whether ptx_update_animation keeps the pose it replaces (snapshotPose).  Owner only, like the update itself.
-static int trackMotion(PtxRenderer *r, int enable)
-{
-    if (!r)
-        return PTX_ERROR_INVALID_ARGUMENT;
-    if (r->sceneOwner)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_track_motion: this renderer shares another renderer's scene (ptx_share_scene)");
-    if (!r->sceneReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_track_motion: no scene uploaded");
-    SceneData::PoseTracking &pose = r->scene.pose;
-    if (!enable && pose.enabled)
-    {
-        // a guide pass in flight may still read the snapshot
-        HIP_TRY(r, hipSetDevice(r->device));
-        quiesceSharers(r);
-        HIP_TRY(r, hipStreamSynchronize(r->stream));
-        pose.release();
-    }
-    pose.enabled = enable != 0;
-    return PTX_OK;
-}
-
-// The first step of ptx_update_animation behind its checks: with tracking on the pose about to be replaced is kept -- the DevPair
-// table and the skinned part of the vertex buffer, device to device on the render stream ahead of the uploads and k_skin.  With
-// tracking off nothing is enqueued.  The snapshot counts, and the pose serial moves on, only once the update has succeeded
-// (updateAnimation): a failed one leaves no snapshot, and the serial where it was.
-static int snapshotPose(PtxRenderer *r)
-{
-    SceneData &sc = r->scene;
-    sc.pose.snapshotValid = false;
-    if (sc.pose.enabled)
-    {
-        HIP_TRY(r, sc.pose.prevPairs.alloc(sc.pairCount));
-        HIP_TRY(r, sc.pose.prevSkinned.alloc(sc.skinnedCount));
-        if (sc.pairCount)
-            HIP_TRY(r, hipMemcpyAsync(sc.pose.prevPairs.p, sc.pairs.p, (size_t)sc.pairCount * sizeof(DevPair), hipMemcpyDeviceToDevice, r->stream));
-        if (sc.skinnedCount)
-            HIP_TRY(r, hipMemcpyAsync(sc.pose.prevSkinned.p, sc.vertices.p + sc.staticVertexCount, (size_t)sc.skinnedCount * sizeof(PtxVertex),
-                                      hipMemcpyDeviceToDevice, r->stream));
-    }
-    return PTX_OK;
-}
-
-static int applyAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate);
-
-// Renderer.cpp:1750-1754 (+ RecordSkinningCommands :854-890, AccelerationStructure::Update :48-57)
-static int updateAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, uint32_t instanceCount, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate)
-{
-    if (!r || accelUpdate > PTX_ACCEL_REBUILD)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_update_animation: bad argument");
-    if (r->sceneOwner)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_update_animation: this renderer shares another renderer's scene (ptx_share_scene)");
-    if (!r->sceneReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_update_animation: no scene uploaded");
-    quiesceSharers(r);
-    if (instanceTransforms && instanceCount != r->scene.instanceCount)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_update_animation: %u instance transforms for a scene of %u instances", instanceCount,
-                    r->scene.instanceCount);
-    HIP_TRY(r, hipSetDevice(r->device));
-    if (const int rc = snapshotPose(r))
-        return rc;
-    const int rc = applyAnimation(r, instanceTransforms, boneTransforms, boneCount, accelUpdate);
-    if (rc == PTX_OK) // accepted: the serial moves on, and what snapshotPose kept is the pose of the serial before
-    {
-        r->scene.pose.serial++;
-        r->scene.pose.snapshotValid = r->scene.pose.enabled;
-    }
-    return rc;
-}
-
-// the update itself, behind ptx_update_animation's checks and the snapshot
-static int applyAnimation(PtxRenderer *r, const PtxTransform *instanceTransforms, const PtxTransform *boneTransforms, uint32_t boneCount, uint32_t accelUpdate)
-{
-    if (instanceTransforms)
-    {
-        for (size_t p = 0; p < r->scene.hostPairs.size(); p++)
-        {
-            DevPair &pr = r->scene.hostPairs[p];
-            composeTransform(instanceTransforms[r->scene.pairInstance[p]].m, r->scene.pairMeshTransform[p].m, pr.M);
-            inverseLinear(pr.M, pr.Rinv);
-            r->scene.hostDebugPairs[p].flags = transformMirrors(instanceTransforms[r->scene.pairInstance[p]].m) ? kDebugPairMirrored : 0u;
-        }
-        if (!r->scene.hostPairs.empty())
-        {
-            HIP_TRY(r, hipMemcpyAsync(r->scene.pairs.p, r->scene.hostPairs.data(), r->scene.hostPairs.size() * sizeof(DevPair), hipMemcpyHostToDevice, r->stream));
-            HIP_TRY(r, hipMemcpyAsync(r->scene.debugPairs.p, r->scene.hostDebugPairs.data(), r->scene.hostDebugPairs.size() * sizeof(DebugPair), hipMemcpyHostToDevice, r->stream));
-        }
-    }
-    if (boneTransforms && r->scene.skinnedCount)
-    {
-        if (boneCount > r->scene.bones.n)
-            HIP_TRY(r, r->scene.bones.alloc(boneCount));
-        r->scene.boneCount = boneCount;
-        if (boneCount)
-            HIP_TRY(r, hipMemcpyAsync(r->scene.bones.p, boneTransforms, (size_t)boneCount * sizeof(PtxTransform), hipMemcpyHostToDevice, r->stream));
-        k_skin<<<(r->scene.skinnedCount + 255) / 256, 256, 0, r->stream>>>(r->scene.animatedVertices.p, r->scene.skinSource.p, r->scene.skinnedCount, r->scene.bones.p, boneCount,
-                                                                  r->scene.vertices.p + r->scene.staticVertexCount);
-    }
-    HIP_TRY(r, hipStreamSynchronize(r->stream)); // the caller's arrays may go away
-    const bool refit = accelUpdate == PTX_ACCEL_REFIT && r->build.valid && r->accelReady;
-    return buildAccel(r, refit, true);
-}
-
-#include "pt_render_host.hpp" // ptx_render, ptx_render_debug: renderImpl and its stages, collectRender, renderDebug
+#include "pt_animation_host.hpp" // ptx_track_motion, ptx_update_animation: trackMotion, snapshotPose, updateAnimation
+#include "pt_render_host.hpp" // ptx_render, ptx_render_debug, ptx_get_stats: renderImpl and its stages, collectRender, getStats, renderDebug
 #include "pt_frame_host.hpp" // accumulation image and its bindings, tile shards, read-back: resizeFrame ... unpackShards
 #include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
 #include "pt_chain_host.hpp" // the guide pass, the temporal accumulation, the three filters and their read-backs
-
-static int testDebugEval(PtxRenderer *r, uint32_t which, const float *in, float *out, uint32_t n)
-{
-    if (!r || which > 1u || !in || !out)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_test_debug_eval: bad argument");
-    if (!n)
-        return PTX_OK;
-    HIP_TRY(r, hipSetDevice(r->device));
-    const size_t ni = (size_t)n * (which == 0u ? 18u : 1u), no = (size_t)n * 3u;
-    HIP_TRY(r, r->testIn.alloc(ni));
-    HIP_TRY(r, r->testOut.alloc(no));
-    HIP_TRY(r, hipMemcpyAsync(r->testIn.p, in, ni * 4, hipMemcpyHostToDevice, r->stream));
-    k_test_debug_eval<<<(n + 63) / 64, 64, 0, r->stream>>>(which, r->testIn.p, r->testOut.p, n);
-    HIP_TRY(r, hipMemcpyAsync(out, r->testOut.p, no * 4, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-static int getStats(PtxRenderer *r, PtxStats *stats)
-{
-    if (!r || !stats)
-        return PTX_ERROR_INVALID_ARGUMENT;
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    {
-        const int rcc = collectRender(r);
-        if (rcc != PTX_OK)
-            return rcc;
-    }
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, r->evA, r->evB) == hipSuccess)
-        r->stats.lastRenderMs = ms;
-    *stats = r->stats;
-    return PTX_OK;
-}
-
-static int testEval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n)
-{
-    if (!r || fn >= PTX_FN_COUNT || !in || !out)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_test_eval: bad argument");
-    if (!n)
-        return PTX_OK;
-    HIP_TRY(r, hipSetDevice(r->device));
-    const size_t ni = (size_t)n * h_inStride[fn], no = (size_t)n * h_outStride[fn];
-    HIP_TRY(r, r->testIn.alloc(ni));
-    HIP_TRY(r, r->testOut.alloc(no));
-    if (fn == PTX_FN_SAMPLE_LIGHT)
-        HIP_TRY(r, r->testUbo.alloc(n));
-    HIP_TRY(r, hipMemcpyAsync(r->testIn.p, in, ni * 4, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(r, hipMemsetAsync(r->testOut.p, 0, no * 4, r->stream));
-    k_test_eval<<<(n + 63) / 64, 64, 0, r->stream>>>(fn, r->testIn.p, r->testOut.p, n, r->testUbo.p);
-    HIP_TRY(r, hipMemcpyAsync(out, r->testOut.p, no * 4, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-static int testTexture(PtxRenderer *r, const float *in, float *out, uint32_t n, int implicitLod)
-{
-    if (!r || !in || !out)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_test_texture: null argument");
-    if (!r->sceneReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_test_texture: no scene uploaded");
-    if (!n)
-        return PTX_OK;
-    HIP_TRY(r, hipSetDevice(r->device));
-    HIP_TRY(r, r->testIn.alloc((size_t)n * 7));
-    HIP_TRY(r, r->testOut.alloc((size_t)n * 4));
-    HIP_TRY(r, hipMemcpyAsync(r->testIn.p, in, (size_t)n * 28, hipMemcpyHostToDevice, r->stream));
-    TextureView tv;
-    tv.textures = r->scene.renderTextures.p; tv.textureCount = r->scene.textureCount; tv.texels8 = nullptr; tv.texelsF = r->scene.renderTexels.p;
-    tv.srgbLut = nullptr;
-    k_test_texture<<<(n + 63) / 64, 64, 0, r->stream>>>(tv, r->testIn.p, r->testOut.p, n, implicitLod);
-    HIP_TRY(r, hipMemcpyAsync(out, r->testOut.p, (size_t)n * 16, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-static int traceRays(PtxRenderer *r, const float *rays, uint32_t n, int anyHit, float *hits, uint32_t *ids)
-{
-    if (!r || !rays || !hits || !ids)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_trace_rays: null argument");
-    if (!sceneUsable(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_trace_rays: no acceleration structure (of a shared scene: the owner's is being replaced)");
-    if (!n)
-        return PTX_OK;
-    HIP_TRY(r, hipSetDevice(r->device));
-    DevBuf<float4> dRays, dHits;
-    DevBuf<uint2> dIds;
-    DevBuf<uint32_t> dOverflow; // the call's own count: a render whose counters are still to be collected keeps its C_OVERFLOW
-    HIP_TRY(r, dRays.alloc((size_t)n * 2));
-    HIP_TRY(r, dHits.alloc(n));
-    HIP_TRY(r, dIds.alloc(n));
-    HIP_TRY(r, dOverflow.alloc(1));
-    if (const int rcCommit = waitForCommits(r))
-        return rcCommit;
-    TraceScene sc;
-    sc = makeTraceScene(r);
-    hipError_t e = hipMemcpyAsync(dRays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice, r->stream);
-    if (e == hipSuccess)
-    {
-        (void)hipEventRecord(r->evT0, r->stream);
-        (void)hipMemsetAsync(&r->counters.p[C_CHUNK], 0, sizeof(uint32_t), r->stream);
-        (void)hipMemsetAsync(dOverflow.p, 0, sizeof(uint32_t), r->stream);
-        withFlag(sceneOf(r)->scene.anyNonOpaque, [&](auto ALPHA) {
-            k_trace_rays<decltype(ALPHA)::value><<<gridFor(n), kBlock, 0, r->stream>>>(sc, dRays.p, n, anyHit, dHits.p, dIds.p, &r->counters.p[C_CHUNK], r->spill.p, dOverflow.p);
-        });
-        (void)hipEventRecord(r->evT1, r->stream);
-        e = hipMemcpyAsync(hits, dHits.p, (size_t)n * 16, hipMemcpyDeviceToHost, r->stream);
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ids, dIds.p, (size_t)n * 8, hipMemcpyDeviceToHost, r->stream);
-    uint32_t overflowed = 0;
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(&overflowed, dOverflow.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(r->stream);
-    if (e == hipSuccess)
-        e = hipGetLastError();
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, r->evT0, r->evT1);
-    r->stats.lastTraceMs = ms;
-    dRays.release(); dHits.release(); dIds.release(); dOverflow.release();
-    if (e != hipSuccess)
-        return fail(r, PTX_ERROR_DEVICE, "ptx_trace_rays: %s", hipGetErrorString(e));
-    if (overflowed)
-        return fail(r, PTX_ERROR_DEVICE, "ptx_trace_rays: traversal stack overflow (tree deeper than %d levels)", kLdsStack + kGlobalSpill);
-    return PTX_OK;
-}
+#include "pt_test_host.hpp" // ptx_test_eval, ptx_test_texture, ptx_test_debug_eval, ptx_trace_rays

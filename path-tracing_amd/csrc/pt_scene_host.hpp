@@ -67,30 +67,30 @@ static int shareScene(PtxRenderer *r, PtxRenderer *owner)
 {
     if (!r || !owner || r == owner)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: need two different renderers");
-    if (owner->sceneOwner || !r->sceneSharers.empty())
+    if (owner->link.owner || !r->link.sharers.empty())
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: the owner must hold its own scene, and a renderer others share from cannot borrow");
     if (owner->device != r->device)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_share_scene: renderers on different devices (%d, %d)", r->device, owner->device);
-    if (!owner->sceneReady || !owner->accelReady)
+    if (!owner->link.ready || !owner->accel.ready)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_share_scene: the owner needs ptx_scene_upload and ptx_build_accel first");
     HIP_TRY(r, hipSetDevice(r->device));
     // the owner's uploads and build are enqueued on ITS stream: finished before any stream of the borrower reads them;
     // the borrower's own frames in flight end before its scene goes away
     HIP_TRY(r, hipStreamSynchronize(owner->stream));
     HIP_TRY(r, hipStreamSynchronize(r->stream));
-    if (r->auxStream)
-        HIP_TRY(r, hipStreamSynchronize(r->auxStream));
+    if (r->streams.aux)
+        HIP_TRY(r, hipStreamSynchronize(r->streams.aux.get()));
     detachSharedScene(r);
     // its own copies are not needed any more (uploads still streaming into them end first)
     r->scene.streaming.reset();
     r->scene = SceneData();
-    r->nodes.release(); r->tris.release(); r->shadeTris.release(); r->alphaTris.release();
-    r->build = PtxRenderer::BuildState();
-    r->sceneReady = false;
-    r->sceneOwner = owner;
-    owner->sceneSharers.push_back(r);
-    r->accelReady = true;
-    r->hint.forget(); // whatever this handle had learnt, it had learnt on another scene
+    r->accel.tree = AccelState::Tree();
+    r->accel.build = BuildState();
+    r->link.ready = false;
+    r->link.owner = owner;
+    owner->link.sharers.push_back(r);
+    r->accel.ready = true;
+    r->launch.hint.forget(); // whatever this handle had learnt, it had learnt on another scene
     r->chain.status.sceneChanged(); // ... and its guides and history lead back to no pose of this one
     r->stats.triangles = owner->stats.triangles;
     r->stats.bvhNodes = owner->stats.bvhNodes;
@@ -728,9 +728,9 @@ struct TextureStreaming
 // stream), on a borrower by this wait.
 static int waitForCommits(PtxRenderer *r)
 {
-    if (!r->sceneOwner)
+    if (!r->link.owner)
         return PTX_OK;
-    const TextureStreaming *st = r->sceneOwner->scene.streaming.get();
+    const TextureStreaming *st = r->link.owner->scene.streaming.get();
     if (st && st->commits)
         HIP_TRY(r, hipStreamWaitEvent(r->stream, st->evCommitted, 0));
     return PTX_OK;
@@ -817,9 +817,9 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s, bool streamed = fa
     detachSharedScene(r); // a renderer that was borrowing a scene gets its own again
     quiesceSharers(r);
     r->scene.streaming.reset(); // (waits for the uploads that still write into the old pools)
-    r->sceneReady = r->accelReady = false;
-    r->sceneEpoch++;
-    r->build = PtxRenderer::BuildState();
+    r->link.ready = r->accel.ready = false;
+    r->link.epoch++;
+    r->accel.build = BuildState();
     // the pose bookkeeping starts over: tracking off, no snapshot, and a serial that no history of the old scene leads back to
     r->scene.pose.release();
     r->scene.pose.enabled = false;
@@ -833,7 +833,7 @@ static int sceneUpload(PtxRenderer *r, const PtxSceneDesc *s, bool streamed = fa
     HIP_TRY(r, hipStreamSynchronize(r->stream)); // `flat`, `plan` and the caller's arrays may go away
     if (streamed)
         HIP_TRY(r, hipGetLastError());
-    r->sceneReady = true;
+    r->link.ready = true;
     r->stats.triangles = flat.triangles;
     return PTX_OK;
 }
@@ -842,9 +842,9 @@ static int streamingOf(PtxRenderer *r, const char *who, TextureStreaming **out)
 {
     if (!r)
         return PTX_ERROR_INVALID_ARGUMENT;
-    if (r->sceneOwner)
+    if (r->link.owner)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: this renderer shares another renderer's scene (ptx_share_scene); uploads are the owner's calls", who);
-    if (!r->sceneReady)
+    if (!r->link.ready)
         return fail(r, PTX_ERROR_NOT_READY, "%s: no scene uploaded", who);
     if (!r->scene.streaming)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the scene was not uploaded by ptx_scene_upload_streamed", who);
@@ -1065,8 +1065,8 @@ static int texturesCommit(PtxRenderer *r, uint32_t *committed)
     quiesceSharers(r); // the borrowers' frames in flight still read the tables
     k_commit_textures<<<(n + 63) / 64, 64, 0, r->stream>>>(st->commitList + first, n, st->finalTextures.p, sc.renderTextures.p,
                                                           sc.anyNonOpaque ? sc.alphaTexOf.p : nullptr, st->finalAlphaTex.p, sc.alphaTex.p);
-    if (alpha && sc.anyNonOpaque && r->accelReady && r->treeTris) // the any-hit records carry the texture's extent and first quad
-        k_alpha_tris<<<(r->treeTris + 255) / 256, 256, 0, r->stream>>>(r->treeTris, r->tris.p, r->shadeTris.p, makeSceneView(r), sc.alphaTexOf.p, sc.alphaTex.p, r->alphaTris.p);
+    if (alpha && sc.anyNonOpaque && r->accel.ready && r->accel.tree.slots) // the any-hit records carry the texture's extent and first quad
+        k_alpha_tris<<<(r->accel.tree.slots + 255) / 256, 256, 0, r->stream>>>(r->accel.tree.slots, r->accel.tree.tris.p, r->accel.tree.shadeTris.p, makeSceneView(r), sc.alphaTexOf.p, sc.alphaTex.p, r->accel.tree.alphaTris.p);
     HIP_TRY(r, hipEventRecord(st->evCommitted, r->stream));
     HIP_TRY(r, hipGetLastError());
     st->commits++;
@@ -1080,7 +1080,7 @@ static int textureResidency(PtxRenderer *r, uint32_t *resident, uint32_t *pendin
     if (!r)
         return PTX_ERROR_INVALID_ARGUMENT;
     const PtxRenderer *s = sceneOf(r);
-    if (!s->sceneReady)
+    if (!s->link.ready)
         return fail(r, PTX_ERROR_NOT_READY, "ptx_texture_residency: no scene uploaded");
     const TextureStreaming *st = s->scene.streaming.get();
     uint32_t notResident = 0;
@@ -1098,7 +1098,7 @@ static uint32_t texturesRejected(PtxRenderer *r, uint32_t *indices, uint32_t cap
     if (!r)
         return 0;
     const PtxRenderer *s = sceneOf(r);
-    if (!s->sceneReady)
+    if (!s->link.ready)
         return 0;
     const std::vector<uint32_t> &rej = s->scene.rejectedTextures;
     for (uint32_t k = 0; indices && k < capacity && k < rej.size(); k++)

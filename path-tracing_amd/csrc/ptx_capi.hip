@@ -1,7 +1,8 @@
 // ptx_capi.hip -- the C-ABI of include/ptx.h (the one translation unit of libptx_hip.so).  Every entry point cites the
 // Renderer member it replaces in include/ptx.h; here each is ONE line (ptx_set_backend, ptx_synchronize and the trivial getters
-// apart) that calls the implementation in pt_runtime.hpp or one of the host files it includes (pt_scene_host.hpp, pt_bvh_host.hpp,
-// pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp, pt_chain_host.hpp);
+// apart) that calls the implementation in pt_runtime.hpp (ptx_create, ptx_destroy) or one of the host files it includes
+// (pt_scene_host.hpp, pt_bvh_host.hpp, pt_animation_host.hpp, pt_render_host.hpp, pt_frame_host.hpp, pt_output_host.hpp,
+// pt_chain_host.hpp, pt_test_host.hpp);
 // device side: pt_wavefront.hpp / pt_bvh.hpp / pt_bvh_build.hpp / pt_device.hpp.  No exceptions cross this boundary: status codes + ptx_last_error.
 #include "pt_runtime.hpp"
 
@@ -40,7 +41,7 @@ int ptx_set_backend(PtxRenderer *r, uint32_t backend)
     if (!r || backend > PTX_BACKEND_MEGAKERNEL)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_set_backend: bad backend %u", backend);
     if (r->backend != backend)
-        r->hint.forget(); // the learnt bounce schedule is the wavefront backend's
+        r->launch.hint.forget(); // the learnt bounce schedule is the wavefront backend's
     r->backend = backend;
     return PTX_OK;
 }
