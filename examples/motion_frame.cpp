@@ -8,6 +8,8 @@
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin     (scene, extent, spp, depth, time step, variance 0 / 1, file)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 1   (... with TemporalSettings::Responsive on: section 19,
 //                                                                        tests/test_responsive.py)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 1 (... with FireflySettings on: section 20, tests/test_fireflies.py)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 1 0   (... and without the denoiser: the plain output path)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
 // height x 16 bytes.
@@ -30,15 +32,17 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc != 9 && argc != 10)
+    if (argc < 9 || argc > 12)
     {
-        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1)]\n");
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1)]]]\n");
         return 1;
     }
     const std::string name = argv[1];
     const uint32_t width = std::atoi(argv[2]), height = std::atoi(argv[3]), spp = std::atoi(argv[4]), bounces = std::atoi(argv[5]);
     const float timeStep = static_cast<float>(std::atof(argv[6]));
-    const bool useVariance = std::atoi(argv[7]) != 0, useResponsive = argc == 10 && std::atoi(argv[9]) != 0;
+    const bool useVariance = std::atoi(argv[7]) != 0, useResponsive = argc >= 10 && std::atoi(argv[9]) != 0;
+    const bool useDespike = argc >= 11 && std::atoi(argv[10]) != 0;
+    const bool useDenoiser = argc < 12 || std::atoi(argv[11]) != 0; // 0: the plain output path, T is left as zeros
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
@@ -46,15 +50,18 @@ int main(int argc, char **argv)
         RendererHip::Init(0);
         // the settings first: the upload below turns the scene's tracking off, and UpdateSceneData has to turn it on again
         RendererHip::DenoiserSettings denoiser;
-        denoiser.Enabled = true;
+        denoiser.Enabled = useDenoiser;
         RendererHip::TemporalSettings temporal;
-        temporal.Enabled = temporal.MotionVectors = true;
+        temporal.Enabled = temporal.MotionVectors = useDenoiser;
         temporal.Responsive = useResponsive;
         RendererHip::VarianceSettings variance;
         variance.Enabled = useVariance;
         RendererHip::SetSettings(denoiser);
         RendererHip::SetSettings(temporal);
         RendererHip::SetSettings(variance);
+        RendererHip::FireflySettings firefly;
+        firefly.Enabled = useDespike;
+        RendererHip::SetSettings(firefly);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);
@@ -84,7 +91,8 @@ int main(int argc, char **argv)
             const std::vector<float> sum = RendererHip::ReadAccumulationImage();
             std::memcpy(&file[(3 * frame) * bytes], sum.data(), bytes);
             RendererHip::SaveOutput({ scratch, { width, height }, 0, OutputFormat::Png });
-            Check(ptx_read_temporal(RendererHip::GetHandle(), &file[(3 * frame + 1) * bytes], bytes), "ptx_read_temporal");
+            if (useDenoiser)
+                Check(ptx_read_temporal(RendererHip::GetHandle(), &file[(3 * frame + 1) * bytes], bytes), "ptx_read_temporal");
             Check(ptx_read_output(RendererHip::GetHandle(), PTX_OUTPUT_RGBA32F, &file[(3 * frame + 2) * bytes], bytes), "ptx_read_output");
         }
         FILE *f = std::fopen(argv[8], "wb");

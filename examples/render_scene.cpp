@@ -14,6 +14,7 @@
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3   (guides + temporal moments + the variance-guided filter)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3 --specular-guides 4   (... whose guides follow mirrors and glass)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3 --responsive   (... whose history follows a change of lighting)
+//   examples/render_scene default 640 360 1 4 despiked.png --despike        (firefly suppression: a rank clamp of every pixel's luminance; with --denoise ahead of the chain)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -117,6 +118,16 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
+    RendererHip::FireflySettings firefly; // --despike: firefly suppression ahead of the output stage, or of the chain where one is configured
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--despike")
+        {
+            firefly.Enabled = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -146,6 +157,7 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(denoiser);
         RendererHip::SetSettings(temporal);
         RendererHip::SetSettings(variance);
+        RendererHip::SetSettings(firefly);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

@@ -1203,6 +1203,65 @@ PTX_API int ptx_read_fast_history(PtxRenderer *r, void *host, size_t bytes);   /
 /* ... or its device address (NULL without one). */
 PTX_API void *ptx_device_fast_history_ptr(PtxRenderer *r);
 
+/* ------------------------------------------------------------------------- */
+/* Firefly suppression (docs/NEXT_ROWS.md section 20): a rank clamp ahead of   */
+/* the chain and the output stage.  Every pixel's luminance is capped at gain  */
+/* times the rank-th largest luminance among its neighbours; only comparisons  */
+/* decide who is clamped, so the result does not depend on the image's scale.  */
+/* An addition: every call above computes what it computed before, and a host  */
+/* that never calls these functions allocates nothing for them.                */
+/* ------------------------------------------------------------------------- */
+
+typedef struct PtxDespikeDesc {
+    uint32_t radius;   /* 1 or 2: the window is (2 radius + 1)^2 without its centre */
+    uint32_t rank;     /* 1 ... 4: which of the neighbours' luminances, counted from the largest, is the bound */
+    uint32_t minTaps;  /* rank ... (2 radius + 1)^2 - 1: a pixel with fewer counting neighbours is left alone */
+    float    gain;     /* >= 1, finite: the bound is gain times that luminance */
+    uint32_t flags;    /* 0 */
+    uint32_t reserved; /* 0 */
+} PtxDespikeDesc;
+
+/* S is the accumulation image (ptx_device_accum_ptr, a bound image included).  C is a renderer-owned RGBA32F image of the render
+ * extent IN THE SUM'S SCALE, so that C can stand wherever S does; S is never written.  All arithmetic is float32 with the operations
+ * in the order written (no contraction).
+ *   1. Y(p) = (0.2126f S(p).r + 0.7152f S(p).g) + 0.0722f S(p).b.
+ *   2. A pixel COUNTS iff Y(p) is finite (a NaN or Inf channel makes Y non-finite).
+ *   3. The window of p is the (2 radius + 1)^2 texels around p without p itself.
+ *   4. A tap q counts iff it is inside the image and the pixel there counts.
+ *   5. n is the number of counting taps.
+ *   6. h is the rank-th largest Y among the counting taps, equal values counted separately.
+ *   7. b = gain h where that product is greater than zero, and b = +0 otherwise (a negative product and -0 alike).
+ *   8. p is CLAMPED iff all four hold: p counts; n >= minTaps; Y(p) >= 2^-126 (a normal number, so that the specified reciprocal
+ *      is finite); Y(p) > b.
+ *   9. If p is clamped, s = b rcp(Y(p)) -- the project's division: rcp is the correctly rounded reciprocal on [2^-126, 2^126] and
+ *      +-0 above -- C(p).rgb = S(p).rgb s, channel by channel, and C(p).a = S(p).a.
+ *  10. Otherwise C(p) = S(p) bit for bit.  A pixel that is not finite keeps its class, so the output stage's markers still appear.
+ * Consequences: (a) a constant image comes back bit for bit; (b) multiplying S by a power of two multiplies C by it, bit for bit
+ * (short of overflow and of denormals); (c) a pixel whose counting neighbours are all black becomes zeros; (d) with rank 1 two adjacent equal
+ * spikes protect each other, with rank 2 both are clamped.
+ * One launch, asynchronous on the render stream; needs no scene and no guides; works on a borrower.  C is of the sum as it stood
+ * when the call was enqueued: a later ptx_render does not refresh it, that is the host's job, as with the guides.  C is allocated by
+ * the first call (16 bytes per pixel).
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL argument, radius other than 1 or 2, rank outside 1 ... 4, minTaps < rank,
+ * minTaps > (2 radius + 1)^2 - 1, gain < 1 or not finite, flags != 0, reserved != 0.  PTX_ERROR_NOT_READY: no image (ptx_resize), a
+ * shard accumulation buffer bound, a tile shard with worldSize > 1 (the taps cross tiles).  A refused call leaves the previous C
+ * intact; ptx_resize drops C.
+ * Known limits: a one-pixel emitter or sun is clamped like a firefly; energy is lost by design; there is no guide term. */
+PTX_API int ptx_despike(PtxRenderer *r, const PtxDespikeDesc *desc);
+/* C, device -> host, width*height*16 bytes; synchronous.  PTX_ERROR_INVALID_ARGUMENT: a NULL argument or a buffer of another size;
+ * PTX_ERROR_NOT_READY: no ptx_despike since the last ptx_resize. */
+PTX_API int ptx_read_despiked(PtxRenderer *r, void *host, size_t bytes);
+/* ... or its device address (NULL without one). */
+PTX_API void *ptx_device_despiked_ptr(PtxRenderer *r);
+/* A sticky switch, like ptx_track_motion: off by default, kept across ptx_resize.  While on, ptx_temporal_accumulate, its moments,
+ * motion and responsive forms and ptx_denoise read C where they read S, and nothing else changes; their refusals gain one last
+ * reason, behind every other: PTX_ERROR_NOT_READY while no C exists since the last ptx_resize, with T, the histories and D intact.
+ * While off those calls are what they were.  PTX_ERROR_INVALID_ARGUMENT: a NULL handle. */
+PTX_API int ptx_chain_use_despiked(PtxRenderer *r, int enable);
+/* ptx_postprocess's chain on C with the caller's TotalSamples (C is in the sum's scale); ptx_read_output and ptx_present follow
+ * unchanged.  PTX_ERROR_INVALID_ARGUMENT as ptx_postprocess; PTX_ERROR_NOT_READY: no ptx_despike since the last ptx_resize. */
+PTX_API int ptx_postprocess_despiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

@@ -70,6 +70,7 @@ PTX_SYMBOLS = [
     "ptx_track_motion", "ptx_render_guides_motion", "ptx_read_motion", "ptx_device_motion_ptr", "ptx_temporal_accumulate_motion",
     "ptx_render_guides_specular", "ptx_read_specular_guide", "ptx_device_specular_guide_ptr",
     "ptx_temporal_accumulate_responsive", "ptx_read_fast_history", "ptx_device_fast_history_ptr",
+    "ptx_despike", "ptx_read_despiked", "ptx_device_despiked_ptr", "ptx_chain_use_despiked", "ptx_postprocess_despiked",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -214,6 +215,14 @@ RESPONSIVE_MOMENTS, RESPONSIVE_MOTION = 1, 2  # PTX_RESPONSIVE_* of include/ptx.
 # The defaults of Renderer.temporal_accumulate_responsive: first in the sweep of tools/temporal_quality.py --responsive
 # (docs/NEXT_ROWS.md section 19)
 RESPONSIVE_DEFAULTS = dict(fast_history=2.0, clamp_sigma=1.0)
+
+
+class DespikeDesc(C.Structure):
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("minTaps", C.c_uint32), ("gain", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# The defaults of Renderer.despike: first in the sweep of tools/firefly_quality.py (docs/NEXT_ROWS.md section 20)
+DESPIKE_DEFAULTS = dict(radius=2, rank=4, gain=1.0, min_taps=8)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -449,6 +458,12 @@ def load_hip() -> C.CDLL:
         lib.ptx_read_fast_history.argtypes = [P, P, C.c_size_t]
         lib.ptx_device_fast_history_ptr.argtypes = [P]
         lib.ptx_device_fast_history_ptr.restype = P
+        lib.ptx_despike.argtypes = [P, C.POINTER(DespikeDesc)]
+        lib.ptx_read_despiked.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_despiked_ptr.argtypes = [P]
+        lib.ptx_device_despiked_ptr.restype = P
+        lib.ptx_chain_use_despiked.argtypes = [P, C.c_int]
+        lib.ptx_postprocess_despiked.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32]
         _hip = lib
     return _hip
 
@@ -883,6 +898,31 @@ class Renderer:
 
     def fast_history_ptr(self) -> int:
         return int(self.lib.ptx_device_fast_history_ptr(self.handle) or 0)
+
+    def despike(self, radius: int = DESPIKE_DEFAULTS["radius"], rank: int = DESPIKE_DEFAULTS["rank"], gain: float = DESPIKE_DEFAULTS["gain"],
+                min_taps: int = DESPIKE_DEFAULTS["min_taps"]):
+        """ptx_despike: firefly suppression.  Every pixel's luminance is capped at `gain` times the `rank`-th largest luminance among
+        the counting neighbours of its (2 radius + 1)^2 window, where there are at least min_taps of them; the result is an image in
+        the accumulation's scale that the renderer keeps.  No scene and no guides needed."""
+        d = DespikeDesc(radius, rank, min_taps, gain, 0, 0)
+        self._check(self.lib.ptx_despike(self.handle, C.byref(d)))
+
+    def read_despiked(self) -> np.ndarray:
+        """The image of the last despike(): H x W x 4 float32, a running sum like readback()'s."""
+        return self._read_image(self.lib.ptx_read_despiked)
+
+    def despiked_ptr(self) -> int:
+        return int(self.lib.ptx_device_despiked_ptr(self.handle) or 0)
+
+    def chain_use_despiked(self, enable: bool = True):
+        """ptx_chain_use_despiked: while on, the accumulate calls and denoise() read despike()'s image where they read the sum."""
+        self._check(self.lib.ptx_chain_use_despiked(self.handle, 1 if enable else 0))
+
+    def postprocess_despiked(self, total_samples: int, exposure: float = 1.0, bloom_threshold: float = 1.0, bloom_intensity: float = 1.0,
+                             tone_mapping: int = TONE_MAPPING_SDR):
+        """ptx_postprocess_despiked: postprocess() on despike()'s image, which is in the sum's scale: total_samples is the caller's."""
+        u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
+        self._check(self.lib.ptx_postprocess_despiked(self.handle, C.byref(u), tone_mapping))
 
     def stats(self) -> Stats:
         s = Stats()

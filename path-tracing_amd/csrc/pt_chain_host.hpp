@@ -1,14 +1,16 @@
 // pt_chain_host.hpp -- host side of the interactive chain, the stages on the render stream between ptx_render and the output stage:
 // the guide pass (plain, with motion guides, following specular chains), the temporal accumulation (plain, with moments, through the
-// motion guides, responsive), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs.  Kernels: pt_denoise.hpp, pt_temporal.hpp,
-// pt_variance.hpp, pt_responsive.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 19; state: ChainState, the member `chain` of
+// motion guides, responsive), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs, and the firefly
+// suppression in front of them (ptx_despike, the switch that puts its image in the sum's place, its output call).  Kernels: pt_denoise.hpp, pt_temporal.hpp,
+// pt_variance.hpp, pt_responsive.hpp, pt_despike.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 20; state: ChainState, the member `chain` of
 // the handle, whose bookkeeping (pt_chain_state.hpp) is told of every accepted call.  Included by pt_runtime.hpp after
 // pt_output_host.hpp (postprocessImage); every function takes a valid or null handle and returns a PTX_* code.
 #pragma once
 
 // What every stage behind the guide pass needs, in the order it is reported.  `taps`: whose taps cross tiles, "filter" or "history";
-// `motion`: the call reads the motion guides.
-static int chainRefusal(PtxRenderer *r, const char *who, const char *taps, bool motion = false)
+// `motion`: the call reads the motion guides.  `readsSum`: the call reads the accumulation image, so C in its place while
+// ptx_chain_use_despiked is on (docs/NEXT_ROWS.md section 20): the last rung.
+static int chainRefusal(PtxRenderer *r, const char *who, const char *taps, bool motion = false, bool readsSum = false)
 {
     if (!imagePtr(r))
         return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
@@ -21,7 +23,15 @@ static int chainRefusal(PtxRenderer *r, const char *who, const char *taps, bool 
                     "ptx_render_guides_motion", who);
     if (r->frame.shard.worldSize > 1u)
         return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; the %s's taps cross tiles", who, r->frame.shard.worldSize, taps);
+    if (readsSum && r->chain.status.useDespiked && !r->chain.status.despikedReady)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: ptx_chain_use_despiked is on and there is no despiked image for this extent (call ptx_despike)", who);
     return PTX_OK;
+}
+
+// The image the accumulate calls and ptx_denoise read as the sum: C while ptx_chain_use_despiked is on (chainRefusal saw that it exists)
+static const float4 *chainSum(const PtxRenderer *r)
+{
+    return r->chain.status.useDespiked ? r->chain.despikedImage.p : imagePtr(r);
 }
 
 // one thread per pixel in 32 x 8 tiles: the grid of every kernel behind the guide pass
@@ -194,7 +204,7 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
                        responsive->reserved != 0u)) // the flags chose `moments` and `motion`: temporalAccumulateResponsive
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need 1 <= fastHistory <= maxHistory (%g, %g), clampSigma > 0 and finite (%g) and reserved 0 (%u)", who,
                     (double)responsive->fastHistory, (double)d->maxHistory, (double)responsive->clampSigma, responsive->reserved);
-    if (const int rc = chainRefusal(r, who, "history", motion))
+    if (const int rc = chainRefusal(r, who, "history", motion, true))
         return rc;
     HIP_TRY(r, hipSetDevice(r->device));
     ChainState &c = r->chain;
@@ -211,7 +221,7 @@ static int temporalAccumulate(PtxRenderer *r, const PtxTemporalDesc *d, bool mom
     ChainStatus next = c.status; // the call counts once its launch is accepted
     const ChainStatus::Accumulate h = next.accumulate(moments, (d->flags & PTX_TEMPORAL_RESET) != 0u, responsive != nullptr);
     TemporalArgs a;
-    a.sum = imagePtr(r);
+    a.sum = chainSum(r);
     setGuides(r, a);
     a.histIn = h.useHistory ? c.temporalHistory[h.src].p : nullptr;
     a.histOut = c.temporalHistory[h.dst].p;
@@ -326,7 +336,7 @@ static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d, const float4 *source
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need 1 <= iterations <= 6 (%u), totalSamples > 0 (%u), sigmaColor >= 0 (%g), sigmaNormal > 0 (%g), "
                     "sigmaPosition > 0 (%g), all finite, flags 0 (0x%x) and reserved 0 (%u)", who, d->iterations, totalSamples, (double)d->sigmaColor,
                     (double)d->sigmaNormal, (double)d->sigmaPosition, d->flags, d->reserved);
-    if (const int rc = chainRefusal(r, who, "filter"))
+    if (const int rc = chainRefusal(r, who, "filter", false, !source))
         return rc;
     HIP_TRY(r, hipSetDevice(r->device));
     ChainState &c = r->chain;
@@ -334,7 +344,7 @@ static int denoise(PtxRenderer *r, const PtxDenoiseDesc *d, const float4 *source
     if (d->iterations > 1u)
         HIP_TRY(r, c.denoisePing[1].alloc(r->frame.pixels()));
     DenoiseArgs a;
-    a.sum = source ? source : imagePtr(r);
+    a.sum = source ? source : chainSum(r);
     setGuides(r, a);
     a.width = r->frame.width;
     a.height = r->frame.height;
@@ -445,4 +455,71 @@ static int postprocessDenoised(PtxRenderer *r, const PtxPostProcessingUniformDat
     PtxPostProcessingUniformData u = *uniform;
     u.TotalSamples = 1u;
     return postprocessImage(r, r->chain.denoised(), &u, toneMappingMode);
+}
+
+// ---- firefly suppression (docs/NEXT_ROWS.md section 20) ------------------------------------------------------------------------------
+
+// ptx_despike: C from the sum as it stands, one launch.  No scene and no guides: the ladder is the image's own.
+static int despike(PtxRenderer *r, const PtxDespikeDesc *d)
+{
+    const char *who = "ptx_despike";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const uint32_t window = d->radius == 1u ? 8u : 24u;
+    if ((d->radius != 1u && d->radius != 2u) || d->rank < 1u || d->rank > 4u || d->minTaps < d->rank || d->minTaps > window ||
+        !(d->gain >= 1.0f && d->gain <= 3.402823466e38f) || d->flags != 0u || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need radius 1 or 2 (%u), 1 <= rank <= 4 (%u), rank <= minTaps <= (2 radius + 1)^2 - 1 (%u), "
+                    "gain >= 1 and finite (%g), flags 0 (0x%x) and reserved 0 (%u)", who, d->radius, d->rank, d->minTaps, (double)d->gain, d->flags, d->reserved);
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+    if (r->frame.boundShard)
+        return frameIsElsewhere(r, who);
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; the window's taps cross tiles", who, r->frame.shard.worldSize);
+    HIP_TRY(r, hipSetDevice(r->device));
+    ChainState &c = r->chain;
+    HIP_TRY(r, c.despikedImage.alloc(r->frame.pixels()));
+    DespikeArgs a;
+    a.sum = imagePtr(r);
+    a.out = c.despikedImage.p;
+    a.width = r->frame.width;
+    a.height = r->frame.height;
+    a.rank = d->rank;
+    a.minTaps = d->minTaps;
+    a.gain = d->gain;
+    if (d->radius == 1u)
+        k_despike<1><<<tileGrid(r), kTileBlock, 0, r->stream>>>(a);
+    else
+        k_despike<2><<<tileGrid(r), kTileBlock, 0, r->stream>>>(a);
+    HIP_TRY(r, hipGetLastError());
+    c.status.despiked();
+    return PTX_OK;
+}
+
+static int readDespiked(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_despiked: null argument");
+    if (!r->chain.despiked())
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_despiked: call ptx_despike first");
+    return readFrameImage(r, r->chain.despiked(), host, bytes, sizeof(float4), "ptx_read_despiked");
+}
+
+// ptx_chain_use_despiked: sticky, like ptx_track_motion; the calls that read the sum look at it when they are made
+static int chainUseDespiked(PtxRenderer *r, int enable)
+{
+    if (!r)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_chain_use_despiked: null argument");
+    r->chain.status.useDespiked = enable != 0;
+    return PTX_OK;
+}
+
+// ptx_postprocess's chain on C, which is in the sum's scale: the caller's TotalSamples
+static int postprocessDespiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+{
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess_despiked: bad argument");
+    if (!r->chain.despiked())
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess_despiked: call ptx_despike first");
+    return postprocessImage(r, r->chain.despiked(), uniform, toneMappingMode);
 }

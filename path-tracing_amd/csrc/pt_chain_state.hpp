@@ -1,5 +1,5 @@
 // pt_chain_state.hpp -- the bookkeeping of the interactive chain (guide pass, temporal accumulation, the filters; semantics:
-// include/ptx.h, docs/NEXT_ROWS.md sections 13-19): what is ready, which ping-pong copy is current, whether the moments are live and
+// include/ptx.h, docs/NEXT_ROWS.md sections 13-20): what is ready, which ping-pong copy is current, whether the moments are live and
 // which pose a history leads back to, with every event that changes them as one member function.  No buffers, no matrices and no HIP
 // in here (tests/test_chain_state.py compiles it alone); ChainState (pt_runtime.hpp) holds one beside the images, and
 // pt_chain_host.hpp, pt_frame_host.hpp and pt_scene_host.hpp report the events.
@@ -21,6 +21,8 @@ struct ChainStatus
     bool varianceReady = false; // V_0 of a ptx_denoise_variance
     bool motionReady = false;   // the motion images belong to the current guides
     bool specularReady = false; // a ptx_render_guides_specular since the last ptx_resize: the fourth image exists
+    bool despikedReady = false; // a ptx_despike since the last ptx_resize: C exists
+    bool useDespiked = false;   // ptx_chain_use_despiked: the calls that read the sum read C; sticky, ptx_resize keeps it
     // pose serials (SceneData::PoseTracking): the one the guides were rendered at, the one the history was made from, and the history
     // pose the motion images lead back to (kNoPose: there was no history)
     uint64_t guidesPose = kNoPose, temporalPose = kNoPose, motionFromPose = kNoPose;
@@ -41,7 +43,7 @@ struct ChainStatus
     // ptx_resize: everything belongs to the extent it was made for (the serials stay: nothing is left that they describe)
     void resize()
     {
-        guidesReady = temporalReady = momentsLive = fastLive = varianceReady = motionReady = specularReady = false;
+        guidesReady = temporalReady = momentsLive = fastLive = varianceReady = motionReady = specularReady = despikedReady = false;
         denoisedIn = historyIn = -1;
     }
     // ptx_scene_upload, its streamed form, ptx_share_scene: guides and history lead back to no pose of the new scene, the motion images are stale
@@ -76,6 +78,8 @@ struct ChainStatus
         temporalPose = guidesPose; // the history now leads back to the pose its guides were rendered at
         return a;
     }
+    // an accepted ptx_despike (docs/NEXT_ROWS.md section 20)
+    void despiked() { despikedReady = true; }
     // the filters: iteration i writes filter image i & 1
     void filtered(uint32_t iterations) { denoisedIn = (int)((iterations - 1u) & 1u); }
     void varianceFiltered(uint32_t iterations) { filtered(iterations); varianceReady = true; }

@@ -36,6 +36,7 @@
 #include "pt_temporal.hpp"
 #include "pt_variance.hpp"
 #include "pt_responsive.hpp"
+#include "pt_despike.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -284,6 +285,7 @@ struct ChainState
     DevBuf<float4> momentHistory[2];                  // the moment history ping-pongs with temporalHistory
     DevBuf<float4> fastHistory[2];                    // ... and so does the fast history of ptx_temporal_accumulate_responsive
     DevBuf<float> varianceImage;                      // V_0 of the last ptx_denoise_variance
+    DevBuf<float4> despikedImage;                     // C of the last ptx_despike, in the sum's scale
     float temporalView[16] = {}, temporalProj[16] = {}; // the matrices the last accepted accumulate call was given
     ChainStatus status;
 
@@ -291,6 +293,7 @@ struct ChainState
     float4 *motionPtr(uint32_t which, size_t pixels) const { return motion.p + which * pixels; }
     float4 *specularPtr(uint32_t which, size_t pixels) const { return specular.p + which * pixels; }
     float4 *denoised() const { return status.denoisedIn >= 0 ? denoisePing[status.denoisedIn].p : nullptr; }
+    float4 *despiked() const { return status.despikedReady ? despikedImage.p : nullptr; }
     void invalidate() { status.resize(); } // the images stay allocated: the next calls of the new extent grow them if they must
 };
 

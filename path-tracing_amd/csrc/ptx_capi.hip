@@ -341,6 +341,31 @@ void *ptx_device_fast_history_ptr(PtxRenderer *r)
     return r && r->chain.status.fastCurrent() ? r->chain.fastHistory[r->chain.status.historyIn].p : nullptr;
 }
 
+int ptx_despike(PtxRenderer *r, const PtxDespikeDesc *desc)
+{
+    return despike(r, desc);
+}
+
+int ptx_read_despiked(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readDespiked(r, host, bytes);
+}
+
+void *ptx_device_despiked_ptr(PtxRenderer *r)
+{
+    return r ? r->chain.despiked() : nullptr;
+}
+
+int ptx_chain_use_despiked(PtxRenderer *r, int enable)
+{
+    return chainUseDespiked(r, enable);
+}
+
+int ptx_postprocess_despiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+{
+    return postprocessDespiked(r, uniform, toneMappingMode);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

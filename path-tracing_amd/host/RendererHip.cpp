@@ -184,14 +184,35 @@ void RendererHip::SetSettings(const VarianceSettings &settings)
     s_VarianceSettings = settings;
 }
 
+static RendererHip::FireflySettings s_FireflySettings;
+
+void RendererHip::SetSettings(const FireflySettings &settings)
+{
+    const bool wasOn = s_FireflySettings.Enabled;
+    s_FireflySettings = settings;
+    if (wasOn && !settings.Enabled && s_Renderer) // the chain reads the sum again
+        Check(ptx_chain_use_despiked(s_Renderer, 0));
+}
+
 // The post-processing chain on the current frame: on the running sum, or -- with the denoiser enabled and the path-tracing pipeline
 // bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser"); with the temporal accumulation enabled as well
 // the filter runs on its result (ptx.h, "Temporal accumulation"), and with the variance settings enabled on top the moments are
 // accumulated beside it and the variance-guided filter takes the fixed-sigma one's place (ptx.h, "Variance-guided denoising").
 static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode)
 {
+    // firefly suppression (ptx.h, "Firefly suppression") ahead of whatever follows: the despiked image stands where the sum did
+    const bool despike = s_FireflySettings.Enabled && !s_DebugPipeline;
+    if (despike)
+    {
+        const PtxDespikeDesc firefly = { s_FireflySettings.Radius, s_FireflySettings.Rank, s_FireflySettings.MinTaps, s_FireflySettings.Gain, 0u, 0u };
+        if (const int rc = ptx_despike(s_Renderer, &firefly))
+            return rc;
+    }
     if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
-        return ptx_postprocess(s_Renderer, &u, mode);
+        return despike ? ptx_postprocess_despiked(s_Renderer, &u, mode) : ptx_postprocess(s_Renderer, &u, mode);
+    if (despike)
+        if (const int rc = ptx_chain_use_despiked(s_Renderer, 1))
+            return rc;
     const PtxRaygenUniformData rgenData = FillRaygenUniform();
     const bool motion = s_MotionVectors && s_TemporalSettings.Enabled;
     const PtxSpecularGuidesDesc specular = { s_DenoiserSettings.SpecularBounces, s_DenoiserSettings.SpecularRoughnessMax, 0u, 0u };

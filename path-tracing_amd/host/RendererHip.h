@@ -102,6 +102,21 @@ public:
         float ClampSigma = 1.0f;
     };
     static void SetSettings(const TemporalSettings &settings);
+    // Firefly suppression (ptx.h "Firefly suppression", docs/NEXT_ROWS.md section 20): a rank clamp of every pixel's luminance ahead of
+    // everything SaveOutput and Present do with the sum.  Enabled without the denoiser: ptx_despike -> ptx_postprocess_despiked in
+    // ptx_postprocess' place.  Enabled with the denoiser (and whatever temporal and variance settings): ptx_despike, then
+    // ptx_chain_use_despiked, then the chain as configured, whose accumulate call or ptx_denoise reads the despiked image where it
+    // read the sum.  Disabled (the default): SaveOutput and Present enqueue exactly what they did; disabling it turns the switch off
+    // again.  A debug-view frame is shown as it is.  The defaults are the measured ones of section 20.
+    struct FireflySettings
+    {
+        bool Enabled = false;
+        uint32_t Radius = 2;
+        uint32_t Rank = 4;
+        float Gain = 1.0f;
+        uint32_t MinTaps = 8;
+    };
+    static void SetSettings(const FireflySettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either

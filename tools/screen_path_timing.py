@@ -20,6 +20,9 @@ which the figure leaves out).  --temporal-only times nothing but the accumulate 
 two.  The wall clock cannot take the call's two launches apart: a kernel trace of `--temporal-only --extent W H` (rocprofv3
 --kernel-trace --stats, in a run of its own) gives k_responsive_clamp's and k_temporal_responsive's device times per extent.
 
+ptx_despike (section 20) stands behind the responsive rows, and so in the --temporal-only run whose kernel trace holds
+k_responsive_clamp: one launch per call at radius 1 and 2, against 37.25 and 43 bytes per pixel (16 B out, 16 B x (tile + halo) / tile in).
+
 ptx_render_guides_specular (section 18) at the package's defaults stands beside ptx_render_guides of the same run on chess_like and on
 `default`; --guides-only times nothing but the two guide passes.
 
@@ -43,6 +46,8 @@ DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
 TEMPORAL_BYTES_PER_PIXEL = 176
 MOMENTS_BYTES_PER_PIXEL = 208
 RESPONSIVE_BYTES_PER_PIXEL = 240
+# 16 B out and 16 B x (tile + halo) / tile in: the halo is 84 entries of 256 at radius 1 and 176 at radius 2
+DESPIKE_BYTES_PER_PIXEL = {1: 16 + 16 * (256 + 84) / 256, 2: 16 + 16 * (256 + 176) / 256}
 
 
 def timed(r, call):
@@ -143,6 +148,12 @@ def main():
             T = r.read_temporal()
             t["share_of_valid_pixels_below_max_history"] = float((T[..., 3][T[..., 3] > 0] < pkg.TEMPORAL_DEFAULTS["max_history"]).mean())
             rec[key] = t
+        # ptx_despike (section 20) on the 8-spp sum, both radii at the package's rank, gain and a third of the window: one launch each
+        for radius, min_taps in ((1, 3), (2, 8)):
+            p = dict(pkg.DESPIKE_DEFAULTS, radius=radius, min_taps=max(min_taps, pkg.DESPIKE_DEFAULTS["rank"]))
+            t = timed(r, lambda: r.despike(**p))
+            t["algorithmic_GB_per_s"] = w * h * DESPIKE_BYTES_PER_PIXEL[radius] / (t["median_ms"] * 1e-3) / 1e9
+            rec[f"despike_radius_{radius}"] = t
         if temporal_only:
             out[f"{w}x{h}"] = rec
             for k, v in rec.items():
