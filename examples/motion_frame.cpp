@@ -10,6 +10,10 @@
 //                                                                        tests/test_responsive.py)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 1 (... with FireflySettings on: section 20, tests/test_fireflies.py)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 1 0   (... and without the denoiser: the plain output path)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 1 (... with ExposureSettings on: section 21, tests/test_metering.py;
+//                                                                            every frame is announced with OnUpdate(timeStep)
+//                                                                            and, without the denoiser, saved twice)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 1 1 (... with the denoiser: the denoised image is metered)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
 // height x 16 bytes.
@@ -32,9 +36,9 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 9 || argc > 12)
+    if (argc < 9 || argc > 13)
     {
-        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1)]]]\n");
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1)]]]]\n");
         return 1;
     }
     const std::string name = argv[1];
@@ -43,6 +47,7 @@ int main(int argc, char **argv)
     const bool useVariance = std::atoi(argv[7]) != 0, useResponsive = argc >= 10 && std::atoi(argv[9]) != 0;
     const bool useDespike = argc >= 11 && std::atoi(argv[10]) != 0;
     const bool useDenoiser = argc < 12 || std::atoi(argv[11]) != 0; // 0: the plain output path, T is left as zeros
+    const bool useExposure = argc >= 13 && std::atoi(argv[12]) != 0;
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
@@ -62,6 +67,9 @@ int main(int argc, char **argv)
         RendererHip::FireflySettings firefly;
         firefly.Enabled = useDespike;
         RendererHip::SetSettings(firefly);
+        RendererHip::ExposureSettings exposure;
+        exposure.Enabled = useExposure;
+        RendererHip::SetSettings(exposure);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);
@@ -86,11 +94,15 @@ int main(int argc, char **argv)
                                            static_cast<uint32_t>(bones.size()), PTX_ACCEL_REFIT), "ptx_update_animation");
                 RendererHip::UpdateSceneData(scene, true); // the same scene, moved: the accumulation restarts, the history stays
             }
+            if (useExposure)
+                RendererHip::OnUpdate(timeStep);
             for (uint32_t i = 0; i < spp; i++)
                 RendererHip::Render();
             const std::vector<float> sum = RendererHip::ReadAccumulationImage();
             std::memcpy(&file[(3 * frame) * bytes], sum.data(), bytes);
             RendererHip::SaveOutput({ scratch, { width, height }, 0, OutputFormat::Png });
+            if (useExposure && !useDenoiser) // a second output call of the same frame: the time step is used up, the exposure stays
+                RendererHip::SaveOutput({ scratch, { width, height }, 0, OutputFormat::Png });
             if (useDenoiser)
                 Check(ptx_read_temporal(RendererHip::GetHandle(), &file[(3 * frame + 1) * bytes], bytes), "ptx_read_temporal");
             Check(ptx_read_output(RendererHip::GetHandle(), PTX_OUTPUT_RGBA32F, &file[(3 * frame + 2) * bytes], bytes), "ptx_read_output");

@@ -15,6 +15,7 @@
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3 --specular-guides 4   (... whose guides follow mirrors and glass)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3 --responsive   (... whose history follows a change of lighting)
 //   examples/render_scene default 640 360 1 4 despiked.png --despike        (firefly suppression: a rank clamp of every pixel's luminance; with --denoise ahead of the chain)
+//   examples/render_scene default 640 360 16 4 metered.png --auto-exposure  (exposure metering: a luminance histogram sets the output stage's exposure)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -128,6 +129,16 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
+    RendererHip::ExposureSettings exposure; // --auto-exposure: the image about to be post-processed is metered and sets its own exposure
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--auto-exposure")
+        {
+            exposure.Enabled = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -158,6 +169,7 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(temporal);
         RendererHip::SetSettings(variance);
         RendererHip::SetSettings(firefly);
+        RendererHip::SetSettings(exposure);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

@@ -1262,6 +1262,119 @@ PTX_API int ptx_chain_use_despiked(PtxRenderer *r, int enable);
  * unchanged.  PTX_ERROR_INVALID_ARGUMENT as ptx_postprocess; PTX_ERROR_NOT_READY: no ptx_despike since the last ptx_resize. */
 PTX_API int ptx_postprocess_despiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode);
 
+/* ------------------------------------------------------------------------- */
+/* Exposure metering (docs/NEXT_ROWS.md section 21): a luminance histogram of  */
+/* the image the output stage is about to read sets that stage's exposure, on  */
+/* the device.  An addition: every call above computes what it computed        */
+/* before, and a host that never calls ptx_meter allocates nothing for it.     */
+/* ------------------------------------------------------------------------- */
+
+enum {
+    PTX_METER_SUM = 0,      /* the accumulation image, as ptx_postprocess reads it: totalSamples is the caller's */
+    PTX_METER_DESPIKED = 1, /* C of ptx_despike, as ptx_postprocess_despiked reads it: in the sum's scale, totalSamples is the caller's */
+    PTX_METER_DENOISED = 2  /* D of the filters, as ptx_postprocess_denoised reads it: D holds the mean, so 1 stands for totalSamples */
+};
+enum {
+    PTX_METER_AVERAGE = 0,
+    PTX_METER_CENTRE = 1,
+    PTX_METER_REGION = 2
+};
+
+typedef struct PtxMeterDesc {
+    uint32_t source;          /* PTX_METER_SUM / _DESPIKED / _DENOISED */
+    uint32_t mode;            /* PTX_METER_AVERAGE / _CENTRE / _REGION */
+    uint32_t totalSamples;    /* > 0; what PtxPostProcessingUniformData::TotalSamples will be (PTX_METER_DENOISED: checked, then 1 is used) */
+    uint32_t region[4];       /* x0, x1, y0, y1: [x0, x1) x [y0, y1), read in PTX_METER_REGION only */
+    uint32_t lowPermille;     /* the share of the counted weight cut off at the dark end ... */
+    uint32_t highPermille;    /* ... and at the bright end; lowPermille + highPermille < 1000 */
+    float    keyLog2;         /* log2 of the luminance the kept mean is brought to (log2(0.18): middle grey) */
+    float    compensation;    /* stops added on top */
+    float    minLog2Exposure; /* the target is clamped to [minLog2Exposure, maxLog2Exposure] */
+    float    maxLog2Exposure;
+    float    speedUp;         /* 1 / seconds, >= 0: the rate while the exposure rises ... */
+    float    speedDown;       /* ... and while it falls */
+    float    deltaSeconds;    /* >= 0: the time since the previous ptx_meter */
+    uint32_t flags;           /* 0 */
+    uint32_t reserved;        /* 0 */
+} PtxMeterDesc;
+
+typedef struct PtxMeterResult {
+    float    exposure;     /* the factor ptx_postprocess_metered multiplies PtxPostProcessingUniformData::Exposure by; 1 after a reset */
+    float    log2Exposure; /* its logarithm, the adapted state; 0 after a reset */
+    float    avgLog2;      /* the mean log2 luminance of the kept weight (step 6) of the last valid call */
+    float    targetLog2;   /* where the last valid call was heading (step 7) */
+    uint32_t counted;      /* N: the weight in the 256 bins */
+    uint32_t kept;         /* K: what the trim left of it */
+    uint32_t black;        /* the weight of the black class ... */
+    uint32_t rejected;     /* ... and of the rejected one */
+    uint32_t under;        /* the part of bin 0 that lies below 2^-16 */
+    uint32_t over;         /* the part of bin 255 that lies at or above 2^16 */
+    uint32_t valid;        /* 1: the last call had K > 0 and moved the exposure; 0: it left it alone */
+    uint32_t calls;        /* accepted ptx_meter calls since the last reset */
+} PtxMeterResult;
+
+/* ptx_meter.  W x H is the render extent, p = (x, y) a pixel.  Unless stated otherwise the arithmetic is float32 up to the histogram
+ * (steps 1 - 4) and float64 behind it (steps 5 - 8), IEEE operations in the order written with no contraction; rcp, exp2 and the
+ * division f3 / float are the project's own specified kernels.
+ *   1. LUMINANCE.  c(p) = source(p).rgb / (float)totalSamples: one rcp of (float)totalSamples and three multiplies, exactly as the
+ *      output stage forms the value it multiplies by Exposure.  Y(p) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b.
+ *   2. CLASSES.  Every pixel of weight above zero falls into exactly one of three: REJECTED iff Y is not finite (the output stage's
+ *      NaN / Inf marker pixels); BLACK iff Y <= 0 or Y < 2^-126 (zero of either sign, negatives, denormals); COUNTED otherwise.
+ *   3. BIN.  Comparisons and shifts only, no logarithm per pixel: k = bits(Y) >> 20 (the eight exponent bits and the top three
+ *      mantissa bits: eight sub-bins per octave), i = k - 888.  i < 0 goes to bin 0 and counts in `under`; i > 255 goes to bin 255 and
+ *      counts in `over`.  The 256 bins span [2^-16, 2^16); Y = 1 lands in bin 128.
+ *   4. WEIGHT.  w(p) is an integer.  PTX_METER_AVERAGE: w = 1.  PTX_METER_CENTRE: w = wx wy with
+ *      wx = 1 + [W <= 4x + 2 <= 3W] + [3W <= 8x + 4 <= 5W] and wy the same expression in y and H: 1 ... 9, integers only.
+ *      PTX_METER_REGION: w = 1 inside region = [x0, x1) x [y0, y1) and 0 outside; a pixel of weight 0 belongs to no class.
+ *      Bins and class counters are sums of weights in uint32.  A call whose largest possible total -- W H, 9 W H, or the region's
+ *      area -- reaches 2^32 is refused.
+ *   5. TRIM.  n_i is bin i, N = SUM n_i.  lo = floor(N lowPermille / 1000), hi = floor(N highPermille / 1000) in 64-bit integers.
+ *      P_i is the exclusive prefix sum of n.  kept_i = max(0, min(P_i + n_i, N - hi) - max(P_i, lo)).  K = SUM kept_i (= N - lo - hi).
+ *      If K = 0: valid = 0, and the four floats of the result keep their previous values; steps 6 - 8 do not run.
+ *   6. MEAN.  A = SUM kept_i (i >> 3) and B_j = SUM over i & 7 = j of kept_i, exact in uint64.  T_j is the double nearest to
+ *      log2(1 + (2j + 1) / 16), the centre of sub-bin j:
+ *        T_0 = 0x1.663f6fac91316p-4   T_1 = 0x1.fbc16b902680ap-3   T_2 = 0x1.91bba891f1709p-2   T_3 = 0x1.0c10500d63aa6p-1
+ *        T_4 = 0x1.49a784bcd1b8bp-1   T_5 = 0x1.82809d5be7073p-1   T_6 = 0x1.b74948f5532dap-1   T_7 = 0x1.e88c6b3626a73p-1
+ *      avg = ((double)A + ((...((double)B_0 T_0 + (double)B_1 T_1) + ...) + (double)B_7 T_7)) / (double)K - 16.
+ *      avgLog2 = (float)avg.
+ *   7. TARGET.  target = clamp(((double)keyLog2 - avg) + (double)compensation, minLog2Exposure, maxLog2Exposure), the clamp being
+ *      min(max(x, lo), hi).  targetLog2 = (float)target.
+ *   8. ADAPTATION.  cur is a double of the device state.  On the first valid call after creation, after ptx_resize or after
+ *      ptx_meter_reset: cur = target.  Otherwise rate = speedUp if target > cur, else speedDown;
+ *      a = 1 - exp2(max(((-(double)deltaSeconds) (double)rate) 1.4426950408889634, -300)); cur = cur + (target - cur) a, and
+ *      cur = target where a = 1 (the rounded sum cur + (target - cur) can miss target by an ulp).
+ *      log2Exposure = (float)cur.  exposure = (float)exp2(clamp(cur, -300, 300)).
+ *   9. STATE.  The result, the 256 bins and cur live in device memory, allocated by the first accepted call.  ptx_meter is
+ *      asynchronous on the render stream and never synchronises: two launches, the second a single workgroup.
+ * Consequences: (a) the exposure is quantised to sub-bin centres: a constant image is off by at most 1.0625 = 6.25 %, the width of
+ * the widest sub-bin over its centre, and nothing else in the stage is approximate; (b) deltaSeconds = 0 leaves cur where it is;
+ * (c) a deltaSeconds large enough for a = 1 (deltaSeconds rate >= 38) lands on the target exactly.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL argument, an unknown source or mode, totalSamples = 0, lowPermille + highPermille >= 1000, a
+ * float field that is not finite, minLog2Exposure > maxLog2Exposure, a negative speed or deltaSeconds, flags != 0, reserved != 0.
+ * PTX_ERROR_NOT_READY: no image (ptx_resize), a shard accumulation buffer bound, a tile shard with worldSize > 1.  Then, against the
+ * extent, PTX_ERROR_INVALID_ARGUMENT: in PTX_METER_REGION x0 >= x1, y0 >= y1, x1 > W or y1 > H; the bound of step 4.  Last,
+ * PTX_ERROR_NOT_READY: a source that does not exist since the last ptx_resize (no C, no D).  A refused call leaves the state and the
+ * bins intact; ptx_resize resets the state.
+ * Known limits: the quantisation of (a); the range is fixed at 32 octaves; sharded frames are refused (a host can still sum bins256
+ * across ranks itself); there is no perceptual model: no scotopic shift, no local adaptation. */
+PTX_API int ptx_meter(PtxRenderer *r, const PtxMeterDesc *desc);
+/* The result and, where bins256 is not NULL, the 256 bins of the last ptx_meter, device -> host; synchronous, as ptx_read_output is.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL handle or result; PTX_ERROR_NOT_READY: no accepted ptx_meter on this handle yet. */
+PTX_API int ptx_read_meter(PtxRenderer *r, PtxMeterResult *out, uint32_t *bins256 /* may be NULL */);
+/* ... or the PtxMeterResult's device address (NULL before the first accepted ptx_meter); it stays where it is until ptx_destroy. */
+PTX_API void *ptx_device_meter_ptr(PtxRenderer *r);
+/* The state becomes what ptx_resize leaves: exposure 1, log2Exposure 0, everything else zero, and the next valid ptx_meter jumps to
+ * its target instead of adapting.  Asynchronous on the render stream; PTX_OK and nothing to do before the first ptx_meter.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL handle. */
+PTX_API int ptx_meter_reset(PtxRenderer *r);
+/* The output stage on `source` (PTX_METER_*: ptx_postprocess, ptx_postprocess_despiked or ptx_postprocess_denoised, with that call's
+ * TotalSamples convention) with Exposure = uniform->Exposure * exposure, the float product, `exposure` being read from the device
+ * state inside the first kernel: no synchronisation, no read-back.  Everything behind that kernel is the existing chain, and
+ * ptx_read_output and ptx_present follow unchanged.  With a reset state exposure is 1 and the call gives the plain call's bits.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL argument, an unknown mode or source; PTX_ERROR_NOT_READY: as the plain call of that source,
+ * or no accepted ptx_meter on this handle yet. */
+PTX_API int ptx_postprocess_metered(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode, uint32_t source);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

@@ -71,6 +71,7 @@ PTX_SYMBOLS = [
     "ptx_render_guides_specular", "ptx_read_specular_guide", "ptx_device_specular_guide_ptr",
     "ptx_temporal_accumulate_responsive", "ptx_read_fast_history", "ptx_device_fast_history_ptr",
     "ptx_despike", "ptx_read_despiked", "ptx_device_despiked_ptr", "ptx_chain_use_despiked", "ptx_postprocess_despiked",
+    "ptx_meter", "ptx_read_meter", "ptx_device_meter_ptr", "ptx_meter_reset", "ptx_postprocess_metered",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -223,6 +224,27 @@ class DespikeDesc(C.Structure):
 
 # The defaults of Renderer.despike: first in the sweep of tools/firefly_quality.py (docs/NEXT_ROWS.md section 20)
 DESPIKE_DEFAULTS = dict(radius=2, rank=4, gain=1.0, min_taps=8)
+
+
+class MeterDesc(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("mode", C.c_uint32), ("totalSamples", C.c_uint32), ("region", C.c_uint32 * 4), ("lowPermille", C.c_uint32),
+                ("highPermille", C.c_uint32), ("keyLog2", C.c_float), ("compensation", C.c_float), ("minLog2Exposure", C.c_float),
+                ("maxLog2Exposure", C.c_float), ("speedUp", C.c_float), ("speedDown", C.c_float), ("deltaSeconds", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MeterResult(C.Structure):
+    _fields_ = [("exposure", C.c_float), ("log2Exposure", C.c_float), ("avgLog2", C.c_float), ("targetLog2", C.c_float), ("counted", C.c_uint32),
+                ("kept", C.c_uint32), ("black", C.c_uint32), ("rejected", C.c_uint32), ("under", C.c_uint32), ("over", C.c_uint32), ("valid", C.c_uint32),
+                ("calls", C.c_uint32)]
+
+
+METER_SUM, METER_DESPIKED, METER_DENOISED = 0, 1, 2  # PTX_METER_* of include/ptx.h: the image ...
+METER_AVERAGE, METER_CENTRE, METER_REGION = 0, 1, 2  # ... and the weighting
+# The defaults of Renderer.meter and of RendererHip::ExposureSettings (docs/NEXT_ROWS.md section 21): middle grey, a tenth cut off at
+# the dark end and a twentieth at the bright one, +-8 stops, three times faster towards a brighter image than towards a darker one
+METER_DEFAULTS = dict(mode=METER_AVERAGE, key_log2=-2.473931, compensation=0.0, min_log2_exposure=-8.0, max_log2_exposure=8.0, speed_up=1.0,
+                      speed_down=3.0, low_permille=100, high_permille=50)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -464,6 +486,12 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_despiked_ptr.restype = P
         lib.ptx_chain_use_despiked.argtypes = [P, C.c_int]
         lib.ptx_postprocess_despiked.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32]
+        lib.ptx_meter.argtypes = [P, C.POINTER(MeterDesc)]
+        lib.ptx_read_meter.argtypes = [P, C.POINTER(MeterResult), P]
+        lib.ptx_device_meter_ptr.argtypes = [P]
+        lib.ptx_device_meter_ptr.restype = P
+        lib.ptx_meter_reset.argtypes = [P]
+        lib.ptx_postprocess_metered.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32, C.c_uint32]
         _hip = lib
     return _hip
 
@@ -923,6 +951,40 @@ class Renderer:
         """ptx_postprocess_despiked: postprocess() on despike()'s image, which is in the sum's scale: total_samples is the caller's."""
         u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
         self._check(self.lib.ptx_postprocess_despiked(self.handle, C.byref(u), tone_mapping))
+
+    def meter(self, total_samples: int, delta_seconds: float = 0.0, source: int = METER_SUM, mode: int = METER_DEFAULTS["mode"], region=(0, 0, 0, 0),
+              low_permille: int = METER_DEFAULTS["low_permille"], high_permille: int = METER_DEFAULTS["high_permille"],
+              key_log2: float = METER_DEFAULTS["key_log2"], compensation: float = METER_DEFAULTS["compensation"],
+              min_log2_exposure: float = METER_DEFAULTS["min_log2_exposure"], max_log2_exposure: float = METER_DEFAULTS["max_log2_exposure"],
+              speed_up: float = METER_DEFAULTS["speed_up"], speed_down: float = METER_DEFAULTS["speed_down"]):
+        """ptx_meter: a weighted luminance histogram of `source` (METER_SUM, METER_DESPIKED, METER_DENOISED: the image the output call
+        of that name reads, with its total_samples convention) moves the exposure kept on the device towards
+        2^(key_log2 - mean log2 luminance + compensation), at speed_up or speed_down per second over delta_seconds; the first call
+        after a reset jumps.  region = (x0, x1, y0, y1) counts in METER_REGION only.  Asynchronous."""
+        d = MeterDesc(source, mode, total_samples, (C.c_uint32 * 4)(*region), low_permille, high_permille, key_log2, compensation, min_log2_exposure,
+                      max_log2_exposure, speed_up, speed_down, delta_seconds, 0, 0)
+        self._check(self.lib.ptx_meter(self.handle, C.byref(d)))
+
+    def read_meter(self, bins: bool = False):
+        """ptx_read_meter: the MeterResult of the last meter(), with bins=True also the 256 bins (uint32); synchronises."""
+        out = MeterResult()
+        hist = np.empty(256, np.uint32) if bins else None
+        self._check(self.lib.ptx_read_meter(self.handle, C.byref(out), hist.ctypes.data if bins else None))
+        return (out, hist) if bins else out
+
+    def meter_ptr(self) -> int:
+        return int(self.lib.ptx_device_meter_ptr(self.handle) or 0)
+
+    def meter_reset(self):
+        """ptx_meter_reset: exposure 1 again, and the next meter() jumps to its target."""
+        self._check(self.lib.ptx_meter_reset(self.handle))
+
+    def postprocess_metered(self, total_samples: int, exposure: float = 1.0, bloom_threshold: float = 1.0, bloom_intensity: float = 1.0,
+                            tone_mapping: int = TONE_MAPPING_SDR, source: int = METER_SUM):
+        """ptx_postprocess_metered: postprocess(), postprocess_despiked() or postprocess_denoised() by `source`, with `exposure`
+        multiplied by the metered exposure on the device."""
+        u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
+        self._check(self.lib.ptx_postprocess_metered(self.handle, C.byref(u), tone_mapping, source))
 
     def stats(self) -> Stats:
         s = Stats()

@@ -15,6 +15,8 @@ static int resetAccumulation(PtxRenderer *r)
     return PTX_OK;
 }
 
+static int meterReset(PtxRenderer *r); // pt_output_host.hpp
+
 static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
 {
     if (!r || !width || !height || (uint64_t)width * height > 0x7fffffffull)
@@ -26,6 +28,8 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->output.invalidate();
     r->chain.invalidate(); // guides, D, T, the histories, V_0 and the motion guides belong to the extent they were made for
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
+    if (const int rc = meterReset(r)) // the exposure was metered on an image of the old extent
+        return rc;
     return resetAccumulation(r);
 }
 

@@ -1,11 +1,14 @@
 // pt_output_host.hpp -- the output stage (ptx_postprocess, ptx_read_output: row N4) and the screen path (ptx_present, ptx_read_present:
-// row D15; docs/NEXT_ROWS.md section 12).  Kernels: pt_post.hpp, pt_present.hpp; state: OutputState, the member `output` of the handle.
+// row D15; docs/NEXT_ROWS.md section 12), and the exposure metering in front of them (ptx_meter, ptx_read_meter, ptx_meter_reset,
+// ptx_postprocess_metered: section 21).  Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_chain_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
 #pragma once
 
 // Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)
 // the chain on `source` (width x height running sums of uniform->TotalSamples samples): the accumulation image, or the denoised mean
-static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+// meterExposure: the device address of the metered exposure that ptx_postprocess_metered multiplies in (k_postprocess_metered), or none
+static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode,
+                            const float *meterExposure = nullptr)
 {
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t W = r->frame.width, H = r->frame.height, n = W * H;
@@ -31,7 +34,10 @@ static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostP
         L[l].rgb = r->output.bloomRgb.p + off;
         off += (size_t)L[l].w * L[l].h * 3;
     }
-    k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->output.postRgb.p, L[0].rgb);
+    if (meterExposure)
+        k_postprocess_metered<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, r->output.postRgb.p, L[0].rgb);
+    else
+        k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->output.postRgb.p, L[0].rgb);
     for (uint32_t i = 0; i + 1 < used; i++)
         k_bloom_downsample<<<gridFor((size_t)L[i + 1].w * L[i + 1].h), kBlock, 0, r->stream>>>(L[i], L[i + 1]);
     for (uint32_t i = used - 1; i > 0; i--)
@@ -150,4 +156,143 @@ static int readPresent(PtxRenderer *r, void *host, size_t bytes)
     HIP_TRY(r, hipStreamSynchronize(r->stream));
     HIP_TRY(r, hipGetLastError());
     return PTX_OK;
+}
+
+// ---- exposure metering (docs/NEXT_ROWS.md section 21; semantics: include/ptx.h ptx_meter; kernels: pt_meter.hpp) --------------------
+
+// the image a PTX_METER_* source names, as the output call of that source reads it (nullptr: it does not exist for this extent)
+static const float4 *meterSource(const PtxRenderer *r, uint32_t source)
+{
+    return source == PTX_METER_SUM ? imagePtr(r) : source == PTX_METER_DESPIKED ? r->chain.despiked() : r->chain.denoised();
+}
+
+// ptx_meter_reset, and ptx_resize's part in it: nothing to do while no ptx_meter has made a state
+static int meterReset(PtxRenderer *r)
+{
+    if (!r)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_meter_reset: null argument");
+    if (!r->output.meterState.p)
+        return PTX_OK;
+    HIP_TRY(r, hipSetDevice(r->device));
+    k_meter_reset<<<1, kMeterBlock, 0, r->stream>>>(r->output.meterState.p);
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+// ptx_meter: the histogram's slabs, then one workgroup that sums them and moves the exposure.  Two launches, no synchronisation.
+static int meter(PtxRenderer *r, const PtxMeterDesc *d)
+{
+    const char *who = "ptx_meter";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
+    if (d->source > PTX_METER_DENOISED || d->mode > PTX_METER_REGION || !d->totalSamples || (uint64_t)d->lowPermille + d->highPermille >= 1000u ||
+        d->flags != 0u || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need source <= 2 (%u), mode <= 2 (%u), totalSamples > 0 (%u), lowPermille + highPermille < 1000 "
+                    "(%u + %u), flags 0 (0x%x) and reserved 0 (%u)", who, d->source, d->mode, d->totalSamples, d->lowPermille, d->highPermille, d->flags, d->reserved);
+    if (!finite(d->keyLog2) || !finite(d->compensation) || !finite(d->minLog2Exposure) || !finite(d->maxLog2Exposure) || !finite(d->speedUp) ||
+        !finite(d->speedDown) || !finite(d->deltaSeconds) || d->minLog2Exposure > d->maxLog2Exposure || d->speedUp < 0.0f || d->speedDown < 0.0f ||
+        d->deltaSeconds < 0.0f)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need finite keyLog2 (%g) and compensation (%g), finite minLog2Exposure <= maxLog2Exposure (%g, %g), "
+                    "finite speedUp, speedDown and deltaSeconds >= 0 (%g, %g, %g)", who, (double)d->keyLog2, (double)d->compensation, (double)d->minLog2Exposure,
+                    (double)d->maxLog2Exposure, (double)d->speedUp, (double)d->speedDown, (double)d->deltaSeconds);
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+    if (r->frame.boundShard)
+        return frameIsElsewhere(r, who);
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; sum the bins of ptx_read_meter across ranks on the host", who,
+                    r->frame.shard.worldSize);
+    const uint32_t W = r->frame.width, H = r->frame.height;
+    const uint32_t *g = d->region;
+    if (d->mode == PTX_METER_REGION && (g[0] >= g[1] || g[2] >= g[3] || g[1] > W || g[3] > H))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the region [%u, %u) x [%u, %u) is empty or leaves the %u x %u image", who, g[0], g[1], g[2], g[3], W, H);
+    // step 4: the largest total a counter can reach
+    const uint64_t total = d->mode == PTX_METER_REGION ? (uint64_t)(g[1] - g[0]) * (g[3] - g[2]) : (uint64_t)W * H * (d->mode == PTX_METER_CENTRE ? 9u : 1u);
+    if (total >= (1ull << 32))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the weights of a %u x %u image can sum to %llu, which a 32-bit counter does not hold", who, W, H,
+                    (unsigned long long)total);
+    const float4 *source = meterSource(r, d->source);
+    if (!source)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no %s image for this extent (call %s first)", who, d->source == PTX_METER_DESPIKED ? "despiked" : "denoised",
+                    d->source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    HIP_TRY(r, hipSetDevice(r->device));
+    OutputState &o = r->output;
+    HIP_TRY(r, o.meterSlabs.alloc((size_t)kMeterGridCap * kMeterSlabWords));
+    if (!o.meterState.p)
+    {
+        HIP_TRY(r, o.meterState.alloc(1));
+        k_meter_reset<<<1, kMeterBlock, 0, r->stream>>>(o.meterState.p);
+    }
+    MeterArgs a;
+    a.source = source;
+    a.slabs = o.meterSlabs.p;
+    a.n = W * H;
+    a.width = W;
+    a.height = H;
+    a.totalSamples = d->source == PTX_METER_DENOISED ? 1.0f : (float)d->totalSamples; // ptx_postprocess_denoised: D holds the mean
+    a.x0 = g[0]; a.x1 = g[1]; a.y0 = g[2]; a.y1 = g[3];
+    const uint32_t grid = gridFor(a.n, kMeterBlock, kMeterGridCap);
+    switch (d->mode)
+    {
+    case PTX_METER_AVERAGE: k_meter_histogram<PTX_METER_AVERAGE><<<grid, kMeterBlock, 0, r->stream>>>(a); break;
+    case PTX_METER_CENTRE: k_meter_histogram<PTX_METER_CENTRE><<<grid, kMeterBlock, 0, r->stream>>>(a); break;
+    default: k_meter_histogram<PTX_METER_REGION><<<grid, kMeterBlock, 0, r->stream>>>(a);
+    }
+    MeterResolveArgs v;
+    v.slabs = o.meterSlabs.p;
+    v.slabCount = grid;
+    v.state = o.meterState.p;
+    v.lowPermille = d->lowPermille;
+    v.highPermille = d->highPermille;
+    v.keyLog2 = d->keyLog2;
+    v.compensation = d->compensation;
+    v.minLog2Exposure = d->minLog2Exposure;
+    v.maxLog2Exposure = d->maxLog2Exposure;
+    v.speedUp = d->speedUp;
+    v.speedDown = d->speedDown;
+    v.deltaSeconds = d->deltaSeconds;
+    k_meter_resolve<<<1, kMeterResolveBlock, 0, r->stream>>>(v);
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+static int readMeter(PtxRenderer *r, PtxMeterResult *out, uint32_t *bins256)
+{
+    if (!r || !out)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_meter: null argument");
+    if (!r->output.meterState.p)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_meter: call ptx_meter first");
+    HIP_TRY(r, hipSetDevice(r->device));
+    const MeterState *st = r->output.meterState.p;
+    HIP_TRY(r, hipMemcpyAsync(out, &st->result, sizeof(PtxMeterResult), hipMemcpyDeviceToHost, r->stream));
+    if (bins256)
+        HIP_TRY(r, hipMemcpyAsync(bins256, st->bins, sizeof(st->bins), hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+// ptx_postprocess_metered: the output call of `source` with the metered exposure multiplied in on the device
+static int postprocessMetered(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source)
+{
+    const char *who = "ptx_postprocess_metered";
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR || source > PTX_METER_DENOISED)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad argument", who);
+    if (source == PTX_METER_SUM)
+    {
+        if (!imagePtr(r))
+            return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+        if (r->frame.boundShard)
+            return frameIsElsewhere(r, who);
+    }
+    const float4 *image = meterSource(r, source);
+    if (!image)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call %s first", who, source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    if (!r->output.meterState.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_meter first", who);
+    PtxPostProcessingUniformData u = *uniform;
+    if (source == PTX_METER_DENOISED)
+        u.TotalSamples = 1u; // ptx_postprocess_denoised: D holds the mean
+    return postprocessImage(r, image, &u, toneMappingMode, &r->output.meterState.p->result.exposure);
 }

@@ -3,6 +3,7 @@
 // and OutputSaver's conversion into its sRGB8 / RGBA32F image (OutputSaver.cpp:64-86).
 //
 //   k_postprocess      postprocess.comp:16-40      sum / TotalSamples * Exposure, NaN / Inf markers, bloom prefilter
+//   k_postprocess_metered  the same with Exposure times the metered exposure of ptx_meter, read from device memory (section 21)
 //   k_bloom_downsample bloomDownsample.comp:18-62  13-tap filter, level i -> i + 1
 //   k_bloom_upsample   bloomUpsample.comp:18-55    3x3 tent of level i added onto level i - 1
 //   k_compose_tonemap  composition.comp:16-26 + toneMapping.comp:13-25 (two stores of the reference fused: the
@@ -113,6 +114,26 @@ PT_DEV f3 add4(f3 a, f3 b, f3 c, f3 d) { return ((a + b) + c) + d; }
 __global__ void k_postprocess(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, float *__restrict__ post,
                               float *__restrict__ bloom0)
 {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    {
+        const float4 a = accum[i];
+        f3 color, bloom;
+        postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
+        color = f16Round(color);
+        bloom = f16Round(bloom);
+        post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
+        bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
+    }
+}
+
+// k_postprocess with Exposure = u.Exposure x the metered exposure, read from the meter's device state (include/ptx.h
+// ptx_postprocess_metered, docs/NEXT_ROWS.md section 21): one float product ahead of the same postprocessPixel.  The loop is
+// k_postprocess's, restated and not shared: moved into a helper it changed the code the compiler emits for k_postprocess, which this
+// stage leaves as it was.  tests/test_metering.py holds the two together: with a reset state the metered call gives the plain call's bits.
+__global__ void k_postprocess_metered(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, const float *__restrict__ meterExposure,
+                                      float *__restrict__ post, float *__restrict__ bloom0)
+{
+    u.Exposure = u.Exposure * *meterExposure;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
         const float4 a = accum[i];

@@ -37,6 +37,7 @@
 #include "pt_variance.hpp"
 #include "pt_responsive.hpp"
 #include "pt_despike.hpp"
+#include "pt_meter.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -270,6 +271,9 @@ struct OutputState
     DevBuf<uint32_t> presentImage, presentUi;
     uint32_t presentWidth = 0, presentHeight = 0, presentFormat = 0;
     size_t presentBytes = 0; // 0: nothing presented yet
+    // exposure metering (ptx_meter, docs/NEXT_ROWS.md section 21): both allocated by the first accepted ptx_meter
+    DevBuf<MeterState> meterState;  // result, bins and the adapted exposure
+    DevBuf<uint32_t> meterSlabs;    // kMeterGridCap slabs of kMeterSlabWords words, rewritten whole by every call
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
 };
 

@@ -366,6 +366,31 @@ int ptx_postprocess_despiked(PtxRenderer *r, const PtxPostProcessingUniformData 
     return postprocessDespiked(r, uniform, toneMappingMode);
 }
 
+int ptx_meter(PtxRenderer *r, const PtxMeterDesc *desc)
+{
+    return meter(r, desc);
+}
+
+int ptx_read_meter(PtxRenderer *r, PtxMeterResult *out, uint32_t *bins256)
+{
+    return readMeter(r, out, bins256);
+}
+
+void *ptx_device_meter_ptr(PtxRenderer *r)
+{
+    return r && r->output.meterState.p ? &r->output.meterState.p->result : nullptr;
+}
+
+int ptx_meter_reset(PtxRenderer *r)
+{
+    return meterReset(r);
+}
+
+int ptx_postprocess_metered(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode, uint32_t source)
+{
+    return postprocessMetered(r, u, toneMappingMode, source);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

@@ -194,6 +194,36 @@ void RendererHip::SetSettings(const FireflySettings &settings)
         Check(ptx_chain_use_despiked(s_Renderer, 0));
 }
 
+static RendererHip::ExposureSettings s_ExposureSettings;
+static float s_TimeStep = 0.0f; // OnUpdate: the seconds since the last metered frame, used up by the ptx_meter that adapts over them
+
+void RendererHip::SetSettings(const ExposureSettings &settings)
+{
+    s_ExposureSettings = settings;
+}
+
+void RendererHip::OnUpdate(float timeStep)
+{
+    s_TimeStep += timeStep;
+}
+
+// The output stage on the sum, on the despiked image or on the denoised one (PTX_METER_*).  With the ExposureSettings on (ptx.h,
+// "Exposure metering") that image is metered first, with the frame's time step, and the metered call multiplies the exposure in.
+static int OutputStage(const PtxPostProcessingUniformData &u, uint32_t mode, uint32_t source)
+{
+    if (!s_ExposureSettings.Enabled || s_DebugPipeline)
+        return source == PTX_METER_SUM        ? ptx_postprocess(s_Renderer, &u, mode)
+               : source == PTX_METER_DESPIKED ? ptx_postprocess_despiked(s_Renderer, &u, mode)
+                                              : ptx_postprocess_denoised(s_Renderer, &u, mode);
+    const RendererHip::ExposureSettings &e = s_ExposureSettings;
+    const PtxMeterDesc meter = { source, e.Mode, u.TotalSamples, { 0u, 0u, 0u, 0u }, e.LowPermille, e.HighPermille, e.KeyLog2, e.Compensation, e.MinLog2Exposure,
+                                 e.MaxLog2Exposure, e.SpeedUp, e.SpeedDown, s_TimeStep, 0u, 0u };
+    if (const int rc = ptx_meter(s_Renderer, &meter))
+        return rc;
+    s_TimeStep = 0.0f; // a second SaveOutput or Present of the same frame meters with deltaSeconds = 0, which leaves the exposure where it is
+    return ptx_postprocess_metered(s_Renderer, &u, mode, source);
+}
+
 // The post-processing chain on the current frame: on the running sum, or -- with the denoiser enabled and the path-tracing pipeline
 // bound -- guides, filter, and the chain on the denoised mean (ptx.h, "Denoiser"); with the temporal accumulation enabled as well
 // the filter runs on its result (ptx.h, "Temporal accumulation"), and with the variance settings enabled on top the moments are
@@ -209,7 +239,7 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
             return rc;
     }
     if (!s_DenoiserSettings.Enabled || s_DebugPipeline)
-        return despike ? ptx_postprocess_despiked(s_Renderer, &u, mode) : ptx_postprocess(s_Renderer, &u, mode);
+        return OutputStage(u, mode, despike ? PTX_METER_DESPIKED : PTX_METER_SUM);
     if (despike)
         if (const int rc = ptx_chain_use_despiked(s_Renderer, 1))
             return rc;
@@ -247,11 +277,11 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
         }
         else if (const int rc = ptx_denoise_temporal(s_Renderer, &desc))
             return rc;
-        return ptx_postprocess_denoised(s_Renderer, &u, mode);
+        return OutputStage(u, mode, PTX_METER_DENOISED);
     }
     if (const int rc = ptx_denoise(s_Renderer, &desc))
         return rc;
-    return ptx_postprocess_denoised(s_Renderer, &u, mode);
+    return OutputStage(u, mode, PTX_METER_DENOISED);
 }
 
 void RendererHip::SaveOutput(const OutputInfo &info)

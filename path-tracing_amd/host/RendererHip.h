@@ -117,6 +117,30 @@ public:
         uint32_t MinTaps = 8;
     };
     static void SetSettings(const FireflySettings &settings);
+    // Exposure metering (ptx.h "Exposure metering", docs/NEXT_ROWS.md section 21).  Enabled: SaveOutput and Present meter the image
+    // they are about to post-process -- the sum, the despiked image or the denoised one, as the FireflySettings and the denoiser's
+    // settings decide -- with ptx_meter over the time OnUpdate has counted since the last metered frame, and ptx_postprocess_metered takes the output call's
+    // place: PostProcessSettings::Exposure times the metered exposure.  Disabled (the default): SaveOutput and Present enqueue exactly
+    // what they did.  A debug-view frame is shown as it is.  PTX_METER_REGION is not offered here.  The defaults are METER_DEFAULTS of
+    // the Python package.
+    struct ExposureSettings
+    {
+        bool Enabled = false;
+        uint32_t Mode = 0; // PTX_METER_AVERAGE
+        float KeyLog2 = -2.473931f; // log2(0.18)
+        float Compensation = 0.0f;
+        float MinLog2Exposure = -8.0f;
+        float MaxLog2Exposure = 8.0f;
+        float SpeedUp = 1.0f;
+        float SpeedDown = 3.0f;
+        uint32_t LowPermille = 100;
+        uint32_t HighPermille = 50;
+    };
+    static void SetSettings(const ExposureSettings &settings);
+    // Renderer::OnUpdate (Renderer.cpp:1615-1657): the seconds since the previous frame.  They add up until a SaveOutput or Present
+    // meters a frame, which adapts over them and uses them up: a second output call of the same frame, or every frame of a host that
+    // never calls OnUpdate again, meters with deltaSeconds = 0 and leaves the exposure where it is.
+    static void OnUpdate(float timeStep);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either

@@ -26,7 +26,13 @@ k_responsive_clamp: one launch per call at radius 1 and 2, against 37.25 and 43 
 ptx_render_guides_specular (section 18) at the package's defaults stands beside ptx_render_guides of the same run on chess_like and on
 `default`; --guides-only times nothing but the two guide passes.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--extent W H]"""
+ptx_meter and ptx_postprocess_metered (section 21): --meter times nothing but them, on the 8-spp chess_like sum and on a constant
+frame (every lane of a wave on one bin: the contention case of the LDS atomics), with ptx_despike at radius 1 (the same 16 bytes per
+pixel in) and ptx_postprocess of the same run beside them.  ptx_meter is given against its 16 algorithmic bytes per pixel -- a rate, not
+a bandwidth: at 1920 x 1080 the 33 MB frame of a back-to-back run is served from the last-level cache.  A kernel trace of `--meter
+--extent W H` gives k_meter_histogram's, k_meter_resolve's and k_despike<1>'s device times.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--extent W H]"""
 import json
 import math
 import os
@@ -46,6 +52,7 @@ DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
 TEMPORAL_BYTES_PER_PIXEL = 176
 MOMENTS_BYTES_PER_PIXEL = 208
 RESPONSIVE_BYTES_PER_PIXEL = 240
+METER_BYTES_PER_PIXEL = 16  # one load of the pixel; the slabs (1 MB at the most) and the state are noise beside it
 # 16 B out and 16 B x (tile + halo) / tile in: the halo is 84 entries of 256 at radius 1 and 176 at radius 2
 DESPIKE_BYTES_PER_PIXEL = {1: 16 + 16 * (256 + 84) / 256, 2: 16 + 16 * (256 + 176) / 256}
 
@@ -69,8 +76,8 @@ def main():
     pkg = graft.load_package()
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
-    guides_only, temporal_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only else ("chess_like", "default") if guides_only else
+    guides_only, temporal_only, meter_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv, "--meter" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only else ("chess_like", "default") if guides_only else
                                                           ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
@@ -96,6 +103,28 @@ def main():
             ud = sd.uniform(w, h, bounces=STEP_DEPTH)
             rec["render_guides_default"] = timed(rd, lambda: rd.render_guides(ud))
             specular_row("default", rd, ud)
+        if meter_only:
+            r.reset()
+            r.render_frames(u, scene.lights, 0, STEP_SPP)
+            p1 = dict(pkg.DESPIKE_DEFAULTS, radius=1, min_taps=max(3, pkg.DESPIKE_DEFAULTS["rank"]))
+            rec["despike_radius_1"] = timed(r, lambda: r.despike(**p1))
+            rec["postprocess"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
+            frames = {"chess_like_8spp": None, "constant": np.full((h, w, 4), 0.18 * STEP_SPP, np.float32)}
+            for frame, image in frames.items():
+                if image is not None:
+                    r.write_accumulation(image)
+                for mode, name in ((pkg.METER_AVERAGE, "average"), (pkg.METER_CENTRE, "centre"), (pkg.METER_REGION, "region_of_a_quarter")):
+                    region = (w // 4, w // 4 + w // 2, h // 4, h // 4 + h // 2)
+                    t = timed(r, lambda: r.meter(STEP_SPP, delta_seconds=1.0 / 60, mode=mode, region=region))
+                    t["algorithmic_GB_per_s"] = w * h * METER_BYTES_PER_PIXEL * (0.25 if mode == pkg.METER_REGION else 1.0) / (t["median_ms"] * 1e-3) / 1e9
+                    rec[f"meter_{name}_{frame}"] = t
+                res = r.read_meter()
+                rec[f"meter_result_{frame}"] = {"exposure": res.exposure, "avg_log2": res.avgLog2, "counted": res.counted, "black": res.black}
+                rec[f"postprocess_metered_{frame}"] = timed(r, lambda: r.postprocess_metered(STEP_SPP, **POST))
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
         if guides_only:
             rec["render_guides_chess_like"] = timed(r, lambda: r.render_guides(u))
             specular_row("chess_like", r, u)
