@@ -14,9 +14,13 @@
 //                                                                            every frame is announced with OnUpdate(timeStep)
 //                                                                            and, without the denoiser, saved twice)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 1 1 (... with the denoiser: the denoised image is metered)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 0 1 [look.cube] (... with GradeSettings on: section 22,
+//                                                                            tests/test_grade.py: Hable's curve, 4500 K, a CDL grade,
+//                                                                            the LUT where a file is named; every frame is also
+//                                                                            presented at 100 x 37 and that image appended)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
-// height x 16 bytes.
+// height x 16 bytes.  With the grade argument given -- 0 or 1 -- the two presented images follow, 2 x 100 x 37 x 4 bytes (R8G8B8A8).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,9 +40,10 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 9 || argc > 13)
+    if (argc < 9 || argc > 15)
     {
-        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1)]]]]\n");
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1) "
+                             "[grade(0|1) [lut.cube]]]]]]\n");
         return 1;
     }
     const std::string name = argv[1];
@@ -48,6 +53,8 @@ int main(int argc, char **argv)
     const bool useDespike = argc >= 11 && std::atoi(argv[10]) != 0;
     const bool useDenoiser = argc < 12 || std::atoi(argv[11]) != 0; // 0: the plain output path, T is left as zeros
     const bool useExposure = argc >= 13 && std::atoi(argv[12]) != 0;
+    const bool presentToo = argc >= 14, useGrade = presentToo && std::atoi(argv[13]) != 0;
+    const uint32_t screenWidth = 100, screenHeight = 37;
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
@@ -70,6 +77,15 @@ int main(int argc, char **argv)
         RendererHip::ExposureSettings exposure;
         exposure.Enabled = useExposure;
         RendererHip::SetSettings(exposure);
+        RendererHip::GradeSettings grade; // the values tests/test_grade.py repeats by hand
+        grade.Enabled = useGrade;
+        grade.Curve = PTX_CURVE_HABLE;
+        grade.TemperatureKelvin = 4500.0f;
+        grade.Slope[0] = 1.1f; grade.Offset[1] = 0.01f; grade.Power[2] = 0.9f;
+        grade.Saturation = 1.2f;
+        if (argc >= 15)
+            grade.LutFile = argv[14];
+        RendererHip::SetSettings(grade);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);
@@ -77,7 +93,8 @@ int main(int argc, char **argv)
         settings.BounceCount = bounces;
         RendererHip::SetSettings(settings);
         const size_t bytes = static_cast<size_t>(width) * height * 16;
-        std::vector<char> file(6 * bytes);
+        const size_t screenBytes = static_cast<size_t>(screenWidth) * screenHeight * 4;
+        std::vector<char> file(6 * bytes + (presentToo ? 2 * screenBytes : 0));
         const std::string scratch = std::string(argv[8]) + ".png";
         for (int frame = 0; frame < 2; frame++)
         {
@@ -106,6 +123,14 @@ int main(int argc, char **argv)
             if (useDenoiser)
                 Check(ptx_read_temporal(RendererHip::GetHandle(), &file[(3 * frame + 1) * bytes], bytes), "ptx_read_temporal");
             Check(ptx_read_output(RendererHip::GetHandle(), PTX_OUTPUT_RGBA32F, &file[(3 * frame + 2) * bytes], bytes), "ptx_read_output");
+            if (presentToo)
+            {
+                RendererHip::Present(screenWidth, screenHeight, nullptr);
+                const std::vector<std::byte> screen = RendererHip::ReadPresent();
+                if (screen.size() != screenBytes)
+                    throw error("the presented image has another size");
+                std::memcpy(&file[6 * bytes + frame * screenBytes], screen.data(), screenBytes);
+            }
         }
         FILE *f = std::fopen(argv[8], "wb");
         if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size())

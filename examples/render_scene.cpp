@@ -16,6 +16,8 @@
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3 --responsive   (... whose history follows a change of lighting)
 //   examples/render_scene default 640 360 1 4 despiked.png --despike        (firefly suppression: a rank clamp of every pixel's luminance; with --denoise ahead of the chain)
 //   examples/render_scene default 640 360 16 4 metered.png --auto-exposure  (exposure metering: a luminance histogram sets the output stage's exposure)
+//   examples/render_scene default 640 360 16 4 graded.png --curve aces --temperature 4500 --lut look.cube   (display transform: tone curve reference | reinhard | hable | aces,
+//                                                                            white balance for a light of that many kelvin, a .cube 3-D LUT)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -139,6 +141,41 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
+    // --curve NAME, --lut FILE, --temperature K: the display transform; any of the three turns it on
+    RendererHip::GradeSettings grade;
+    for (const char *option : { "--curve", "--lut", "--temperature" })
+        for (int i = 1; i < argc; i++)
+            if (std::string(argv[i]) == option)
+            {
+                if (i + 1 >= argc)
+                {
+                    std::fprintf(stderr, "error: %s takes a value\n", option);
+                    return 1;
+                }
+                const std::string value = argv[i + 1];
+                grade.Enabled = true;
+                if (option[2] == 'c')
+                {
+                    const char *names[] = { "reference", "reinhard", "hable", "aces" };
+                    uint32_t curve = 0;
+                    while (curve < 4u && value != names[curve])
+                        curve++;
+                    if (curve == 4u)
+                    {
+                        std::fprintf(stderr, "error: --curve takes reference, reinhard, hable or aces\n");
+                        return 1;
+                    }
+                    grade.Curve = curve;
+                }
+                else if (option[2] == 'l')
+                    grade.LutFile = value;
+                else
+                    grade.TemperatureKelvin = static_cast<float>(std::atof(value.c_str()));
+                for (int k = i; k + 2 < argc; k++)
+                    argv[k] = argv[k + 2];
+                argc -= 2;
+                break;
+            }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -170,6 +207,7 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(variance);
         RendererHip::SetSettings(firefly);
         RendererHip::SetSettings(exposure);
+        RendererHip::SetSettings(grade);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

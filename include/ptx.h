@@ -1375,6 +1375,113 @@ PTX_API int ptx_meter_reset(PtxRenderer *r);
  * or no accepted ptx_meter on this handle yet. */
 PTX_API int ptx_postprocess_metered(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode, uint32_t source);
 
+/* ------------------------------------------------------------------------- */
+/* Display transform (docs/NEXT_ROWS.md section 22): a colour matrix, an ASC   */
+/* CDL grade, a choice of tone curves and a 3-D LUT in the place of the output */
+/* stage's last step.  An addition: every call above computes what it computed */
+/* before, and a host that never calls these allocates nothing for them.       */
+/* ------------------------------------------------------------------------- */
+
+enum {
+    PTX_CURVE_REFERENCE = 0, /* toneMapping.comp's 1 - exp(-c) */
+    PTX_CURVE_REINHARD = 1,  /* extended Reinhard with a white point */
+    PTX_CURVE_HABLE = 2,     /* Hable's filmic curve, exposure bias 2, white 11.2 */
+    PTX_CURVE_ACES_FIT = 3   /* Hill's fit of the ACES RRT + ODT */
+};
+enum {
+    PTX_GRADE_USE_LUT = 1u,        /* step 4 runs, on the LUT of ptx_grade_lut */
+    PTX_GRADE_LUT_SRGB_DOMAIN = 2u /* the LUT is indexed by, and holds, sRGB-encoded values; needs PTX_GRADE_USE_LUT */
+};
+
+/* The constants of step 3, written once: the curves of csrc/pt_grade.hpp read these macros. */
+#define PTX_HABLE_A 0.15f
+#define PTX_HABLE_B 0.50f
+#define PTX_HABLE_C 0.10f
+#define PTX_HABLE_D 0.20f
+#define PTX_HABLE_E 0.02f
+#define PTX_HABLE_F 0.30f
+#define PTX_HABLE_EXPOSURE_BIAS 2.0f
+#define PTX_HABLE_WHITE 11.2f
+#define PTX_ACES_IN { 0.59719f, 0.35458f, 0.04823f, 0.07600f, 0.90834f, 0.01566f, 0.02840f, 0.13383f, 0.83777f }       /* rows */
+#define PTX_ACES_OUT { 1.60475f, -0.53108f, -0.07367f, -0.10208f, 1.10813f, -0.00605f, -0.00327f, -0.07276f, 1.07602f } /* rows */
+#define PTX_ACES_A 0.0245786f
+#define PTX_ACES_B 0.000090537f
+#define PTX_ACES_C 0.983729f
+#define PTX_ACES_D 0.4329510f
+#define PTX_ACES_E 0.238081f
+#define PTX_GRADE_LUT_MIN_SIZE 2u
+#define PTX_GRADE_LUT_MAX_SIZE 65u
+
+typedef struct PtxGradeDesc {
+    float    colourMatrix[9];   /* row-major, applied to scene-linear RGB */
+    float    slope[3], offset[3], power[3];   /* ASC CDL */
+    float    saturation;
+    uint32_t curve;             /* PTX_CURVE_REFERENCE | _REINHARD | _HABLE | _ACES_FIT */
+    float    whitePoint;        /* PTX_CURVE_REINHARD only */
+    uint32_t flags;             /* PTX_GRADE_USE_LUT, PTX_GRADE_LUT_SRGB_DOMAIN */
+    uint32_t reserved;
+} PtxGradeDesc;
+
+/* ptx_grade: the display transform on what the last accepted ptx_postprocess / _denoised / _despiked / _metered left behind -- the
+ * post-process image, bloom level 0 and that call's uniform, as ptx_present reads them -- into the image ptx_read_output reads, which
+ * it overwrites: ptx_read_output follows unchanged in both formats.  Per pixel, all arithmetic float32 in the order written with no
+ * contraction; every `/` is the specified division a * rcp(b), pow and exp the project's fixed kernels,
+ * luminance (0.2126f r + 0.7152f g) + 0.0722f b, f16Round the rounding to binary16 of every store into an rgba16f image.
+ *   0. COMPOSITION.  c = f16Round(bloom0 * (BloomIntensity * 0.1f) + post * 1.0f): composition.comp's store, the first half of
+ *      ptx_postprocess's last kernel.  In ptx_present_graded c is the value after the scaling blit's f16Round (step 2 there).
+ *   1. MATRIX.  m = colourMatrix.  c'_i = (m[3i] c.x + m[3i+1] c.y) + m[3i+2] c.z for i = 0, 1, 2; c = c'.
+ *   2. CDL, v = c, per channel k:
+ *      2a. SLOPE, OFFSET.  v_k = max(v_k slope_k + offset_k, 0), max(a, b) being a < b ? b : a (a NaN passes through).
+ *      2b. POWER.          v_k = pow(v_k, power_k).
+ *      2c. SATURATION.     Y = luminance(v); v_k = Y + (v_k - Y) saturation.
+ *   3. CURVE, in PTX_TONE_MAPPING_SDR only (PTX_TONE_MAPPING_HDR skips steps 3 and 4, as the reference skips its own curve), per channel:
+ *      PTX_CURVE_REFERENCE  v = 1 - exp(-v), ptx_postprocess's curve.
+ *      PTX_CURVE_REINHARD   v = (v (1 + v / (w w))) / (1 + v), w = whitePoint.
+ *      PTX_CURVE_HABLE      v = f(2 v) / f(11.2), f(x) = (x (A x + C B) + D E) / (x (A x + B) + D F) - E / F, A ... F = PTX_HABLE_A ... _F;
+ *                           C B, D E, D F, E / F and f(11.2) are float32 values formed in that order.
+ *      PTX_CURVE_ACES_FIT   t_i = (a[3i] v.x + a[3i+1] v.y) + a[3i+2] v.z with a = PTX_ACES_IN; per channel
+ *                           t = (t (t + PTX_ACES_A) - PTX_ACES_B) / (t (PTX_ACES_C t + PTX_ACES_D) + PTX_ACES_E);
+ *                           v_i = (o[3i] t.x + o[3i+1] t.y) + o[3i+2] t.z with o = PTX_ACES_OUT; v = min(max(v, 0), 1).
+ *   4. LUT, with PTX_GRADE_USE_LUT; N and the table are ptx_grade_lut's, entry (r, g, b) at 3 ((b N + g) N + r):
+ *      x_k = min(max(v_k, 0), 1) (a NaN passes through, and reads as 0 in the next line); with PTX_GRADE_LUT_SRGB_DOMAIN
+ *      x_k = linearToSrgb(x_k) = x <= 0.0031308f ? 12.92f x : 1.055f pow(x, 1 / 2.4f) - 0.055f first.
+ *      s_k = x_k (float)(N - 1); i_k = min((int)floor(s_k), N - 2), and 0 where s_k is a NaN; f_k = s_k - (float)i_k.
+ *      Tetrahedral interpolation between V000 = LUT[i_r, i_g, i_b] and V111 = LUT[i_r + 1, i_g + 1, i_b + 1].  The order of the
+ *      fractions is decided by >= comparisons in this order:
+ *        f_r >= f_g:  f_g >= f_b -> rgb;  else f_r >= f_b -> rbg;  else brg.
+ *        otherwise:   f_b >= f_g -> bgr;  else f_b >= f_r -> gbr;  else grb.
+ *      An order "pqs" names f_hi = f_p, f_mid = f_q, f_lo = f_s; V_a is V000 stepped by one along p, V_b along p and q.
+ *      out = ((V000 (1 - f_hi) + V_a (f_hi - f_mid)) + V_b (f_mid - f_lo)) + V111 f_lo, per channel of the entries.
+ *      With PTX_GRADE_LUT_SRGB_DOMAIN out_k = srgbToLinear(out_k) = x <= 0.04045f ? x / 12.92f : pow((x + 0.055f) / 1.055f, 2.4f),
+ *      these two divisions being IEEE quotients.  v = out.
+ *   5. STORE.  f16Round(v), alpha 1.
+ * SKIP RULE.  A step whose parameters are the identity bit for bit does not run, so it rounds nothing and clamps nothing: step 1 for the
+ * identity matrix (1, 0, 0, 0, 1, 0, 0, 0, 1), step 2a for slope (1, 1, 1) and offset (+0, +0, +0) -- the max with 0 included --, step
+ * 2b for power (1, 1, 1), step 2c for saturation 1.  The host decides; the kernel gets wave-uniform switches.  An identity desc with
+ * PTX_CURVE_REFERENCE and no LUT therefore gives ptx_postprocess's bits, and ptx_present_graded then gives ptx_present's.
+ * The renderer keeps the accepted desc (not the mode); ptx_resize keeps it, and the LUT.  Asynchronous on the render stream; works
+ * on a borrower; touches neither the sum nor any image of the chain.
+ * Refusals, in this order; a refused call leaves the output image, the kept desc and the LUT intact.  PTX_ERROR_INVALID_ARGUMENT: a
+ * NULL argument; an unknown curve, mode or flag bit; reserved != 0; a float field that is not finite; a negative slope, power or
+ * saturation; whitePoint <= 0 with PTX_CURVE_REINHARD; PTX_GRADE_LUT_SRGB_DOMAIN without PTX_GRADE_USE_LUT.  PTX_ERROR_NOT_READY: nothing
+ * post-processed since the last ptx_resize; a shard accumulation buffer bound, or a tile shard with worldSize > 1; PTX_GRADE_USE_LUT
+ * with no LUT set.
+ * Known limits: the curves are fixed-parameter fits, no AgX and no full ACES RRT; the LUT has no 1-D shaper in front, so a linear-domain
+ * LUT spends its lattice on the highlights (PTX_GRADE_LUT_SRGB_DOMAIN is the remedy); the 8-bit encodes are not dithered; the grade is
+ * global, there is no local tone mapping; sharded frames are refused. */
+PTX_API int ptx_grade(PtxRenderer *r, const PtxGradeDesc *d, uint32_t toneMappingMode);
+/* The LUT of step 4: size^3 RGB entries of float32, red fastest, copied into a device buffer owned by the handle (synchronous, as
+ * ptx_write_accumulation is); rgb = NULL clears it and frees the buffer, whatever `size` is.  The LUT belongs to the display, not to
+ * the render extent: ptx_resize keeps it.  PTX_ERROR_INVALID_ARGUMENT: a NULL handle; size outside PTX_GRADE_LUT_MIN_SIZE ...
+ * PTX_GRADE_LUT_MAX_SIZE (2 ... 65) with rgb != NULL.  The values are not inspected. */
+PTX_API int ptx_grade_lut(PtxRenderer *r, uint32_t size, const float *rgb /* size^3 * 3, red fastest; NULL clears */);
+/* ptx_present with the kept desc of the last accepted ptx_grade applied, steps 1 - 5 above with desc->toneMappingMode, in the place
+ * of the tone mapping between the scaling blit and the UI composition (step 3 of the screen path).  A function of its own and not a
+ * flag of ptx_present, whose unknown flag bits stay refused.  Arguments, result and refusals are ptx_present's; in addition
+ * PTX_ERROR_NOT_READY: a tile shard with worldSize > 1; no accepted ptx_grade on this handle yet; the kept desc has PTX_GRADE_USE_LUT
+ * and the LUT has been cleared. */
+PTX_API int ptx_present_graded(PtxRenderer *r, const PtxPresentDesc *desc);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

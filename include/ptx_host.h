@@ -77,6 +77,15 @@ PTX_API int pth_write_image(const char *path, uint32_t format, uint32_t width, u
 PTX_API int pth_save_checkpoint(const char *path, uint32_t width, uint32_t height, uint32_t totalSamples, const float *rgba);
 PTX_API int pth_load_checkpoint(const char *path, uint32_t *width, uint32_t *height, uint32_t *totalSamples, float *rgba, size_t bytes);
 
+/* Display transform (ptx.h "Display transform"; host/CubeLut.h).  pth_read_cube reads a .cube 3-D LUT file into what ptx_grade_lut
+ * takes: *size = N, and, where rgb is not NULL, the N^3 x 3 floats, red fastest; floats must then be N^3 * 3 (rgb == NULL: size
+ * query only).  LUT_3D_SIZE 2 .. 65, DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1, TITLE and # comments are read; anything else, malformed
+ * or truncated is PTX_ERROR_INVALID_ARGUMENT with the line in pth_last_error. */
+PTX_API int pth_read_cube(const char *path, uint32_t *size, float *rgb, size_t floats);
+/* PtxGradeDesc::colourMatrix for a light source of `kelvin` (1000 .. 15000; 0: the identity): Krystek's Planckian approximation,
+ * Bradford adaptation to the sRGB white, in linear sRGB, row-major; computed in float64. */
+PTX_API int pth_white_balance_matrix(double kelvin, float matrix[9]);
+
 #ifdef __cplusplus
 }
 #endif

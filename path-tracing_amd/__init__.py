@@ -72,11 +72,13 @@ PTX_SYMBOLS = [
     "ptx_temporal_accumulate_responsive", "ptx_read_fast_history", "ptx_device_fast_history_ptr",
     "ptx_despike", "ptx_read_despiked", "ptx_device_despiked_ptr", "ptx_chain_use_despiked", "ptx_postprocess_despiked",
     "ptx_meter", "ptx_read_meter", "ptx_device_meter_ptr", "ptx_meter_reset", "ptx_postprocess_metered",
+    "ptx_grade", "ptx_grade_lut", "ptx_present_graded",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
     "pth_scene_lights", "pth_scene_triangle_count", "pth_scene_raygen_uniform", "pth_scene_camera_matrices", "pth_scene_set_active_camera",
     "pth_scene_set_camera_pose", "pth_scene_update", "pth_scene_bone_count", "pth_scene_animation_state", "pth_decode_image", "pth_decode_image_levels", "pth_write_image", "pth_save_checkpoint", "pth_load_checkpoint",
+    "pth_read_cube", "pth_white_balance_matrix",
 ]
 
 SCENE_NATIVE_BC = 1  # PTH_SCENE_NATIVE_BC
@@ -246,6 +248,21 @@ METER_AVERAGE, METER_CENTRE, METER_REGION = 0, 1, 2  # ... and the weighting
 METER_DEFAULTS = dict(mode=METER_AVERAGE, key_log2=-2.473931, compensation=0.0, min_log2_exposure=-8.0, max_log2_exposure=8.0, speed_up=1.0,
                       speed_down=3.0, low_permille=100, high_permille=50)
 
+
+class GradeDesc(C.Structure):
+    _fields_ = [("colourMatrix", C.c_float * 9), ("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float),
+                ("curve", C.c_uint32), ("whitePoint", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CURVE_REFERENCE, CURVE_REINHARD, CURVE_HABLE, CURVE_ACES_FIT = range(4)  # PTX_CURVE_* of include/ptx.h
+CURVE_NAMES = {"reference": CURVE_REFERENCE, "reinhard": CURVE_REINHARD, "hable": CURVE_HABLE, "aces": CURVE_ACES_FIT}  # render_scene --curve
+GRADE_USE_LUT, GRADE_LUT_SRGB_DOMAIN = 1, 2  # PTX_GRADE_*: the flag bits
+GRADE_LUT_MIN_SIZE, GRADE_LUT_MAX_SIZE = 2, 65
+# The defaults of Renderer.grade and of RendererHip::GradeSettings (docs/NEXT_ROWS.md section 22): the identity grade, under which
+# ptx_grade gives ptx_postprocess's bits; the white point is read by CURVE_REINHARD only
+GRADE_DEFAULTS = dict(colour_matrix=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), slope=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0), power=(1.0, 1.0, 1.0),
+                      saturation=1.0, curve=CURVE_REFERENCE, white_point=4.0)
+
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
 OUTPUT_RGBA8_SRGB, OUTPUT_RGBA32F = 0, 1
@@ -367,6 +384,8 @@ def load_host() -> C.CDLL:
         lib.pth_write_image.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
         lib.pth_save_checkpoint.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.pth_load_checkpoint.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
+        lib.pth_read_cube.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t]
+        lib.pth_white_balance_matrix.argtypes = [C.c_double, C.POINTER(C.c_float)]
         _host = lib
     return _host
 
@@ -492,6 +511,9 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_meter_ptr.restype = P
         lib.ptx_meter_reset.argtypes = [P]
         lib.ptx_postprocess_metered.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32, C.c_uint32]
+        lib.ptx_grade.argtypes = [P, C.POINTER(GradeDesc), C.c_uint32]
+        lib.ptx_grade_lut.argtypes = [P, C.c_uint32, P]
+        lib.ptx_present_graded.argtypes = [P, C.POINTER(PresentDesc)]
         _hip = lib
     return _hip
 
@@ -735,7 +757,7 @@ class Renderer:
         self._check(self.lib.ptx_read_output(self.handle, fmt, out.ctypes.data, out.nbytes))
         return out
 
-    def present(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None):
+    def present(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None, _call=None):
         """ptx_present: the last postprocess()' frame at the screen extent width x height in the swapchain format `fmt`, under
         the UI image `ui`: None, an H x W x 4 uint8 array (RGBA8 UNORM), or a torch tensor of that shape on the renderer's device,
         which is read in place."""
@@ -755,8 +777,34 @@ class Renderer:
             ptr = ui.ctypes.data
         self._present_ui = ui  # the copy is asynchronous: keep the image alive
         d = PresentDesc(width, height, fmt, tone_mapping, ptr, flags, 0)
-        self._check(self.lib.ptx_present(self.handle, C.byref(d)))
+        self._check((_call or self.lib.ptx_present)(self.handle, C.byref(d)))
         self._present = (width, height, fmt)
+
+    def present_graded(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None):
+        """ptx_present_graded: present() with the desc of the last grade() applied between the scaling blit and the UI."""
+        self.present(width, height, fmt, tone_mapping, ui, _call=self.lib.ptx_present_graded)
+
+    def grade(self, tone_mapping: int = TONE_MAPPING_SDR, colour_matrix=GRADE_DEFAULTS["colour_matrix"], slope=GRADE_DEFAULTS["slope"],
+              offset=GRADE_DEFAULTS["offset"], power=GRADE_DEFAULTS["power"], saturation: float = GRADE_DEFAULTS["saturation"],
+              curve: int = GRADE_DEFAULTS["curve"], white_point: float = GRADE_DEFAULTS["white_point"], use_lut: bool = False, lut_srgb_domain: bool = False):
+        """ptx_grade: the display transform -- colour matrix (row-major, 9 values), ASC CDL slope / offset / power and saturation, the
+        tone curve CURVE_* and, with use_lut, the LUT of set_lut() -- on what the last postprocess*() left, into the image
+        read_output() reads.  The desc is kept for present_graded().  Asynchronous."""
+        d = GradeDesc((C.c_float * 9)(*np.asarray(colour_matrix, np.float32).reshape(9)), (C.c_float * 3)(*slope), (C.c_float * 3)(*offset),
+                      (C.c_float * 3)(*power), saturation, curve, white_point, (GRADE_USE_LUT if use_lut else 0) | (GRADE_LUT_SRGB_DOMAIN if lut_srgb_domain else 0), 0)
+        self._check(self.lib.ptx_grade(self.handle, C.byref(d), tone_mapping))
+
+    def set_lut(self, lut):
+        """ptx_grade_lut: an N x N x N x 3 float32 array indexed [blue, green, red] (red fastest: a .cube file's order, read_cube()'s
+        result), 2 <= N <= 65; None clears it."""
+        if lut is None:
+            self._check(self.lib.ptx_grade_lut(self.handle, 0, None))
+            return
+        lut = np.ascontiguousarray(lut, dtype=np.float32)
+        n = lut.shape[0]
+        if lut.shape != (n, n, n, 3):
+            raise ValueError("lut must be N x N x N x 3")
+        self._check(self.lib.ptx_grade_lut(self.handle, n, lut.ctypes.data))
 
     def read_present(self) -> np.ndarray:
         """The image of the last present(): H x W x 4 uint8 (bytes in the format's order), H x W uint32 for A2B10G10R10,
@@ -1081,6 +1129,30 @@ def decode_image_levels(data: bytes):
         out.append(flat[at:at + h * w * 4].reshape(h, w, 4))
         at += h * w * 4
     return out
+
+
+def read_cube(path: str) -> np.ndarray:
+    """host/CubeLut.h ReadCubeLut: a .cube 3-D LUT file as an N x N x N x 3 float32 array indexed [blue, green, red], what
+    Renderer.set_lut takes.  A malformed, truncated or oversized file raises PtxError."""
+    lib = load_host()
+    size = C.c_uint32(0)
+    if lib.pth_read_cube(str(path).encode(), C.byref(size), None, 0):
+        raise PtxError(lib.pth_last_error().decode())
+    n = size.value
+    lut = np.empty((n, n, n, 3), np.float32)
+    if lib.pth_read_cube(str(path).encode(), C.byref(size), lut.ctypes.data, lut.size):
+        raise PtxError(lib.pth_last_error().decode())
+    return lut
+
+
+def white_balance_matrix(kelvin: float) -> np.ndarray:
+    """host/CubeLut.h WhiteBalanceMatrix: the 3 x 3 colour matrix (float32, row-major, linear sRGB) that turns the light of a
+    `kelvin` black body into white; 0 is the identity."""
+    m = np.empty(9, np.float32)
+    lib = load_host()
+    if lib.pth_white_balance_matrix(float(kelvin), m.ctypes.data_as(C.POINTER(C.c_float))):
+        raise PtxError(lib.pth_last_error().decode())
+    return m.reshape(3, 3)
 
 
 def write_image(path: str, img: np.ndarray, fmt: int = OUTPUT_PNG):

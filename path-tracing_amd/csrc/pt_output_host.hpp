@@ -1,6 +1,8 @@
 // pt_output_host.hpp -- the output stage (ptx_postprocess, ptx_read_output: row N4) and the screen path (ptx_present, ptx_read_present:
 // row D15; docs/NEXT_ROWS.md section 12), and the exposure metering in front of them (ptx_meter, ptx_read_meter, ptx_meter_reset,
-// ptx_postprocess_metered: section 21).  Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp; state: OutputState, the member `output` of the handle.
+// ptx_postprocess_metered: section 21), and the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded: section 22),
+// which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping.
+// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_chain_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
 #pragma once
 
@@ -85,22 +87,34 @@ static int readOutput(PtxRenderer *r, uint32_t outputFormat, void *host, size_t 
     return PTX_OK;
 }
 
-// The screen path: RecordPostProcessCommands' final blit + RecordUICommands (Renderer.cpp:1075-1203) in one launch of k_present
-static int present(PtxRenderer *r, const PtxPresentDesc *d)
+static GradeArgs gradeArgs(const PtxRenderer *r, const PtxGradeDesc &d, bool hdr); // below: the display transform
+
+// The screen path: RecordPostProcessCommands' final blit + RecordUICommands (Renderer.cpp:1075-1203) in one launch of k_present, or, for
+// ptx_present_graded (`graded`, section 22), of k_present_graded with the desc the last accepted ptx_grade left
+static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who, bool graded)
 {
     if (!r || !d)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: null argument");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
     if (!d->width || !d->height || d->width > 16384u || d->height > 16384u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: bad screen extent %ux%u (1 .. 16384 each)", d->width, d->height);
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad screen extent %ux%u (1 .. 16384 each)", who, d->width, d->height);
     if (d->format > PTX_PRESENT_R16G16B16A16_SFLOAT || d->toneMappingMode > PTX_TONE_MAPPING_HDR || (d->flags & ~(uint32_t)PTX_PRESENT_UI_ON_DEVICE) || d->reserved)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: unknown format %u, mode %u or flags 0x%x, or reserved != 0", d->format, d->toneMappingMode, d->flags);
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: unknown format %u, mode %u or flags 0x%x, or reserved != 0", who, d->format, d->toneMappingMode, d->flags);
     const bool hdr = d->toneMappingMode == PTX_TONE_MAPPING_HDR;
     if ((hdr && d->format <= PTX_PRESENT_B8G8R8A8_SRGB) || (!hdr && d->format == PTX_PRESENT_A2B10G10R10_UNORM))
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_present: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)");
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)", who);
     if (!r->output.ready)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_present: call ptx_postprocess first");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_postprocess first", who);
     if (r->frame.boundShard)
-        return frameIsElsewhere(r, "ptx_present");
+        return frameIsElsewhere(r, who);
+    if (graded)
+    {
+        if (r->frame.shard.worldSize > 1u)
+            return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
+        if (!r->output.gradeSet)
+            return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_grade first", who);
+        if ((r->output.gradeDesc.flags & PTX_GRADE_USE_LUT) && !r->output.gradeLut.p)
+            return fail(r, PTX_ERROR_NOT_READY, "%s: the kept desc uses a LUT and the LUT has been cleared (ptx_grade_lut)", who);
+    }
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t n = d->width * d->height;
     const size_t words = (size_t)n * (d->format == PTX_PRESENT_R16G16B16A16_SFLOAT ? 2 : 1);
@@ -124,23 +138,44 @@ static int present(PtxRenderer *r, const PtxPresentDesc *d)
         a.ui = r->output.presentUi.p;
     }
     const uint32_t grid = (n + kPresentBlock - 1) / kPresentBlock;
-    switch (d->format)
+    if (graded)
     {
-    case PTX_PRESENT_R8G8B8A8_SRGB: k_present<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    case PTX_PRESENT_B8G8R8A8_SRGB: k_present<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    case PTX_PRESENT_A2B10G10R10_UNORM: k_present<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-    default:
-        if (hdr)
-            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a);
-        else
-            k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a);
+        const GradeArgs g = gradeArgs(r, r->output.gradeDesc, hdr);
+        switch (d->format)
+        {
+        case PTX_PRESENT_R8G8B8A8_SRGB: k_present_graded<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
+        case PTX_PRESENT_B8G8R8A8_SRGB: k_present_graded<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
+        case PTX_PRESENT_A2B10G10R10_UNORM: k_present_graded<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
+        default:
+            if (hdr)
+                k_present_graded<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a, g);
+            else
+                k_present_graded<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g);
+        }
     }
+    else
+        switch (d->format)
+        {
+        case PTX_PRESENT_R8G8B8A8_SRGB: k_present<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+        case PTX_PRESENT_B8G8R8A8_SRGB: k_present<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+        case PTX_PRESENT_A2B10G10R10_UNORM: k_present<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
+        default:
+            if (hdr)
+                k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a);
+            else
+                k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a);
+        }
     HIP_TRY(r, hipGetLastError());
     r->output.presentWidth = d->width;
     r->output.presentHeight = d->height;
     r->output.presentFormat = d->format;
     r->output.presentBytes = words * 4;
     return PTX_OK;
+}
+
+static int present(PtxRenderer *r, const PtxPresentDesc *d)
+{
+    return presentFrame(r, d, "ptx_present", false);
 }
 
 static int readPresent(PtxRenderer *r, void *host, size_t bytes)
@@ -295,4 +330,114 @@ static int postprocessMetered(PtxRenderer *r, const PtxPostProcessingUniformData
     if (source == PTX_METER_DENOISED)
         u.TotalSamples = 1u; // ptx_postprocess_denoised: D holds the mean
     return postprocessImage(r, image, &u, toneMappingMode, &r->output.meterState.p->result.exposure);
+}
+
+// ---- display transform (docs/NEXT_ROWS.md section 22; semantics: include/ptx.h ptx_grade; kernels: pt_grade.hpp) ---------------------
+
+// the skip rule: which steps of the header run for this desc and mode, decided here, bit for bit, and handed to the kernel as switches
+static GradeArgs gradeArgs(const PtxRenderer *r, const PtxGradeDesc &d, bool hdr)
+{
+    const auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    const uint32_t one = 0x3f800000u;
+    GradeArgs g;
+    uint32_t steps = 0u;
+    for (int i = 0; i < 9; i++)
+    {
+        g.m[i] = d.colourMatrix[i];
+        if (bits(d.colourMatrix[i]) != (i % 4 == 0 ? one : 0u))
+            steps |= GRADE_STEP_MATRIX;
+    }
+    for (int k = 0; k < 3; k++)
+    {
+        g.slope[k] = d.slope[k]; g.offset[k] = d.offset[k]; g.power[k] = d.power[k];
+        if (bits(d.slope[k]) != one || bits(d.offset[k]) != 0u)
+            steps |= GRADE_STEP_SLOPE_OFFSET;
+        if (bits(d.power[k]) != one)
+            steps |= GRADE_STEP_POWER;
+    }
+    if (bits(d.saturation) != one)
+        steps |= GRADE_STEP_SATURATION;
+    if (!hdr)
+    {
+        steps |= GRADE_STEP_CURVE;
+        if (d.flags & PTX_GRADE_USE_LUT)
+            steps |= GRADE_STEP_LUT | (d.flags & PTX_GRADE_LUT_SRGB_DOMAIN ? GRADE_STEP_LUT_SRGB : 0u);
+    }
+    g.saturation = d.saturation;
+    g.whitePoint = d.whitePoint;
+    g.curve = d.curve;
+    g.steps = steps;
+    g.lut = steps & GRADE_STEP_LUT ? r->output.gradeLut.p : nullptr;
+    g.lutSize = r->output.gradeLutSize;
+    return g;
+}
+
+// ptx_grade: k_compose_tonemap's launch with k_compose_grade in its place, on what the last output call left
+static int grade(PtxRenderer *r, const PtxGradeDesc *d, uint32_t toneMappingMode)
+{
+    const char *who = "ptx_grade";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (d->curve > PTX_CURVE_ACES_FIT || toneMappingMode > PTX_TONE_MAPPING_HDR || (d->flags & ~(uint32_t)(PTX_GRADE_USE_LUT | PTX_GRADE_LUT_SRGB_DOMAIN)) ||
+        d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: unknown curve %u, mode %u or flags 0x%x, or reserved != 0 (%u)", who, d->curve, toneMappingMode, d->flags,
+                    d->reserved);
+    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
+    bool ok = finite(d->saturation) && finite(d->whitePoint) && d->saturation >= 0.0f;
+    for (int i = 0; i < 9; i++)
+        ok = ok && finite(d->colourMatrix[i]);
+    for (int k = 0; k < 3; k++)
+        ok = ok && finite(d->slope[k]) && finite(d->offset[k]) && finite(d->power[k]) && d->slope[k] >= 0.0f && d->power[k] >= 0.0f;
+    if (!ok)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: every float field must be finite, and slope, power and saturation >= 0", who);
+    if (d->curve == PTX_CURVE_REINHARD && !(d->whitePoint > 0.0f))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: PTX_CURVE_REINHARD needs whitePoint > 0 (%g)", who, (double)d->whitePoint);
+    if ((d->flags & PTX_GRADE_LUT_SRGB_DOMAIN) && !(d->flags & PTX_GRADE_USE_LUT))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: PTX_GRADE_LUT_SRGB_DOMAIN needs PTX_GRADE_USE_LUT", who);
+    OutputState &o = r->output;
+    if (!o.ready)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_postprocess first", who);
+    if (r->frame.boundShard)
+        return frameIsElsewhere(r, who);
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
+    if ((d->flags & PTX_GRADE_USE_LUT) && !o.gradeLut.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: PTX_GRADE_USE_LUT and no LUT set (call ptx_grade_lut)", who);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t n = r->frame.width * r->frame.height;
+    const GradeArgs g = gradeArgs(r, *d, toneMappingMode == PTX_TONE_MAPPING_HDR);
+    // postRgb, level 0 of bloomRgb and outLinear are those of the output call that set `ready`, at this extent
+    k_compose_grade<<<gridFor(n), kBlock, 0, r->stream>>>(o.postRgb.p, o.bloomRgb.p, n, o.postUniform, g, o.outLinear.p);
+    HIP_TRY(r, hipGetLastError());
+    o.gradeDesc = *d;
+    o.gradeSet = true;
+    return PTX_OK;
+}
+
+// ptx_grade_lut: the table goes into a buffer of its own first and takes the old one's place once it has arrived, so a kernel still
+// in flight reads the LUT it was launched with and a failed call leaves that LUT where it is
+static int setGradeLut(PtxRenderer *r, uint32_t size, const float *rgb)
+{
+    const char *who = "ptx_grade_lut";
+    if (!r)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (rgb && (size < PTX_GRADE_LUT_MIN_SIZE || size > PTX_GRADE_LUT_MAX_SIZE))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: size %u outside %u .. %u", who, size, PTX_GRADE_LUT_MIN_SIZE, PTX_GRADE_LUT_MAX_SIZE);
+    HIP_TRY(r, hipSetDevice(r->device));
+    DevBuf<float> table;
+    if (rgb)
+    {
+        const size_t count = (size_t)size * size * size * 3u;
+        HIP_TRY(r, table.alloc(count));
+        HIP_TRY(r, hipMemcpyAsync(table.p, rgb, count * sizeof(float), hipMemcpyHostToDevice, r->stream));
+    }
+    HIP_TRY(r, hipStreamSynchronize(r->stream)); // the copy has landed, and nothing in flight reads the table that is about to go
+    r->output.gradeLut.swap(table);
+    r->output.gradeLutSize = rgb ? size : 0u;
+    return PTX_OK;
+}
+
+static int presentGraded(PtxRenderer *r, const PtxPresentDesc *d)
+{
+    return presentFrame(r, d, "ptx_present_graded", true);
 }

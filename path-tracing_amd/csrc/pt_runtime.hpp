@@ -38,6 +38,7 @@
 #include "pt_responsive.hpp"
 #include "pt_despike.hpp"
 #include "pt_meter.hpp"
+#include "pt_grade.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -274,6 +275,11 @@ struct OutputState
     // exposure metering (ptx_meter, docs/NEXT_ROWS.md section 21): both allocated by the first accepted ptx_meter
     DevBuf<MeterState> meterState;  // result, bins and the adapted exposure
     DevBuf<uint32_t> meterSlabs;    // kMeterGridCap slabs of kMeterSlabWords words, rewritten whole by every call
+    // display transform (ptx_grade, docs/NEXT_ROWS.md section 22): the LUT is allocated by ptx_grade_lut, nothing else is device memory
+    DevBuf<float> gradeLut;         // gradeLutSize^3 x 3 floats, red fastest; belongs to the display and outlives ptx_resize ...
+    uint32_t gradeLutSize = 0;
+    PtxGradeDesc gradeDesc = {};    // ... as does the desc of the last accepted ptx_grade, which ptx_present_graded applies
+    bool gradeSet = false;
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
 };
 

@@ -391,6 +391,21 @@ int ptx_postprocess_metered(PtxRenderer *r, const PtxPostProcessingUniformData *
     return postprocessMetered(r, u, toneMappingMode, source);
 }
 
+int ptx_grade(PtxRenderer *r, const PtxGradeDesc *d, uint32_t toneMappingMode)
+{
+    return grade(r, d, toneMappingMode);
+}
+
+int ptx_grade_lut(PtxRenderer *r, uint32_t size, const float *rgb)
+{
+    return setGradeLut(r, size, rgb);
+}
+
+int ptx_present_graded(PtxRenderer *r, const PtxPresentDesc *desc)
+{
+    return presentGraded(r, desc);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

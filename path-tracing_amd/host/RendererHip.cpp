@@ -1,5 +1,7 @@
 #include "RendererHip.h"
 
+#include "CubeLut.h"
+
 namespace PathTracing
 {
 
@@ -284,13 +286,52 @@ static int PostProcessFrame(const PtxPostProcessingUniformData &u, uint32_t mode
     return OutputStage(u, mode, PTX_METER_DENOISED);
 }
 
+static RendererHip::GradeSettings s_GradeSettings;
+static PtxGradeDesc s_GradeDesc;
+
+void RendererHip::SetSettings(const GradeSettings &settings)
+{
+    PtxGradeDesc d = {};
+    WhiteBalanceMatrix(settings.TemperatureKelvin, d.colourMatrix);
+    for (int k = 0; k < 3; k++)
+    {
+        d.slope[k] = settings.Slope[k];
+        d.offset[k] = settings.Offset[k];
+        d.power[k] = settings.Power[k];
+    }
+    d.saturation = settings.Saturation;
+    d.curve = settings.Curve;
+    d.whitePoint = settings.WhitePoint;
+    if (settings.Enabled && !settings.LutFile.empty())
+    {
+        if (settings.LutFile != s_GradeSettings.LutFile || !s_GradeSettings.Enabled)
+        {
+            const CubeLut lut = ReadCubeLut(settings.LutFile);
+            Check(ptx_grade_lut(s_Renderer, lut.Size, lut.Rgb.data()));
+        }
+        d.flags = (uint32_t)PTX_GRADE_USE_LUT | (settings.LutSrgbDomain ? (uint32_t)PTX_GRADE_LUT_SRGB_DOMAIN : 0u);
+    }
+    else if (s_GradeSettings.Enabled && !s_GradeSettings.LutFile.empty())
+        Check(ptx_grade_lut(s_Renderer, 0u, nullptr));
+    s_GradeSettings = settings;
+    s_GradeDesc = d;
+}
+
+static bool GradeIsOn()
+{
+    return s_GradeSettings.Enabled && !s_DebugPipeline;
+}
+
 void RendererHip::SaveOutput(const OutputInfo &info)
 {
     if (info.Extent.width != s_Width || info.Extent.height != s_Height)
         throw error("SaveOutput: the output extent must equal the render extent");
     const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
                                              s_PostProcessSettings.BloomIntensity };
-    Check(PostProcessFrame(u, s_PostProcessSettings.Hdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR));
+    const uint32_t mode = s_PostProcessSettings.Hdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR;
+    Check(PostProcessFrame(u, mode));
+    if (GradeIsOn())
+        Check(ptx_grade(s_Renderer, &s_GradeDesc, mode));
     const uint32_t format = OutputSaver::SelectImageFormat(info.Format);
     std::vector<std::byte> bytes(static_cast<size_t>(s_Width) * s_Height * (format == PTX_OUTPUT_RGBA32F ? 16 : 4));
     Check(ptx_read_output(s_Renderer, format, bytes.data(), bytes.size()));
@@ -312,8 +353,10 @@ void RendererHip::Present(uint32_t width, uint32_t height, const uint8_t *ui)
                                              s_PostProcessSettings.BloomIntensity };
     const uint32_t mode = s_SurfaceIsHdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR; // Renderer.cpp:737-742
     Check(PostProcessFrame(u, mode));
+    if (GradeIsOn())
+        Check(ptx_grade(s_Renderer, &s_GradeDesc, mode));
     const PtxPresentDesc desc = { width, height, s_SurfaceIsHdr ? (uint32_t)PTX_PRESENT_A2B10G10R10_UNORM : (uint32_t)PTX_PRESENT_R8G8B8A8_SRGB, mode, ui, 0u, 0u };
-    Check(ptx_present(s_Renderer, &desc));
+    Check(GradeIsOn() ? ptx_present_graded(s_Renderer, &desc) : ptx_present(s_Renderer, &desc));
 }
 
 std::vector<std::byte> RendererHip::ReadPresent()

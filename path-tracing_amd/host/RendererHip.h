@@ -8,6 +8,7 @@
 #pragma once
 
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "OutputSaver.h"
@@ -141,6 +142,26 @@ public:
     // meters a frame, which adapts over them and uses them up: a second output call of the same frame, or every frame of a host that
     // never calls OnUpdate again, meters with deltaSeconds = 0 and leaves the exposure where it is.
     static void OnUpdate(float timeStep);
+    // Display transform (ptx.h "Display transform", docs/NEXT_ROWS.md section 22).  Enabled: ptx_grade follows whichever post-process
+    // call SaveOutput and Present make -- with the same tone-mapping mode, so ptx_read_output returns the graded image -- and Present
+    // calls ptx_present_graded in ptx_present's place.  Disabled (the default): both enqueue exactly what they did, and nothing is
+    // allocated.  TemperatureKelvin != 0 sets the colour matrix to WhiteBalanceMatrix(TemperatureKelvin) (CubeLut.h); LutFile, where not
+    // empty, is read as a .cube file (ReadCubeLut) and handed to ptx_grade_lut by SetSettings, which throws on a file it cannot take.
+    // A debug-view frame is shown as it is.  The defaults are GRADE_DEFAULTS of the Python package.
+    struct GradeSettings
+    {
+        bool Enabled = false;
+        uint32_t Curve = 0; // PTX_CURVE_REFERENCE
+        float WhitePoint = 4.0f;
+        float TemperatureKelvin = 0.0f;
+        float Slope[3] = { 1.0f, 1.0f, 1.0f };
+        float Offset[3] = { 0.0f, 0.0f, 0.0f };
+        float Power[3] = { 1.0f, 1.0f, 1.0f };
+        float Saturation = 1.0f;
+        std::string LutFile;
+        bool LutSrgbDomain = false;
+    };
+    static void SetSettings(const GradeSettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either

@@ -3,6 +3,7 @@
 
 #include <string>
 
+#include "CubeLut.h"
 #include "ExampleScenes.h"
 #include "OutputSaver.h"
 #include "TextureImporter.h"
@@ -228,5 +229,44 @@ int pth_load_checkpoint(const char *path, uint32_t *width, uint32_t *height, uin
         std::memcpy(rgba, data.data(), bytes);
     }
     return PTX_OK;
+}
+
+int pth_read_cube(const char *path, uint32_t *size, float *rgb, size_t floats)
+{
+    if (!path || !size)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    try
+    {
+        const CubeLut lut = ReadCubeLut(path);
+        *size = lut.Size;
+        if (rgb) // rgb == NULL: size query only
+        {
+            if (floats != lut.Rgb.size())
+                throw error("pth_read_cube: the buffer must hold size^3 * 3 floats");
+            std::memcpy(rgb, lut.Rgb.data(), floats * sizeof(float));
+        }
+        return PTX_OK;
+    }
+    catch (const std::exception &e)
+    {
+        g_error = e.what();
+        return PTX_ERROR_INVALID_ARGUMENT;
+    }
+}
+
+int pth_white_balance_matrix(double kelvin, float matrix[9])
+{
+    if (!matrix)
+        return PTX_ERROR_INVALID_ARGUMENT;
+    try
+    {
+        WhiteBalanceMatrix(kelvin, matrix);
+        return PTX_OK;
+    }
+    catch (const std::exception &e)
+    {
+        g_error = e.what();
+        return PTX_ERROR_INVALID_ARGUMENT;
+    }
 }
 }

@@ -32,7 +32,12 @@ pixel in) and ptx_postprocess of the same run beside them.  ptx_meter is given a
 a bandwidth: at 1920 x 1080 the 33 MB frame of a back-to-back run is served from the last-level cache.  A kernel trace of `--meter
 --extent W H` gives k_meter_histogram's, k_meter_resolve's and k_despike<1>'s device times.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--extent W H]"""
+ptx_grade and ptx_present_graded (section 22): --grade times nothing but them, on the 8-spp chess_like frame behind one ptx_postprocess:
+the identity desc, each curve, a CDL grade with and without power, and a 33^3 LUT in the linear and in the sRGB domain, with
+ptx_postprocess and ptx_present of the same run beside them.  ptx_grade is one launch of k_compose_grade, which moves k_compose_tonemap's
+40 bytes per pixel; a kernel trace of `--grade --extent W H` gives both kernels' device times.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--extent W H]"""
 import json
 import math
 import os
@@ -52,6 +57,7 @@ DENOISE_BYTES_PER_PIXEL_AND_PASS = 80
 TEMPORAL_BYTES_PER_PIXEL = 176
 MOMENTS_BYTES_PER_PIXEL = 208
 RESPONSIVE_BYTES_PER_PIXEL = 240
+GRADE_BYTES_PER_PIXEL = 40  # 24 in (post-process image, bloom level 0), 16 out; the LUT's reads are cache hits
 METER_BYTES_PER_PIXEL = 16  # one load of the pixel; the slabs (1 MB at the most) and the state are noise beside it
 # 16 B out and 16 B x (tile + halo) / tile in: the halo is 84 entries of 256 at radius 1 and 176 at radius 2
 DESPIKE_BYTES_PER_PIXEL = {1: 16 + 16 * (256 + 84) / 256, 2: 16 + 16 * (256 + 176) / 256}
@@ -77,7 +83,8 @@ def main():
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
     guides_only, temporal_only, meter_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv, "--meter" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only else ("chess_like", "default") if guides_only else
+    grade_only = "--grade" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only else ("chess_like", "default") if guides_only else
                                                           ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
@@ -103,6 +110,31 @@ def main():
             ud = sd.uniform(w, h, bounces=STEP_DEPTH)
             rec["render_guides_default"] = timed(rd, lambda: rd.render_guides(ud))
             specular_row("default", rd, ud)
+        if grade_only:
+            r.reset()
+            r.render_frames(u, scene.lights, 0, STEP_SPP)
+            rec["postprocess"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
+            rec["present_own_size"] = timed(r, lambda: r.present(w, h))
+            n = 33
+            g = np.arange(n, dtype=np.float32) / np.float32(n - 1)
+            lut = np.stack(np.broadcast_arrays(g[None, None, :], g[None, :, None], g[:, None, None]), axis=-1) ** np.float32(0.9)
+            r.set_lut(lut)
+            cdl = dict(slope=(1.1, 0.9, 1.0), offset=(0.01, -0.02, 0.0), saturation=1.3)
+            descs = {"identity": {}, "reinhard": dict(curve=pkg.CURVE_REINHARD), "hable": dict(curve=pkg.CURVE_HABLE), "aces_fit": dict(curve=pkg.CURVE_ACES_FIT),
+                     "matrix_cdl_hable": dict(cdl, colour_matrix=pkg.white_balance_matrix(4500.0), curve=pkg.CURVE_HABLE),
+                     "cdl_power_hable": dict(cdl, power=(0.9, 1.1, 1.2), curve=pkg.CURVE_HABLE),
+                     "hable_lut33": dict(curve=pkg.CURVE_HABLE, use_lut=True), "hable_lut33_srgb_domain": dict(curve=pkg.CURVE_HABLE, use_lut=True, lut_srgb_domain=True)}
+            if "--desc" in sys.argv:  # one desc alone, so that a kernel trace of the run shows k_compose_grade under that desc
+                descs = {sys.argv[sys.argv.index("--desc") + 1]: descs[sys.argv[sys.argv.index("--desc") + 1]]}
+            for name, d in descs.items():
+                t = timed(r, lambda: r.grade(**d))
+                t["algorithmic_GB_per_s"] = w * h * GRADE_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
+                rec[f"grade_{name}"] = t
+                rec[f"present_graded_own_size_{name}"] = timed(r, lambda: r.present_graded(w, h))
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
         if meter_only:
             r.reset()
             r.render_frames(u, scene.lights, 0, STEP_SPP)
