@@ -14,6 +14,8 @@
 //                                                                            every frame is announced with OnUpdate(timeStep)
 //                                                                            and, without the denoiser, saved twice)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 1 1 (... with the denoiser: the denoised image is metered)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 2 (... with ExposureSettings and LocalExposureSettings on: section 23,
+//                                                                            tests/test_local_exposure.py; the exposure argument is 2)
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 0 1 [look.cube] (... with GradeSettings on: section 22,
 //                                                                            tests/test_grade.py: Hable's curve, 4500 K, a CDL grade,
 //                                                                            the LUT where a file is named; every frame is also
@@ -42,7 +44,7 @@ int main(int argc, char **argv)
 {
     if (argc < 9 || argc > 15)
     {
-        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1) "
+        std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1|2: with local exposure) "
                              "[grade(0|1) [lut.cube]]]]]]\n");
         return 1;
     }
@@ -53,6 +55,7 @@ int main(int argc, char **argv)
     const bool useDespike = argc >= 11 && std::atoi(argv[10]) != 0;
     const bool useDenoiser = argc < 12 || std::atoi(argv[11]) != 0; // 0: the plain output path, T is left as zeros
     const bool useExposure = argc >= 13 && std::atoi(argv[12]) != 0;
+    const bool useLocalExposure = argc >= 13 && std::atoi(argv[12]) == 2; // behind the meter
     const bool presentToo = argc >= 14, useGrade = presentToo && std::atoi(argv[13]) != 0;
     const uint32_t screenWidth = 100, screenHeight = 37;
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
@@ -77,6 +80,9 @@ int main(int argc, char **argv)
         RendererHip::ExposureSettings exposure;
         exposure.Enabled = useExposure;
         RendererHip::SetSettings(exposure);
+        RendererHip::LocalExposureSettings localExposure;
+        localExposure.Enabled = useLocalExposure;
+        RendererHip::SetSettings(localExposure);
         RendererHip::GradeSettings grade; // the values tests/test_grade.py repeats by hand
         grade.Enabled = useGrade;
         grade.Curve = PTX_CURVE_HABLE;

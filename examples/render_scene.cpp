@@ -16,6 +16,7 @@
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3 --responsive   (... whose history follows a change of lighting)
 //   examples/render_scene default 640 360 1 4 despiked.png --despike        (firefly suppression: a rank clamp of every pixel's luminance; with --denoise ahead of the chain)
 //   examples/render_scene default 640 360 16 4 metered.png --auto-exposure  (exposure metering: a luminance histogram sets the output stage's exposure)
+//   examples/render_scene atrium_like 640 360 16 4 local.png --local-exposure  (local exposure behind the meter: highlights and shadows move towards middle grey)
 //   examples/render_scene default 640 360 16 4 graded.png --curve aces --temperature 4500 --lut look.cube   (display transform: tone curve reference | reinhard | hable | aces,
 //                                                                            white balance for a light of that many kelvin, a .cube 3-D LUT)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
@@ -176,6 +177,17 @@ int main(int argc, char **argv)
                 argc -= 2;
                 break;
             }
+    RendererHip::LocalExposureSettings localExposure; // --local-exposure: behind the meter, a bilateral grid compresses the scene's contrast (implies --auto-exposure)
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--local-exposure")
+        {
+            localExposure.Enabled = true;
+            exposure.Enabled = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -207,6 +219,7 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(variance);
         RendererHip::SetSettings(firefly);
         RendererHip::SetSettings(exposure);
+        RendererHip::SetSettings(localExposure);
         RendererHip::SetSettings(grade);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));

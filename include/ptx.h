@@ -1356,7 +1356,8 @@ typedef struct PtxMeterResult {
  * PTX_ERROR_NOT_READY: a source that does not exist since the last ptx_resize (no C, no D).  A refused call leaves the state and the
  * bins intact; ptx_resize resets the state.
  * Known limits: the quantisation of (a); the range is fixed at 32 octaves; sharded frames are refused (a host can still sum bins256
- * across ranks itself); there is no perceptual model: no scotopic shift, no local adaptation. */
+ * across ranks itself); there is no perceptual model: no scotopic shift, and no local adaptation in the meter itself (that is
+ * ptx_local_exposure's part, below). */
 PTX_API int ptx_meter(PtxRenderer *r, const PtxMeterDesc *desc);
 /* The result and, where bins256 is not NULL, the 256 bins of the last ptx_meter, device -> host; synchronous, as ptx_read_output is.
  * PTX_ERROR_INVALID_ARGUMENT: a NULL handle or result; PTX_ERROR_NOT_READY: no accepted ptx_meter on this handle yet. */
@@ -1481,6 +1482,86 @@ PTX_API int ptx_grade_lut(PtxRenderer *r, uint32_t size, const float *rgb /* siz
  * PTX_ERROR_NOT_READY: a tile shard with worldSize > 1; no accepted ptx_grade on this handle yet; the kept desc has PTX_GRADE_USE_LUT
  * and the LUT has been cleared. */
 PTX_API int ptx_present_graded(PtxRenderer *r, const PtxPresentDesc *desc);
+
+/* ------------------------------------------------------------------------- */
+/* Local exposure (docs/NEXT_ROWS.md section 23): a bilateral grid over the    */
+/* log of the luminance gives every pixel a gain that compresses the scene's   */
+/* contrast and leaves local detail alone.  An addition: every call above      */
+/* computes what it computed before, and a host that never calls these         */
+/* allocates nothing for them.                                                 */
+/* ------------------------------------------------------------------------- */
+
+enum {
+    PTX_LOCAL_EXPOSURE_PIVOT_METERED = 1u /* the pivot is a display luminance: the meter state's cur is subtracted from pivotLog2 on the device */
+};
+
+typedef struct PtxLocalExposureDesc {
+    uint32_t source;            /* PTX_METER_SUM / _DESPIKED / _DENOISED, with ptx_meter's totalSamples convention */
+    uint32_t totalSamples;      /* > 0 */
+    uint32_t cellShift;         /* 3 ... 6: a grid cell is 2^cellShift x 2^cellShift pixels */
+    float    pivotLog2;         /* log2 of the display luminance the base is compressed towards (log2(0.18)) */
+    float    highlightContrast; /* 0 ... 2, finite: slope of the base above the pivot; 1 = untouched */
+    float    shadowContrast;    /* 0 ... 2, finite: ... below it */
+    float    maxStops;          /* >= 0, finite: |log2 gain| is clamped to it */
+    uint32_t flags;             /* PTX_LOCAL_EXPOSURE_PIVOT_METERED or 0 */
+    uint32_t reserved;          /* 0 */
+} PtxLocalExposureDesc;
+
+/* ptx_local_exposure computes G, an R32F image of the render extent W x H.  p = (x, y) is a pixel, s = cellShift.  Everything is
+ * integer up to one float64 division; the float64 operations are IEEE operations in the order written with no contraction, and exp2 is
+ * the project's specified kernel, so a reference in integers and doubles reproduces G bit for bit.
+ *   1. LUMINANCE AND CLASSES.  Exactly ptx_meter's steps 1 and 2: c(p) = source(p).rgb / (float)totalSamples (one rcp, three
+ *      multiplies; PTX_METER_DENOISED: 1 stands for totalSamples), Y(p) = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b; REJECTED iff Y is
+ *      not finite, BLACK iff Y <= 0 or Y < 2^-126, COUNTED otherwise.
+ *   2. FIXED-POINT LOG.  For a counted pixel l = clamp((int)(bits(Y) >> 15) - 888 * 32, 0, 8191): the eight exponent bits and the top
+ *      eight mantissa bits, 256 steps per octave over [2^-16, 2^16).  l / 256 - 16 is the piecewise-linear log2 e + m of
+ *      Y = (1 + m) 2^e, which lies at most 0.0861 below log2 Y and is smooth within an octave, with m cut to eight bits: less than
+ *      1 / 256 further below.
+ *   3. SPLAT.  The grid has nx = ceil(W / 2^s) by ny = ceil(H / 2^s) cells and 32 slices.  Every counted pixel adds l to
+ *      sum[cy][cx][z] and 1 to cnt[cy][cx][z] with cx = x >> s, cy = y >> s, z = l >> 8.  Both arrays are uint32.
+ *   4. BLUR.  One 1-2-1 pass along each of x, y and z over both arrays, clamp to edge: the edge cell stands in for the missing
+ *      neighbour, so the weights of the three passes always sum to 64.  Integer arithmetic, nothing is divided.  A cell holds at most
+ *      4096 pixels, so a blurred sum is at most 4096 * 8191 * 64 = 2,147,221,504 < 2^32.
+ *   5. SLICE, for a counted pixel.  Along x: u = 2x + 1 - 2^s.  If u < 0 both taps are cell 0 and fx = 0; otherwise cx0 = u >> (s + 1),
+ *      fx = u & (2^(s+1) - 1), cx1 = min(cx0 + 1, nx - 1); the weights are wx0 = 2^(s+1) - fx and wx1 = fx.  y is the same with ny.
+ *      Along z: v = 2l + 1 - 256; if v < 0 both taps are slice 0 and fz = 0; otherwise z0 = v >> 9, fz = v & 511, z1 = min(z0 + 1, 31);
+ *      weights 512 - fz and fz.  N = SUM wx wy wz sum and D = SUM wx wy wz cnt over the eight taps of the blurred arrays, in uint64
+ *      (at most 2^54).  The pixel's own cell and slice carry a positive weight, so D > 0.  B = (double)N / (double)D / 256 - 16.
+ *   6. GAIN.  pv = (double)pivotLog2; with PTX_LOCAL_EXPOSURE_PIVOT_METERED pv = pv - cur, cur being the double of the meter's device
+ *      state (ptx_meter step 8), read on the device: no synchronisation.  d = B - pv; c = d > 0 ? highlightContrast : shadowContrast;
+ *      g = clamp(((double)c - 1) d, -maxStops, maxStops), the clamp being min(max(x, lo), hi), and then clamp(g, -300, 300), the domain
+ *      of exp2.  G(p) = (float)exp2(g).  A BLACK or REJECTED pixel gets G(p) = 1.
+ *   7. OUTPUT.  ptx_postprocess_local is the output call of `source` with one change: its first kernel uses, per pixel,
+ *      Exposure_p = (u->Exposure * m) * G(p), float products in that order; m is the metered exposure read on the device when
+ *      `metered` is 1 and exactly 1.0f when it is 0.  Everything behind that kernel is the existing chain: bloom, composition,
+ *      ptx_read_output, ptx_grade, ptx_present.
+ * Consequences: (a) both contrasts at 1 give G = 1 everywhere, and with metered = 0 ptx_postprocess_local then gives the plain call's
+ * bits; (b) on a constant counted image B = l / 256 - 16 exactly, so G is one known value everywhere; (c) multiplying the source by a
+ * power of two shifts B by that many stops exactly, short of the range's ends; (d) two plateaus at least three octaves apart share no
+ * slice after the blur and the slice, so each gets its own constant gain right up to the edge: no halo; (e) the approximate log
+ * moves the gain by at most |c - 1| * (0.0861 + 1 / 256) stops against the exact one, smoothly: 0.0861 for the piecewise-linear
+ * log, 1 / 256 for its eight bits.
+ * Asynchronous on the render stream: three launches, no global atomics, nothing to zero between calls.  Works on a borrower; touches
+ * neither the sum nor any image of the chain.
+ * Refusals, in this order; a refused call leaves G intact.  PTX_ERROR_INVALID_ARGUMENT: a NULL argument, an unknown source,
+ * totalSamples = 0, cellShift outside 3 ... 6, an unknown flag bit, reserved != 0; a float field that is not finite, a contrast outside
+ * 0 ... 2, maxStops < 0.  PTX_ERROR_NOT_READY: no image (ptx_resize), a shard accumulation buffer bound, a tile shard with
+ * worldSize > 1; a source that does not exist since the last ptx_resize (no C, no D); PTX_LOCAL_EXPOSURE_PIVOT_METERED without an
+ * accepted ptx_meter on this handle.  ptx_resize drops G and the grid.
+ * Known limits: there is no detail-strength control (the approximate log would print its sawtooth into the image); the pass count is
+ * fixed at one; the range is fixed at 32 octaves; sharded frames are refused. */
+PTX_API int ptx_local_exposure(PtxRenderer *r, const PtxLocalExposureDesc *desc);
+/* G of the last accepted ptx_local_exposure, device -> host: width * height * 4 bytes, row-major; synchronous, as ptx_read_output is.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL argument, another size; PTX_ERROR_NOT_READY: no accepted ptx_local_exposure since the last
+ * ptx_resize. */
+PTX_API int ptx_read_local_exposure(PtxRenderer *r, void *host, size_t bytes);
+/* ... or its device address (NULL without one); it stays where it is until the next ptx_resize. */
+PTX_API void *ptx_device_local_exposure_ptr(PtxRenderer *r);
+/* Step 7.  PTX_ERROR_INVALID_ARGUMENT: a NULL argument, an unknown mode or source, metered > 1; PTX_ERROR_NOT_READY: as the plain call
+ * of that source; metered = 1 without an accepted ptx_meter; no accepted ptx_local_exposure since the last ptx_resize; a tile shard
+ * with worldSize > 1. */
+PTX_API int ptx_postprocess_local(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode,
+                                  uint32_t source, uint32_t metered /* 0 or 1 */);
 
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);

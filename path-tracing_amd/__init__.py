@@ -73,6 +73,7 @@ PTX_SYMBOLS = [
     "ptx_despike", "ptx_read_despiked", "ptx_device_despiked_ptr", "ptx_chain_use_despiked", "ptx_postprocess_despiked",
     "ptx_meter", "ptx_read_meter", "ptx_device_meter_ptr", "ptx_meter_reset", "ptx_postprocess_metered",
     "ptx_grade", "ptx_grade_lut", "ptx_present_graded",
+    "ptx_local_exposure", "ptx_read_local_exposure", "ptx_device_local_exposure_ptr", "ptx_postprocess_local",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -262,6 +263,18 @@ GRADE_LUT_MIN_SIZE, GRADE_LUT_MAX_SIZE = 2, 65
 # ptx_grade gives ptx_postprocess's bits; the white point is read by CURVE_REINHARD only
 GRADE_DEFAULTS = dict(colour_matrix=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), slope=(1.0, 1.0, 1.0), offset=(0.0, 0.0, 0.0), power=(1.0, 1.0, 1.0),
                       saturation=1.0, curve=CURVE_REFERENCE, white_point=4.0)
+
+
+class LocalExposureDesc(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("totalSamples", C.c_uint32), ("cellShift", C.c_uint32), ("pivotLog2", C.c_float), ("highlightContrast", C.c_float),
+                ("shadowContrast", C.c_float), ("maxStops", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LOCAL_EXPOSURE_PIVOT_METERED = 1  # PTX_LOCAL_EXPOSURE_PIVOT_METERED
+# The defaults of Renderer.local_exposure and of RendererHip::LocalExposureSettings (docs/NEXT_ROWS.md section 23): cells of 32 x 32
+# pixels, middle grey, highlights compressed to 0.6 of their distance from it and shadows to 0.8, at most four stops either way.
+# Nobody has tuned them: they are a starting point that shows the effect, not the result of a sweep.
+LOCAL_EXPOSURE_DEFAULTS = dict(cell_shift=5, pivot_log2=-2.473931, highlight_contrast=0.6, shadow_contrast=0.8, max_stops=4.0)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -514,6 +527,11 @@ def load_hip() -> C.CDLL:
         lib.ptx_grade.argtypes = [P, C.POINTER(GradeDesc), C.c_uint32]
         lib.ptx_grade_lut.argtypes = [P, C.c_uint32, P]
         lib.ptx_present_graded.argtypes = [P, C.POINTER(PresentDesc)]
+        lib.ptx_local_exposure.argtypes = [P, C.POINTER(LocalExposureDesc)]
+        lib.ptx_read_local_exposure.argtypes = [P, P, C.c_size_t]
+        lib.ptx_device_local_exposure_ptr.argtypes = [P]
+        lib.ptx_device_local_exposure_ptr.restype = P
+        lib.ptx_postprocess_local.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32, C.c_uint32, C.c_uint32]
         _hip = lib
     return _hip
 
@@ -1033,6 +1051,34 @@ class Renderer:
         multiplied by the metered exposure on the device."""
         u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
         self._check(self.lib.ptx_postprocess_metered(self.handle, C.byref(u), tone_mapping, source))
+
+    def local_exposure(self, total_samples: int, source: int = METER_SUM, cell_shift: int = LOCAL_EXPOSURE_DEFAULTS["cell_shift"],
+                       pivot_log2: float = LOCAL_EXPOSURE_DEFAULTS["pivot_log2"], highlight_contrast: float = LOCAL_EXPOSURE_DEFAULTS["highlight_contrast"],
+                       shadow_contrast: float = LOCAL_EXPOSURE_DEFAULTS["shadow_contrast"], max_stops: float = LOCAL_EXPOSURE_DEFAULTS["max_stops"],
+                       pivot_metered: bool = False):
+        """ptx_local_exposure: the per-pixel gain G of `source` (METER_SUM, METER_DESPIKED, METER_DENOISED, with meter()'s total_samples
+        convention): the base layer of the log2 luminance, taken from a bilateral grid of 2^cell_shift-pixel cells and 32 octave slices,
+        is moved towards pivot_log2 by the factor highlight_contrast above it and shadow_contrast below, by at most max_stops.
+        pivot_metered: the pivot is a display luminance, the metered exposure's log2 is taken off it on the device.  Asynchronous."""
+        d = LocalExposureDesc(source, total_samples, cell_shift, pivot_log2, highlight_contrast, shadow_contrast, max_stops,
+                              LOCAL_EXPOSURE_PIVOT_METERED if pivot_metered else 0, 0)
+        self._check(self.lib.ptx_local_exposure(self.handle, C.byref(d)))
+
+    def read_local_exposure(self) -> np.ndarray:
+        """ptx_read_local_exposure: G of the last local_exposure(), H x W float32; synchronises."""
+        img = np.empty((self.height, self.width), dtype=np.float32)
+        self._check(self.lib.ptx_read_local_exposure(self.handle, img.ctypes.data, img.nbytes))
+        return img
+
+    def local_exposure_ptr(self) -> int:
+        return int(self.lib.ptx_device_local_exposure_ptr(self.handle) or 0)
+
+    def postprocess_local(self, total_samples: int, exposure: float = 1.0, bloom_threshold: float = 1.0, bloom_intensity: float = 1.0,
+                          tone_mapping: int = TONE_MAPPING_SDR, source: int = METER_SUM, metered: bool = False):
+        """ptx_postprocess_local: postprocess(), postprocess_despiked() or postprocess_denoised() by `source`, with `exposure` multiplied
+        by the metered exposure (metered=True) or by 1, and then per pixel by G of local_exposure(), on the device."""
+        u = PostProcessingUniformData(total_samples, exposure, bloom_threshold, bloom_intensity)
+        self._check(self.lib.ptx_postprocess_local(self.handle, C.byref(u), tone_mapping, source, 1 if metered else 0))
 
     def stats(self) -> Stats:
         s = Stats()

@@ -27,6 +27,7 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->frame.unbind();
     r->output.invalidate();
     r->chain.invalidate(); // guides, D, T, the histories, V_0 and the motion guides belong to the extent they were made for
+    r->output.dropLocalExposure(); // ... and so do G and the grid of ptx_local_exposure
     HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     if (const int rc = meterReset(r)) // the exposure was metered on an image of the old extent
         return rc;

@@ -1,16 +1,18 @@
 // pt_output_host.hpp -- the output stage (ptx_postprocess, ptx_read_output: row N4) and the screen path (ptx_present, ptx_read_present:
 // row D15; docs/NEXT_ROWS.md section 12), and the exposure metering in front of them (ptx_meter, ptx_read_meter, ptx_meter_reset,
 // ptx_postprocess_metered: section 21), and the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded: section 22),
-// which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping.
-// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp; state: OutputState, the member `output` of the handle.
+// which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and the local
+// exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23).
+// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_chain_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
 #pragma once
 
 // Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)
 // the chain on `source` (width x height running sums of uniform->TotalSamples samples): the accumulation image, or the denoised mean
 // meterExposure: the device address of the metered exposure that ptx_postprocess_metered multiplies in (k_postprocess_metered), or none
+// localGain: G of ptx_local_exposure, which ptx_postprocess_local multiplies in per pixel (k_postprocess_local), or none
 static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode,
-                            const float *meterExposure = nullptr)
+                            const float *meterExposure = nullptr, const float *localGain = nullptr)
 {
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t W = r->frame.width, H = r->frame.height, n = W * H;
@@ -36,7 +38,9 @@ static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostP
         L[l].rgb = r->output.bloomRgb.p + off;
         off += (size_t)L[l].w * L[l].h * 3;
     }
-    if (meterExposure)
+    if (localGain)
+        k_postprocess_local<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, localGain, r->output.postRgb.p, L[0].rgb);
+    else if (meterExposure)
         k_postprocess_metered<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, r->output.postRgb.p, L[0].rgb);
     else
         k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->output.postRgb.p, L[0].rgb);
@@ -440,4 +444,112 @@ static int setGradeLut(PtxRenderer *r, uint32_t size, const float *rgb)
 static int presentGraded(PtxRenderer *r, const PtxPresentDesc *d)
 {
     return presentFrame(r, d, "ptx_present_graded", true);
+}
+
+// ---- local exposure (docs/NEXT_ROWS.md section 23; semantics: include/ptx.h ptx_local_exposure; kernels: pt_local_exposure.hpp) -------
+
+// ptx_local_exposure: splat, blur, gain.  Three launches, no synchronisation; the refusals follow ptx_meter's ladder, and every one of
+// them comes before the first allocation or launch, so a refused call leaves G as it was.
+static int localExposure(PtxRenderer *r, const PtxLocalExposureDesc *d)
+{
+    const char *who = "ptx_local_exposure";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
+    if (d->source > PTX_METER_DENOISED || !d->totalSamples || d->cellShift < kLocalMinShift || d->cellShift > kLocalMaxShift ||
+        (d->flags & ~(uint32_t)PTX_LOCAL_EXPOSURE_PIVOT_METERED) || d->reserved != 0u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need source <= 2 (%u), totalSamples > 0 (%u), cellShift in 3 .. 6 (%u), no unknown flag (0x%x) and "
+                    "reserved 0 (%u)", who, d->source, d->totalSamples, d->cellShift, d->flags, d->reserved);
+    if (!finite(d->pivotLog2) || !finite(d->highlightContrast) || !finite(d->shadowContrast) || !finite(d->maxStops) || d->highlightContrast < 0.0f ||
+        d->highlightContrast > 2.0f || d->shadowContrast < 0.0f || d->shadowContrast > 2.0f || d->maxStops < 0.0f)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a finite pivotLog2 (%g), highlightContrast and shadowContrast in 0 .. 2 (%g, %g) and a finite "
+                    "maxStops >= 0 (%g)", who, (double)d->pivotLog2, (double)d->highlightContrast, (double)d->shadowContrast, (double)d->maxStops);
+    if (!imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+    if (r->frame.boundShard)
+        return frameIsElsewhere(r, who);
+    if (r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
+    const float4 *source = meterSource(r, d->source);
+    if (!source)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no %s image for this extent (call %s first)", who, d->source == PTX_METER_DESPIKED ? "despiked" : "denoised",
+                    d->source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    OutputState &o = r->output;
+    const bool metered = (d->flags & PTX_LOCAL_EXPOSURE_PIVOT_METERED) != 0u;
+    if (metered && !o.meterState.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: PTX_LOCAL_EXPOSURE_PIVOT_METERED and no accepted ptx_meter on this handle yet", who);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t W = r->frame.width, H = r->frame.height, s = d->cellShift;
+    const uint32_t nx = (W + (1u << s) - 1u) >> s, ny = (H + (1u << s) - 1u) >> s;
+    const size_t entries = (size_t)nx * ny * kLocalSlices;
+    // the grid grows with a smaller cellShift; G has one size per extent (ptx_resize releases both), so a G that exists is never reallocated
+    HIP_TRY(r, o.localGrid.alloc(2u * entries));
+    HIP_TRY(r, o.localGain.alloc((size_t)W * H));
+    LocalSplatArgs a;
+    a.source = source;
+    a.grid = o.localGrid.p;
+    a.width = W; a.height = H; a.shift = s; a.nx = nx; a.ny = ny;
+    a.totalSamples = d->source == PTX_METER_DENOISED ? 1.0f : (float)d->totalSamples; // ptx_postprocess_denoised: D holds the mean
+    const uint32_t block = 1u << kLocalBlockShift;
+    k_local_splat<<<dim3((W + block - 1u) / block, (H + block - 1u) / block), kLocalSplatThreads, 0, r->stream>>>(a);
+    k_local_blur<<<(uint32_t)((entries + 255u) / 256u), 256, 0, r->stream>>>(o.localGrid.p, o.localGrid.p + entries, nx, ny);
+    LocalGainArgs g;
+    g.source = source;
+    g.grid = o.localGrid.p + entries;
+    g.gain = o.localGain.p;
+    g.meterCur = metered ? &o.meterState.p->cur : nullptr;
+    g.width = W; g.height = H; g.shift = s; g.nx = nx; g.ny = ny;
+    g.totalSamples = a.totalSamples;
+    g.pivotLog2 = d->pivotLog2;
+    g.highlightContrast = d->highlightContrast;
+    g.shadowContrast = d->shadowContrast;
+    g.maxStops = d->maxStops;
+    k_local_gain<<<dim3((W + kDenoiseTileX - 1) / kDenoiseTileX, (H + kDenoiseTileY - 1) / kDenoiseTileY), dim3(kDenoiseTileX, kDenoiseTileY), 0, r->stream>>>(g);
+    HIP_TRY(r, hipGetLastError());
+    o.localReady = true;
+    return PTX_OK;
+}
+
+static int readLocalExposure(PtxRenderer *r, void *host, size_t bytes)
+{
+    if (!r || !host)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_local_exposure: null argument");
+    if (!r->output.localReady)
+        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_local_exposure: call ptx_local_exposure first");
+    const size_t want = (size_t)r->frame.width * r->frame.height * sizeof(float);
+    if (bytes != want)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_local_exposure: buffer must be %zu bytes", want);
+    HIP_TRY(r, hipSetDevice(r->device));
+    HIP_TRY(r, hipMemcpyAsync(host, r->output.localGain.p, bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+// ptx_postprocess_local: the output call of `source` with Exposure = (uniform->Exposure x m) x G(p), m the metered exposure or 1
+static int postprocessLocal(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source, uint32_t metered)
+{
+    const char *who = "ptx_postprocess_local";
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR || source > PTX_METER_DENOISED || metered > 1u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad argument", who);
+    if (source == PTX_METER_SUM)
+    {
+        if (!imagePtr(r))
+            return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+        if (r->frame.boundShard)
+            return frameIsElsewhere(r, who);
+    }
+    const float4 *image = meterSource(r, source);
+    if (!image)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call %s first", who, source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    if (metered && !r->output.meterState.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_meter first", who);
+    if (!r->output.localReady)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_local_exposure first", who);
+    if (r->frame.shard.worldSize > 1u) // G covers the frame, a shard's image does not
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
+    PtxPostProcessingUniformData u = *uniform;
+    if (source == PTX_METER_DENOISED)
+        u.TotalSamples = 1u; // ptx_postprocess_denoised: D holds the mean
+    return postprocessImage(r, image, &u, toneMappingMode, metered ? &r->output.meterState.p->result.exposure : nullptr, r->output.localGain.p);
 }

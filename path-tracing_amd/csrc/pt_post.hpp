@@ -4,6 +4,7 @@
 //
 //   k_postprocess      postprocess.comp:16-40      sum / TotalSamples * Exposure, NaN / Inf markers, bloom prefilter
 //   k_postprocess_metered  the same with Exposure times the metered exposure of ptx_meter, read from device memory (section 21)
+//   k_postprocess_local    the same with Exposure times that, or times 1, times the per-pixel gain of ptx_local_exposure (section 23)
 //   k_bloom_downsample bloomDownsample.comp:18-62  13-tap filter, level i -> i + 1
 //   k_bloom_upsample   bloomUpsample.comp:18-55    3x3 tent of level i added onto level i - 1
 //   k_compose_tonemap  composition.comp:16-26 + toneMapping.comp:13-25 (two stores of the reference fused: the
@@ -137,6 +138,28 @@ __global__ void k_postprocess_metered(const float4 *__restrict__ accum, uint32_t
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
         const float4 a = accum[i];
+        f3 color, bloom;
+        postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
+        color = f16Round(color);
+        bloom = f16Round(bloom);
+        post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
+        bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
+    }
+}
+
+// k_postprocess with a per-pixel Exposure = (u.Exposure x m) x G(p) (include/ptx.h ptx_postprocess_local, docs/NEXT_ROWS.md section 23):
+// m is the metered exposure read from the meter's device state, or exactly 1.0f where `meterExposure` is null (x * 1.0f is x, bit for
+// bit), G the image ptx_local_exposure left: one more 4-byte load per pixel beside the 16 bytes of the sum.  Restated and not shared,
+// as k_postprocess_metered is and for its reason.  tests/test_local_exposure.py holds them together: with G = 1 everywhere this kernel
+// gives k_postprocess's bits, or k_postprocess_metered's.
+__global__ void k_postprocess_local(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, const float *__restrict__ meterExposure,
+                                    const float *__restrict__ localGain, float *__restrict__ post, float *__restrict__ bloom0)
+{
+    const float base = u.Exposure * (meterExposure ? *meterExposure : 1.0f);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    {
+        const float4 a = accum[i];
+        u.Exposure = base * localGain[i];
         f3 color, bloom;
         postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
         color = f16Round(color);

@@ -39,6 +39,7 @@
 #include "pt_despike.hpp"
 #include "pt_meter.hpp"
 #include "pt_grade.hpp"
+#include "pt_local_exposure.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -280,7 +281,18 @@ struct OutputState
     uint32_t gradeLutSize = 0;
     PtxGradeDesc gradeDesc = {};    // ... as does the desc of the last accepted ptx_grade, which ptx_present_graded applies
     bool gradeSet = false;
+    // local exposure (ptx_local_exposure, docs/NEXT_ROWS.md section 23): both allocated by the first accepted ptx_local_exposure and
+    // released by ptx_resize, whose extent they were made for
+    DevBuf<float> localGain;        // G, one float per pixel
+    DevBuf<uint2> localGrid;        // the splatted grid and the blurred one behind it: 2 x ny x nx x 32 entries of (sum, count)
+    bool localReady = false;        // an accepted ptx_local_exposure since the last ptx_resize
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
+    void dropLocalExposure() // ptx_resize
+    {
+        localGain.release();
+        localGrid.release();
+        localReady = false;
+    }
 };
 
 // The interactive chain behind ptx_render (pt_chain_host.hpp): the images of the guide pass, the temporal accumulation and the

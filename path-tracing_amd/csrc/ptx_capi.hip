@@ -406,6 +406,26 @@ int ptx_present_graded(PtxRenderer *r, const PtxPresentDesc *desc)
     return presentGraded(r, desc);
 }
 
+int ptx_local_exposure(PtxRenderer *r, const PtxLocalExposureDesc *desc)
+{
+    return localExposure(r, desc);
+}
+
+int ptx_read_local_exposure(PtxRenderer *r, void *host, size_t bytes)
+{
+    return readLocalExposure(r, host, bytes);
+}
+
+void *ptx_device_local_exposure_ptr(PtxRenderer *r)
+{
+    return r && r->output.localReady ? r->output.localGain.p : nullptr;
+}
+
+int ptx_postprocess_local(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode, uint32_t source, uint32_t metered)
+{
+    return postprocessLocal(r, u, toneMappingMode, source, metered);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

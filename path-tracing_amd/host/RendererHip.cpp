@@ -209,8 +209,16 @@ void RendererHip::OnUpdate(float timeStep)
     s_TimeStep += timeStep;
 }
 
+static RendererHip::LocalExposureSettings s_LocalExposureSettings;
+
+void RendererHip::SetSettings(const LocalExposureSettings &settings)
+{
+    s_LocalExposureSettings = settings;
+}
+
 // The output stage on the sum, on the despiked image or on the denoised one (PTX_METER_*).  With the ExposureSettings on (ptx.h,
-// "Exposure metering") that image is metered first, with the frame's time step, and the metered call multiplies the exposure in.
+// "Exposure metering") that image is metered first, with the frame's time step, and the metered call multiplies the exposure in;
+// with the LocalExposureSettings on as well, ptx_local_exposure follows the meter and ptx_postprocess_local takes the metered call's place.
 static int OutputStage(const PtxPostProcessingUniformData &u, uint32_t mode, uint32_t source)
 {
     if (!s_ExposureSettings.Enabled || s_DebugPipeline)
@@ -223,6 +231,15 @@ static int OutputStage(const PtxPostProcessingUniformData &u, uint32_t mode, uin
     if (const int rc = ptx_meter(s_Renderer, &meter))
         return rc;
     s_TimeStep = 0.0f; // a second SaveOutput or Present of the same frame meters with deltaSeconds = 0, which leaves the exposure where it is
+    if (s_LocalExposureSettings.Enabled) // behind the meter (ptx.h, "Local exposure"): the pivot is a display luminance, so the metered exposure comes off it
+    {
+        const RendererHip::LocalExposureSettings &l = s_LocalExposureSettings;
+        const PtxLocalExposureDesc local = { source, u.TotalSamples, l.CellShift, l.PivotLog2, l.HighlightContrast, l.ShadowContrast, l.MaxStops,
+                                             PTX_LOCAL_EXPOSURE_PIVOT_METERED, 0u };
+        if (const int rc = ptx_local_exposure(s_Renderer, &local))
+            return rc;
+        return ptx_postprocess_local(s_Renderer, &u, mode, source, 1u);
+    }
     return ptx_postprocess_metered(s_Renderer, &u, mode, source);
 }
 

@@ -142,6 +142,21 @@ public:
     // meters a frame, which adapts over them and uses them up: a second output call of the same frame, or every frame of a host that
     // never calls OnUpdate again, meters with deltaSeconds = 0 and leaves the exposure where it is.
     static void OnUpdate(float timeStep);
+    // Local exposure (ptx.h "Local exposure", docs/NEXT_ROWS.md section 23).  Enabled together with the ExposureSettings: behind the
+    // ptx_meter of the frame SaveOutput and Present call ptx_local_exposure on the same image with PTX_LOCAL_EXPOSURE_PIVOT_METERED, and
+    // ptx_postprocess_local (metered = 1) takes ptx_postprocess_metered's place.  Disabled (the default), or without the
+    // ExposureSettings: SaveOutput and Present enqueue exactly what they did.  The defaults are LOCAL_EXPOSURE_DEFAULTS of the Python
+    // package; nobody has tuned them.
+    struct LocalExposureSettings
+    {
+        bool Enabled = false;
+        uint32_t CellShift = 5;
+        float PivotLog2 = -2.473931f; // log2(0.18)
+        float HighlightContrast = 0.6f;
+        float ShadowContrast = 0.8f;
+        float MaxStops = 4.0f;
+    };
+    static void SetSettings(const LocalExposureSettings &settings);
     // Display transform (ptx.h "Display transform", docs/NEXT_ROWS.md section 22).  Enabled: ptx_grade follows whichever post-process
     // call SaveOutput and Present make -- with the same tone-mapping mode, so ptx_read_output returns the graded image -- and Present
     // calls ptx_present_graded in ptx_present's place.  Disabled (the default): both enqueue exactly what they did, and nothing is

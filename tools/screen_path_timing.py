@@ -37,7 +37,14 @@ the identity desc, each curve, a CDL grade with and without power, and a 33^3 LU
 ptx_postprocess and ptx_present of the same run beside them.  ptx_grade is one launch of k_compose_grade, which moves k_compose_tonemap's
 40 bytes per pixel; a kernel trace of `--grade --extent W H` gives both kernels' device times.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--extent W H]"""
+ptx_local_exposure and ptx_postprocess_local (section 23): --local times nothing but them, with ptx_meter, ptx_postprocess and
+ptx_postprocess_metered of the same run beside them, on the 8-spp chess_like sum and on a constant frame (every pixel of a cell in one
+slice: up to 2^cellShift lanes of a wave on one LDS address, all 64 at cellShift 6 -- the contention case of k_local_splat), at every
+cellShift.  ptx_local_exposure is given against 36 algorithmic bytes per pixel (16 B in for the splat, 16 B in and 4 B out for the
+gain; the grid is noise beside them at cellShift 5) -- a rate, not a bandwidth.  A kernel trace of `--local --extent W H` gives
+k_local_splat's, k_local_blur's, k_local_gain's and k_postprocess_local's device times.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--local] [--extent W H]"""
 import json
 import math
 import os
@@ -58,6 +65,7 @@ TEMPORAL_BYTES_PER_PIXEL = 176
 MOMENTS_BYTES_PER_PIXEL = 208
 RESPONSIVE_BYTES_PER_PIXEL = 240
 GRADE_BYTES_PER_PIXEL = 40  # 24 in (post-process image, bloom level 0), 16 out; the LUT's reads are cache hits
+LOCAL_EXPOSURE_BYTES_PER_PIXEL = 36  # the sum twice (splat, gain) and G out; the grid is 2 x 16 B x 32 slices per cell
 METER_BYTES_PER_PIXEL = 16  # one load of the pixel; the slabs (1 MB at the most) and the state are noise beside it
 # 16 B out and 16 B x (tile + halo) / tile in: the halo is 84 entries of 256 at radius 1 and 176 at radius 2
 DESPIKE_BYTES_PER_PIXEL = {1: 16 + 16 * (256 + 84) / 256, 2: 16 + 16 * (256 + 176) / 256}
@@ -83,8 +91,8 @@ def main():
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
     guides_only, temporal_only, meter_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv, "--meter" in sys.argv
-    grade_only = "--grade" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only else ("chess_like", "default") if guides_only else
+    grade_only, local_only = "--grade" in sys.argv, "--local" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only or local_only else ("chess_like", "default") if guides_only else
                                                           ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
@@ -131,6 +139,28 @@ def main():
                 t["algorithmic_GB_per_s"] = w * h * GRADE_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
                 rec[f"grade_{name}"] = t
                 rec[f"present_graded_own_size_{name}"] = timed(r, lambda: r.present_graded(w, h))
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
+        if local_only:
+            r.reset()
+            r.render_frames(u, scene.lights, 0, STEP_SPP)
+            frames = {"chess_like_8spp": None, "constant": np.full((h, w, 4), 0.18 * STEP_SPP, np.float32)}
+            for frame, image in frames.items():
+                if image is not None:
+                    r.write_accumulation(image)
+                rec[f"meter_average_{frame}"] = timed(r, lambda: r.meter(STEP_SPP, delta_seconds=1.0 / 60))
+                rec[f"postprocess_{frame}"] = timed(r, lambda: r.postprocess(STEP_SPP, **POST))
+                rec[f"postprocess_metered_{frame}"] = timed(r, lambda: r.postprocess_metered(STEP_SPP, **POST))
+                for shift in (3, 4, 5, 6):
+                    t = timed(r, lambda: r.local_exposure(STEP_SPP, cell_shift=shift, pivot_metered=True))
+                    t["algorithmic_GB_per_s"] = w * h * LOCAL_EXPOSURE_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
+                    rec[f"local_exposure_shift_{shift}_{frame}"] = t
+                r.local_exposure(STEP_SPP, pivot_metered=True)  # the package's defaults: cellShift 5
+                G = r.read_local_exposure()
+                rec[f"local_exposure_result_{frame}"] = {"min_gain": float(G.min()), "max_gain": float(G.max()), "exposure": r.read_meter().exposure}
+                rec[f"postprocess_local_{frame}"] = timed(r, lambda: r.postprocess_local(STEP_SPP, metered=True, **POST))
             out[f"{w}x{h}"] = rec
             for k, v in rec.items():
                 print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
