@@ -1,10 +1,11 @@
 // pt_chain_host.hpp -- host side of the interactive chain, the stages on the render stream between ptx_render and the output stage:
 // the guide pass (plain, with motion guides, following specular chains), the temporal accumulation (plain, with moments, through the
 // motion guides, responsive), the three filters (on the accumulation image, on T, variance-guided on T) and their read-backs, and the firefly
-// suppression in front of them (ptx_despike, the switch that puts its image in the sum's place, its output call).  Kernels: pt_denoise.hpp, pt_temporal.hpp,
+// suppression in front of them (ptx_despike, the switch that puts its image in the sum's place).  The output calls on C and D are the output stage's
+// (pt_output_host.hpp).  Kernels: pt_denoise.hpp, pt_temporal.hpp,
 // pt_variance.hpp, pt_responsive.hpp, pt_despike.hpp; semantics: include/ptx.h, docs/NEXT_ROWS.md sections 13, 14 and 16 - 20; state: ChainState, the member `chain` of
 // the handle, whose bookkeeping (pt_chain_state.hpp) is told of every accepted call.  Included by pt_runtime.hpp after
-// pt_output_host.hpp (postprocessImage); every function takes a valid or null handle and returns a PTX_* code.
+// pt_frame_host.hpp; every function takes a valid or null handle and returns a PTX_* code.
 #pragma once
 
 // What every stage behind the guide pass needs, in the order it is reported.  `taps`: whose taps cross tiles, "filter" or "history";
@@ -445,18 +446,6 @@ static int readVariance(PtxRenderer *r, void *host, size_t bytes)
     return readFrameImage(r, r->chain.varianceImage.p, host, bytes, sizeof(float), "ptx_read_variance");
 }
 
-// ptx_postprocess's chain on the denoised image, which holds the mean: TotalSamples = 1
-static int postprocessDenoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
-{
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess_denoised: bad argument");
-    if (!r->chain.denoised())
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess_denoised: call ptx_denoise first");
-    PtxPostProcessingUniformData u = *uniform;
-    u.TotalSamples = 1u;
-    return postprocessImage(r, r->chain.denoised(), &u, toneMappingMode);
-}
-
 // ---- firefly suppression (docs/NEXT_ROWS.md section 20) ------------------------------------------------------------------------------
 
 // ptx_despike: C from the sum as it stands, one launch.  No scene and no guides: the ladder is the image's own.
@@ -512,14 +501,4 @@ static int chainUseDespiked(PtxRenderer *r, int enable)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_chain_use_despiked: null argument");
     r->chain.status.useDespiked = enable != 0;
     return PTX_OK;
-}
-
-// ptx_postprocess's chain on C, which is in the sum's scale: the caller's TotalSamples
-static int postprocessDespiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
-{
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess_despiked: bad argument");
-    if (!r->chain.despiked())
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess_despiked: call ptx_despike first");
-    return postprocessImage(r, r->chain.despiked(), uniform, toneMappingMode);
 }

@@ -2,7 +2,7 @@
 // ptx_set_tile_shard, ptx_reset_accumulation, the two bindings of the accumulation image, the blocking and the pipelined read-back,
 // and the tile-shard message of a multi-GPU frame (pack, unpack, gather).  Kernels: pt_wavefront.hpp (k_copy_out, k_pack_shard,
 // k_unpack_shard, k_gather_frame); shard geometry: pt_shard_layout.hpp; state: FrameState, the member `frame` of the handle.
-// Included by pt_runtime.hpp after pt_render_host.hpp (collectRender); every function takes a valid or null handle and returns a
+// Included by pt_runtime.hpp after pt_render_host.hpp (collectRender) and pt_output_host.hpp (outputResized); every function takes a valid or null handle and returns a
 // PTX_* code.
 #pragma once
 
@@ -15,8 +15,6 @@ static int resetAccumulation(PtxRenderer *r)
     return PTX_OK;
 }
 
-static int meterReset(PtxRenderer *r); // pt_output_host.hpp
-
 static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
 {
     if (!r || !width || !height || (uint64_t)width * height > 0x7fffffffull)
@@ -25,12 +23,10 @@ static int resizeFrame(PtxRenderer *r, uint32_t width, uint32_t height)
     r->frame.width = width;
     r->frame.height = height;
     r->frame.unbind();
-    r->output.invalidate();
     r->chain.invalidate(); // guides, D, T, the histories, V_0 and the motion guides belong to the extent they were made for
-    r->output.dropLocalExposure(); // ... and so do G and the grid of ptx_local_exposure
-    HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
-    if (const int rc = meterReset(r)) // the exposure was metered on an image of the old extent
+    if (const int rc = outputResized(r)) // ... and so does what the output stage keeps per extent
         return rc;
+    HIP_TRY(r, r->frame.image.alloc(r->frame.pixels()));
     return resetAccumulation(r);
 }
 

@@ -2,9 +2,10 @@
 // a colour matrix, an ASC CDL grade, one of four tone curves and a tetrahedral 3-D LUT in the place of the output stage's last step.
 //
 //   k_compose_grade        k_compose_tonemap with gradePixel where toneMapPixel stands: 24 B in, 16 B out per pixel, grid-stride.
-//   k_present_graded<F, H> k_present with gradePixel where toneMapPixel stands.  The body is k_present's, restated and not shared, as
-//                          k_postprocess_metered restates k_postprocess: k_present and PresentArgs stay as they were, to the
-//                          instruction.  tests/test_grade.py holds the two together: under an identity desc they give the same bits.
+//   k_present_graded<F, H> k_present with gradePixel where toneMapPixel stands.
+// Both bodies are the older kernels' own, composeStore (pt_post.hpp) and presentPixel (pt_present.hpp), which take the step between the
+// composed colour and the UI as a functor: Grade here.  Those two files know nothing of the grade.  tests/test_grade.py holds each
+// pair together: under an identity desc the two kernels give the same bits.
 //
 // Which steps run is decided on the host (the skip rule of the header) and arrives as bits of GradeArgs::steps, a kernel argument:
 // every branch on it is a scalar branch, and a wave never diverges on the grade.  The four curves share one kernel; the registers
@@ -159,62 +160,24 @@ PT_DEV f3 gradePixel(f3 c, const GradeArgs &g)
     return f16Round(c);
 }
 
+// the tone step of composeStore (pt_post.hpp) and presentPixel (pt_present.hpp): gradePixel rounds by itself
+struct Grade
+{
+    const GradeArgs &g;
+    PT_DEV f3 operator()(f3 c) const { return gradePixel(c, g); }
+};
+
 __global__ void k_compose_grade(const float *__restrict__ post, const float *__restrict__ bloom0, uint32_t n, PtxPostProcessingUniformData u, GradeArgs g,
                                 float4 *__restrict__ out)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    {
-        const f3 pp = F3(post[3 * (size_t)i], post[3 * (size_t)i + 1], post[3 * (size_t)i + 2]);
-        const f3 bl = F3(bloom0[3 * (size_t)i], bloom0[3 * (size_t)i + 1], bloom0[3 * (size_t)i + 2]);
-        const f3 c = f16Round(compositionPixel(pp, bl, u));
-        const f3 t = gradePixel(c, g);
-        out[i] = make_float4(t.x, t.y, t.z, 1.0f);
-    }
+        composeStore(post, bloom0, i, u, Grade{ g }, out);
 }
 
+// the blit's store is step 0; the host leaves the curve and the LUT out of g.steps in the HDR mode
 template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentBlock) k_present_graded(PresentArgs a, GradeArgs g)
 {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // SW * SH <= 2^28
-    if (p >= a.SW * a.SH)
-        return;
-    const uint32_t sx = p % a.SW, sy = p / a.SW;
-    const bool filterX = a.SW != a.W, filterY = a.SH != a.H;
-    uint32_t ix0 = sx, ix1 = sx, iy0 = sy, iy1 = sy;
-    float ax = 0.0f, ay = 0.0f;
-    if (filterX)
-        presentAxis(sx, a.W, a.SW, ix0, ix1, ax);
-    if (filterY)
-        presentAxis(sy, a.H, a.SH, iy0, iy1, ay);
-    f3 c = presentRow(a, filterX, ix0, ix1, ax, iy0);
-    if (filterY)
-    {
-        const f3 bot = presentRow(a, filterX, ix0, ix1, ax, iy1);
-        c = c * (1.0f - ay) + bot * ay;
-    }
-    c = f16Round(c);     // ScreenImage after the blit: step 0
-    c = gradePixel(c, g); // steps 1 - 5; the host leaves the curve and the LUT out of g.steps in the HDR mode
-    if (a.ui)            // uiComposition.comp:53-62
-    {
-        const uint32_t t = a.ui[p];
-        if (t >> 24)
-        {
-            const f3 ui = F3(uiSrgbToLinear(div_((float)(t & 255u), 255.0f)), uiSrgbToLinear(div_((float)((t >> 8) & 255u), 255.0f)),
-                             uiSrgbToLinear(div_((float)((t >> 16) & 255u), 255.0f)));
-            c = ui * 0.99f + c * 0.01f;
-        }
-    }
-    if (HDR)
-        c = linearToHdr10(c, 203.0f);
-    c = f16Round(c);
-    if (FORMAT == PTX_PRESENT_R16G16B16A16_SFLOAT)
-        static_cast<uint2 *>(a.out)[p] = make_uint2(f16Bits(c.x) | f16Bits(c.y) << 16, f16Bits(c.z) | 0x3c00u << 16);
-    else if (FORMAT == PTX_PRESENT_A2B10G10R10_UNORM)
-        static_cast<uint32_t *>(a.out)[p] = quantize10(c.x) | quantize10(c.y) << 10 | quantize10(c.z) << 20 | 3u << 30;
-    else
-    {
-        const uint32_t r8 = quantize8(linearToSrgb(c.x)), g8 = quantize8(linearToSrgb(c.y)), b8 = quantize8(linearToSrgb(c.z));
-        static_cast<uint32_t *>(a.out)[p] = FORMAT == PTX_PRESENT_B8G8R8A8_SRGB ? (b8 | g8 << 8 | r8 << 16 | 255u << 24) : (r8 | g8 << 8 | b8 << 16 | 255u << 24);
-    }
+    presentPixel<FORMAT, HDR>(a, Grade{ g });
 }
 
 } // namespace ptd

@@ -1,69 +1,158 @@
-// pt_output_host.hpp -- the output stage (ptx_postprocess, ptx_read_output: row N4) and the screen path (ptx_present, ptx_read_present:
-// row D15; docs/NEXT_ROWS.md section 12), and the exposure metering in front of them (ptx_meter, ptx_read_meter, ptx_meter_reset,
-// ptx_postprocess_metered: section 21), and the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded: section 22),
-// which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and the local
-// exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23).
+// pt_output_host.hpp -- the output stage (ptx_postprocess and its calls on C and D, ptx_read_output: row N4) and the screen path
+// (ptx_present, ptx_read_present: row D15; docs/NEXT_ROWS.md section 12), the exposure metering in front of them (ptx_meter, ptx_read_meter,
+// ptx_meter_reset, ptx_postprocess_metered: section 21), the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded:
+// section 22), which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and
+// the local exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23).
+// What the entry points share stands first: the source rule, the refusal ladder, the read-back's end, ptx_resize's part (section 24).
 // Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp; state: OutputState, the member `output` of the handle.
-// Included by pt_runtime.hpp ahead of pt_chain_host.hpp, whose ptx_postprocess_denoised runs postprocessImage on the denoised image.
+// Included by pt_runtime.hpp ahead of pt_frame_host.hpp, whose ptx_resize ends in outputResized; every function takes a valid or null
+// handle and returns a PTX_* code.
 #pragma once
+
+static bool finiteFloat(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; } // a NaN fails both
+
+// The source rule: the image a PTX_METER_* source names, as the output call of that source reads it (null: it does not exist for this
+// extent), and the sample count its values are divided by.  The sum and C are running sums of the caller's count; D holds the mean.
+struct OutputSource
+{
+    const float4 *image;
+    uint32_t totalSamples;
+};
+static OutputSource outputSource(const PtxRenderer *r, uint32_t source, uint32_t totalSamples)
+{
+    if (source == PTX_METER_SUM)
+        return { imagePtr(r), totalSamples };
+    if (source == PTX_METER_DESPIKED)
+        return { r->chain.despiked(), totalSamples };
+    return { r->chain.denoised(), 1u };
+}
+
+// What an entry point needs before its first allocation or launch, in the order it is reported (chainRefusal is the chain's)
+enum : uint32_t
+{
+    NEEDS_OUTPUT = 1u,        // an accepted output call since the last ptx_resize / ptx_render_debug
+    NEEDS_FRAME = 2u,         // the accumulation image, and in this renderer: no shard buffer bound
+    NEEDS_ONE_SHARD = 4u,     // ... the whole frame, not one tile shard of several
+    NEEDS_SOURCE = 8u,        // the image of `source`, in the words of an output call
+    NEEDS_SOURCE_IMAGE = 16u, // ... or in those of ptx_meter and ptx_local_exposure
+    NEEDS_METER = 32u,        // an accepted ptx_meter on this handle
+    NEEDS_GAIN = 64u          // G: an accepted ptx_local_exposure since the last ptx_resize
+};
+static int outputRefusal(PtxRenderer *r, const char *who, uint32_t needs, uint32_t source = PTX_METER_SUM)
+{
+    if ((needs & NEEDS_OUTPUT) && !r->output.ready)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_postprocess first", who);
+    if ((needs & NEEDS_FRAME) && !imagePtr(r))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
+    if ((needs & NEEDS_FRAME) && r->frame.boundShard)
+        return frameIsElsewhere(r, who);
+    if ((needs & NEEDS_ONE_SHARD) && r->frame.shard.worldSize > 1u)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
+    if ((needs & (NEEDS_SOURCE | NEEDS_SOURCE_IMAGE)) && !outputSource(r, source, 1u).image)
+    {
+        const bool c = source == PTX_METER_DESPIKED;
+        if (needs & NEEDS_SOURCE)
+            return fail(r, PTX_ERROR_NOT_READY, "%s: call %s first", who, c ? "ptx_despike" : "ptx_denoise");
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no %s image for this extent (call %s first)", who, c ? "despiked" : "denoised", c ? "ptx_despike" : "ptx_denoise");
+    }
+    if ((needs & NEEDS_METER) && !r->output.meterState.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_meter first", who);
+    if ((needs & NEEDS_GAIN) && !r->output.localReady)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_local_exposure first", who);
+    return PTX_OK;
+}
+
+// the end of every synchronous read-back of this file: the last copy on the render stream, the wait, and what the launches left
+static int readBack(PtxRenderer *r, void *host, const void *device, size_t bytes)
+{
+    HIP_TRY(r, hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
+    return PTX_OK;
+}
+
+// The bloom chain's levels for a W x H frame, laid end to end from `base` (null: the extents and the size alone).  Mips 0 .. maxMipLevel - 1
+// take part, maxMipLevel = min(levels - 3, MaxBloomMipmapLevel) (Renderer.cpp:955-956).
+struct BloomPlan
+{
+    BloomLevel level[13];
+    uint32_t used;
+    size_t floats; // of the whole chain
+};
+static BloomPlan bloomPlan(uint32_t W, uint32_t H, float *base)
+{
+    uint32_t levels = 1;
+    for (uint32_t m = W > H ? W : H; m > 1; m >>= 1)
+        levels++;
+    BloomPlan b;
+    b.used = levels >= 5 ? (levels - 3 < 12 ? levels - 3 : 12) : 1;
+    b.floats = 0;
+    for (uint32_t l = 0; l < b.used; l++)
+    {
+        b.level[l].w = (W >> l) ? (W >> l) : 1;
+        b.level[l].h = (H >> l) ? (H >> l) : 1;
+        b.level[l].rgb = base ? base + b.floats : nullptr;
+        b.floats += (size_t)b.level[l].w * b.level[l].h * 3;
+    }
+    return b;
+}
 
 // Renderer::RecordPostProcessCommands + RecordSaveOutputCommands (Renderer.cpp:928-1085, :1204-1246)
 // the chain on `source` (width x height running sums of uniform->TotalSamples samples): the accumulation image, or the denoised mean
 // meterExposure: the device address of the metered exposure that ptx_postprocess_metered multiplies in (k_postprocess_metered), or none
 // localGain: G of ptx_local_exposure, which ptx_postprocess_local multiplies in per pixel (k_postprocess_local), or none
 static int postprocessImage(PtxRenderer *r, const float4 *source, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode,
-                            const float *meterExposure = nullptr, const float *localGain = nullptr)
+                            const float *meterExposure, const float *localGain)
 {
     HIP_TRY(r, hipSetDevice(r->device));
+    OutputState &o = r->output;
     const uint32_t W = r->frame.width, H = r->frame.height, n = W * H;
-    uint32_t levels = 1;
-    for (uint32_t m = W > H ? W : H; m > 1; m >>= 1)
-        levels++;
-    // mips 0 .. maxMipLevel-1 take part, maxMipLevel = min(levels - 3, MaxBloomMipmapLevel) (Renderer.cpp:955-956)
-    uint32_t used = levels >= 5 ? (levels - 3 < 12 ? levels - 3 : 12) : 1;
-    BloomLevel L[13];
-    size_t total = 0;
-    for (uint32_t l = 0; l < used; l++)
-    {
-        L[l].w = (W >> l) ? (W >> l) : 1;
-        L[l].h = (H >> l) ? (H >> l) : 1;
-        total += (size_t)L[l].w * L[l].h * 3;
-    }
-    HIP_TRY(r, r->output.postRgb.alloc((size_t)n * 3));
-    HIP_TRY(r, r->output.bloomRgb.alloc(total));
-    HIP_TRY(r, r->output.outLinear.alloc(n));
-    size_t off = 0;
-    for (uint32_t l = 0; l < used; l++)
-    {
-        L[l].rgb = r->output.bloomRgb.p + off;
-        off += (size_t)L[l].w * L[l].h * 3;
-    }
+    HIP_TRY(r, o.postRgb.alloc((size_t)n * 3));
+    HIP_TRY(r, o.bloomRgb.alloc(bloomPlan(W, H, nullptr).floats));
+    HIP_TRY(r, o.outLinear.alloc(n));
+    const BloomPlan b = bloomPlan(W, H, o.bloomRgb.p);
+    const BloomLevel *L = b.level;
     if (localGain)
-        k_postprocess_local<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, localGain, r->output.postRgb.p, L[0].rgb);
+        k_postprocess_local<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, localGain, o.postRgb.p, L[0].rgb);
     else if (meterExposure)
-        k_postprocess_metered<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, r->output.postRgb.p, L[0].rgb);
+        k_postprocess_metered<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, meterExposure, o.postRgb.p, L[0].rgb);
     else
-        k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, r->output.postRgb.p, L[0].rgb);
-    for (uint32_t i = 0; i + 1 < used; i++)
+        k_postprocess<<<gridFor(n), kBlock, 0, r->stream>>>(source, n, *uniform, o.postRgb.p, L[0].rgb);
+    for (uint32_t i = 0; i + 1 < b.used; i++)
         k_bloom_downsample<<<gridFor((size_t)L[i + 1].w * L[i + 1].h), kBlock, 0, r->stream>>>(L[i], L[i + 1]);
-    for (uint32_t i = used - 1; i > 0; i--)
+    for (uint32_t i = b.used - 1; i > 0; i--)
         k_bloom_upsample<<<gridFor((size_t)L[i - 1].w * L[i - 1].h), kBlock, 0, r->stream>>>(L[i], L[i - 1]);
-    k_compose_tonemap<<<gridFor(n), kBlock, 0, r->stream>>>(r->output.postRgb.p, L[0].rgb, n, *uniform, toneMappingMode, r->output.outLinear.p);
+    k_compose_tonemap<<<gridFor(n), kBlock, 0, r->stream>>>(o.postRgb.p, L[0].rgb, n, *uniform, toneMappingMode, o.outLinear.p);
     HIP_TRY(r, hipGetLastError());
-    r->output.postUniform = *uniform;
-    r->output.ready = true;
+    o.postUniform = *uniform;
+    o.ready = true;
     return PTX_OK;
 }
 
-static int postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
+// The five output calls are one: the chain on the image of `source`, which is all the plain call of that source needs (ptx_postprocess
+// the sum in this renderer, ptx_postprocess_despiked C, ptx_postprocess_denoised D), with the metered exposure multiplied in on the
+// device (`metered`: ptx_postprocess_metered) and G per pixel, Exposure = (uniform->Exposure x m) x G(p) (`local`: ptx_postprocess_local;
+// G covers the frame, a shard's image does not)
+static int postprocessSource(PtxRenderer *r, const char *who, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source,
+                             bool metered = false, bool local = false)
 {
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess: bad argument");
-    if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_postprocess: no accumulation image (call ptx_resize)");
-    if (r->frame.boundShard)
-        return frameIsElsewhere(r, "ptx_postprocess");
-    return postprocessImage(r, imagePtr(r), uniform, toneMappingMode);
+    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR || source > PTX_METER_DENOISED)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad argument", who);
+    const uint32_t needs = (source == PTX_METER_SUM ? NEEDS_FRAME : NEEDS_SOURCE) | (metered ? NEEDS_METER : 0u) | (local ? NEEDS_ONE_SHARD | NEEDS_GAIN : 0u);
+    if (const int rc = outputRefusal(r, who, needs, source))
+        return rc;
+    const OutputSource s = outputSource(r, source, uniform->TotalSamples);
+    PtxPostProcessingUniformData u = *uniform;
+    u.TotalSamples = s.totalSamples;
+    return postprocessImage(r, s.image, &u, toneMappingMode, metered ? &r->output.meterState.p->result.exposure : nullptr,
+                            local ? r->output.localGain.p : nullptr);
+}
+
+static int postprocessLocal(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source, uint32_t metered)
+{
+    if (metered > 1u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_postprocess_local: bad argument");
+    return postprocessSource(r, "ptx_postprocess_local", uniform, toneMappingMode, source, metered != 0u, true);
 }
 
 // OutputSaver: blit of the tone-mapped image into its output image + readback (OutputSaver.cpp:64-86, :120-199)
@@ -71,24 +160,30 @@ static int readOutput(PtxRenderer *r, uint32_t outputFormat, void *host, size_t 
 {
     if (!r || !host || outputFormat > PTX_OUTPUT_RGBA32F)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_output: bad argument");
-    if (!r->output.ready)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_output: call ptx_postprocess first");
+    if (const int rc = outputRefusal(r, "ptx_read_output", NEEDS_OUTPUT))
+        return rc;
     const uint32_t n = r->frame.width * r->frame.height;
     const size_t want = (size_t)n * (outputFormat == PTX_OUTPUT_RGBA32F ? 16 : 4);
     if (bytes != want)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_output: buffer must be %zu bytes", want);
     HIP_TRY(r, hipSetDevice(r->device));
     if (outputFormat == PTX_OUTPUT_RGBA32F)
-        HIP_TRY(r, hipMemcpyAsync(host, r->output.outLinear.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    else
+        return readBack(r, host, r->output.outLinear.p, bytes);
+    HIP_TRY(r, r->output.outSrgb8.alloc(n));
+    k_encode_srgb8<<<gridFor(n), kBlock, 0, r->stream>>>(r->output.outLinear.p, n, r->output.outSrgb8.p);
+    return readBack(r, host, r->output.outSrgb8.p, bytes);
+}
+
+// the five (surface format, HDR) pairs presentFrame lets through, as compile-time constants: f(format, hdr)
+template <typename F> static void withPresentFormat(uint32_t format, bool hdr, F &&f)
+{
+    switch (format)
     {
-        HIP_TRY(r, r->output.outSrgb8.alloc(n));
-        k_encode_srgb8<<<gridFor(n), kBlock, 0, r->stream>>>(r->output.outLinear.p, n, r->output.outSrgb8.p);
-        HIP_TRY(r, hipMemcpyAsync(host, r->output.outSrgb8.p, bytes, hipMemcpyDeviceToHost, r->stream));
+    case PTX_PRESENT_R8G8B8A8_SRGB: f(std::integral_constant<uint32_t, PTX_PRESENT_R8G8B8A8_SRGB>(), std::false_type()); break;
+    case PTX_PRESENT_B8G8R8A8_SRGB: f(std::integral_constant<uint32_t, PTX_PRESENT_B8G8R8A8_SRGB>(), std::false_type()); break;
+    case PTX_PRESENT_A2B10G10R10_UNORM: f(std::integral_constant<uint32_t, PTX_PRESENT_A2B10G10R10_UNORM>(), std::true_type()); break;
+    default: withFlag(hdr, [&](auto Hdr) { f(std::integral_constant<uint32_t, PTX_PRESENT_R16G16B16A16_SFLOAT>(), Hdr); });
     }
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
 }
 
 static GradeArgs gradeArgs(const PtxRenderer *r, const PtxGradeDesc &d, bool hdr); // below: the display transform
@@ -106,80 +201,50 @@ static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who
     const bool hdr = d->toneMappingMode == PTX_TONE_MAPPING_HDR;
     if ((hdr && d->format <= PTX_PRESENT_B8G8R8A8_SRGB) || (!hdr && d->format == PTX_PRESENT_A2B10G10R10_UNORM))
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)", who);
-    if (!r->output.ready)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_postprocess first", who);
-    if (r->frame.boundShard)
-        return frameIsElsewhere(r, who);
-    if (graded)
-    {
-        if (r->frame.shard.worldSize > 1u)
-            return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
-        if (!r->output.gradeSet)
-            return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_grade first", who);
-        if ((r->output.gradeDesc.flags & PTX_GRADE_USE_LUT) && !r->output.gradeLut.p)
-            return fail(r, PTX_ERROR_NOT_READY, "%s: the kept desc uses a LUT and the LUT has been cleared (ptx_grade_lut)", who);
-    }
+    if (const int rc = outputRefusal(r, who, NEEDS_OUTPUT | NEEDS_FRAME | (graded ? NEEDS_ONE_SHARD : 0u)))
+        return rc;
+    OutputState &o = r->output;
+    if (graded && !o.gradeSet)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_grade first", who);
+    if (graded && (o.gradeDesc.flags & PTX_GRADE_USE_LUT) && !o.gradeLut.p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: the kept desc uses a LUT and the LUT has been cleared (ptx_grade_lut)", who);
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t n = d->width * d->height;
     const size_t words = (size_t)n * (d->format == PTX_PRESENT_R16G16B16A16_SFLOAT ? 2 : 1);
-    if (words > r->output.presentImage.n || !r->output.presentImage.p) // a failed allocation keeps the previous image
+    if (words > o.presentImage.n || !o.presentImage.p) // a failed allocation keeps the previous image
     {
         DevBuf<uint32_t> grown;
         HIP_TRY(r, grown.alloc(words));
-        r->output.presentImage.swap(grown);
+        o.presentImage.swap(grown);
     }
     PresentArgs a;
-    a.post = r->output.postRgb.p;
-    a.bloom0 = r->output.bloomRgb.p; // level 0 of the chain
+    a.post = o.postRgb.p;
+    a.bloom0 = o.bloomRgb.p; // level 0 of the chain
     a.ui = static_cast<const uint32_t *>(d->ui);
-    a.out = r->output.presentImage.p;
-    a.u = r->output.postUniform;
+    a.out = o.presentImage.p;
+    a.u = o.postUniform;
     a.W = r->frame.width; a.H = r->frame.height; a.SW = d->width; a.SH = d->height;
     if (d->ui && !(d->flags & PTX_PRESENT_UI_ON_DEVICE))
     {
-        HIP_TRY(r, r->output.presentUi.alloc(n));
-        HIP_TRY(r, hipMemcpyAsync(r->output.presentUi.p, d->ui, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
-        a.ui = r->output.presentUi.p;
+        HIP_TRY(r, o.presentUi.alloc(n));
+        HIP_TRY(r, hipMemcpyAsync(o.presentUi.p, d->ui, (size_t)n * 4, hipMemcpyHostToDevice, r->stream));
+        a.ui = o.presentUi.p;
     }
     const uint32_t grid = (n + kPresentBlock - 1) / kPresentBlock;
-    if (graded)
-    {
-        const GradeArgs g = gradeArgs(r, r->output.gradeDesc, hdr);
-        switch (d->format)
-        {
-        case PTX_PRESENT_R8G8B8A8_SRGB: k_present_graded<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
-        case PTX_PRESENT_B8G8R8A8_SRGB: k_present_graded<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
-        case PTX_PRESENT_A2B10G10R10_UNORM: k_present_graded<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a, g); break;
-        default:
-            if (hdr)
-                k_present_graded<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a, g);
-            else
-                k_present_graded<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a, g);
-        }
-    }
-    else
-        switch (d->format)
-        {
-        case PTX_PRESENT_R8G8B8A8_SRGB: k_present<PTX_PRESENT_R8G8B8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-        case PTX_PRESENT_B8G8R8A8_SRGB: k_present<PTX_PRESENT_B8G8R8A8_SRGB, false><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-        case PTX_PRESENT_A2B10G10R10_UNORM: k_present<PTX_PRESENT_A2B10G10R10_UNORM, true><<<grid, kPresentBlock, 0, r->stream>>>(a); break;
-        default:
-            if (hdr)
-                k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, true><<<grid, kPresentBlock, 0, r->stream>>>(a);
-            else
-                k_present<PTX_PRESENT_R16G16B16A16_SFLOAT, false><<<grid, kPresentBlock, 0, r->stream>>>(a);
-        }
+    withPresentFormat(d->format, hdr, [&](auto Format, auto Hdr) {
+        constexpr uint32_t format = decltype(Format)::value;
+        constexpr bool isHdr = decltype(Hdr)::value;
+        if (graded)
+            k_present_graded<format, isHdr><<<grid, kPresentBlock, 0, r->stream>>>(a, gradeArgs(r, o.gradeDesc, hdr));
+        else
+            k_present<format, isHdr><<<grid, kPresentBlock, 0, r->stream>>>(a);
+    });
     HIP_TRY(r, hipGetLastError());
-    r->output.presentWidth = d->width;
-    r->output.presentHeight = d->height;
-    r->output.presentFormat = d->format;
-    r->output.presentBytes = words * 4;
+    o.presentWidth = d->width;
+    o.presentHeight = d->height;
+    o.presentFormat = d->format;
+    o.presentBytes = words * 4;
     return PTX_OK;
-}
-
-static int present(PtxRenderer *r, const PtxPresentDesc *d)
-{
-    return presentFrame(r, d, "ptx_present", false);
 }
 
 static int readPresent(PtxRenderer *r, void *host, size_t bytes)
@@ -191,19 +256,10 @@ static int readPresent(PtxRenderer *r, void *host, size_t bytes)
     if (bytes != r->output.presentBytes)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_present: buffer must be %zu bytes", r->output.presentBytes);
     HIP_TRY(r, hipSetDevice(r->device));
-    HIP_TRY(r, hipMemcpyAsync(host, r->output.presentImage.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
+    return readBack(r, host, r->output.presentImage.p, bytes);
 }
 
 // ---- exposure metering (docs/NEXT_ROWS.md section 21; semantics: include/ptx.h ptx_meter; kernels: pt_meter.hpp) --------------------
-
-// the image a PTX_METER_* source names, as the output call of that source reads it (nullptr: it does not exist for this extent)
-static const float4 *meterSource(const PtxRenderer *r, uint32_t source)
-{
-    return source == PTX_METER_SUM ? imagePtr(r) : source == PTX_METER_DESPIKED ? r->chain.despiked() : r->chain.denoised();
-}
 
 // ptx_meter_reset, and ptx_resize's part in it: nothing to do while no ptx_meter has made a state
 static int meterReset(PtxRenderer *r)
@@ -224,24 +280,22 @@ static int meter(PtxRenderer *r, const PtxMeterDesc *d)
     const char *who = "ptx_meter";
     if (!r || !d)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
-    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
     if (d->source > PTX_METER_DENOISED || d->mode > PTX_METER_REGION || !d->totalSamples || (uint64_t)d->lowPermille + d->highPermille >= 1000u ||
         d->flags != 0u || d->reserved != 0u)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need source <= 2 (%u), mode <= 2 (%u), totalSamples > 0 (%u), lowPermille + highPermille < 1000 "
                     "(%u + %u), flags 0 (0x%x) and reserved 0 (%u)", who, d->source, d->mode, d->totalSamples, d->lowPermille, d->highPermille, d->flags, d->reserved);
-    if (!finite(d->keyLog2) || !finite(d->compensation) || !finite(d->minLog2Exposure) || !finite(d->maxLog2Exposure) || !finite(d->speedUp) ||
-        !finite(d->speedDown) || !finite(d->deltaSeconds) || d->minLog2Exposure > d->maxLog2Exposure || d->speedUp < 0.0f || d->speedDown < 0.0f ||
-        d->deltaSeconds < 0.0f)
+    if (!finiteFloat(d->keyLog2) || !finiteFloat(d->compensation) || !finiteFloat(d->minLog2Exposure) || !finiteFloat(d->maxLog2Exposure) ||
+        !finiteFloat(d->speedUp) || !finiteFloat(d->speedDown) || !finiteFloat(d->deltaSeconds) || d->minLog2Exposure > d->maxLog2Exposure || d->speedUp < 0.0f ||
+        d->speedDown < 0.0f || d->deltaSeconds < 0.0f)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need finite keyLog2 (%g) and compensation (%g), finite minLog2Exposure <= maxLog2Exposure (%g, %g), "
                     "finite speedUp, speedDown and deltaSeconds >= 0 (%g, %g, %g)", who, (double)d->keyLog2, (double)d->compensation, (double)d->minLog2Exposure,
                     (double)d->maxLog2Exposure, (double)d->speedUp, (double)d->speedDown, (double)d->deltaSeconds);
-    if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
-    if (r->frame.boundShard)
-        return frameIsElsewhere(r, who);
-    if (r->frame.shard.worldSize > 1u)
+    if (const int rc = outputRefusal(r, who, NEEDS_FRAME))
+        return rc;
+    if (r->frame.shard.worldSize > 1u) // the ladder's rung, with the way out
         return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u; sum the bins of ptx_read_meter across ranks on the host", who,
                     r->frame.shard.worldSize);
+    // the header puts the checks against the extent between the frame's rungs and the source's
     const uint32_t W = r->frame.width, H = r->frame.height;
     const uint32_t *g = d->region;
     if (d->mode == PTX_METER_REGION && (g[0] >= g[1] || g[2] >= g[3] || g[1] > W || g[3] > H))
@@ -251,10 +305,9 @@ static int meter(PtxRenderer *r, const PtxMeterDesc *d)
     if (total >= (1ull << 32))
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the weights of a %u x %u image can sum to %llu, which a 32-bit counter does not hold", who, W, H,
                     (unsigned long long)total);
-    const float4 *source = meterSource(r, d->source);
-    if (!source)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: no %s image for this extent (call %s first)", who, d->source == PTX_METER_DESPIKED ? "despiked" : "denoised",
-                    d->source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    if (const int rc = outputRefusal(r, who, NEEDS_SOURCE_IMAGE, d->source))
+        return rc;
+    const OutputSource s = outputSource(r, d->source, d->totalSamples);
     HIP_TRY(r, hipSetDevice(r->device));
     OutputState &o = r->output;
     HIP_TRY(r, o.meterSlabs.alloc((size_t)kMeterGridCap * kMeterSlabWords));
@@ -264,12 +317,12 @@ static int meter(PtxRenderer *r, const PtxMeterDesc *d)
         k_meter_reset<<<1, kMeterBlock, 0, r->stream>>>(o.meterState.p);
     }
     MeterArgs a;
-    a.source = source;
+    a.source = s.image;
     a.slabs = o.meterSlabs.p;
     a.n = W * H;
     a.width = W;
     a.height = H;
-    a.totalSamples = d->source == PTX_METER_DENOISED ? 1.0f : (float)d->totalSamples; // ptx_postprocess_denoised: D holds the mean
+    a.totalSamples = (float)s.totalSamples;
     a.x0 = g[0]; a.x1 = g[1]; a.y0 = g[2]; a.y1 = g[3];
     const uint32_t grid = gridFor(a.n, kMeterBlock, kMeterGridCap);
     switch (d->mode)
@@ -300,40 +353,14 @@ static int readMeter(PtxRenderer *r, PtxMeterResult *out, uint32_t *bins256)
 {
     if (!r || !out)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_meter: null argument");
-    if (!r->output.meterState.p)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_meter: call ptx_meter first");
+    if (const int rc = outputRefusal(r, "ptx_read_meter", NEEDS_METER))
+        return rc;
     HIP_TRY(r, hipSetDevice(r->device));
     const MeterState *st = r->output.meterState.p;
+    if (!bins256)
+        return readBack(r, out, &st->result, sizeof(PtxMeterResult));
     HIP_TRY(r, hipMemcpyAsync(out, &st->result, sizeof(PtxMeterResult), hipMemcpyDeviceToHost, r->stream));
-    if (bins256)
-        HIP_TRY(r, hipMemcpyAsync(bins256, st->bins, sizeof(st->bins), hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
-}
-
-// ptx_postprocess_metered: the output call of `source` with the metered exposure multiplied in on the device
-static int postprocessMetered(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source)
-{
-    const char *who = "ptx_postprocess_metered";
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR || source > PTX_METER_DENOISED)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad argument", who);
-    if (source == PTX_METER_SUM)
-    {
-        if (!imagePtr(r))
-            return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
-        if (r->frame.boundShard)
-            return frameIsElsewhere(r, who);
-    }
-    const float4 *image = meterSource(r, source);
-    if (!image)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call %s first", who, source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
-    if (!r->output.meterState.p)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_meter first", who);
-    PtxPostProcessingUniformData u = *uniform;
-    if (source == PTX_METER_DENOISED)
-        u.TotalSamples = 1u; // ptx_postprocess_denoised: D holds the mean
-    return postprocessImage(r, image, &u, toneMappingMode, &r->output.meterState.p->result.exposure);
+    return readBack(r, bins256, st->bins, sizeof(st->bins));
 }
 
 // ---- display transform (docs/NEXT_ROWS.md section 22; semantics: include/ptx.h ptx_grade; kernels: pt_grade.hpp) ---------------------
@@ -386,25 +413,20 @@ static int grade(PtxRenderer *r, const PtxGradeDesc *d, uint32_t toneMappingMode
         d->reserved != 0u)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: unknown curve %u, mode %u or flags 0x%x, or reserved != 0 (%u)", who, d->curve, toneMappingMode, d->flags,
                     d->reserved);
-    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
-    bool ok = finite(d->saturation) && finite(d->whitePoint) && d->saturation >= 0.0f;
+    bool ok = finiteFloat(d->saturation) && finiteFloat(d->whitePoint) && d->saturation >= 0.0f;
     for (int i = 0; i < 9; i++)
-        ok = ok && finite(d->colourMatrix[i]);
+        ok = ok && finiteFloat(d->colourMatrix[i]);
     for (int k = 0; k < 3; k++)
-        ok = ok && finite(d->slope[k]) && finite(d->offset[k]) && finite(d->power[k]) && d->slope[k] >= 0.0f && d->power[k] >= 0.0f;
+        ok = ok && finiteFloat(d->slope[k]) && finiteFloat(d->offset[k]) && finiteFloat(d->power[k]) && d->slope[k] >= 0.0f && d->power[k] >= 0.0f;
     if (!ok)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: every float field must be finite, and slope, power and saturation >= 0", who);
     if (d->curve == PTX_CURVE_REINHARD && !(d->whitePoint > 0.0f))
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: PTX_CURVE_REINHARD needs whitePoint > 0 (%g)", who, (double)d->whitePoint);
     if ((d->flags & PTX_GRADE_LUT_SRGB_DOMAIN) && !(d->flags & PTX_GRADE_USE_LUT))
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: PTX_GRADE_LUT_SRGB_DOMAIN needs PTX_GRADE_USE_LUT", who);
+    if (const int rc = outputRefusal(r, who, NEEDS_OUTPUT | NEEDS_FRAME | NEEDS_ONE_SHARD))
+        return rc;
     OutputState &o = r->output;
-    if (!o.ready)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_postprocess first", who);
-    if (r->frame.boundShard)
-        return frameIsElsewhere(r, who);
-    if (r->frame.shard.worldSize > 1u)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
     if ((d->flags & PTX_GRADE_USE_LUT) && !o.gradeLut.p)
         return fail(r, PTX_ERROR_NOT_READY, "%s: PTX_GRADE_USE_LUT and no LUT set (call ptx_grade_lut)", who);
     HIP_TRY(r, hipSetDevice(r->device));
@@ -441,43 +463,30 @@ static int setGradeLut(PtxRenderer *r, uint32_t size, const float *rgb)
     return PTX_OK;
 }
 
-static int presentGraded(PtxRenderer *r, const PtxPresentDesc *d)
-{
-    return presentFrame(r, d, "ptx_present_graded", true);
-}
-
 // ---- local exposure (docs/NEXT_ROWS.md section 23; semantics: include/ptx.h ptx_local_exposure; kernels: pt_local_exposure.hpp) -------
 
-// ptx_local_exposure: splat, blur, gain.  Three launches, no synchronisation; the refusals follow ptx_meter's ladder, and every one of
-// them comes before the first allocation or launch, so a refused call leaves G as it was.
+// ptx_local_exposure: splat, blur, gain.  Three launches, no synchronisation; every refusal comes before the first allocation or
+// launch, so a refused call leaves G as it was.
 static int localExposure(PtxRenderer *r, const PtxLocalExposureDesc *d)
 {
     const char *who = "ptx_local_exposure";
     if (!r || !d)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
-    const auto finite = [](float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }; // a NaN fails both
     if (d->source > PTX_METER_DENOISED || !d->totalSamples || d->cellShift < kLocalMinShift || d->cellShift > kLocalMaxShift ||
         (d->flags & ~(uint32_t)PTX_LOCAL_EXPOSURE_PIVOT_METERED) || d->reserved != 0u)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need source <= 2 (%u), totalSamples > 0 (%u), cellShift in 3 .. 6 (%u), no unknown flag (0x%x) and "
                     "reserved 0 (%u)", who, d->source, d->totalSamples, d->cellShift, d->flags, d->reserved);
-    if (!finite(d->pivotLog2) || !finite(d->highlightContrast) || !finite(d->shadowContrast) || !finite(d->maxStops) || d->highlightContrast < 0.0f ||
-        d->highlightContrast > 2.0f || d->shadowContrast < 0.0f || d->shadowContrast > 2.0f || d->maxStops < 0.0f)
+    if (!finiteFloat(d->pivotLog2) || !finiteFloat(d->highlightContrast) || !finiteFloat(d->shadowContrast) || !finiteFloat(d->maxStops) ||
+        d->highlightContrast < 0.0f || d->highlightContrast > 2.0f || d->shadowContrast < 0.0f || d->shadowContrast > 2.0f || d->maxStops < 0.0f)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a finite pivotLog2 (%g), highlightContrast and shadowContrast in 0 .. 2 (%g, %g) and a finite "
                     "maxStops >= 0 (%g)", who, (double)d->pivotLog2, (double)d->highlightContrast, (double)d->shadowContrast, (double)d->maxStops);
-    if (!imagePtr(r))
-        return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
-    if (r->frame.boundShard)
-        return frameIsElsewhere(r, who);
-    if (r->frame.shard.worldSize > 1u)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
-    const float4 *source = meterSource(r, d->source);
-    if (!source)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: no %s image for this extent (call %s first)", who, d->source == PTX_METER_DESPIKED ? "despiked" : "denoised",
-                    d->source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
+    if (const int rc = outputRefusal(r, who, NEEDS_FRAME | NEEDS_ONE_SHARD | NEEDS_SOURCE_IMAGE, d->source))
+        return rc;
     OutputState &o = r->output;
     const bool metered = (d->flags & PTX_LOCAL_EXPOSURE_PIVOT_METERED) != 0u;
     if (metered && !o.meterState.p)
         return fail(r, PTX_ERROR_NOT_READY, "%s: PTX_LOCAL_EXPOSURE_PIVOT_METERED and no accepted ptx_meter on this handle yet", who);
+    const OutputSource src = outputSource(r, d->source, d->totalSamples);
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t W = r->frame.width, H = r->frame.height, s = d->cellShift;
     const uint32_t nx = (W + (1u << s) - 1u) >> s, ny = (H + (1u << s) - 1u) >> s;
@@ -486,15 +495,15 @@ static int localExposure(PtxRenderer *r, const PtxLocalExposureDesc *d)
     HIP_TRY(r, o.localGrid.alloc(2u * entries));
     HIP_TRY(r, o.localGain.alloc((size_t)W * H));
     LocalSplatArgs a;
-    a.source = source;
+    a.source = src.image;
     a.grid = o.localGrid.p;
     a.width = W; a.height = H; a.shift = s; a.nx = nx; a.ny = ny;
-    a.totalSamples = d->source == PTX_METER_DENOISED ? 1.0f : (float)d->totalSamples; // ptx_postprocess_denoised: D holds the mean
+    a.totalSamples = (float)src.totalSamples;
     const uint32_t block = 1u << kLocalBlockShift;
     k_local_splat<<<dim3((W + block - 1u) / block, (H + block - 1u) / block), kLocalSplatThreads, 0, r->stream>>>(a);
     k_local_blur<<<(uint32_t)((entries + 255u) / 256u), 256, 0, r->stream>>>(o.localGrid.p, o.localGrid.p + entries, nx, ny);
     LocalGainArgs g;
-    g.source = source;
+    g.source = src.image;
     g.grid = o.localGrid.p + entries;
     g.gain = o.localGain.p;
     g.meterCur = metered ? &o.meterState.p->cur : nullptr;
@@ -514,42 +523,24 @@ static int readLocalExposure(PtxRenderer *r, void *host, size_t bytes)
 {
     if (!r || !host)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_local_exposure: null argument");
-    if (!r->output.localReady)
-        return fail(r, PTX_ERROR_NOT_READY, "ptx_read_local_exposure: call ptx_local_exposure first");
+    if (const int rc = outputRefusal(r, "ptx_read_local_exposure", NEEDS_GAIN))
+        return rc;
     const size_t want = (size_t)r->frame.width * r->frame.height * sizeof(float);
     if (bytes != want)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_read_local_exposure: buffer must be %zu bytes", want);
     HIP_TRY(r, hipSetDevice(r->device));
-    HIP_TRY(r, hipMemcpyAsync(host, r->output.localGain.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(r, hipStreamSynchronize(r->stream));
-    HIP_TRY(r, hipGetLastError());
-    return PTX_OK;
+    return readBack(r, host, r->output.localGain.p, bytes);
 }
 
-// ptx_postprocess_local: the output call of `source` with Exposure = (uniform->Exposure x m) x G(p), m the metered exposure or 1
-static int postprocessLocal(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode, uint32_t source, uint32_t metered)
+// What ptx_resize does to the output stage: the output is not ready, G and the grid of ptx_local_exposure go with the extent they were
+// made for, and the meter starts over, its exposure having been metered on an image of the old extent.  The present image, the LUT and
+// the kept grade desc stay: they belong to the window and the display.
+static int outputResized(PtxRenderer *r)
 {
-    const char *who = "ptx_postprocess_local";
-    if (!r || !uniform || toneMappingMode > PTX_TONE_MAPPING_HDR || source > PTX_METER_DENOISED || metered > 1u)
-        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: bad argument", who);
-    if (source == PTX_METER_SUM)
-    {
-        if (!imagePtr(r))
-            return fail(r, PTX_ERROR_NOT_READY, "%s: no accumulation image (call ptx_resize)", who);
-        if (r->frame.boundShard)
-            return frameIsElsewhere(r, who);
-    }
-    const float4 *image = meterSource(r, source);
-    if (!image)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call %s first", who, source == PTX_METER_DESPIKED ? "ptx_despike" : "ptx_denoise");
-    if (metered && !r->output.meterState.p)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_meter first", who);
-    if (!r->output.localReady)
-        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_local_exposure first", who);
-    if (r->frame.shard.worldSize > 1u) // G covers the frame, a shard's image does not
-        return fail(r, PTX_ERROR_NOT_READY, "%s: this renderer holds one tile shard of %u", who, r->frame.shard.worldSize);
-    PtxPostProcessingUniformData u = *uniform;
-    if (source == PTX_METER_DENOISED)
-        u.TotalSamples = 1u; // ptx_postprocess_denoised: D holds the mean
-    return postprocessImage(r, image, &u, toneMappingMode, metered ? &r->output.meterState.p->result.exposure : nullptr, r->output.localGain.p);
+    OutputState &o = r->output;
+    o.invalidate();
+    o.localGain.release();
+    o.localGrid.release();
+    o.localReady = false;
+    return meterReset(r);
 }

@@ -5,10 +5,12 @@
 //   k_postprocess      postprocess.comp:16-40      sum / TotalSamples * Exposure, NaN / Inf markers, bloom prefilter
 //   k_postprocess_metered  the same with Exposure times the metered exposure of ptx_meter, read from device memory (section 21)
 //   k_postprocess_local    the same with Exposure times that, or times 1, times the per-pixel gain of ptx_local_exposure (section 23)
+//                      (one pixel body, postprocessStore, under the three names)
 //   k_bloom_downsample bloomDownsample.comp:18-62  13-tap filter, level i -> i + 1
 //   k_bloom_upsample   bloomUpsample.comp:18-55    3x3 tent of level i added onto level i - 1
 //   k_compose_tonemap  composition.comp:16-26 + toneMapping.comp:13-25 (two stores of the reference fused: the
-//                      value is rounded to binary16 between them exactly as the rgba16f image would)
+//                      value is rounded to binary16 between them exactly as the rgba16f image would); its pixel body,
+//                      composeStore, is k_compose_grade's too (pt_grade.hpp), with the tone step passed in
 //   k_encode_srgb8     the blit into VK_FORMAT_R8G8B8A8_SRGB
 //
 // The reference's intermediate images are rgba16f; here they are float arrays whose values are rounded to
@@ -112,60 +114,49 @@ PT_DEV f3 bloomTap(const BloomLevel &L, float u, float v)
 
 PT_DEV f3 add4(f3 a, f3 b, f3 c, f3 d) { return ((a + b) + c) + d; }
 
+// One pixel of the three post kernels, which differ in where u.Exposure comes from and in nothing else.  The grid-stride loop itself
+// stays in each kernel: read in a helper, blockDim becomes a vector load ahead of the first pixel (docs/NEXT_ROWS.md section 24).
+PT_DEV void postprocessStore(const float4 *__restrict__ accum, uint32_t i, const PtxPostProcessingUniformData &u, float *__restrict__ post,
+                             float *__restrict__ bloom0)
+{
+    const float4 a = accum[i];
+    f3 color, bloom;
+    postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
+    color = f16Round(color);
+    bloom = f16Round(bloom);
+    post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
+    bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
+}
+
 __global__ void k_postprocess(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, float *__restrict__ post,
                               float *__restrict__ bloom0)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    {
-        const float4 a = accum[i];
-        f3 color, bloom;
-        postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
-        color = f16Round(color);
-        bloom = f16Round(bloom);
-        post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
-        bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
-    }
+        postprocessStore(accum, i, u, post, bloom0);
 }
 
-// k_postprocess with Exposure = u.Exposure x the metered exposure, read from the meter's device state (include/ptx.h
-// ptx_postprocess_metered, docs/NEXT_ROWS.md section 21): one float product ahead of the same postprocessPixel.  The loop is
-// k_postprocess's, restated and not shared: moved into a helper it changed the code the compiler emits for k_postprocess, which this
-// stage leaves as it was.  tests/test_metering.py holds the two together: with a reset state the metered call gives the plain call's bits.
+// Exposure = u.Exposure x the metered exposure, read from the meter's device state (include/ptx.h ptx_postprocess_metered,
+// docs/NEXT_ROWS.md section 21).  tests/test_metering.py: with a reset state this kernel gives k_postprocess's bits.
 __global__ void k_postprocess_metered(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, const float *__restrict__ meterExposure,
                                       float *__restrict__ post, float *__restrict__ bloom0)
 {
     u.Exposure = u.Exposure * *meterExposure;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    {
-        const float4 a = accum[i];
-        f3 color, bloom;
-        postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
-        color = f16Round(color);
-        bloom = f16Round(bloom);
-        post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
-        bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
-    }
+        postprocessStore(accum, i, u, post, bloom0);
 }
 
-// k_postprocess with a per-pixel Exposure = (u.Exposure x m) x G(p) (include/ptx.h ptx_postprocess_local, docs/NEXT_ROWS.md section 23):
-// m is the metered exposure read from the meter's device state, or exactly 1.0f where `meterExposure` is null (x * 1.0f is x, bit for
-// bit), G the image ptx_local_exposure left: one more 4-byte load per pixel beside the 16 bytes of the sum.  Restated and not shared,
-// as k_postprocess_metered is and for its reason.  tests/test_local_exposure.py holds them together: with G = 1 everywhere this kernel
-// gives k_postprocess's bits, or k_postprocess_metered's.
+// A per-pixel Exposure = (u.Exposure x m) x G(p) (include/ptx.h ptx_postprocess_local, docs/NEXT_ROWS.md section 23): m is the metered
+// exposure, or exactly 1.0f where `meterExposure` is null (x * 1.0f is x, bit for bit), G the image ptx_local_exposure left: one more
+// 4-byte load per pixel beside the 16 bytes of the sum.  tests/test_local_exposure.py: with G = 1 everywhere this kernel gives
+// k_postprocess's bits, or k_postprocess_metered's.
 __global__ void k_postprocess_local(const float4 *__restrict__ accum, uint32_t n, PtxPostProcessingUniformData u, const float *__restrict__ meterExposure,
                                     const float *__restrict__ localGain, float *__restrict__ post, float *__restrict__ bloom0)
 {
     const float base = u.Exposure * (meterExposure ? *meterExposure : 1.0f);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     {
-        const float4 a = accum[i];
         u.Exposure = base * localGain[i];
-        f3 color, bloom;
-        postprocessPixel(F3(a.x, a.y, a.z), u, color, bloom);
-        color = f16Round(color);
-        bloom = f16Round(bloom);
-        post[3 * (size_t)i] = color.x; post[3 * (size_t)i + 1] = color.y; post[3 * (size_t)i + 2] = color.z;
-        bloom0[3 * (size_t)i] = bloom.x; bloom0[3 * (size_t)i + 1] = bloom.y; bloom0[3 * (size_t)i + 2] = bloom.z;
+        postprocessStore(accum, i, u, post, bloom0);
     }
 }
 
@@ -216,17 +207,30 @@ __global__ void k_bloom_upsample(BloomLevel src, BloomLevel dst)
     }
 }
 
+// One pixel of the two compose kernels: composition.comp's store, then `tone` on it.  A tone step returns a binary16-valued colour:
+// ToneMap below, or Grade of pt_grade.hpp.
+template <class Tone>
+PT_DEV void composeStore(const float *__restrict__ post, const float *__restrict__ bloom0, uint32_t i, const PtxPostProcessingUniformData &u, const Tone &tone,
+                         float4 *__restrict__ out)
+{
+    const f3 pp = F3(post[3 * (size_t)i], post[3 * (size_t)i + 1], post[3 * (size_t)i + 2]);
+    const f3 bl = F3(bloom0[3 * (size_t)i], bloom0[3 * (size_t)i + 1], bloom0[3 * (size_t)i + 2]);
+    const f3 t = tone(f16Round(compositionPixel(pp, bl, u)));
+    out[i] = make_float4(t.x, t.y, t.z, 1.0f);
+}
+
+// toneMapping.comp and its store
+struct ToneMap
+{
+    uint32_t mode;
+    PT_DEV f3 operator()(f3 c) const { return f16Round(toneMapPixel(c, mode)); }
+};
+
 __global__ void k_compose_tonemap(const float *__restrict__ post, const float *__restrict__ bloom0, uint32_t n, PtxPostProcessingUniformData u,
                                   uint32_t toneMode, float4 *__restrict__ out)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    {
-        const f3 pp = F3(post[3 * (size_t)i], post[3 * (size_t)i + 1], post[3 * (size_t)i + 2]);
-        const f3 bl = F3(bloom0[3 * (size_t)i], bloom0[3 * (size_t)i + 1], bloom0[3 * (size_t)i + 2]);
-        const f3 c = f16Round(compositionPixel(pp, bl, u));
-        const f3 t = f16Round(toneMapPixel(c, toneMode));
-        out[i] = make_float4(t.x, t.y, t.z, 1.0f);
-    }
+        composeStore(post, bloom0, i, u, ToneMap{ toneMode }, out);
 }
 
 __global__ void k_encode_srgb8(const float4 *__restrict__ linear, uint32_t n, uint32_t *__restrict__ out)

@@ -6,7 +6,8 @@
 //   uiComposition.comp:49-63 (:1160-1168)                                      UI over the frame, BT.2020 / ST 2084 encode
 //   the blit into the swapchain image (:1174-1191)                             the store in the surface's format
 //
-// One kernel, k_present, one thread per SCREEN pixel in row-major order: up to four taps of the post-process image and bloom
+// One body, presentPixel, under k_present (and k_present_graded of pt_grade.hpp, with the grade where the tone mapping stands), one
+// thread per SCREEN pixel in row-major order: up to four taps of the post-process image and bloom
 // level 0 in (composition.comp is evaluated per tap, as the reference blits the composed image), one word of the UI image, one
 // 4- or 8-byte store out.  The tone-mapping mode and the surface format are template parameters; whether an axis is filtered
 // and whether there is a UI image are wave-uniform arguments.  No LDS, no scratch.  Every store of the reference into an rgba16f
@@ -105,7 +106,9 @@ PT_DEV f3 presentRow(const PresentArgs &a, bool filterX, uint32_t ix0, uint32_t 
     return l * (1.0f - ax) + r * ax;
 }
 
-template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentBlock) k_present(PresentArgs a)
+// One screen pixel, from the blit to the store.  `tone` is what stands between the blit and the UI and returns a binary16-valued
+// colour: ToneMap (pt_post.hpp) in k_present, the grade in k_present_graded (pt_grade.hpp).
+template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentPixel(const PresentArgs &a, const Tone &tone)
 {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // SW * SH <= 2^28
     if (p >= a.SW * a.SH)
@@ -124,9 +127,9 @@ template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentB
         const f3 bot = presentRow(a, filterX, ix0, ix1, ax, iy1);
         c = c * (1.0f - ay) + bot * ay;
     }
-    c = f16Round(c);                                                            // ScreenImage after the blit
-    c = f16Round(toneMapPixel(c, HDR ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR)); // toneMapping.comp on ScreenImage
-    if (a.ui)                                                                   // uiComposition.comp:53-62
+    c = f16Round(c); // ScreenImage after the blit
+    c = tone(c);     // toneMapping.comp on ScreenImage, or the grade
+    if (a.ui)        // uiComposition.comp:53-62
     {
         const uint32_t t = a.ui[p];
         if (t >> 24)
@@ -148,6 +151,11 @@ template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentB
         const uint32_t r8 = quantize8(linearToSrgb(c.x)), g8 = quantize8(linearToSrgb(c.y)), b8 = quantize8(linearToSrgb(c.z));
         static_cast<uint32_t *>(a.out)[p] = FORMAT == PTX_PRESENT_B8G8R8A8_SRGB ? (b8 | g8 << 8 | r8 << 16 | 255u << 24) : (r8 | g8 << 8 | b8 << 16 | 255u << 24);
     }
+}
+
+template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentBlock) k_present(PresentArgs a)
+{
+    presentPixel<FORMAT, HDR>(a, ToneMap{ HDR ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR });
 }
 
 } // namespace ptd

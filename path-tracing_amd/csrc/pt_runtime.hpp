@@ -282,17 +282,11 @@ struct OutputState
     PtxGradeDesc gradeDesc = {};    // ... as does the desc of the last accepted ptx_grade, which ptx_present_graded applies
     bool gradeSet = false;
     // local exposure (ptx_local_exposure, docs/NEXT_ROWS.md section 23): both allocated by the first accepted ptx_local_exposure and
-    // released by ptx_resize, whose extent they were made for
+    // released by ptx_resize (outputResized), whose extent they were made for
     DevBuf<float> localGain;        // G, one float per pixel
     DevBuf<uint2> localGrid;        // the splatted grid and the blurred one behind it: 2 x ny x nx x 32 entries of (sum, count)
     bool localReady = false;        // an accepted ptx_local_exposure since the last ptx_resize
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
-    void dropLocalExposure() // ptx_resize
-    {
-        localGain.release();
-        localGrid.release();
-        localReady = false;
-    }
 };
 
 // The interactive chain behind ptx_render (pt_chain_host.hpp): the images of the guide pass, the temporal accumulation and the
@@ -826,7 +820,7 @@ static bool transformMirrors(const float *m); // (pt_animation_host.hpp; the upl
 #include "pt_bvh_host.hpp" // the tree build: buildAccel, buildBestTree
 #include "pt_animation_host.hpp" // ptx_track_motion, ptx_update_animation: trackMotion, snapshotPose, updateAnimation
 #include "pt_render_host.hpp" // ptx_render, ptx_render_debug, ptx_get_stats: renderImpl and its stages, collectRender, getStats, renderDebug
+#include "pt_output_host.hpp" // the output calls, the meter, the grade, the local exposure, the screen path and their read-backs
 #include "pt_frame_host.hpp" // accumulation image and its bindings, tile shards, read-back: resizeFrame ... unpackShards
-#include "pt_output_host.hpp" // ptx_postprocess, ptx_read_output, ptx_present, ptx_read_present
 #include "pt_chain_host.hpp" // the guide pass, the temporal accumulation, the three filters and their read-backs
 #include "pt_test_host.hpp" // ptx_test_eval, ptx_test_texture, ptx_test_debug_eval, ptx_trace_rays

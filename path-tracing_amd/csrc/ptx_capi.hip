@@ -198,7 +198,7 @@ int ptx_bind_shard_accumulation(PtxRenderer *r, void *devShard, size_t bytes)
 
 int ptx_postprocess(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
 {
-    return postprocess(r, uniform, toneMappingMode);
+    return postprocessSource(r, "ptx_postprocess", uniform, toneMappingMode, PTX_METER_SUM);
 }
 
 int ptx_read_output(PtxRenderer *r, uint32_t outputFormat, void *host, size_t bytes)
@@ -208,7 +208,7 @@ int ptx_read_output(PtxRenderer *r, uint32_t outputFormat, void *host, size_t by
 
 int ptx_present(PtxRenderer *r, const PtxPresentDesc *desc)
 {
-    return present(r, desc);
+    return presentFrame(r, desc, "ptx_present", false);
 }
 
 int ptx_read_present(PtxRenderer *r, void *host, size_t bytes)
@@ -258,7 +258,7 @@ void *ptx_device_denoised_ptr(PtxRenderer *r)
 
 int ptx_postprocess_denoised(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
 {
-    return postprocessDenoised(r, uniform, toneMappingMode);
+    return postprocessSource(r, "ptx_postprocess_denoised", uniform, toneMappingMode, PTX_METER_DENOISED);
 }
 
 int ptx_temporal_accumulate(PtxRenderer *r, const PtxTemporalDesc *desc)
@@ -363,7 +363,7 @@ int ptx_chain_use_despiked(PtxRenderer *r, int enable)
 
 int ptx_postprocess_despiked(PtxRenderer *r, const PtxPostProcessingUniformData *uniform, uint32_t toneMappingMode)
 {
-    return postprocessDespiked(r, uniform, toneMappingMode);
+    return postprocessSource(r, "ptx_postprocess_despiked", uniform, toneMappingMode, PTX_METER_DESPIKED);
 }
 
 int ptx_meter(PtxRenderer *r, const PtxMeterDesc *desc)
@@ -388,7 +388,7 @@ int ptx_meter_reset(PtxRenderer *r)
 
 int ptx_postprocess_metered(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode, uint32_t source)
 {
-    return postprocessMetered(r, u, toneMappingMode, source);
+    return postprocessSource(r, "ptx_postprocess_metered", u, toneMappingMode, source, true);
 }
 
 int ptx_grade(PtxRenderer *r, const PtxGradeDesc *d, uint32_t toneMappingMode)
@@ -403,7 +403,7 @@ int ptx_grade_lut(PtxRenderer *r, uint32_t size, const float *rgb)
 
 int ptx_present_graded(PtxRenderer *r, const PtxPresentDesc *desc)
 {
-    return presentGraded(r, desc);
+    return presentFrame(r, desc, "ptx_present_graded", true);
 }
 
 int ptx_local_exposure(PtxRenderer *r, const PtxLocalExposureDesc *desc)
