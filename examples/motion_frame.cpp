@@ -20,9 +20,13 @@
 //                                                                            tests/test_grade.py: Hable's curve, 4500 K, a CDL grade,
 //                                                                            the LUT where a file is named; every frame is also
 //                                                                            presented at 100 x 37 and that image appended)
+//   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 0 1 - 1 (... with UpscaleSettings on as well: section 25,
+//                                                                            tests/test_upscale.py; "-" names no LUT, and every frame is
+//                                                                            presented at 100 x 68, where the adapter enlarges)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
-// height x 16 bytes.  With the grade argument given -- 0 or 1 -- the two presented images follow, 2 x 100 x 37 x 4 bytes (R8G8B8A8).
+// height x 16 bytes.  With the grade argument given -- 0 or 1 -- the two presented images follow, 2 x 100 x 37 x 4 bytes (R8G8B8A8), or
+// 2 x 100 x 68 x 4 with the upscale argument at 1.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,10 +46,10 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 9 || argc > 15)
+    if (argc < 9 || argc > 16)
     {
         std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1|2: with local exposure) "
-                             "[grade(0|1) [lut.cube]]]]]]\n");
+                             "[grade(0|1) [lut.cube|- [upscale(0|1)]]]]]]]\n");
         return 1;
     }
     const std::string name = argv[1];
@@ -57,7 +61,9 @@ int main(int argc, char **argv)
     const bool useExposure = argc >= 13 && std::atoi(argv[12]) != 0;
     const bool useLocalExposure = argc >= 13 && std::atoi(argv[12]) == 2; // behind the meter
     const bool presentToo = argc >= 14, useGrade = presentToo && std::atoi(argv[13]) != 0;
-    const uint32_t screenWidth = 100, screenHeight = 37;
+    const bool useLut = argc >= 15 && std::strcmp(argv[14], "-") != 0;
+    const bool useUpscale = argc >= 16 && std::atoi(argv[15]) != 0;
+    const uint32_t screenWidth = 100, screenHeight = useUpscale ? 68 : 37; // below the render extent on one axis, or above it on both
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
     {
@@ -89,9 +95,12 @@ int main(int argc, char **argv)
         grade.TemperatureKelvin = 4500.0f;
         grade.Slope[0] = 1.1f; grade.Offset[1] = 0.01f; grade.Power[2] = 0.9f;
         grade.Saturation = 1.2f;
-        if (argc >= 15)
+        if (useLut)
             grade.LutFile = argv[14];
         RendererHip::SetSettings(grade);
+        RendererHip::UpscaleSettings upscale; // the default sharpness
+        upscale.Enabled = useUpscale;
+        RendererHip::SetSettings(upscale);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);

@@ -10,6 +10,7 @@
 //   examples/render_scene default 640 360 1 4 normals.png --debug-mode 2    (the debug view instead: PTX_DEBUG_MODE_*)
 //   examples/render_scene default 640 360 16 4 screen.png --present 1280x720          (the screen path: the frame as an SDR window of that size shows it)
 //   examples/render_scene default 640 360 16 4 screen.a2b10g10r10 --present 1280x720 --hdr10   (... an HDR10 one: the raw packed words)
+//   examples/render_scene default 640 360 16 4 screen.png --present 1280x720 --upscale 0.5   (... enlarged by the clamped Catmull-Rom filter and sharpened, not by the linear blit)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3       (guides + the a-trous filter, 3 iterations, in front of the output stage)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise-variance 3   (guides + temporal moments + the variance-guided filter)
 //   examples/render_scene default 640 360 4 4 denoised.png --denoise 3 --specular-guides 4   (... whose guides follow mirrors and glass)
@@ -188,6 +189,22 @@ int main(int argc, char **argv)
             argc -= 1;
             break;
         }
+    RendererHip::UpscaleSettings upscale; // --upscale [sharpness]: with --present WxH at or above the render extent, the clamped bicubic enlargement and unsharp mask
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--upscale")
+        {
+            upscale.Enabled = true;
+            char *end = nullptr;
+            const float sharpness = i + 1 < argc ? std::strtof(argv[i + 1], &end) : 0.0f;
+            const bool given = i + 1 < argc && end != argv[i + 1] && *end == '\0' && argv[i + 1][0] != '-';
+            if (given)
+                upscale.Sharpness = sharpness;
+            const int drop = given ? 2 : 1;
+            for (int k = i; k + drop < argc; k++)
+                argv[k] = argv[k + drop];
+            argc -= drop;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -221,6 +238,7 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(exposure);
         RendererHip::SetSettings(localExposure);
         RendererHip::SetSettings(grade);
+        RendererHip::SetSettings(upscale);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)

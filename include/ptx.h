@@ -1563,6 +1563,67 @@ PTX_API void *ptx_device_local_exposure_ptr(PtxRenderer *r);
 PTX_API int ptx_postprocess_local(PtxRenderer *r, const PtxPostProcessingUniformData *u, uint32_t toneMappingMode,
                                   uint32_t source, uint32_t metered /* 0 or 1 */);
 
+/* ------------------------------------------------------------------------- */
+/* Enlarging screen path (docs/NEXT_ROWS.md section 25): a host that renders   */
+/* below the window's extent gets a clamped bicubic enlargement and a clamped  */
+/* unsharp mask where ptx_present has the reference's linear blit.  An         */
+/* addition: every call above computes what it computed before, and a host     */
+/* that never calls this allocates nothing for it.                             */
+/* ------------------------------------------------------------------------- */
+
+enum { PTX_UPSCALE_CATMULL_ROM = 0 };
+enum { PTX_UPSCALE_GRADED = 1u };   /* the kept desc of the last accepted ptx_grade stands where the tone mapping stands */
+typedef struct PtxUpscaleDesc {
+    uint32_t filter;    /* PTX_UPSCALE_CATMULL_ROM */
+    float    sharpness; /* 0 ... 2, finite; +0 skips step 5 */
+    uint32_t flags;     /* PTX_UPSCALE_GRADED or 0 */
+    uint32_t reserved;  /* 0 */
+} PtxUpscaleDesc;
+
+/* ptx_present_upscaled writes the image ptx_present writes -- ptx_read_present, ptx_device_present_ptr, ptx_present_bytes and ptx_resize
+ * behave as after ptx_present -- from the same inputs: the post-process image, bloom level 0 and the uniform of the last accepted output
+ * call.  It only enlarges: the screen extent SW x SH is at least the render extent W x H on both axes (a smaller window is
+ * ptx_present's).  Per screen pixel (sx, sy) and colour channel, all arithmetic float32 in the order written with no contraction; every
+ * `/` is the specified division a * rcp(b); f16Round is the rounding to binary16 of every store into an rgba16f image; min and max
+ * are spelled out as selections, so what a NaN or an infinity does is part of the text.
+ *   1. COMPOSED TEXEL.  T(x, y) = f16Round(bloom0 * (BloomIntensity * 0.1f) + post * 1.0f) at render pixel (x, y): step 1 of the screen
+ *      path, composition.comp's store, unchanged.
+ *   2. AXIS SET-UP, for x (y is the same with sy, H, SH):  x = ((float)sx + 0.5f) * ((float)W / (float)SW) - 0.5f; x0 = floor(x);
+ *      t = x - x0.  Taps i_k = (uint32_t)min(max(x0 + (float)k, 0), (float)(W - 1)) for k = -1, 0, 1, 2 (clamp to edge).  Weights
+ *        w0 = ((-0.5f t + 1.0f) t - 0.5f) t        w1 = ((1.5f t - 2.5f) t) t + 1.0f
+ *        w2 = ((-1.5f t + 2.0f) t + 0.5f) t        w3 = ((0.5f t - 0.5f) t) t
+ *      (Catmull-Rom).  An axis whose two extents are equal is NOT filtered: one texel, no arithmetic -- ptx_present's rule, for
+ *      ptx_present's reason (W * rcp(W) is not 1 for every W).
+ *   3. ROW PASS, on each of the source rows j_k the y taps name:
+ *        a = ((T(i_-1, j) w0 + T(i_0, j) w1) + T(i_1, j) w2) + T(i_2, j) w3;
+ *        lo = T(i_1, j) < T(i_0, j) ? T(i_1, j) : T(i_0, j);   hi = T(i_0, j) < T(i_1, j) ? T(i_1, j) : T(i_0, j);
+ *        a = a >= lo ? a : lo;  then  a = a <= hi ? a : hi      (a NaN becomes lo).
+ *      R(j) = a, not rounded.  On an unfiltered x axis R(j) = T(sx, j).
+ *   4. COLUMN PASS.  The same expression and the same two selections over R(j_-1) ... R(j_2) with the y weights, lo and hi from R(j_0)
+ *      and R(j_1) as above from T(i_0) and T(i_1); on an unfiltered y axis the value is R(sy).  S = f16Round(that value): the screen
+ *      image after the enlargement.  The clamp is per axis on purpose: one clamp against the 2 x 2 central texels jumps where floor()
+ *      flips, per axis S is continuous in t.  S lies within the range of the four central texels (an anti-ringing clamp: a 5000-valued
+ *      marker pixel or an emitter does not ring), and a constant image comes through exactly.
+ *   5. SHARPEN, skipped when sharpness is +0.0f bit for bit (the host decides; the kernel gets a wave-uniform switch).  c = S(sx, sy);
+ *      N = S(sx, sy - 1), Sd = S(sx, sy + 1), Wt = S(sx - 1, sy), E = S(sx + 1, sy), coordinates clamped to the screen's edge.
+ *        m = ((N + Sd) + (Wt + E)) * 0.25f;   v = c + (c - m) * sharpness;
+ *        lo = c, hi = c, then for q = N, Sd, Wt, E in that order:  lo = q < lo ? q : lo;  hi = hi < q ? q : hi;
+ *        v = v >= lo ? v : lo;  then  v = v <= hi ? v : hi;   S' = f16Round(v).
+ *      A channel whose c is not finite passes through: S' = c.  The mask steepens edges and cannot leave the five-tap range, so it
+ *      adds no halo, and a local extremum stays as it is.
+ *   6. TONE OR GRADE, UI, HDR10, STORE.  ptx_present's steps from the tone mapping on, on S' (S without step 5): toneMapping.comp with
+ *      desc->toneMappingMode, or under PTX_UPSCALE_GRADED steps 1 - 5 of ptx_grade with the kept desc, as in ptx_present_graded; then
+ *      uiComposition.comp, the HDR10 encode, the store in desc->format.  The UI image is not scaled.
+ * SKIP RULE.  With SW = W, SH = H and sharpness +0 the call enqueues exactly what ptx_present (ptx_present_graded) enqueues.
+ * Asynchronous on the render stream, one launch; works on a borrower; touches neither the sum nor ptx_read_output's image.
+ * Refusals, in this order; a refused call leaves the present image intact.  (1) PTX_ERROR_INVALID_ARGUMENT: everything ptx_present
+ * refuses about desc, in its order.  (2) PTX_ERROR_INVALID_ARGUMENT: a NULL up; filter != PTX_UPSCALE_CATMULL_ROM; an unknown flag
+ * bit; reserved != 0; a sharpness that is not finite, < 0 or > 2.  (3) PTX_ERROR_NOT_READY: ptx_present's refusals, and under
+ * PTX_UPSCALE_GRADED ptx_present_graded's.  (4) PTX_ERROR_INVALID_ARGUMENT: desc->width < W or desc->height < H.
+ * Known limits: one filter; the UI is not scaled; no temporal super-resolution and no jittered history; the default sharpness of the
+ * layers above (0.5) has not been tuned by anybody; sharded frames are refused under PTX_UPSCALE_GRADED as everywhere behind ptx_grade. */
+PTX_API int ptx_present_upscaled(PtxRenderer *r, const PtxPresentDesc *desc, const PtxUpscaleDesc *up);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

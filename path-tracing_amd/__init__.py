@@ -74,6 +74,7 @@ PTX_SYMBOLS = [
     "ptx_meter", "ptx_read_meter", "ptx_device_meter_ptr", "ptx_meter_reset", "ptx_postprocess_metered",
     "ptx_grade", "ptx_grade_lut", "ptx_present_graded",
     "ptx_local_exposure", "ptx_read_local_exposure", "ptx_device_local_exposure_ptr", "ptx_postprocess_local",
+    "ptx_present_upscaled",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -275,6 +276,16 @@ LOCAL_EXPOSURE_PIVOT_METERED = 1  # PTX_LOCAL_EXPOSURE_PIVOT_METERED
 # pixels, middle grey, highlights compressed to 0.6 of their distance from it and shadows to 0.8, at most four stops either way.
 # Nobody has tuned them: they are a starting point that shows the effect, not the result of a sweep.
 LOCAL_EXPOSURE_DEFAULTS = dict(cell_shift=5, pivot_log2=-2.473931, highlight_contrast=0.6, shadow_contrast=0.8, max_stops=4.0)
+
+
+class UpscaleDesc(C.Structure):
+    _fields_ = [("filter", C.c_uint32), ("sharpness", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+UPSCALE_CATMULL_ROM = 0  # PTX_UPSCALE_CATMULL_ROM
+UPSCALE_GRADED = 1  # PTX_UPSCALE_GRADED
+# The default of Renderer.present_upscaled and of RendererHip::UpscaleSettings (docs/NEXT_ROWS.md section 25).  Nobody has tuned it.
+UPSCALE_DEFAULTS = dict(sharpness=0.5)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -528,6 +539,7 @@ def load_hip() -> C.CDLL:
         lib.ptx_grade_lut.argtypes = [P, C.c_uint32, P]
         lib.ptx_present_graded.argtypes = [P, C.POINTER(PresentDesc)]
         lib.ptx_local_exposure.argtypes = [P, C.POINTER(LocalExposureDesc)]
+        lib.ptx_present_upscaled.argtypes = [P, C.POINTER(PresentDesc), C.POINTER(UpscaleDesc)]
         lib.ptx_read_local_exposure.argtypes = [P, P, C.c_size_t]
         lib.ptx_device_local_exposure_ptr.argtypes = [P]
         lib.ptx_device_local_exposure_ptr.restype = P
@@ -801,6 +813,14 @@ class Renderer:
     def present_graded(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None):
         """ptx_present_graded: present() with the desc of the last grade() applied between the scaling blit and the UI."""
         self.present(width, height, fmt, tone_mapping, ui, _call=self.lib.ptx_present_graded)
+
+    def present_upscaled(self, width: int, height: int, fmt: int = PRESENT_R8G8B8A8_SRGB, tone_mapping: int = TONE_MAPPING_SDR, ui=None,
+                         sharpness: float = UPSCALE_DEFAULTS["sharpness"], graded: bool = False):
+        """ptx_present_upscaled: present() for a screen extent of at least the render extent, with a clamped Catmull-Rom enlargement in
+        the place of the linear blit and a clamped unsharp mask of strength `sharpness` (0 ... 2; 0 skips it) behind it; `graded`: with
+        the desc of the last grade() where the tone mapping stands, as present_graded() has it."""
+        up = UpscaleDesc(UPSCALE_CATMULL_ROM, sharpness, UPSCALE_GRADED if graded else 0, 0)
+        self.present(width, height, fmt, tone_mapping, ui, _call=lambda handle, desc: self.lib.ptx_present_upscaled(handle, desc, C.byref(up)))
 
     def grade(self, tone_mapping: int = TONE_MAPPING_SDR, colour_matrix=GRADE_DEFAULTS["colour_matrix"], slope=GRADE_DEFAULTS["slope"],
               offset=GRADE_DEFAULTS["offset"], power=GRADE_DEFAULTS["power"], saturation: float = GRADE_DEFAULTS["saturation"],

@@ -2,9 +2,10 @@
 // (ptx_present, ptx_read_present: row D15; docs/NEXT_ROWS.md section 12), the exposure metering in front of them (ptx_meter, ptx_read_meter,
 // ptx_meter_reset, ptx_postprocess_metered: section 21), the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded:
 // section 22), which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and
-// the local exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23).
+// the local exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23),
+// and the enlarging screen path (ptx_present_upscaled: section 25), which is presentFrame with pt_upscale.hpp's kernel at its end.
 // What the entry points share stands first: the source rule, the refusal ladder, the read-back's end, ptx_resize's part (section 24).
-// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp; state: OutputState, the member `output` of the handle.
+// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp, pt_upscale.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_frame_host.hpp, whose ptx_resize ends in outputResized; every function takes a valid or null
 // handle and returns a PTX_* code.
 #pragma once
@@ -189,8 +190,10 @@ template <typename F> static void withPresentFormat(uint32_t format, bool hdr, F
 static GradeArgs gradeArgs(const PtxRenderer *r, const PtxGradeDesc &d, bool hdr); // below: the display transform
 
 // The screen path: RecordPostProcessCommands' final blit + RecordUICommands (Renderer.cpp:1075-1203) in one launch of k_present, or, for
-// ptx_present_graded (`graded`, section 22), of k_present_graded with the desc the last accepted ptx_grade left
-static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who, bool graded)
+// ptx_present_graded (`graded`, section 22), of k_present_graded with the desc the last accepted ptx_grade left.  ptx_present_upscaled
+// (`upscaled`, section 25; `up` may be null and is then refused) takes the same road -- the desc's refusals, its own, the ladder, the
+// image, the UI -- and ends in one launch of k_present_upscaled instead, unless its skip rule leaves exactly the plain launch.
+static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who, bool graded, bool upscaled = false, const PtxUpscaleDesc *up = nullptr)
 {
     if (!r || !d)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
@@ -201,6 +204,16 @@ static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who
     const bool hdr = d->toneMappingMode == PTX_TONE_MAPPING_HDR;
     if ((hdr && d->format <= PTX_PRESENT_B8G8R8A8_SRGB) || (!hdr && d->format == PTX_PRESENT_A2B10G10R10_UNORM))
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: an 8-bit sRGB surface is SDR and A2B10G10R10 is HDR10 (Swapchain.cpp:317-340)", who);
+    if (upscaled)
+    {
+        if (!up)
+            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null PtxUpscaleDesc", who);
+        if (up->filter != PTX_UPSCALE_CATMULL_ROM || (up->flags & ~(uint32_t)PTX_UPSCALE_GRADED) || up->reserved)
+            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: unknown filter %u or flags 0x%x, or reserved != 0 (%u)", who, up->filter, up->flags, up->reserved);
+        if (!finiteFloat(up->sharpness) || up->sharpness < 0.0f || up->sharpness > 2.0f)
+            return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a finite sharpness in 0 .. 2 (%g)", who, (double)up->sharpness);
+        graded = (up->flags & PTX_UPSCALE_GRADED) != 0u;
+    }
     if (const int rc = outputRefusal(r, who, NEEDS_OUTPUT | NEEDS_FRAME | (graded ? NEEDS_ONE_SHARD : 0u)))
         return rc;
     OutputState &o = r->output;
@@ -208,6 +221,15 @@ static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who
         return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_grade first", who);
     if (graded && (o.gradeDesc.flags & PTX_GRADE_USE_LUT) && !o.gradeLut.p)
         return fail(r, PTX_ERROR_NOT_READY, "%s: the kept desc uses a LUT and the LUT has been cleared (ptx_grade_lut)", who);
+    if (upscaled && (d->width < r->frame.width || d->height < r->frame.height))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the screen extent %ux%u is below the render extent %ux%u on an axis (a smaller window is ptx_present's)", who,
+                    d->width, d->height, r->frame.width, r->frame.height);
+    // the skip rule: whether step 5 runs, bit for bit, and whether anything but the plain launch is left
+    uint32_t sharpnessBits = 0u;
+    if (upscaled)
+        memcpy(&sharpnessBits, &up->sharpness, 4);
+    const bool sharpen = sharpnessBits != 0u;
+    const bool enlarge = upscaled && (sharpen || d->width != r->frame.width || d->height != r->frame.height);
     HIP_TRY(r, hipSetDevice(r->device));
     const uint32_t n = d->width * d->height;
     const size_t words = (size_t)n * (d->format == PTX_PRESENT_R16G16B16A16_SFLOAT ? 2 : 1);
@@ -234,7 +256,19 @@ static int presentFrame(PtxRenderer *r, const PtxPresentDesc *d, const char *who
     withPresentFormat(d->format, hdr, [&](auto Format, auto Hdr) {
         constexpr uint32_t format = decltype(Format)::value;
         constexpr bool isHdr = decltype(Hdr)::value;
-        if (graded)
+        if (enlarge)
+        {
+            const dim3 tiles((d->width + kUpscaleTileX - 1) / kUpscaleTileX, (d->height + kUpscaleTileY - 1) / kUpscaleTileY); // <= 512 x 2048
+            withFlag(sharpen, [&](auto Sharpen) {
+                constexpr bool sh = decltype(Sharpen)::value;
+                if (graded)
+                    k_present_upscaled<format, isHdr, sh, GradeArgs><<<tiles, kUpscaleBlock, 0, r->stream>>>(a, up->sharpness, gradeArgs(r, o.gradeDesc, hdr));
+                else
+                    k_present_upscaled<format, isHdr, sh, ToneMap><<<tiles, kUpscaleBlock, 0, r->stream>>>(
+                        a, up->sharpness, ToneMap{ isHdr ? (uint32_t)PTX_TONE_MAPPING_HDR : (uint32_t)PTX_TONE_MAPPING_SDR });
+            });
+        }
+        else if (graded)
             k_present_graded<format, isHdr><<<grid, kPresentBlock, 0, r->stream>>>(a, gradeArgs(r, o.gradeDesc, hdr));
         else
             k_present<format, isHdr><<<grid, kPresentBlock, 0, r->stream>>>(a);

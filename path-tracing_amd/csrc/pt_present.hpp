@@ -106,14 +106,9 @@ PT_DEV f3 presentRow(const PresentArgs &a, bool filterX, uint32_t ix0, uint32_t 
     return l * (1.0f - ax) + r * ax;
 }
 
-// One screen pixel, from the blit to the store.  `tone` is what stands between the blit and the UI and returns a binary16-valued
-// colour: ToneMap (pt_post.hpp) in k_present, the grade in k_present_graded (pt_grade.hpp).
-template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentPixel(const PresentArgs &a, const Tone &tone)
+// The scaling blit at screen pixel (sx, sy): the value ScreenImage is about to store, not yet rounded
+PT_DEV f3 presentBlit(const PresentArgs &a, uint32_t sx, uint32_t sy)
 {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // SW * SH <= 2^28
-    if (p >= a.SW * a.SH)
-        return;
-    const uint32_t sx = p % a.SW, sy = p / a.SW;
     const bool filterX = a.SW != a.W, filterY = a.SH != a.H;
     uint32_t ix0 = sx, ix1 = sx, iy0 = sy, iy1 = sy;
     float ax = 0.0f, ay = 0.0f;
@@ -127,7 +122,13 @@ template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentPixel(const 
         const f3 bot = presentRow(a, filterX, ix0, ix1, ax, iy1);
         c = c * (1.0f - ay) + bot * ay;
     }
-    c = f16Round(c); // ScreenImage after the blit
+    return c;
+}
+
+// Screen pixel p = sy * SW + sx from `tone` on: c is ScreenImage's binary16-valued texel.  `tone` is what stands between the blit and
+// the UI and returns a binary16-valued colour: ToneMap (pt_post.hpp) in k_present, the grade in k_present_graded (pt_grade.hpp).
+template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentStore(const PresentArgs &a, const Tone &tone, uint32_t p, f3 c)
+{
     c = tone(c);     // toneMapping.comp on ScreenImage, or the grade
     if (a.ui)        // uiComposition.comp:53-62
     {
@@ -151,6 +152,18 @@ template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentPixel(const 
         const uint32_t r8 = quantize8(linearToSrgb(c.x)), g8 = quantize8(linearToSrgb(c.y)), b8 = quantize8(linearToSrgb(c.z));
         static_cast<uint32_t *>(a.out)[p] = FORMAT == PTX_PRESENT_B8G8R8A8_SRGB ? (b8 | g8 << 8 | r8 << 16 | 255u << 24) : (r8 | g8 << 8 | b8 << 16 | 255u << 24);
     }
+}
+
+// One screen pixel, from the blit to the store.  The two halves above are k_present_upscaled's too (pt_upscale.hpp), which puts its
+// own enlargement where the blit stands; inlined here they assemble to the one function's instructions, a few of them in another
+// order at the store (docs/NEXT_ROWS.md section 25 has the comparison).
+template <uint32_t FORMAT, bool HDR, class Tone> PT_DEV void presentPixel(const PresentArgs &a, const Tone &tone)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // SW * SH <= 2^28
+    if (p >= a.SW * a.SH)
+        return;
+    const f3 c = f16Round(presentBlit(a, p % a.SW, p / a.SW)); // ScreenImage after the blit
+    presentStore<FORMAT, HDR>(a, tone, p, c);
 }
 
 template <uint32_t FORMAT, bool HDR> __global__ void __launch_bounds__(kPresentBlock) k_present(PresentArgs a)

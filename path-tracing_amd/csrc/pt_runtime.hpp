@@ -40,6 +40,7 @@
 #include "pt_meter.hpp"
 #include "pt_grade.hpp"
 #include "pt_local_exposure.hpp"
+#include "pt_upscale.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI

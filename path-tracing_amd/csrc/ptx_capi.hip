@@ -426,6 +426,11 @@ int ptx_postprocess_local(PtxRenderer *r, const PtxPostProcessingUniformData *u,
     return postprocessLocal(r, u, toneMappingMode, source, metered);
 }
 
+int ptx_present_upscaled(PtxRenderer *r, const PtxPresentDesc *desc, const PtxUpscaleDesc *up)
+{
+    return presentFrame(r, desc, "ptx_present_upscaled", false, true, up);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

@@ -356,6 +356,13 @@ void RendererHip::SaveOutput(const OutputInfo &info)
         throw error("SaveOutput: cannot write " + info.Path.string());
 }
 
+static RendererHip::UpscaleSettings s_UpscaleSettings;
+
+void RendererHip::SetSettings(const UpscaleSettings &settings)
+{
+    s_UpscaleSettings = settings;
+}
+
 static bool s_SurfaceIsHdr = false; // Swapchain::IsHdr()
 
 void RendererHip::UpdateHdr(bool isHdr)
@@ -373,6 +380,12 @@ void RendererHip::Present(uint32_t width, uint32_t height, const uint8_t *ui)
     if (GradeIsOn())
         Check(ptx_grade(s_Renderer, &s_GradeDesc, mode));
     const PtxPresentDesc desc = { width, height, s_SurfaceIsHdr ? (uint32_t)PTX_PRESENT_A2B10G10R10_UNORM : (uint32_t)PTX_PRESENT_R8G8B8A8_SRGB, mode, ui, 0u, 0u };
+    if (s_UpscaleSettings.Enabled && width >= s_Width && height >= s_Height) // ptx.h, "Enlarging screen path": a smaller window stays with the blit
+    {
+        const PtxUpscaleDesc up = { PTX_UPSCALE_CATMULL_ROM, s_UpscaleSettings.Sharpness, GradeIsOn() ? (uint32_t)PTX_UPSCALE_GRADED : 0u, 0u };
+        Check(ptx_present_upscaled(s_Renderer, &desc, &up));
+        return;
+    }
     Check(GradeIsOn() ? ptx_present_graded(s_Renderer, &desc) : ptx_present(s_Renderer, &desc));
 }
 

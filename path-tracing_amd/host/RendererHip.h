@@ -177,6 +177,18 @@ public:
         bool LutSrgbDomain = false;
     };
     static void SetSettings(const GradeSettings &settings);
+    // Enlarging screen path (ptx.h "Enlarging screen path", docs/NEXT_ROWS.md section 25), for a host that renders below the window's
+    // extent.  Enabled, and the extent given to Present at least the render extent on both axes: Present calls ptx_present_upscaled --
+    // a clamped Catmull-Rom enlargement and a clamped unsharp mask of strength Sharpness (0 ... 2) where ptx_present has the linear
+    // blit -- with PTX_UPSCALE_GRADED when the GradeSettings are on.  Disabled (the default), or for a smaller window: Present enqueues
+    // exactly what it did.  SaveOutput is not concerned: it writes the render extent.  The default is UPSCALE_DEFAULTS of the Python
+    // package; nobody has tuned it.
+    struct UpscaleSettings
+    {
+        bool Enabled = false;
+        float Sharpness = 0.5f;
+    };
+    static void SetSettings(const UpscaleSettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either

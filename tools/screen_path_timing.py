@@ -44,7 +44,12 @@ cellShift.  ptx_local_exposure is given against 36 algorithmic bytes per pixel (
 gain; the grid is noise beside them at cellShift 5) -- a rate, not a bandwidth.  A kernel trace of `--local --extent W H` gives
 k_local_splat's, k_local_blur's, k_local_gain's and k_postprocess_local's device times.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--local] [--extent W H]"""
+ptx_present_upscaled (section 25): --upscale times nothing but it, at sharpness 0 and 0.5, with ptx_present at the same extents in the
+same run beside it: the 8-spp chess_like frame rendered at 1920 x 1080 and shown at 3840 x 2160, and at 1280 x 720 shown at 2560 x 1440,
+as an SDR sRGB8 and as an HDR10 surface.  --extent W H takes one render extent in place of the two; the screen is twice it on both axes.
+A kernel trace of `--upscale --extent W H` gives k_present_upscaled's and k_present's device times.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--local] [--upscale] [--extent W H]"""
 import json
 import math
 import os
@@ -91,14 +96,14 @@ def main():
     detail = float(sys.argv[sys.argv.index("--detail") + 1]) if "--detail" in sys.argv else 1.0
     out = {}
     guides_only, temporal_only, meter_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv, "--meter" in sys.argv
-    grade_only, local_only = "--grade" in sys.argv, "--local" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only or local_only else ("chess_like", "default") if guides_only else
+    grade_only, local_only, upscale_only = "--grade" in sys.argv, "--local" in sys.argv, "--upscale" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only or local_only or upscale_only else ("chess_like", "default") if guides_only else
                                                           ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
         renderers[name] = pkg.Renderer()
         renderers[name].upload(scene)
-    extents = ((1920, 1080), (3840, 2160))
+    extents = ((1920, 1080), (1280, 720)) if upscale_only else ((1920, 1080), (3840, 2160))
     if "--extent" in sys.argv:
         extents = ((int(sys.argv[sys.argv.index("--extent") + 1]), int(sys.argv[sys.argv.index("--extent") + 2])),)
     for w, h in extents:
@@ -118,6 +123,23 @@ def main():
             ud = sd.uniform(w, h, bounces=STEP_DEPTH)
             rec["render_guides_default"] = timed(rd, lambda: rd.render_guides(ud))
             specular_row("default", rd, ud)
+        if upscale_only:
+            r.reset()
+            r.render_frames(u, scene.lights, 0, STEP_SPP)
+            sw, sh = 2 * w, 2 * h
+            for surface, fmt, mode in (("sdr_srgb8", pkg.PRESENT_R8G8B8A8_SRGB, pkg.TONE_MAPPING_SDR), ("hdr10", pkg.PRESENT_A2B10G10R10_UNORM, pkg.TONE_MAPPING_HDR)):
+                r.postprocess(STEP_SPP, tone_mapping=mode, **POST)
+                base = timed(r, lambda: r.present(sw, sh, fmt, mode))
+                rec[f"present_to_{sw}x{sh}_{surface}"] = base
+                for sharpness in (0.0, 0.5):
+                    t = timed(r, lambda: r.present_upscaled(sw, sh, fmt, mode, sharpness=sharpness))
+                    t["ratio_to_present"] = t["median_ms"] / base["median_ms"]
+                    rec[f"present_upscaled_to_{sw}x{sh}_{surface}_sharpness_{sharpness}"] = t
+                rec[f"present_to_{sw}x{sh}_{surface}_again"] = timed(r, lambda: r.present(sw, sh, fmt, mode))
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
         if grade_only:
             r.reset()
             r.render_frames(u, scene.lights, 0, STEP_SPP)
