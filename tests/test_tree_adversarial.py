@@ -1,5 +1,7 @@
 """The tree build (pt_bvh_build.hpp) and the traversal (pt_bvh.hpp) on geometry chosen to reach the branches friendly scenes
-do not: leaf and tile counts at the sort / scan block boundaries, zero-area triangles, exact duplicates and shared centroids
+do not: leaf and tile counts at the sort / scan block boundaries (up to 16,384 references a radix pass scans its 256 counters per
+2,048-reference tile in one block; from 16,385 on -- more than 8 tiles -- in three kernels: sizes 16,383 - 16,385, and 18,433 = nine
+tiles and one reference), zero-area triangles, exact duplicates and shared centroids
 (PLOC ties, equal-t ties that must go to the smallest id), coplanar overlaps far from the ray origin (the case the traversal's
 cull slack is for -- with today's box padding these scenes do not need it: they also pass with a slack of 1.0), scenes scaled by powers of two and moved far from the origin, flat scenes, slivers, a tiny cluster inside a huge box, and
 nested triangles deep enough to spill the traversal stack into its global region or past it.
@@ -18,7 +20,8 @@ import pytest
 import util
 
 DEEP_RATIO, DEEP_STEP = 0.93, 1e-4
-SIZES = (1, 2, 3, 4, 5, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097)
+SIZES = (1, 2, 3, 4, 5, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097, 16383, 16384, 16385,
+         18433)
 SCALE_EXPONENTS = (-40, -20, 20, 40)
 EXACT_EXPONENTS = (-20, 20, 40)  # at 2^-40 cancelling products of the triangle test leave the normal range (measured on the oracle)
 
