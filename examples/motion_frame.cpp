@@ -23,10 +23,14 @@
 //   examples/motion_frame animated_test 67 45 2 4 0.37 0 frames.bin 0 0 0 0 1 - 1 (... with UpscaleSettings on as well: section 25,
 //                                                                            tests/test_upscale.py; "-" names no LUT, and every frame is
 //                                                                            presented at 100 x 68, where the adapter enlarges)
+//   examples/motion_frame animated_test 67 45 16 4 0.37 0 frames.bin 0 0 0 0 0 - 0 1 (... with NoiseSettings on: section 26,
+//                                                                            tests/test_noise_meter.py; CheckEvery 4, MinSamples 4; with the
+//                                                                            argument given, 0 or 1, a trailer follows the presented images)
 //
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
 // height x 16 bytes.  With the grade argument given -- 0 or 1 -- the two presented images follow, 2 x 100 x 37 x 4 bytes (R8G8B8A8), or
-// 2 x 100 x 68 x 4 with the upscale argument at 1.
+// 2 x 100 x 68 x 4 with the upscale argument at 1.  The trailer of the noise argument: per frame the PtxNoiseResult GetNoise() returned after
+// the frame's render calls and IsConverged() as a uint32, then one uint32 that says whether the handle holds halves at the end.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,10 +50,10 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 9 || argc > 16)
+    if (argc < 9 || argc > 17)
     {
         std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1|2: with local exposure) "
-                             "[grade(0|1) [lut.cube|- [upscale(0|1)]]]]]]]\n");
+                             "[grade(0|1) [lut.cube|- [upscale(0|1) [noise(0|1)]]]]]]]]\n");
         return 1;
     }
     const std::string name = argv[1];
@@ -63,6 +67,7 @@ int main(int argc, char **argv)
     const bool presentToo = argc >= 14, useGrade = presentToo && std::atoi(argv[13]) != 0;
     const bool useLut = argc >= 15 && std::strcmp(argv[14], "-") != 0;
     const bool useUpscale = argc >= 16 && std::atoi(argv[15]) != 0;
+    const bool noiseTrailer = argc >= 17, useNoise = noiseTrailer && std::atoi(argv[16]) != 0;
     const uint32_t screenWidth = 100, screenHeight = useUpscale ? 68 : 37; // below the render extent on one axis, or above it on both
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
@@ -101,6 +106,11 @@ int main(int argc, char **argv)
         RendererHip::UpscaleSettings upscale; // the default sharpness
         upscale.Enabled = useUpscale;
         RendererHip::SetSettings(upscale);
+        RendererHip::NoiseSettings noise; // the values tests/test_noise_meter.py repeats by hand
+        noise.Enabled = useNoise;
+        noise.CheckEvery = 4;
+        noise.MinSamples = 4;
+        RendererHip::SetSettings(noise);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);
@@ -109,7 +119,8 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(settings);
         const size_t bytes = static_cast<size_t>(width) * height * 16;
         const size_t screenBytes = static_cast<size_t>(screenWidth) * screenHeight * 4;
-        std::vector<char> file(6 * bytes + (presentToo ? 2 * screenBytes : 0));
+        const size_t trailerAt = 6 * bytes + (presentToo ? 2 * screenBytes : 0), perFrame = sizeof(PtxNoiseResult) + 4;
+        std::vector<char> file(trailerAt + (noiseTrailer ? 2 * perFrame + 4 : 0));
         const std::string scratch = std::string(argv[8]) + ".png";
         for (int frame = 0; frame < 2; frame++)
         {
@@ -130,6 +141,13 @@ int main(int argc, char **argv)
                 RendererHip::OnUpdate(timeStep);
             for (uint32_t i = 0; i < spp; i++)
                 RendererHip::Render();
+            if (noiseTrailer)
+            {
+                const PtxNoiseResult res = RendererHip::GetNoise();
+                const uint32_t converged = RendererHip::IsConverged() ? 1u : 0u;
+                std::memcpy(&file[trailerAt + frame * perFrame], &res, sizeof(res));
+                std::memcpy(&file[trailerAt + frame * perFrame + sizeof(res)], &converged, 4);
+            }
             const std::vector<float> sum = RendererHip::ReadAccumulationImage();
             std::memcpy(&file[(3 * frame) * bytes], sum.data(), bytes);
             RendererHip::SaveOutput({ scratch, { width, height }, 0, OutputFormat::Png });
@@ -146,6 +164,11 @@ int main(int argc, char **argv)
                     throw error("the presented image has another size");
                 std::memcpy(&file[6 * bytes + frame * screenBytes], screen.data(), screenBytes);
             }
+        }
+        if (noiseTrailer)
+        {
+            const uint32_t halves = ptx_device_noise_half_ptr(RendererHip::GetHandle(), 0u) ? 1u : 0u;
+            std::memcpy(&file[trailerAt + 2 * perFrame], &halves, 4);
         }
         FILE *f = std::fopen(argv[8], "wb");
         if (!f || std::fwrite(file.data(), 1, file.size(), f) != file.size())

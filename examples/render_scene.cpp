@@ -20,6 +20,8 @@
 //   examples/render_scene atrium_like 640 360 16 4 local.png --local-exposure  (local exposure behind the meter: highlights and shadows move towards middle grey)
 //   examples/render_scene default 640 360 16 4 graded.png --curve aces --temperature 4500 --lut look.cube   (display transform: tone curve reference | reinhard | hable | aces,
 //                                                                            white balance for a light of that many kelvin, a .cube 3-D LUT)
+//   examples/render_scene default 640 360 4096 4 out.png --noise-threshold 0.02   (noise metering: the sample count is the maximum; the render stops at the
+//                                                                            first check where every tile's error is at or below the threshold)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
 #include <cmath>
 #include <cstdio>
@@ -205,6 +207,23 @@ int main(int argc, char **argv)
             argc -= drop;
             break;
         }
+    RendererHip::NoiseSettings noise; // --noise-threshold T: the two half-sums are compared every CheckEvery samples, and the render stops when every tile is converged
+    for (int i = 1; i + 1 < argc; i++)
+        if (std::string(argv[i]) == "--noise-threshold")
+        {
+            char *end = nullptr;
+            noise.Threshold = std::strtof(argv[i + 1], &end);
+            if (end == argv[i + 1] || *end != '\0' || !(noise.Threshold >= 0.0f) || !std::isfinite(noise.Threshold))
+            {
+                std::fprintf(stderr, "--noise-threshold takes a finite number >= 0\n");
+                return 1;
+            }
+            noise.Enabled = true;
+            for (int k = i; k + 2 < argc; k++)
+                argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -239,10 +258,26 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(localExposure);
         RendererHip::SetSettings(grade);
         RendererHip::SetSettings(upscale);
+        RendererHip::SetSettings(noise);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
+        uint32_t used = 0;
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)
+        {
             RendererHip::Render();
+            used++;
+            // the third stop condition beside MaxSampleCount and MaxTime (Renderer.cpp:1701-1704): asked only after a check, so that
+            // the other render calls stay asynchronous
+            if (noise.Enabled && debugMode < 0 && used % noise.CheckEvery == 0u && RendererHip::IsConverged())
+                break;
+        }
+        if (noise.Enabled && debugMode < 0)
+        {
+            const PtxNoiseResult res = RendererHip::GetNoise();
+            std::printf("noise threshold %g: %u of at most %u samples used, %s; last check: mean error %.6g, max %.6g, %u of %u tiles converged\n", (double)noise.Threshold,
+                        used, spp, RendererHip::IsConverged() ? "converged" : "not converged", (double)res.meanError, (double)res.maxError, res.converged,
+                        res.tilesX * res.tilesY);
+        }
         const std::vector<float> acc = RendererHip::ReadAccumulationImage();
         const float inv = 1.0f / static_cast<float>(RendererHip::GetTotalSamples());
         double sum = 0.0;
@@ -280,7 +315,7 @@ int main(int argc, char **argv)
         }
         else
             RendererHip::SaveOutput({ out, { width, height }, 0, format });
-        std::printf("scene %s %ux%u %u spp depth %u: mean radiance %.9g -> %s\n", name.c_str(), width, height, spp, bounces,
+        std::printf("scene %s %ux%u %u spp depth %u: mean radiance %.9g -> %s\n", name.c_str(), width, height, debugMode >= 0 ? spp : used, bounces,
                     sum / (3.0 * width * height), out);
         RendererHip::Shutdown();
     }

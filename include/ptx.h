@@ -1624,6 +1624,84 @@ typedef struct PtxUpscaleDesc {
  * layers above (0.5) has not been tuned by anybody; sharded frames are refused under PTX_UPSCALE_GRADED as everywhere behind ptx_grade. */
 PTX_API int ptx_present_upscaled(PtxRenderer *r, const PtxPresentDesc *desc, const PtxUpscaleDesc *up);
 
+/* ------------------------------------------------------------------------- */
+/* Noise metering (docs/NEXT_ROWS.md section 26): two half-sums of an offline  */
+/* render give an error estimate per tile, on the device and in the units of   */
+/* the displayed mean, so that a render stops on a noise threshold and not on  */
+/* a sample count.  An addition: every call above computes what it computed    */
+/* before, and a host that never calls these allocates nothing for them.       */
+/* ------------------------------------------------------------------------- */
+
+enum { PTX_NOISE_WRITE_SUM = 1u }; /* step 1 stores S = A + B to the internal accumulation image */
+
+typedef struct PtxNoiseDesc {
+    uint32_t samplesA, samplesB; /* samples summed in half 0 / half 1, each 1 .. 2^24 */
+    float    exposure;           /* the output stage's Exposure: the error is measured on mean * exposure */
+    float    threshold;          /* a tile is converged iff its error <= threshold */
+    uint32_t tileShift;          /* tiles of 2^tileShift pixels a side, 3 .. 6 */
+    uint32_t flags;              /* PTX_NOISE_WRITE_SUM */
+    uint32_t reserved[2];
+} PtxNoiseDesc;
+
+typedef struct PtxNoiseResult {
+    float    meanError, maxError;
+    uint32_t tilesX, tilesY, converged;   /* tiles whose error <= threshold */
+    uint32_t counted, black, rejected;    /* pixels */
+    uint32_t valid, calls;
+} PtxNoiseResult;
+
+/* The two halves.  enable = 1 makes and zeroes two width * height * 16-byte images owned by the handle (asynchronous on the render
+ * stream; where they exist already they are zeroed again); enable = 0 releases them and returns the binding to the internal image if
+ * one of them was bound.  They belong to the extent: ptx_resize drops them, as it already unbinds.  The host binds them with the
+ * existing ptx_bind_accumulation(r, ptx_device_noise_half_ptr(r, which), ptx_accum_bytes(r)): ptx_render, ptx_render_frames (a block of
+ * frames into whichever half is bound), ptx_reset_accumulation, ptx_write_accumulation and ptx_readback then act on the bound half as
+ * they do on any bound buffer, unchanged.  The accumulation image is a kernel argument of the launch that adds a frame's samples, on
+ * the handle's stream, and the random numbers are a function of pixel, width and frame alone: a host that binds half 0 before its even
+ * render calls and half 1 before its odd ones gets two independent sums, each bit for bit what a handle of its own would have
+ * accumulated from those frames, with no kernel touched.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL handle, enable > 1.  PTX_ERROR_NOT_READY: enable = 1 before ptx_resize. */
+PTX_API int ptx_noise_halves(PtxRenderer *r, uint32_t enable);
+/* The device address of half `which` (0 / 1); NULL when there are none, for a NULL handle and for which > 1. */
+PTX_API void *ptx_device_noise_half_ptr(PtxRenderer *r, uint32_t which);
+/* ptx_noise_meter.  W x H is the render extent, p = (x, y) a pixel, A(p) the float4 of half 0 and B(p) that of half 1.  All arithmetic
+ * is float32 in the order written with no contraction; rcp, sqrt and the division a / b = a * rcp(b) are the project's specified
+ * kernels, rcp being the correctly rounded 1 / x on every argument met here; fmin(a, b) = b < a ? b : a.  The
+ * integers are exact and the two float64 divisions are IEEE.
+ *   1. SUM.  S = A + B, component by component, alpha included.  With PTX_NOISE_WRITE_SUM, S is stored to the handle's internal
+ *      accumulation image, the image ptx_bind_accumulation(NULL) selects.  The binding is not changed.  This is what the output stage
+ *      and the chain read afterwards, so no existing call needs to know about halves.
+ *   2. SCALE FACTORS.  sa = exposure * rcp((float)samplesA), sb likewise from samplesB, st = exposure * rcp((float)(samplesA + samplesB)).
+ *   3. SCALED VALUES.  a = A.rgb * sa, b = B.rgb * sb, c = S.rgb * st.  D = (|a.r - b.r| + |a.g - b.g|) + |a.b - b.b|.
+ *      m = (c.r + c.g) + c.b.
+ *   4. CLASSES.  REJECTED iff any of the six input colour values, D or m is not finite.  BLACK iff not rejected and not (m >= 2^-20):
+ *      zeros, negatives and everything near the denormals.  COUNTED = not rejected; black pixels count with error 0.
+ *   5. PER-PIXEL ERROR.  For a counted pixel that is not black e = fmin(0.5f * (D / sqrt(m)), 255.0f) and q = (uint32_t)(e * 65536.0f),
+ *      truncated, so q < 2^24.  Black pixels have q = 0.  e is the per-pixel term of Dammertz, Hanika, Keller and Lensch, "A hierarchical
+ *      automatic stopping condition for Monte Carlo global illumination" (2010): |I - A| / sqrt(I) with A the image of half the samples.
+ *      With equal halves it estimates the standard error of the pixel's mean over the square root of its value.
+ *   6. PER TILE.  A tile is the pixels with x >> tileShift and y >> tileShift equal; ragged tiles lie at the right and bottom edges;
+ *      tilesX = ceil(W / 2^tileShift), tilesY likewise.  Q_t = SUM q in uint64, n_t = the counted pixels of the tile.
+ *      E_t = n_t ? (float)((double)Q_t / ((double)n_t * 65536.0)) : 0.  The tile is converged iff E_t <= threshold.
+ *   7. RESULT.  maxError = max E_t.  meanError = (float)((double)SUM Q_t / ((double)SUM n_t * 65536.0)).  counted = SUM n_t, black and
+ *      rejected the pixels of those classes (black ones are in counted too), converged the number of converged tiles.  valid = 0 with
+ *      both errors 0 when SUM n_t = 0, and 1 otherwise.  calls counts accepted calls since creation or ptx_resize.  All sums are
+ *      integers, so there is no order for the result to depend on.
+ * Asynchronous on the render stream, two launches, the second a single workgroup; it never synchronises, has no global atomics and
+ * nothing to zero between calls.  It needs no scene and so works on a borrower of a shared one.  The result, the tile map and the
+ * other state are allocated by the first accepted call.
+ * Refusals, in this order; a refused call leaves the state, the tile map and the internal image intact.  PTX_ERROR_INVALID_ARGUMENT:
+ * a NULL argument; a sample count of 0 or above 2^24; tileShift outside 3 ... 6; unknown flag bits; reserved != 0; an exposure or
+ * threshold that is not finite; exposure <= 0; threshold < 0.  PTX_ERROR_NOT_READY: no image (ptx_resize); a shard accumulation buffer
+ * bound; a tile shard with worldSize > 1; no halves.
+ * Known limits: S = A + B is not the bits of one sum accumulated in frame order; unequal halves bias e; the criterion is per tile, with
+ * no hierarchy; sharded frames are refused; there is no adaptive sampling: the estimate stops a render, it does not steer one. */
+PTX_API int ptx_noise_meter(PtxRenderer *r, const PtxNoiseDesc *desc);
+/* The result of the last accepted ptx_noise_meter and, where tileErrors is not NULL, its tile map: tilesX * tilesY floats E_t,
+ * row-major, `bytes` being exactly their size (with tileErrors NULL `bytes` is not read).  Synchronous, as ptx_read_output is.
+ * PTX_ERROR_INVALID_ARGUMENT: a NULL handle or result.  PTX_ERROR_NOT_READY: no accepted ptx_noise_meter since creation or the last
+ * ptx_resize.  PTX_ERROR_INVALID_ARGUMENT: a `bytes` that does not match. */
+PTX_API int ptx_read_noise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors /* may be NULL */, size_t bytes);
+
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);
 PTX_API int ptx_test_eval(PtxRenderer *r, uint32_t fn, const float *in, float *out, uint32_t n);

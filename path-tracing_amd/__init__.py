@@ -75,6 +75,7 @@ PTX_SYMBOLS = [
     "ptx_grade", "ptx_grade_lut", "ptx_present_graded",
     "ptx_local_exposure", "ptx_read_local_exposure", "ptx_device_local_exposure_ptr", "ptx_postprocess_local",
     "ptx_present_upscaled",
+    "ptx_noise_halves", "ptx_device_noise_half_ptr", "ptx_noise_meter", "ptx_read_noise",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -286,6 +287,22 @@ UPSCALE_CATMULL_ROM = 0  # PTX_UPSCALE_CATMULL_ROM
 UPSCALE_GRADED = 1  # PTX_UPSCALE_GRADED
 # The default of Renderer.present_upscaled and of RendererHip::UpscaleSettings (docs/NEXT_ROWS.md section 25).  Nobody has tuned it.
 UPSCALE_DEFAULTS = dict(sharpness=0.5)
+
+
+class NoiseDesc(C.Structure):
+    _fields_ = [("samplesA", C.c_uint32), ("samplesB", C.c_uint32), ("exposure", C.c_float), ("threshold", C.c_float), ("tileShift", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class NoiseResult(C.Structure):
+    _fields_ = [("meanError", C.c_float), ("maxError", C.c_float), ("tilesX", C.c_uint32), ("tilesY", C.c_uint32), ("converged", C.c_uint32),
+                ("counted", C.c_uint32), ("black", C.c_uint32), ("rejected", C.c_uint32), ("valid", C.c_uint32), ("calls", C.c_uint32)]
+
+
+NOISE_WRITE_SUM = 1  # PTX_NOISE_WRITE_SUM
+# The defaults of Renderer.noise_meter and of RendererHip::NoiseSettings (docs/NEXT_ROWS.md section 26): tiles of 16 x 16 pixels, a check
+# every eight render calls, none before 16 samples.  Nobody has tuned the threshold: it is a starting point, not the result of a sweep.
+NOISE_DEFAULTS = dict(threshold=0.02, tile_shift=4, check_every=8, min_samples=16)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -544,6 +561,11 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_local_exposure_ptr.argtypes = [P]
         lib.ptx_device_local_exposure_ptr.restype = P
         lib.ptx_postprocess_local.argtypes = [P, C.POINTER(PostProcessingUniformData), C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.ptx_noise_halves.argtypes = [P, C.c_uint32]
+        lib.ptx_device_noise_half_ptr.argtypes = [P, C.c_uint32]
+        lib.ptx_device_noise_half_ptr.restype = P
+        lib.ptx_noise_meter.argtypes = [P, C.POINTER(NoiseDesc)]
+        lib.ptx_read_noise.argtypes = [P, C.POINTER(NoiseResult), P, C.c_size_t]
         _hip = lib
     return _hip
 
@@ -1104,6 +1126,32 @@ class Renderer:
         s = Stats()
         self._check(self.lib.ptx_get_stats(self.handle, C.byref(s)))
         return s
+
+    def noise_halves(self, enable: bool = True):
+        """ptx_noise_halves: make and zero the two half-images of the render extent (enable) or release them; bind one with
+        bind_accumulation(noise_half_ptr(which), accum_bytes) and render into it."""
+        self._check(self.lib.ptx_noise_halves(self.handle, 1 if enable else 0))
+
+    def noise_half_ptr(self, which: int) -> int:
+        return int(self.lib.ptx_device_noise_half_ptr(self.handle, which) or 0)
+
+    def noise_meter(self, samples_a: int, samples_b: int, exposure: float = 1.0, threshold: float = NOISE_DEFAULTS["threshold"],
+                    tile_shift: int = NOISE_DEFAULTS["tile_shift"], write_sum: bool = False):
+        """ptx_noise_meter: the per-tile error of the two halves (samples_a in half 0, samples_b in half 1) on mean * exposure; with
+        write_sum the internal accumulation image becomes A + B.  Asynchronous."""
+        d = NoiseDesc(samples_a, samples_b, exposure, threshold, tile_shift, NOISE_WRITE_SUM if write_sum else 0, (C.c_uint32 * 2)(0, 0))
+        self._check(self.lib.ptx_noise_meter(self.handle, C.byref(d)))
+
+    def read_noise(self, tile_errors: bool = False):
+        """ptx_read_noise: the NoiseResult of the last noise_meter(), with tile_errors=True also the tilesY x tilesX map of E_t
+        (float32); synchronises."""
+        out = NoiseResult()
+        self._check(self.lib.ptx_read_noise(self.handle, C.byref(out), None, 0))
+        if not tile_errors:
+            return out
+        tiles = np.empty((out.tilesY, out.tilesX), dtype=np.float32)
+        self._check(self.lib.ptx_read_noise(self.handle, C.byref(out), tiles.ctypes.data, tiles.nbytes))
+        return out, tiles
 
     def accum_ptr(self) -> int:
         return int(self.lib.ptx_device_accum_ptr(self.handle) or 0)

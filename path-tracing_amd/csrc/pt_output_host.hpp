@@ -3,9 +3,10 @@
 // ptx_meter_reset, ptx_postprocess_metered: section 21), the display transform behind them (ptx_grade, ptx_grade_lut, ptx_present_graded:
 // section 22), which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and
 // the local exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23),
-// and the enlarging screen path (ptx_present_upscaled: section 25), which is presentFrame with pt_upscale.hpp's kernel at its end.
+// and the enlarging screen path (ptx_present_upscaled: section 25), which is presentFrame with pt_upscale.hpp's kernel at its end,
+// and the noise metering of an offline render's two half-sums (ptx_noise_halves, ptx_noise_meter, ptx_read_noise: section 26).
 // What the entry points share stands first: the source rule, the refusal ladder, the read-back's end, ptx_resize's part (section 24).
-// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp, pt_upscale.hpp; state: OutputState, the member `output` of the handle.
+// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp, pt_upscale.hpp, pt_noise.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_frame_host.hpp, whose ptx_resize ends in outputResized; every function takes a valid or null
 // handle and returns a PTX_* code.
 #pragma once
@@ -566,9 +567,133 @@ static int readLocalExposure(PtxRenderer *r, void *host, size_t bytes)
     return readBack(r, host, r->output.localGain.p, bytes);
 }
 
+// ---- noise metering (docs/NEXT_ROWS.md section 26; semantics: include/ptx.h ptx_noise_meter; kernels: pt_noise.hpp) ------------------
+
+// ptx_noise_halves: the two images a host binds in turn.  Nothing here touches the render path: a half is bound with
+// ptx_bind_accumulation like any buffer of the caller's.
+static void dropNoiseHalves(PtxRenderer *r)
+{
+    OutputState::NoiseState &s = r->output.noise;
+    for (DevBuf<float4> &h : s.half)
+    {
+        if (h.p && r->frame.boundImage == h.p) // the binding returns to the internal image
+            r->frame.boundImage = nullptr;
+        h.release();
+    }
+}
+
+static int noiseHalves(PtxRenderer *r, uint32_t enable)
+{
+    const char *who = "ptx_noise_halves";
+    if (!r || enable > 1u)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a handle and enable 0 or 1", who);
+    if (!enable)
+    {
+        if (r->output.noise.half[0].p || r->output.noise.half[1].p)
+            HIP_TRY(r, hipSetDevice(r->device));
+        dropNoiseHalves(r);
+        return PTX_OK;
+    }
+    if (!r->frame.width)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_resize first", who);
+    HIP_TRY(r, hipSetDevice(r->device));
+    OutputState::NoiseState &s = r->output.noise;
+    for (DevBuf<float4> &h : s.half)
+    {
+        const hipError_t e = h.alloc(r->frame.pixels());
+        if (e != hipSuccess)
+        {
+            dropNoiseHalves(r); // both or none
+            HIP_TRY(r, e);
+        }
+    }
+    for (DevBuf<float4> &h : s.half)
+        HIP_TRY(r, hipMemsetAsync(h.p, 0, r->frame.bytes(), r->stream));
+    return PTX_OK;
+}
+
+// ptx_noise_meter: the tiles, then one workgroup that sums the workgroups' records.  Two launches, no synchronisation; every refusal
+// comes before the first allocation or launch.
+static int noiseMeter(PtxRenderer *r, const PtxNoiseDesc *d)
+{
+    const char *who = "ptx_noise_meter";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const uint32_t maxSamples = 1u << 24;
+    if (!d->samplesA || d->samplesA > maxSamples || !d->samplesB || d->samplesB > maxSamples || d->tileShift < 3u || d->tileShift > kNoiseBlockShift ||
+        (d->flags & ~(uint32_t)PTX_NOISE_WRITE_SUM) || d->reserved[0] || d->reserved[1])
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need samplesA and samplesB in 1 .. 2^24 (%u, %u), tileShift in 3 .. 6 (%u), no unknown flag (0x%x) and "
+                    "reserved 0 (%u, %u)", who, d->samplesA, d->samplesB, d->tileShift, d->flags, d->reserved[0], d->reserved[1]);
+    if (!finiteFloat(d->exposure) || !finiteFloat(d->threshold) || !(d->exposure > 0.0f) || d->threshold < 0.0f)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a finite exposure > 0 (%g) and a finite threshold >= 0 (%g)", who, (double)d->exposure,
+                    (double)d->threshold);
+    if (const int rc = outputRefusal(r, who, NEEDS_FRAME | NEEDS_ONE_SHARD))
+        return rc;
+    OutputState::NoiseState &s = r->output.noise;
+    if (!s.half[0].p || !s.half[1].p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no halves (call ptx_noise_halves)", who);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t W = r->frame.width, H = r->frame.height, sh = d->tileShift;
+    const uint32_t tilesX = (W + (1u << sh) - 1u) >> sh, tilesY = (H + (1u << sh) - 1u) >> sh;
+    const dim3 grid((W + kNoiseBlockSide - 1u) / kNoiseBlockSide, (H + kNoiseBlockSide - 1u) / kNoiseBlockSide);
+    const size_t tiles = (size_t)tilesX * tilesY, groups = (size_t)grid.x * grid.y;
+    HIP_TRY(r, s.result.alloc(1));
+    HIP_TRY(r, s.tiles.alloc(tiles));
+    HIP_TRY(r, s.tileErrors.alloc(tiles));
+    HIP_TRY(r, s.records.alloc(groups * kNoiseRecordWords));
+    NoiseArgs a;
+    a.halfA = s.half[0].p;
+    a.halfB = s.half[1].p;
+    a.sum = r->frame.image.p; // the internal image, whatever is bound
+    a.tiles = s.tiles.p;
+    a.tileErrors = s.tileErrors.p;
+    a.records = s.records.p;
+    a.width = W; a.height = H; a.tileShift = sh; a.tilesX = tilesX; a.tilesY = tilesY;
+    // step 2: rcp_ is the correctly rounded reciprocal on these arguments (1 .. 2^25), and so is the host's 1 / x
+    a.sa = d->exposure * (1.0f / (float)d->samplesA);
+    a.sb = d->exposure * (1.0f / (float)d->samplesB);
+    a.st = d->exposure * (1.0f / (float)(d->samplesA + d->samplesB));
+    a.threshold = d->threshold;
+    if (d->flags & PTX_NOISE_WRITE_SUM)
+        k_noise_tiles<true><<<grid, kNoiseBlock, 0, r->stream>>>(a);
+    else
+        k_noise_tiles<false><<<grid, kNoiseBlock, 0, r->stream>>>(a);
+    NoiseResolveArgs v;
+    v.records = s.records.p;
+    v.recordCount = (uint32_t)groups;
+    v.result = s.result.p;
+    v.tilesX = tilesX;
+    v.tilesY = tilesY;
+    v.calls = s.calls + 1u;
+    k_noise_resolve<<<1, kNoiseResolveBlock, 0, r->stream>>>(v);
+    HIP_TRY(r, hipGetLastError());
+    s.calls += 1u;
+    s.tilesX = tilesX;
+    s.tilesY = tilesY;
+    return PTX_OK;
+}
+
+static int readNoise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors, size_t bytes)
+{
+    const char *who = "ptx_read_noise";
+    if (!r || !out)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const OutputState::NoiseState &s = r->output.noise;
+    if (!s.calls)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_noise_meter first", who);
+    const size_t want = (size_t)s.tilesX * s.tilesY * sizeof(float);
+    if (tileErrors && bytes != want)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the tile map of %u x %u tiles is %zu bytes", who, s.tilesX, s.tilesY, want);
+    HIP_TRY(r, hipSetDevice(r->device));
+    if (tileErrors)
+        HIP_TRY(r, hipMemcpyAsync(tileErrors, s.tileErrors.p, want, hipMemcpyDeviceToHost, r->stream));
+    return readBack(r, out, s.result.p, sizeof(PtxNoiseResult));
+}
+
 // What ptx_resize does to the output stage: the output is not ready, G and the grid of ptx_local_exposure go with the extent they were
-// made for, and the meter starts over, its exposure having been metered on an image of the old extent.  The present image, the LUT and
-// the kept grade desc stay: they belong to the window and the display.
+// made for, as do the halves of ptx_noise_halves and the count of ptx_noise_meter calls, and the meter starts over, its exposure having
+// been metered on an image of the old extent.  The present image, the LUT and the kept grade desc stay: they belong to the window and
+// the display.
 static int outputResized(PtxRenderer *r)
 {
     OutputState &o = r->output;
@@ -576,5 +701,8 @@ static int outputResized(PtxRenderer *r)
     o.localGain.release();
     o.localGrid.release();
     o.localReady = false;
+    dropNoiseHalves(r);
+    o.noise.calls = 0u;
+    o.noise.tilesX = o.noise.tilesY = 0u;
     return meterReset(r);
 }

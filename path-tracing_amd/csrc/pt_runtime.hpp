@@ -41,6 +41,7 @@
 #include "pt_grade.hpp"
 #include "pt_local_exposure.hpp"
 #include "pt_upscale.hpp"
+#include "pt_noise.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -287,6 +288,18 @@ struct OutputState
     DevBuf<float> localGain;        // G, one float per pixel
     DevBuf<uint2> localGrid;        // the splatted grid and the blurred one behind it: 2 x ny x nx x 32 entries of (sum, count)
     bool localReady = false;        // an accepted ptx_local_exposure since the last ptx_resize
+    // noise metering (ptx_noise_halves, ptx_noise_meter, docs/NEXT_ROWS.md section 26): the halves are made by ptx_noise_halves(1), the
+    // rest by the first accepted ptx_noise_meter; ptx_resize (outputResized) releases the halves, whose extent they were made for
+    struct NoiseState
+    {
+        DevBuf<float4> half[2];         // A and B: two accumulation images the host binds with ptx_bind_accumulation
+        DevBuf<PtxNoiseResult> result;  // written whole by every call's second kernel
+        DevBuf<NoiseTile> tiles;        // (Q_t, n_t, converged) per tile ...
+        DevBuf<float> tileErrors;       // ... and E_t, the map ptx_read_noise copies out
+        DevBuf<uint32_t> records;       // kNoiseRecordWords words per workgroup of k_noise_tiles
+        uint32_t tilesX = 0, tilesY = 0; // of the last accepted call
+        uint32_t calls = 0;             // accepted calls since creation or ptx_resize
+    } noise;
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
 };
 

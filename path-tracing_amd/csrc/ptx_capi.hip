@@ -431,6 +431,26 @@ int ptx_present_upscaled(PtxRenderer *r, const PtxPresentDesc *desc, const PtxUp
     return presentFrame(r, desc, "ptx_present_upscaled", false, true, up);
 }
 
+int ptx_noise_halves(PtxRenderer *r, uint32_t enable)
+{
+    return noiseHalves(r, enable);
+}
+
+void *ptx_device_noise_half_ptr(PtxRenderer *r, uint32_t which)
+{
+    return r && which < 2u ? r->output.noise.half[which].p : nullptr;
+}
+
+int ptx_noise_meter(PtxRenderer *r, const PtxNoiseDesc *desc)
+{
+    return noiseMeter(r, desc);
+}
+
+int ptx_read_noise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors, size_t bytes)
+{
+    return readNoise(r, out, tileErrors, bytes);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

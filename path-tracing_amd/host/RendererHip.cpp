@@ -7,6 +7,7 @@ namespace PathTracing
 
 namespace
 {
+float PostProcessExposure(); // PostProcessSettings::Exposure, below
 PtxRenderer *s_Renderer = nullptr;
 std::shared_ptr<Scene> s_Scene; // SceneData::Handle (Renderer.h:187)
 RendererHip::PathTracingSettings s_PathTracingSettings;
@@ -17,6 +18,32 @@ bool s_DebugPipeline = false; // s_ActiveRaytracingPipeline == the debug pipelin
 PtxDebugViewDesc s_DebugView = { PTX_DEBUG_MODE_COLOR, 0u, 0u, 0u };
 bool s_AccumulationRestarted = true; // since the last temporal accumulation: the sum holds samples of a frame the history has not seen
 bool s_MotionVectors = false; // denoiser, temporal accumulation and TemporalSettings.MotionVectors are all on (UpdateMotionVectors)
+// noise metering (ptx.h "Noise metering"): the render calls alternate between the two halves
+RendererHip::NoiseSettings s_NoiseSettings;
+uint32_t s_NoiseSamples[2] = { 0, 0 }; // samples summed in half 0 / half 1
+uint32_t s_NoiseCalls = 0;             // render calls since the accumulation restarted: its parity names the next half
+PtxNoiseResult s_NoiseResult = {};     // of the last metered check, once read
+bool s_NoisePending = false;           // a ptx_noise_meter has been enqueued since s_NoiseResult was read
+
+bool NoiseIsOn()
+{
+    return s_NoiseSettings.Enabled && !s_DebugPipeline;
+}
+
+int BindNoiseHalf(uint32_t which)
+{
+    return ptx_bind_accumulation(s_Renderer, ptx_device_noise_half_ptr(s_Renderer, which), ptx_accum_bytes(s_Renderer));
+}
+
+// the check of Render, and with PTX_NOISE_WRITE_SUM what SaveOutput, Present and ReadAccumulationImage do first
+int MeterNoise(uint32_t flags)
+{
+    const PtxNoiseDesc desc = { s_NoiseSamples[0], s_NoiseSamples[1], PostProcessExposure(), s_NoiseSettings.Threshold, s_NoiseSettings.TileShift, flags, { 0u, 0u } };
+    const int rc = ptx_noise_meter(s_Renderer, &desc);
+    if (rc == PTX_OK)
+        s_NoisePending = true;
+    return rc;
+}
 }
 
 void RendererHip::Check(int status)
@@ -90,6 +117,13 @@ void RendererHip::ResetAccumulationImage()
 {
     s_TotalSamples = 0;
     s_AccumulationRestarted = true;
+    s_NoiseSamples[0] = s_NoiseSamples[1] = 0;
+    s_NoiseCalls = 0;
+    if (s_Renderer && s_Width && s_NoiseSettings.Enabled) // makes the halves, or zeroes them again; the sum is formed from them when it is needed
+    {
+        Check(ptx_noise_halves(s_Renderer, 1u));
+        return;
+    }
     if (s_Renderer && s_Width)
         Check(ptx_reset_accumulation(s_Renderer));
 }
@@ -119,10 +153,75 @@ void RendererHip::Render()
     if (s_DebugPipeline) // the debug raygen stores its one sample: nothing accumulates
     {
         s_TotalSamples = 0;
+        if (s_NoiseSettings.Enabled) // ... and it stores it into the internal image
+            Check(ptx_bind_accumulation(s_Renderer, nullptr, 0));
         Check(ptx_render_debug(s_Renderer, &rgenData, &lights, &s_DebugView));
         return;
     }
+    if (!s_NoiseSettings.Enabled)
+    {
+        Check(ptx_render(s_Renderer, &rgenData, &lights));
+        return;
+    }
+    // noise metering: this call's samples go to the half its parity names, and every CheckEvery calls the halves are compared
+    const uint32_t which = s_NoiseCalls & 1u;
+    Check(BindNoiseHalf(which));
     Check(ptx_render(s_Renderer, &rgenData, &lights));
+    s_NoiseSamples[which] += s_SamplesPerFrame;
+    s_NoiseCalls++;
+    const uint32_t every = s_NoiseSettings.CheckEvery ? s_NoiseSettings.CheckEvery : 1u;
+    if (s_NoiseCalls % every == 0u && s_NoiseSamples[1] && s_NoiseSamples[0] + s_NoiseSamples[1] >= s_NoiseSettings.MinSamples)
+        Check(MeterNoise(0u));
+}
+
+// With the NoiseSettings on the running sum is A + B: ptx_noise_meter forms it in the internal image (PTX_NOISE_WRITE_SUM), which is then
+// bound for the calls that read the sum.  Before the second render call there is no B to meter: half 0 is the sum and stays bound.
+static int BindNoiseSum()
+{
+    if (!NoiseIsOn())
+        return PTX_OK;
+    if (!s_NoiseSamples[1])
+        return BindNoiseHalf(0u);
+    if (const int rc = MeterNoise(PTX_NOISE_WRITE_SUM))
+        return rc;
+    return ptx_bind_accumulation(s_Renderer, nullptr, 0);
+}
+
+// ... and afterwards the half of the next render call is bound again
+static int RebindNoiseHalf()
+{
+    return NoiseIsOn() ? BindNoiseHalf(s_NoiseCalls & 1u) : (int)PTX_OK;
+}
+
+void RendererHip::SetSettings(const NoiseSettings &settings)
+{
+    const bool change = settings.Enabled != s_NoiseSettings.Enabled;
+    s_NoiseSettings = settings;
+    if (!change)
+        return;
+    if (!settings.Enabled && s_Renderer) // the binding returns to the internal image
+        Check(ptx_noise_halves(s_Renderer, 0u));
+    s_NoiseResult = {};
+    s_NoisePending = false;
+    ResetAccumulationImage(); // the samples so far are in the other kind of image
+}
+
+PtxNoiseResult RendererHip::GetNoise()
+{
+    if (s_NoisePending)
+    {
+        Check(ptx_read_noise(s_Renderer, &s_NoiseResult, nullptr, 0));
+        s_NoisePending = false;
+    }
+    return s_NoiseResult;
+}
+
+bool RendererHip::IsConverged()
+{
+    if (!NoiseIsOn())
+        return false;
+    const PtxNoiseResult res = GetNoise();
+    return res.valid && res.converged == res.tilesX * res.tilesY && s_NoiseSamples[0] + s_NoiseSamples[1] >= s_NoiseSettings.MinSamples;
 }
 
 // Renderer.cpp:579-610 / :769-772
@@ -147,6 +246,14 @@ uint32_t RendererHip::GetTotalSamples()
 }
 
 static RendererHip::PostProcessSettings s_PostProcessSettings;
+
+namespace
+{
+float PostProcessExposure()
+{
+    return s_PostProcessSettings.Exposure;
+}
+}
 
 void RendererHip::SetPostProcessSettings(const PostProcessSettings &settings)
 {
@@ -346,9 +453,11 @@ void RendererHip::SaveOutput(const OutputInfo &info)
     const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
                                              s_PostProcessSettings.BloomIntensity };
     const uint32_t mode = s_PostProcessSettings.Hdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR;
+    Check(BindNoiseSum());
     Check(PostProcessFrame(u, mode));
     if (GradeIsOn())
         Check(ptx_grade(s_Renderer, &s_GradeDesc, mode));
+    Check(RebindNoiseHalf());
     const uint32_t format = OutputSaver::SelectImageFormat(info.Format);
     std::vector<std::byte> bytes(static_cast<size_t>(s_Width) * s_Height * (format == PTX_OUTPUT_RGBA32F ? 16 : 4));
     Check(ptx_read_output(s_Renderer, format, bytes.data(), bytes.size()));
@@ -376,9 +485,11 @@ void RendererHip::Present(uint32_t width, uint32_t height, const uint8_t *ui)
     const PtxPostProcessingUniformData u = { GetTotalSamples(), s_PostProcessSettings.Exposure, s_PostProcessSettings.BloomThreshold,
                                              s_PostProcessSettings.BloomIntensity };
     const uint32_t mode = s_SurfaceIsHdr ? PTX_TONE_MAPPING_HDR : PTX_TONE_MAPPING_SDR; // Renderer.cpp:737-742
+    Check(BindNoiseSum());
     Check(PostProcessFrame(u, mode));
     if (GradeIsOn())
         Check(ptx_grade(s_Renderer, &s_GradeDesc, mode));
+    Check(RebindNoiseHalf());
     const PtxPresentDesc desc = { width, height, s_SurfaceIsHdr ? (uint32_t)PTX_PRESENT_A2B10G10R10_UNORM : (uint32_t)PTX_PRESENT_R8G8B8A8_SRGB, mode, ui, 0u, 0u };
     if (s_UpscaleSettings.Enabled && width >= s_Width && height >= s_Height) // ptx.h, "Enlarging screen path": a smaller window stays with the blit
     {
@@ -399,7 +510,9 @@ std::vector<std::byte> RendererHip::ReadPresent()
 std::vector<float> RendererHip::ReadAccumulationImage()
 {
     std::vector<float> image(static_cast<size_t>(s_Width) * s_Height * 4);
+    Check(BindNoiseSum());
     Check(ptx_readback(s_Renderer, image.data(), image.size() * sizeof(float)));
+    Check(RebindNoiseHalf());
     return image;
 }
 

@@ -189,6 +189,27 @@ public:
         float Sharpness = 0.5f;
     };
     static void SetSettings(const UpscaleSettings &settings);
+    // Noise metering (ptx.h "Noise metering", docs/NEXT_ROWS.md section 26), for an offline render that should stop on a noise
+    // threshold and not on a sample count.  Enabled: Render() binds one of the two halves of ptx_noise_halves -- half 0 on its even
+    // calls since the accumulation restarted, half 1 on its odd ones -- before ptx_render and keeps both sample counts; every
+    // CheckEvery calls, once MinSamples samples are in, it enqueues ptx_noise_meter on PostProcessSettings::Exposure.  GetNoise() reads
+    // the last check's result (it synchronises when one is outstanding) and IsConverged() is true when every tile of it is converged.
+    // SaveOutput, Present and ReadAccumulationImage first meter with PTX_NOISE_WRITE_SUM, bind the internal image, which then holds
+    // A + B, for their calls and bind the next half again; before the second render call half 0 is the sum.  ResetAccumulationImage
+    // zeroes both halves and the counts.  A debug-view frame is shown as it is.  Disabled (the default): Render, SaveOutput and
+    // Present enqueue exactly what they did, and nothing is allocated.  The defaults are NOISE_DEFAULTS of the Python package; nobody
+    // has tuned the threshold.
+    struct NoiseSettings
+    {
+        bool Enabled = false;
+        float Threshold = 0.02f;
+        uint32_t TileShift = 4;
+        uint32_t CheckEvery = 8;
+        uint32_t MinSamples = 16;
+    };
+    static void SetSettings(const NoiseSettings &settings);
+    static bool IsConverged();
+    static PtxNoiseResult GetNoise();
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either

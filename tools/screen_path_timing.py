@@ -49,7 +49,14 @@ same run beside it: the 8-spp chess_like frame rendered at 1920 x 1080 and shown
 as an SDR sRGB8 and as an HDR10 surface.  --extent W H takes one render extent in place of the two; the screen is twice it on both axes.
 A kernel trace of `--upscale --extent W H` gives k_present_upscaled's and k_present's device times.
 
-Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--local] [--upscale] [--extent W H]"""
+ptx_noise_meter (section 26): --noise times nothing but it, with and without PTX_NOISE_WRITE_SUM at every tileShift, on two halves of four
+chess_like frames each rendered by alternating bindings, with ptx_despike at radius 1 and ptx_meter of the same run beside it (the
+neighbours that read 16 bytes per pixel).  It is given against 32 algorithmic bytes per pixel (both halves in) and 48 with the flag (S
+out) -- a rate, not a bandwidth: the halves of a back-to-back run at 1920 x 1080 are 66 MB and fit the last-level cache, at 3840 x 2160
+they are 265 MB and do not.  A kernel trace of `--noise --extent W H` gives k_noise_tiles', k_noise_resolve's, k_despike<1>'s and
+k_meter_histogram's device times.
+
+Not a test and no part of bench.py.  Usage: tools/screen_path_timing.py [--json FILE] [--detail D] [--guides-only] [--temporal-only] [--meter] [--grade [--desc NAME]] [--local] [--upscale] [--noise] [--extent W H]"""
 import json
 import math
 import os
@@ -71,6 +78,7 @@ MOMENTS_BYTES_PER_PIXEL = 208
 RESPONSIVE_BYTES_PER_PIXEL = 240
 GRADE_BYTES_PER_PIXEL = 40  # 24 in (post-process image, bloom level 0), 16 out; the LUT's reads are cache hits
 LOCAL_EXPOSURE_BYTES_PER_PIXEL = 36  # the sum twice (splat, gain) and G out; the grid is 2 x 16 B x 32 slices per cell
+NOISE_BYTES_PER_PIXEL = {False: 32, True: 48}  # both halves in; S out with PTX_NOISE_WRITE_SUM; tile and workgroup records are noise beside them
 METER_BYTES_PER_PIXEL = 16  # one load of the pixel; the slabs (1 MB at the most) and the state are noise beside it
 # 16 B out and 16 B x (tile + halo) / tile in: the halo is 84 entries of 256 at radius 1 and 176 at radius 2
 DESPIKE_BYTES_PER_PIXEL = {1: 16 + 16 * (256 + 84) / 256, 2: 16 + 16 * (256 + 176) / 256}
@@ -97,7 +105,8 @@ def main():
     out = {}
     guides_only, temporal_only, meter_only = "--guides-only" in sys.argv, "--temporal-only" in sys.argv, "--meter" in sys.argv
     grade_only, local_only, upscale_only = "--grade" in sys.argv, "--local" in sys.argv, "--upscale" in sys.argv
-    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only or local_only or upscale_only else ("chess_like", "default") if guides_only else
+    noise_only = "--noise" in sys.argv
+    scenes = {name: pkg.Scene(name, detail) for name in (("chess_like",) if temporal_only or meter_only or grade_only or local_only or upscale_only or noise_only else ("chess_like", "default") if guides_only else
                                                           ("chess_like", "atrium_like", "default"))}
     renderers = {}
     for name, scene in scenes.items():
@@ -183,6 +192,32 @@ def main():
                 G = r.read_local_exposure()
                 rec[f"local_exposure_result_{frame}"] = {"min_gain": float(G.min()), "max_gain": float(G.max()), "exposure": r.read_meter().exposure}
                 rec[f"postprocess_local_{frame}"] = timed(r, lambda: r.postprocess_local(STEP_SPP, metered=True, **POST))
+            out[f"{w}x{h}"] = rec
+            for k, v in rec.items():
+                print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
+            continue
+        if noise_only:
+            half = STEP_SPP // 2
+            r.noise_halves(True)
+            for f in range(STEP_SPP):
+                r.bind_accumulation(r.noise_half_ptr(f & 1), w * h * 16)
+                u.TotalSamples = f
+                r.render(u, scene.lights)
+            r.bind_accumulation(0, 0)
+            for write_sum in (False, True):
+                for shift in (3, 4, 5, 6):
+                    t = timed(r, lambda: r.noise_meter(half, half, POST["exposure"], tile_shift=shift, write_sum=write_sum))
+                    t["algorithmic_GB_per_s"] = w * h * NOISE_BYTES_PER_PIXEL[write_sum] / (t["median_ms"] * 1e-3) / 1e9
+                    rec[f"noise_meter_shift_{shift}{'_write_sum' if write_sum else ''}"] = t
+            res = r.read_noise()
+            rec["noise_result"] = {"mean_error": res.meanError, "max_error": res.maxError, "converged": res.converged, "tiles": res.tilesX * res.tilesY,
+                                   "counted": res.counted, "black": res.black, "rejected": res.rejected}
+            p1 = dict(pkg.DESPIKE_DEFAULTS, radius=1, min_taps=max(3, pkg.DESPIKE_DEFAULTS["rank"]))
+            rec["despike_radius_1"] = timed(r, lambda: r.despike(**p1))  # on the internal image, which holds A + B now
+            t = timed(r, lambda: r.meter(STEP_SPP, delta_seconds=1.0 / 60))
+            t["algorithmic_GB_per_s"] = w * h * METER_BYTES_PER_PIXEL / (t["median_ms"] * 1e-3) / 1e9
+            rec["meter_average"] = t
+            r.noise_halves(False)
             out[f"{w}x{h}"] = rec
             for k, v in rec.items():
                 print(f"{w}x{h} {k}: {json.dumps(v)}", flush=True)
