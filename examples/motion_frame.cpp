@@ -30,7 +30,10 @@
 // The file holds, per frame, the running sum, T (ptx_read_temporal) and the output image (ptx_read_output, RGBA32F): 2 x 3 x width x
 // height x 16 bytes.  With the grade argument given -- 0 or 1 -- the two presented images follow, 2 x 100 x 37 x 4 bytes (R8G8B8A8), or
 // 2 x 100 x 68 x 4 with the upscale argument at 1.  The trailer of the noise argument: per frame the PtxNoiseResult GetNoise() returned after
-// the frame's render calls and IsConverged() as a uint32, then one uint32 that says whether the handle holds halves at the end.
+// the frame's render calls and IsConverged() as a uint32, then one uint32 that says whether the handle holds halves at the end.  The trailer
+// of the adaptive argument (AdaptiveSettings, section 27, tests/test_adaptive.py; 0: off, d + 1: on with Dilate d and a noise threshold
+// of 0.05, at which the plans of the test's small frame are partial) follows it: per frame the PtxAdaptivePlan in force after the frame's
+// render calls.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,10 +53,10 @@ static void Check(int status, const char *what)
 
 int main(int argc, char **argv)
 {
-    if (argc < 9 || argc > 17)
+    if (argc < 9 || argc > 18)
     {
         std::fprintf(stderr, "usage: motion_frame scene width height spp depth timeStep variance(0|1) out.bin [responsive(0|1) [despike(0|1) [denoiser(0|1) [exposure(0|1|2: with local exposure) "
-                             "[grade(0|1) [lut.cube|- [upscale(0|1) [noise(0|1)]]]]]]]]\n");
+                             "[grade(0|1) [lut.cube|- [upscale(0|1) [noise(0|1) [adaptive(0: off, d + 1: on with Dilate d)]]]]]]]]]\n");
         return 1;
     }
     const std::string name = argv[1];
@@ -68,6 +71,8 @@ int main(int argc, char **argv)
     const bool useLut = argc >= 15 && std::strcmp(argv[14], "-") != 0;
     const bool useUpscale = argc >= 16 && std::atoi(argv[15]) != 0;
     const bool noiseTrailer = argc >= 17, useNoise = noiseTrailer && std::atoi(argv[16]) != 0;
+    const bool adaptiveTrailer = argc >= 18, useAdaptive = adaptiveTrailer && std::atoi(argv[17]) != 0;
+    const uint32_t adaptiveDilate = useAdaptive ? static_cast<uint32_t>(std::atoi(argv[17])) - 1u : 0u;
     const uint32_t screenWidth = 100, screenHeight = useUpscale ? 68 : 37; // below the render extent on one axis, or above it on both
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     try
@@ -110,7 +115,14 @@ int main(int argc, char **argv)
         noise.Enabled = useNoise;
         noise.CheckEvery = 4;
         noise.MinSamples = 4;
+        if (useAdaptive)
+            noise.Threshold = 0.05f; // where some tiles of animated_test at 67 x 45 pass at the first check and some never do: partial plans
         RendererHip::SetSettings(noise);
+        RendererHip::AdaptiveSettings adaptive; // the margin and the threshold above are what tests/test_adaptive.py repeats by hand
+        adaptive.Enabled = useAdaptive;
+        if (useAdaptive)
+            adaptive.Dilate = adaptiveDilate;
+        RendererHip::SetSettings(adaptive);
         scene->Update(0.0f);
         RendererHip::UpdateSceneData(scene, true);
         RendererHip::OnResize(width, height);
@@ -120,7 +132,8 @@ int main(int argc, char **argv)
         const size_t bytes = static_cast<size_t>(width) * height * 16;
         const size_t screenBytes = static_cast<size_t>(screenWidth) * screenHeight * 4;
         const size_t trailerAt = 6 * bytes + (presentToo ? 2 * screenBytes : 0), perFrame = sizeof(PtxNoiseResult) + 4;
-        std::vector<char> file(trailerAt + (noiseTrailer ? 2 * perFrame + 4 : 0));
+        const size_t adaptiveAt = trailerAt + (noiseTrailer ? 2 * perFrame + 4 : 0);
+        std::vector<char> file(adaptiveAt + (adaptiveTrailer ? 2 * sizeof(PtxAdaptivePlan) : 0));
         const std::string scratch = std::string(argv[8]) + ".png";
         for (int frame = 0; frame < 2; frame++)
         {
@@ -147,6 +160,12 @@ int main(int argc, char **argv)
                 const uint32_t converged = RendererHip::IsConverged() ? 1u : 0u;
                 std::memcpy(&file[trailerAt + frame * perFrame], &res, sizeof(res));
                 std::memcpy(&file[trailerAt + frame * perFrame + sizeof(res)], &converged, 4);
+            }
+            if (adaptiveTrailer) // zeros where the handle holds no counts
+            {
+                PtxAdaptivePlan plan = {};
+                (void)ptx_read_adaptive(RendererHip::GetHandle(), &plan, nullptr, 0, nullptr, 0);
+                std::memcpy(&file[adaptiveAt + frame * sizeof(plan)], &plan, sizeof(plan));
             }
             const std::vector<float> sum = RendererHip::ReadAccumulationImage();
             std::memcpy(&file[(3 * frame) * bytes], sum.data(), bytes);

@@ -20,6 +20,7 @@
 //   examples/render_scene atrium_like 640 360 16 4 local.png --local-exposure  (local exposure behind the meter: highlights and shadows move towards middle grey)
 //   examples/render_scene default 640 360 16 4 graded.png --curve aces --temperature 4500 --lut look.cube   (display transform: tone curve reference | reinhard | hable | aces,
 //                                                                            white balance for a light of that many kelvin, a .cube 3-D LUT)
+//   examples/render_scene default 640 360 4096 4 out.png --noise-threshold 0.02 --adaptive   (... and adaptive sampling: each check plans the tiles the next render calls cover)
 //   examples/render_scene default 640 360 4096 4 out.png --noise-threshold 0.02   (noise metering: the sample count is the maximum; the render stops at the
 //                                                                            first check where every tile's error is at or below the threshold)
 //   examples/render_scene file:scene.gltf 640 360 16 4 out.png --native-bc   (.dds textures uploaded as blocks and decoded on the device)
@@ -224,6 +225,21 @@ int main(int argc, char **argv)
             argc -= 2;
             break;
         }
+    RendererHip::AdaptiveSettings adaptive; // --adaptive: beside --noise-threshold, every check plans the tiles the render calls that follow cover
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--adaptive")
+        {
+            adaptive.Enabled = true;
+            for (int k = i; k + 1 < argc; k++)
+                argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
+    if (adaptive.Enabled && !noise.Enabled)
+    {
+        std::fprintf(stderr, "--adaptive needs --noise-threshold T\n");
+        return 1;
+    }
     bool nativeBc = false; // --native-bc: the .dds textures of an imported scene are uploaded as BC1 / BC3 / BC5 blocks
     for (int i = 1; i < argc; i++)
         if (std::string(argv[i]) == "--native-bc")
@@ -259,16 +275,29 @@ int main(int argc, char **argv)
         RendererHip::SetSettings(grade);
         RendererHip::SetSettings(upscale);
         RendererHip::SetSettings(noise);
+        RendererHip::SetSettings(adaptive);
         if (debugMode >= 0)
             RendererHip::SetDebugRaytracingPipeline(static_cast<uint32_t>(debugMode));
+        // RendererHip's own rule: at least 1, and with adaptive sampling rounded up to an even number
+        uint32_t checkEvery = noise.CheckEvery ? noise.CheckEvery : 1u;
+        if (adaptive.Enabled)
+            checkEvery += checkEvery & 1u;
         uint32_t used = 0;
+        uint64_t pathSamples = 0; // --adaptive: what the render calls traced (ptx_get_stats waits for each: the price of the report)
         for (uint32_t i = 0; i < (debugMode >= 0 ? 1u : spp); i++) // one sample per frame, like a Profile/Debug build (Config.h:34-36)
         {
             RendererHip::Render();
             used++;
+            if (adaptive.Enabled && debugMode < 0)
+            {
+                PtxStats stats;
+                if (ptx_get_stats(RendererHip::GetHandle(), &stats) != PTX_OK)
+                    throw error(std::string("ptx_get_stats: ") + ptx_last_error(RendererHip::GetHandle()));
+                pathSamples += stats.pathSamples;
+            }
             // the third stop condition beside MaxSampleCount and MaxTime (Renderer.cpp:1701-1704): asked only after a check, so that
             // the other render calls stay asynchronous
-            if (noise.Enabled && debugMode < 0 && used % noise.CheckEvery == 0u && RendererHip::IsConverged())
+            if (noise.Enabled && debugMode < 0 && used % checkEvery == 0u && RendererHip::IsConverged())
                 break;
         }
         if (noise.Enabled && debugMode < 0)
@@ -277,6 +306,9 @@ int main(int argc, char **argv)
             std::printf("noise threshold %g: %u of at most %u samples used, %s; last check: mean error %.6g, max %.6g, %u of %u tiles converged\n", (double)noise.Threshold,
                         used, spp, RendererHip::IsConverged() ? "converged" : "not converged", (double)res.meanError, (double)res.maxError, res.converged,
                         res.tilesX * res.tilesY);
+            if (adaptive.Enabled)
+                std::printf("adaptive sampling: %.3f samples per pixel on average (%llu path samples over %u pixels), stopped at sample %u\n",
+                            (double)pathSamples / ((double)width * height), (unsigned long long)pathSamples, width * height, used);
         }
         const std::vector<float> acc = RendererHip::ReadAccumulationImage();
         const float inv = 1.0f / static_cast<float>(RendererHip::GetTotalSamples());

@@ -1694,13 +1694,113 @@ PTX_API void *ptx_device_noise_half_ptr(PtxRenderer *r, uint32_t which);
  * threshold that is not finite; exposure <= 0; threshold < 0.  PTX_ERROR_NOT_READY: no image (ptx_resize); a shard accumulation buffer
  * bound; a tile shard with worldSize > 1; no halves.
  * Known limits: S = A + B is not the bits of one sum accumulated in frame order; unequal halves bias e; the criterion is per tile, with
- * no hierarchy; sharded frames are refused; there is no adaptive sampling: the estimate stops a render, it does not steer one. */
+ * no hierarchy; sharded frames are refused; this call does no adaptive sampling itself: ptx_adaptive_plan (below) steers a render by its
+ * tile records. */
 PTX_API int ptx_noise_meter(PtxRenderer *r, const PtxNoiseDesc *desc);
 /* The result of the last accepted ptx_noise_meter and, where tileErrors is not NULL, its tile map: tilesX * tilesY floats E_t,
  * row-major, `bytes` being exactly their size (with tileErrors NULL `bytes` is not read).  Synchronous, as ptx_read_output is.
  * PTX_ERROR_INVALID_ARGUMENT: a NULL handle or result.  PTX_ERROR_NOT_READY: no accepted ptx_noise_meter since creation or the last
  * ptx_resize.  PTX_ERROR_INVALID_ARGUMENT: a `bytes` that does not match. */
 PTX_API int ptx_read_noise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors /* may be NULL */, size_t bytes);
+
+/* ------------------------------------------------------------------------- */
+/* Adaptive sampling (docs/NEXT_ROWS.md section 27): the noise meter's tile    */
+/* records, or a mask of the host's, become the list of tiles the next render  */
+/* calls cover, and the frames every tile has received are counted per half.   */
+/* An addition: every call above computes what it computed before, and a host  */
+/* that never calls these allocates nothing for them.                          */
+/* ------------------------------------------------------------------------- */
+
+enum { PTX_ADAPTIVE_FROM_NOISE = 0u, PTX_ADAPTIVE_FROM_MASK = 1u }; /* PtxAdaptiveDesc::source */
+
+typedef struct PtxAdaptiveDesc {
+    uint32_t       tileShift;        /* tiles of 2^tileShift pixels a side, 3 .. 6 */
+    uint32_t       source;           /* PTX_ADAPTIVE_FROM_NOISE / PTX_ADAPTIVE_FROM_MASK */
+    const uint8_t *mask;             /* FROM_MASK: tilesX * tilesY bytes of the host's, row-major, copied in; else not read */
+    uint32_t       dilate;           /* 0 .. 2: the margin around the seeds, in tiles */
+    uint32_t       framesA, framesB; /* frames rendered into half 0 / half 1 under the plan being replaced, each 0 .. 2^24 */
+    uint32_t       flags;            /* none defined: 0 */
+    uint32_t       reserved[2];
+} PtxAdaptiveDesc;
+
+typedef struct PtxAdaptivePlan {
+    uint32_t tilesX, tilesY;
+    uint32_t activeTiles, activePixels; /* the list's length, and the pixels inside the image of its tiles */
+    uint32_t seedTiles;
+    uint32_t generation;                /* accepted ptx_adaptive_plan calls since the counts were made */
+} PtxAdaptivePlan;
+
+typedef struct PtxAdaptiveMeterDesc {
+    uint32_t pendingA, pendingB; /* frames rendered into half 0 / half 1 under the plan in force, not committed yet, each 0 .. 2^24 */
+    uint32_t normalizeTo;        /* PTX_NOISE_WRITE_SUM stores every tile's sum scaled to this many samples, 1 .. 2^25 */
+    float    exposure;           /* as PtxNoiseDesc's */
+    float    threshold;
+    uint32_t tileShift;          /* the counts' own */
+    uint32_t flags;              /* PTX_NOISE_WRITE_SUM */
+    uint32_t reserved[2];
+} PtxAdaptiveMeterDesc;
+
+/* ptx_adaptive_plan.  W x H is the render extent; tiles are ptx_noise_meter's (step 6): tile t = ty * tilesX + tx holds the pixels with
+ * x >> tileShift = tx and y >> tileShift = ty, tilesX = ceil(W / 2^tileShift), tilesY likewise, ragged tiles at the right and bottom
+ * edges.  The handle keeps two counts per tile, countA[t] and countB[t] (uint32): the frames the tile has received in half 0 and in
+ * half 1.  They are made and zeroed by the first accepted call, zeroed again by ptx_noise_halves(1), and dropped with the plan by
+ * ptx_resize, by a ptx_set_tile_shard that changes the shard and by ptx_noise_halves(0).  One launch of one workgroup on the render
+ * stream, integers only:
+ *   1. COMMIT.  For every tile t active in the plan being replaced, countA[t] += framesA and countB[t] += framesB: the frames the
+ *      host rendered into half 0 and half 1 under that plan.  With no plan in force every tile counts as active: this is how uniform
+ *      warm-up frames enter the counts.
+ *   2. SEED AND DILATE.  PTX_ADAPTIVE_FROM_NOISE: t is a seed iff the tile record of the last accepted ptx_noise_meter or
+ *      ptx_noise_meter_adaptive marks it not converged.  PTX_ADAPTIVE_FROM_MASK: t is a seed iff mask[t] != 0.  A tile is active iff
+ *      some seed lies within Chebyshev distance `dilate` of it: max(|tx - sx|, |ty - sy|) <= dilate, in tiles.  The margin keeps a
+ *      seam from forming between a frozen tile and a neighbour that is still refined.
+ *   3. COMPACT.  The ids of the active tiles are written to a device list in ascending order, by a scan; the order is part of the
+ *      contract and no atomic's arrival order can show in it.  activeTiles is its length, activePixels the pixels of its tiles that
+ *      lie inside the image (a ragged tile counts less), seedTiles the number of seeds.
+ * The list is unique and sorted by construction and no call takes a list from the host, so two slots never own one pixel.
+ * While a plan is in force ptx_render and ptx_render_frames cover the listed tiles only, in tiles of 2^tileShift pixels: a pixel of
+ * an active tile receives, bit for bit, what the unplanned call would have added to it (the random numbers are a function of pixel,
+ * width and frame alone), every other pixel keeps its bits, and PtxStats::pathSamples is activePixels * frames * SampleCount plus
+ * retries.  An empty plan (activeTiles = 0) renders and accumulates nothing.  ptx_render_guides and its kin, ptx_render_debug, the
+ * shard calls and the output stage keep the whole frame.  ptx_bind_shard_accumulation with a buffer drops the plan, as
+ * ptx_adaptive_clear does.
+ * SYNCHRONOUS: the call ends with a read-back of *out, as ptx_read_noise does, because the host sizes the next launches by
+ * activeTiles.  It needs no scene and so works on a borrower of a shared one.
+ * Refusals, in this order, all before the first launch; a refused call leaves the plan, the counts and the list intact.
+ * (1) PTX_ERROR_INVALID_ARGUMENT: a NULL handle, desc or out; tileShift outside 3 ... 6; a source other than the two; a flag bit;
+ * reserved != 0; dilate > 2; framesA or framesB above 2^24; a NULL mask under PTX_ADAPTIVE_FROM_MASK.  (2) PTX_ERROR_NOT_READY: no
+ * image (ptx_resize); a shard accumulation buffer bound; a tile shard with worldSize > 1.  (3) PTX_ERROR_NOT_READY: under
+ * PTX_ADAPTIVE_FROM_NOISE no accepted meter call, or one of another tileShift.  (4) PTX_ERROR_NOT_READY: a tileShift that differs
+ * from the counts' own while a count may be non-zero, or while a plan is in force and framesA or framesB is not 0 (with all counts
+ * zero and nothing to commit the counts are made anew for the new tileShift).
+ * Known limits: one workgroup builds the plan; the learnt bounce schedule is keyed on the slot count and so starts anew with every
+ * plan; sharded frames are refused; counts are per tile, not per pixel. */
+PTX_API int ptx_adaptive_plan(PtxRenderer *r, const PtxAdaptiveDesc *desc, PtxAdaptivePlan *out);
+/* The plan in force, its list (activeTiles uint32 ids, ascending) and the counts (countA[0 .. numTiles), then countB[0 .. numTiles)).
+ * `tiles` and `counts` may each be NULL, and then its byte count is not read; otherwise tileBytes is exactly activeTiles * 4 and
+ * countBytes exactly 2 * tilesX * tilesY * 4.  With no plan in force (ptx_adaptive_clear) activeTiles, activePixels and seedTiles are
+ * 0 and the list is empty.  Synchronous.  PTX_ERROR_INVALID_ARGUMENT: a NULL handle or out.  PTX_ERROR_NOT_READY: no counts (no
+ * accepted ptx_adaptive_plan since they were last dropped).  PTX_ERROR_INVALID_ARGUMENT: a byte count that does not match. */
+PTX_API int ptx_read_adaptive(PtxRenderer *r, PtxAdaptivePlan *out, uint32_t *tiles, size_t tileBytes, uint32_t *counts, size_t countBytes);
+/* Drops the plan: render calls cover the frame again.  The counts stay.  PTX_ERROR_INVALID_ARGUMENT: a NULL handle. */
+PTX_API int ptx_adaptive_clear(PtxRenderer *r);
+/* ptx_noise_meter_adaptive: ptx_noise_meter on halves whose tiles have received different numbers of frames.  It shares
+ * ptx_noise_meter's kernel bodies, writes the same state, and ptx_read_noise reads it.  It differs from ptx_noise_meter's steps so:
+ *   COUNTS PER TILE.  NA_t = countA[t] + (active(t) ? pendingA : 0), NB_t likewise from countB and pendingB, N_t = NA_t + NB_t.
+ *      active(t): t is in the plan in force; with no plan in force every tile is active.
+ *   STEP 2 PER TILE.  sa_t = exposure * rcp((float)NA_t), sb_t = exposure * rcp((float)NB_t), st_t = exposure * rcp((float)N_t),
+ *      and steps 3 - 5 of a pixel use its tile's factors.
+ *   STEPS 3 - 7 are unchanged, with one exception: a tile with NA_t == 0 or NB_t == 0 has all its pixels REJECTED and is not
+ *      converged, whatever E_t = 0 would say.  An unsampled tile never freezes.
+ *   STEP 1 under PTX_NOISE_WRITE_SUM stores S where N_t == normalizeTo or N_t == 0, and S * k_t elsewhere,
+ *      k_t = (float)normalizeTo * rcp((float)N_t), applied per component, alpha included.  ptx_postprocess with TotalSamples =
+ *      normalizeTo then shows every tile's own mean; the output stage and the chain know nothing of halves or of counts.  The host
+ *      passes the largest N_t: the frames of its render calls so far.
+ * Asynchronous, two launches, as ptx_noise_meter.  Refusals, in this order; a refused call leaves the state, the tile map and the
+ * internal image intact.  PTX_ERROR_INVALID_ARGUMENT: a NULL argument; pendingA or pendingB above 2^24; normalizeTo outside
+ * 1 ... 2^25; tileShift outside 3 ... 6; unknown flag bits; reserved != 0; an exposure or threshold that is not finite; exposure <= 0;
+ * threshold < 0.  PTX_ERROR_NOT_READY: ptx_noise_meter's, in its order; then no counts (call ptx_adaptive_plan first); then a
+ * tileShift that differs from the counts' own. */
+PTX_API int ptx_noise_meter_adaptive(PtxRenderer *r, const PtxAdaptiveMeterDesc *desc);
 
 PTX_API int ptx_test_input_stride(uint32_t fn);
 PTX_API int ptx_test_output_stride(uint32_t fn);

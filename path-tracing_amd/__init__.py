@@ -76,6 +76,7 @@ PTX_SYMBOLS = [
     "ptx_local_exposure", "ptx_read_local_exposure", "ptx_device_local_exposure_ptr", "ptx_postprocess_local",
     "ptx_present_upscaled",
     "ptx_noise_halves", "ptx_device_noise_half_ptr", "ptx_noise_meter", "ptx_read_noise",
+    "ptx_adaptive_plan", "ptx_read_adaptive", "ptx_adaptive_clear", "ptx_noise_meter_adaptive",
 ]
 PTH_SYMBOLS = [
     "pth_scene_names", "pth_scene_create", "pth_scene_create_ex", "pth_scene_destroy", "pth_last_error", "pth_scene_desc",
@@ -303,6 +304,26 @@ NOISE_WRITE_SUM = 1  # PTX_NOISE_WRITE_SUM
 # The defaults of Renderer.noise_meter and of RendererHip::NoiseSettings (docs/NEXT_ROWS.md section 26): tiles of 16 x 16 pixels, a check
 # every eight render calls, none before 16 samples.  Nobody has tuned the threshold: it is a starting point, not the result of a sweep.
 NOISE_DEFAULTS = dict(threshold=0.02, tile_shift=4, check_every=8, min_samples=16)
+
+
+class AdaptiveDesc(C.Structure):
+    _fields_ = [("tileShift", C.c_uint32), ("source", C.c_uint32), ("mask", C.c_void_p), ("dilate", C.c_uint32), ("framesA", C.c_uint32),
+                ("framesB", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class AdaptivePlan(C.Structure):
+    _fields_ = [("tilesX", C.c_uint32), ("tilesY", C.c_uint32), ("activeTiles", C.c_uint32), ("activePixels", C.c_uint32), ("seedTiles", C.c_uint32),
+                ("generation", C.c_uint32)]
+
+
+class AdaptiveMeterDesc(C.Structure):
+    _fields_ = [("pendingA", C.c_uint32), ("pendingB", C.c_uint32), ("normalizeTo", C.c_uint32), ("exposure", C.c_float), ("threshold", C.c_float),
+                ("tileShift", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+ADAPTIVE_FROM_NOISE, ADAPTIVE_FROM_MASK = 0, 1  # PTX_ADAPTIVE_FROM_* of include/ptx.h
+# The default margin of Renderer.adaptive_plan and of RendererHip::AdaptiveSettings (docs/NEXT_ROWS.md section 27): one tile.  Not tuned.
+ADAPTIVE_DEFAULTS = dict(dilate=1)
 
 TONE_MAPPING_SDR, TONE_MAPPING_HDR = 0, 1
 ACCEL_REFIT, ACCEL_REBUILD = 0, 1
@@ -566,6 +587,10 @@ def load_hip() -> C.CDLL:
         lib.ptx_device_noise_half_ptr.restype = P
         lib.ptx_noise_meter.argtypes = [P, C.POINTER(NoiseDesc)]
         lib.ptx_read_noise.argtypes = [P, C.POINTER(NoiseResult), P, C.c_size_t]
+        lib.ptx_adaptive_plan.argtypes = [P, C.POINTER(AdaptiveDesc), C.POINTER(AdaptivePlan)]
+        lib.ptx_read_adaptive.argtypes = [P, C.POINTER(AdaptivePlan), P, C.c_size_t, P, C.c_size_t]
+        lib.ptx_adaptive_clear.argtypes = [P]
+        lib.ptx_noise_meter_adaptive.argtypes = [P, C.POINTER(AdaptiveMeterDesc)]
         _hip = lib
     return _hip
 
@@ -1152,6 +1177,45 @@ class Renderer:
         tiles = np.empty((out.tilesY, out.tilesX), dtype=np.float32)
         self._check(self.lib.ptx_read_noise(self.handle, C.byref(out), tiles.ctypes.data, tiles.nbytes))
         return out, tiles
+
+    def adaptive_plan(self, tile_shift: int = NOISE_DEFAULTS["tile_shift"], mask=None, dilate: int = ADAPTIVE_DEFAULTS["dilate"], frames_a: int = 0,
+                      frames_b: int = 0) -> AdaptivePlan:
+        """ptx_adaptive_plan: commit frames_a / frames_b (rendered into half 0 / 1 under the plan being replaced) to the counts, then plan
+        the next render calls: the tiles within `dilate` of a seed -- a tile the last meter call left open or, with `mask` (tilesY x tilesX,
+        non-zero = seed), the host's own.  Synchronises."""
+        d = AdaptiveDesc(tile_shift, ADAPTIVE_FROM_NOISE, None, dilate, frames_a, frames_b, 0, (C.c_uint32 * 2)(0, 0))
+        if mask is not None:
+            m = np.asarray(mask)
+            m = np.ascontiguousarray(m if m.dtype == np.uint8 else m != 0, dtype=np.uint8)  # bytes go to the device as they are
+            side = 1 << tile_shift
+            tiles = ((getattr(self, "width", 0) + side - 1) // side) * ((getattr(self, "height", 0) + side - 1) // side)
+            if 3 <= tile_shift <= 6 and m.size != tiles:  # the library copies tilesX * tilesY bytes: never from a smaller array
+                raise PtxError(f"adaptive_plan: the mask has {m.size} entries, the frame has {tiles} tiles of {side} pixels")
+            d.source, d.mask = ADAPTIVE_FROM_MASK, m.ctypes.data
+        out = AdaptivePlan()
+        self._check(self.lib.ptx_adaptive_plan(self.handle, C.byref(d), C.byref(out)))
+        return out
+
+    def read_adaptive(self):
+        """ptx_read_adaptive: (AdaptivePlan, the active tile ids in ascending order, the counts as a 2 x tilesY x tilesX uint32 array:
+        frames per tile in half 0 and in half 1); synchronises."""
+        out = AdaptivePlan()
+        self._check(self.lib.ptx_read_adaptive(self.handle, C.byref(out), None, 0, None, 0))
+        tiles = np.empty(out.activeTiles, dtype=np.uint32)
+        counts = np.empty((2, out.tilesY, out.tilesX), dtype=np.uint32)
+        self._check(self.lib.ptx_read_adaptive(self.handle, C.byref(out), tiles.ctypes.data, tiles.nbytes, counts.ctypes.data, counts.nbytes))
+        return out, tiles, counts
+
+    def adaptive_clear(self):
+        """ptx_adaptive_clear: render calls cover the frame again; the counts stay."""
+        self._check(self.lib.ptx_adaptive_clear(self.handle))
+
+    def noise_meter_adaptive(self, pending_a: int, pending_b: int, normalize_to: int, exposure: float = 1.0, threshold: float = NOISE_DEFAULTS["threshold"],
+                             tile_shift: int = NOISE_DEFAULTS["tile_shift"], write_sum: bool = False):
+        """ptx_noise_meter_adaptive: noise_meter() with every tile's own sample counts (the committed ones plus pending_a / pending_b on
+        the tiles of the plan in force); with write_sum the internal image holds every tile's sum scaled to normalize_to samples."""
+        d = AdaptiveMeterDesc(pending_a, pending_b, normalize_to, exposure, threshold, tile_shift, NOISE_WRITE_SUM if write_sum else 0, (C.c_uint32 * 2)(0, 0))
+        self._check(self.lib.ptx_noise_meter_adaptive(self.handle, C.byref(d)))
 
     def accum_ptr(self) -> int:
         return int(self.lib.ptx_device_accum_ptr(self.handle) or 0)

@@ -36,7 +36,10 @@ static int setTileShard(PtxRenderer *r, const PtxTileShard *s)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_set_tile_shard: need rank < worldSize and tileSize a multiple of 8");
     const PtxTileShard &now = r->frame.shard;
     if (now.rank != s->rank || now.worldSize != s->worldSize || now.tileSize != s->tileSize)
+    {
         r->frame.unbindShard();
+        dropAdaptive(r); // an adaptive plan and its counts belong to the unsharded frame
+    }
     r->frame.shard = *s;
     return PTX_OK;
 }
@@ -70,6 +73,8 @@ static int bindShardAccumulation(PtxRenderer *r, void *devShard, size_t bytes)
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_bind_shard_accumulation: the buffer must hold ptx_shard_bytes() = %zu bytes", need);
     r->frame.boundShard = static_cast<float4 *>(devShard);
     r->frame.boundShardBytes = devShard ? need : 0;
+    if (devShard) // the shard buffer is laid out by the shard's own tiles: an adaptive plan ends here
+        (void)adaptiveClear(r);
     return PTX_OK;
 }
 

@@ -56,12 +56,20 @@ struct NoiseArgs
 
 PT_DEV bool noiseFinite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-// steps 3 - 5 for one pixel: 0 counted, 1 black, 2 rejected; q is 0 unless counted and not black
-PT_DEV uint32_t noisePixel(const float4 &A, const float4 &B, const float4 &S, const NoiseArgs &a, uint32_t &q)
+// What ptx_noise_meter_adaptive knows per tile (pt_adaptive.hpp): step 2 from the tile's own counts, the factor step 1 stores S with,
+// and flags: 1 a half without a sample (every pixel rejected, the tile not converged), 2 S is stored as S * k
+struct NoiseTileScale
 {
-    const float ar = A.x * a.sa, ag = A.y * a.sa, ab = A.z * a.sa;
-    const float br = B.x * a.sb, bg = B.y * a.sb, bb = B.z * a.sb;
-    const float cr = S.x * a.st, cg = S.y * a.st, cb = S.z * a.st;
+    float sa, sb, st, k;
+    uint32_t flags;
+};
+
+// steps 3 - 5 for one pixel: 0 counted, 1 black, 2 rejected; q is 0 unless counted and not black
+PT_DEV uint32_t noisePixel(const float4 &A, const float4 &B, const float4 &S, float sa, float sb, float st, uint32_t &q)
+{
+    const float ar = A.x * sa, ag = A.y * sa, ab = A.z * sa;
+    const float br = B.x * sb, bg = B.y * sb, bb = B.z * sb;
+    const float cr = S.x * st, cg = S.y * st, cb = S.z * st;
     const float D = (abs_(ar - br) + abs_(ag - bg)) + abs_(ab - bb);
     const float m = (cr + cg) + cb;
     q = 0u;
@@ -74,8 +82,10 @@ PT_DEV uint32_t noisePixel(const float4 &A, const float4 &B, const float4 &S, co
     return 0u;
 }
 
-template <bool WRITE_SUM>
-__global__ void __launch_bounds__(kNoiseBlock) k_noise_tiles(NoiseArgs a)
+// The body of k_noise_tiles and, with ADAPTIVE, of k_noise_tiles_adaptive (pt_adaptive.hpp), which has filled `scale` for the
+// block's tiles before it calls this: the barrier below orders those stores too.
+template <bool WRITE_SUM, bool ADAPTIVE>
+PT_DEV void noiseTilesBody(const NoiseArgs &a, const NoiseTileScale *scale)
 {
     __shared__ unsigned long long tileQ[64];
     __shared__ uint32_t tileN[64];
@@ -126,10 +136,21 @@ __global__ void __launch_bounds__(kNoiseBlock) k_noise_tiles(NoiseArgs a)
             if (!inX || y >= a.height)
                 continue;
             const float4 S = make_float4(A[j].x + B[j].x, A[j].y + B[j].y, A[j].z + B[j].z, A[j].w + B[j].w); // step 1
-            if (WRITE_SUM)
-                a.sum[(size_t)y * a.width + x] = S;
-            uint32_t q;
-            const uint32_t cls = noisePixel(A[j], B[j], S, a, q);
+            uint32_t q, cls;
+            if (ADAPTIVE)
+            {
+                const NoiseTileScale v = scale[lty * perSide + ltx];
+                if (WRITE_SUM)
+                    a.sum[(size_t)y * a.width + x] = (v.flags & 2u) ? make_float4(S.x * v.k, S.y * v.k, S.z * v.k, S.w * v.k) : S;
+                q = 0u;
+                cls = (v.flags & 1u) ? 2u : noisePixel(A[j], B[j], S, v.sa, v.sb, v.st, q);
+            }
+            else
+            {
+                if (WRITE_SUM)
+                    a.sum[(size_t)y * a.width + x] = S;
+                cls = noisePixel(A[j], B[j], S, a.sa, a.sb, a.st, q);
+            }
             if (cls == 2u)
                 rejected++;
             else
@@ -164,6 +185,8 @@ __global__ void __launch_bounds__(kNoiseBlock) k_noise_tiles(NoiseArgs a)
         const uint32_t n = tileN[t];
         const float E = n ? (float)((double)Q / ((double)n * 65536.0)) : 0.0f; // step 6
         conv = E <= a.threshold ? 1u : 0u;
+        if (ADAPTIVE && (scale[t].flags & 1u)) // an unsampled tile never freezes
+            conv = 0u;
         eBits = __float_as_uint(E); // E >= 0 and never a NaN: the order of the bits is the order of the values
         NoiseTile rec;
         rec.Q = Q;
@@ -190,6 +213,12 @@ __global__ void __launch_bounds__(kNoiseBlock) k_noise_tiles(NoiseArgs a)
         reinterpret_cast<uint4 *>(rec)[0] = lo;
         reinterpret_cast<uint4 *>(rec)[1] = hi;
     }
+}
+
+template <bool WRITE_SUM>
+__global__ void __launch_bounds__(kNoiseBlock) k_noise_tiles(NoiseArgs a)
+{
+    noiseTilesBody<WRITE_SUM, false>(a, nullptr);
 }
 
 struct NoiseResolveArgs

@@ -4,9 +4,10 @@
 // section 22), which runs the output stage's last kernel, or the screen path's, again with a grade in the place of the tone mapping, and
 // the local exposure between the meter and the output stage (ptx_local_exposure, ptx_read_local_exposure, ptx_postprocess_local: section 23),
 // and the enlarging screen path (ptx_present_upscaled: section 25), which is presentFrame with pt_upscale.hpp's kernel at its end,
-// and the noise metering of an offline render's two half-sums (ptx_noise_halves, ptx_noise_meter, ptx_read_noise: section 26).
+// and the noise metering of an offline render's two half-sums (ptx_noise_halves, ptx_noise_meter, ptx_read_noise: section 26) with the
+// adaptive sampling it steers (ptx_adaptive_plan, ptx_read_adaptive, ptx_adaptive_clear, ptx_noise_meter_adaptive: section 27).
 // What the entry points share stands first: the source rule, the refusal ladder, the read-back's end, ptx_resize's part (section 24).
-// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp, pt_upscale.hpp, pt_noise.hpp; state: OutputState, the member `output` of the handle.
+// Kernels: pt_post.hpp, pt_present.hpp, pt_meter.hpp, pt_grade.hpp, pt_local_exposure.hpp, pt_upscale.hpp, pt_noise.hpp, pt_adaptive.hpp; state: OutputState, the member `output` of the handle.
 // Included by pt_runtime.hpp ahead of pt_frame_host.hpp, whose ptx_resize ends in outputResized; every function takes a valid or null
 // handle and returns a PTX_* code.
 #pragma once
@@ -582,6 +583,21 @@ static void dropNoiseHalves(PtxRenderer *r)
     }
 }
 
+// What ptx_resize, a ptx_set_tile_shard that changes the shard and ptx_noise_halves(0) do to adaptive sampling: plan and counts go.
+static void dropAdaptive(PtxRenderer *r)
+{
+    OutputState::AdaptiveState &s = r->output.adaptive;
+    s.counts.release();
+    s.list.release();
+    s.active.release();
+    s.seed.release();
+    s.mask.release();
+    s.result.release();
+    s.plan = {};
+    s.tileShift = s.generation = 0u;
+    s.planned = s.counted = false;
+}
+
 static int noiseHalves(PtxRenderer *r, uint32_t enable)
 {
     const char *who = "ptx_noise_halves";
@@ -592,6 +608,7 @@ static int noiseHalves(PtxRenderer *r, uint32_t enable)
         if (r->output.noise.half[0].p || r->output.noise.half[1].p)
             HIP_TRY(r, hipSetDevice(r->device));
         dropNoiseHalves(r);
+        dropAdaptive(r);
         return PTX_OK;
     }
     if (!r->frame.width)
@@ -609,6 +626,12 @@ static int noiseHalves(PtxRenderer *r, uint32_t enable)
     }
     for (DevBuf<float4> &h : s.half)
         HIP_TRY(r, hipMemsetAsync(h.p, 0, r->frame.bytes(), r->stream));
+    OutputState::AdaptiveState &ad = r->output.adaptive;
+    if (ad.tileShift) // the halves start over, and so do the frames counted in them
+    {
+        HIP_TRY(r, hipMemsetAsync(ad.counts.p, 0, 2u * (size_t)ad.numTiles() * sizeof(uint32_t), r->stream));
+        ad.counted = false;
+    }
     return PTX_OK;
 }
 
@@ -670,6 +693,7 @@ static int noiseMeter(PtxRenderer *r, const PtxNoiseDesc *d)
     s.calls += 1u;
     s.tilesX = tilesX;
     s.tilesY = tilesY;
+    s.tileShift = sh;
     return PTX_OK;
 }
 
@@ -690,6 +714,187 @@ static int readNoise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors, siz
     return readBack(r, out, s.result.p, sizeof(PtxNoiseResult));
 }
 
+// ---- adaptive sampling (docs/NEXT_ROWS.md section 27; semantics: include/ptx.h ptx_adaptive_plan; kernels: pt_adaptive.hpp) ----------
+
+// ptx_adaptive_plan: one launch of one workgroup and the read-back of its result.  Every refusal comes before the first allocation,
+// copy or launch.
+static int adaptivePlan(PtxRenderer *r, const PtxAdaptiveDesc *d, PtxAdaptivePlan *out)
+{
+    const char *who = "ptx_adaptive_plan";
+    if (!r || !d || !out)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const uint32_t maxFrames = 1u << 24;
+    if (d->tileShift < 3u || d->tileShift > kNoiseBlockShift || d->source > PTX_ADAPTIVE_FROM_MASK || d->flags || d->reserved[0] || d->reserved[1] || d->dilate > 2u ||
+        d->framesA > maxFrames || d->framesB > maxFrames)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need tileShift in 3 .. 6 (%u), a source of 0 or 1 (%u), no flag (0x%x), reserved 0 (%u, %u), dilate in 0 .. 2 (%u) "
+                    "and frame counts of at most 2^24 (%u, %u)", who, d->tileShift, d->source, d->flags, d->reserved[0], d->reserved[1], d->dilate, d->framesA, d->framesB);
+    if (d->source == PTX_ADAPTIVE_FROM_MASK && !d->mask)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: PTX_ADAPTIVE_FROM_MASK needs a mask", who);
+    if (const int rc = outputRefusal(r, who, NEEDS_FRAME | NEEDS_ONE_SHARD))
+        return rc;
+    const OutputState::NoiseState &ns = r->output.noise;
+    if (d->source == PTX_ADAPTIVE_FROM_NOISE && (!ns.calls || ns.tileShift != d->tileShift))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: PTX_ADAPTIVE_FROM_NOISE needs an accepted meter call of tileShift %u (the last one: %u)", who, d->tileShift, ns.tileShift);
+    OutputState::AdaptiveState &s = r->output.adaptive;
+    if (s.tileShift && s.tileShift != d->tileShift && (s.counted || (s.planned && (d->framesA | d->framesB))))
+        return fail(r, PTX_ERROR_NOT_READY, "%s: the counts are of tileShift %u, not %u, and are not all zero", who, s.tileShift, d->tileShift);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t W = r->frame.width, H = r->frame.height, sh = d->tileShift;
+    const uint32_t tilesX = (W + (1u << sh) - 1u) >> sh, tilesY = (H + (1u << sh) - 1u) >> sh;
+    const size_t tiles = (size_t)tilesX * tilesY;
+    if (s.tileShift != sh) // the first accepted call, or all counts zero and nothing to commit: the counts are made (anew) and zeroed
+    {
+        // no counts and no plan until all of it stands: an allocation that fails below leaves the handle without either
+        s.tileShift = s.generation = 0u;
+        s.planned = s.counted = false;
+        s.plan = {};
+        HIP_TRY(r, s.counts.alloc(2u * tiles));
+        HIP_TRY(r, s.list.alloc(tiles));
+        HIP_TRY(r, s.active.alloc(tiles));
+        HIP_TRY(r, s.seed.alloc(tiles));
+        HIP_TRY(r, s.result.alloc(1));
+        HIP_TRY(r, hipMemsetAsync(s.counts.p, 0, 2u * tiles * sizeof(uint32_t), r->stream));
+        s.tileShift = sh;
+        s.plan.tilesX = tilesX;
+        s.plan.tilesY = tilesY;
+    }
+    if (d->source == PTX_ADAPTIVE_FROM_MASK)
+    {
+        HIP_TRY(r, s.mask.alloc(tiles));
+        HIP_TRY(r, hipMemcpyAsync(s.mask.p, d->mask, tiles, hipMemcpyHostToDevice, r->stream));
+    }
+    AdaptiveArgs a;
+    a.countA = s.counts.p;
+    a.countB = s.counts.p + tiles;
+    a.active = s.active.p;
+    a.seed = s.seed.p;
+    a.records = d->source == PTX_ADAPTIVE_FROM_NOISE ? ns.tiles.p : nullptr;
+    a.mask = d->source == PTX_ADAPTIVE_FROM_MASK ? s.mask.p : nullptr;
+    a.list = s.list.p;
+    a.plan = s.result.p;
+    a.width = W; a.height = H; a.tileShift = sh; a.tilesX = tilesX; a.tilesY = tilesY;
+    a.hadPlan = s.planned ? 1u : 0u;
+    a.framesA = d->framesA; a.framesB = d->framesB; a.dilate = d->dilate;
+    a.generation = s.generation + 1u;
+    k_adaptive_plan<<<1, kAdaptiveBlock, 0, r->stream>>>(a);
+    HIP_TRY(r, hipGetLastError());
+    if ((d->framesA | d->framesB) && (!s.planned || s.plan.activeTiles))
+        s.counted = true;
+    s.generation += 1u;
+    s.planned = true;
+    r->launch.hint.forget(); // learnt on another set of tiles
+    if (const int rc = readBack(r, &s.plan, s.result.p, sizeof(PtxAdaptivePlan)))
+    {
+        s.planned = false; // the list's length is unknown: renders cover the frame
+        return rc;
+    }
+    *out = s.plan;
+    return PTX_OK;
+}
+
+static int adaptiveClear(PtxRenderer *r)
+{
+    if (!r)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_adaptive_clear: null handle");
+    OutputState::AdaptiveState &s = r->output.adaptive;
+    if (s.planned)
+        r->launch.hint.forget();
+    s.planned = false;
+    s.plan.activeTiles = s.plan.activePixels = s.plan.seedTiles = 0u;
+    return PTX_OK;
+}
+
+static int readAdaptive(PtxRenderer *r, PtxAdaptivePlan *out, uint32_t *tiles, size_t tileBytes, uint32_t *counts, size_t countBytes)
+{
+    const char *who = "ptx_read_adaptive";
+    if (!r || !out)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const OutputState::AdaptiveState &s = r->output.adaptive;
+    if (!s.tileShift)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: call ptx_adaptive_plan first", who);
+    const size_t wantTiles = (size_t)s.plan.activeTiles * sizeof(uint32_t), wantCounts = 2u * (size_t)s.numTiles() * sizeof(uint32_t);
+    if ((tiles && tileBytes != wantTiles) || (counts && countBytes != wantCounts))
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: the list of %u tiles is %zu bytes and the counts of %u x %u tiles are %zu", who, s.plan.activeTiles, wantTiles,
+                    s.plan.tilesX, s.plan.tilesY, wantCounts);
+    HIP_TRY(r, hipSetDevice(r->device));
+    if (tiles && wantTiles)
+        HIP_TRY(r, hipMemcpyAsync(tiles, s.list.p, wantTiles, hipMemcpyDeviceToHost, r->stream));
+    if (counts)
+        HIP_TRY(r, hipMemcpyAsync(counts, s.counts.p, wantCounts, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(r, hipStreamSynchronize(r->stream));
+    HIP_TRY(r, hipGetLastError());
+    *out = s.plan;
+    return PTX_OK;
+}
+
+// ptx_noise_meter_adaptive: noiseMeter with the scale factors per tile (k_noise_tiles_adaptive) and the same second launch
+static int noiseMeterAdaptive(PtxRenderer *r, const PtxAdaptiveMeterDesc *d)
+{
+    const char *who = "ptx_noise_meter_adaptive";
+    if (!r || !d)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: null argument", who);
+    const uint32_t maxFrames = 1u << 24;
+    if (d->pendingA > maxFrames || d->pendingB > maxFrames || !d->normalizeTo || d->normalizeTo > (1u << 25) || d->tileShift < 3u || d->tileShift > kNoiseBlockShift ||
+        (d->flags & ~(uint32_t)PTX_NOISE_WRITE_SUM) || d->reserved[0] || d->reserved[1])
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need pendingA and pendingB of at most 2^24 (%u, %u), normalizeTo in 1 .. 2^25 (%u), tileShift in 3 .. 6 (%u), no "
+                    "unknown flag (0x%x) and reserved 0 (%u, %u)", who, d->pendingA, d->pendingB, d->normalizeTo, d->tileShift, d->flags, d->reserved[0], d->reserved[1]);
+    if (!finiteFloat(d->exposure) || !finiteFloat(d->threshold) || !(d->exposure > 0.0f) || d->threshold < 0.0f)
+        return fail(r, PTX_ERROR_INVALID_ARGUMENT, "%s: need a finite exposure > 0 (%g) and a finite threshold >= 0 (%g)", who, (double)d->exposure,
+                    (double)d->threshold);
+    if (const int rc = outputRefusal(r, who, NEEDS_FRAME | NEEDS_ONE_SHARD))
+        return rc;
+    OutputState::NoiseState &s = r->output.noise;
+    if (!s.half[0].p || !s.half[1].p)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no halves (call ptx_noise_halves)", who);
+    const OutputState::AdaptiveState &ad = r->output.adaptive;
+    if (!ad.tileShift)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: no counts (call ptx_adaptive_plan first)", who);
+    if (ad.tileShift != d->tileShift)
+        return fail(r, PTX_ERROR_NOT_READY, "%s: the counts are of tileShift %u, not %u", who, ad.tileShift, d->tileShift);
+    HIP_TRY(r, hipSetDevice(r->device));
+    const uint32_t W = r->frame.width, H = r->frame.height, sh = d->tileShift;
+    const uint32_t tilesX = ad.plan.tilesX, tilesY = ad.plan.tilesY;
+    const dim3 grid((W + kNoiseBlockSide - 1u) / kNoiseBlockSide, (H + kNoiseBlockSide - 1u) / kNoiseBlockSide);
+    const size_t tiles = (size_t)tilesX * tilesY, groups = (size_t)grid.x * grid.y;
+    HIP_TRY(r, s.result.alloc(1));
+    HIP_TRY(r, s.tiles.alloc(tiles));
+    HIP_TRY(r, s.tileErrors.alloc(tiles));
+    HIP_TRY(r, s.records.alloc(groups * kNoiseRecordWords));
+    AdaptiveNoiseArgs a;
+    a.noise.halfA = s.half[0].p;
+    a.noise.halfB = s.half[1].p;
+    a.noise.sum = r->frame.image.p;
+    a.noise.tiles = s.tiles.p;
+    a.noise.tileErrors = s.tileErrors.p;
+    a.noise.records = s.records.p;
+    a.noise.width = W; a.noise.height = H; a.noise.tileShift = sh; a.noise.tilesX = tilesX; a.noise.tilesY = tilesY;
+    a.noise.sa = a.noise.sb = a.noise.st = 0.0f;
+    a.noise.threshold = d->threshold;
+    a.countA = ad.counts.p;
+    a.countB = ad.counts.p + tiles;
+    a.active = ad.planned ? ad.active.p : nullptr;
+    a.pendingA = d->pendingA; a.pendingB = d->pendingB; a.normalizeTo = d->normalizeTo;
+    a.exposure = d->exposure;
+    if (d->flags & PTX_NOISE_WRITE_SUM)
+        k_noise_tiles_adaptive<true><<<grid, kNoiseBlock, 0, r->stream>>>(a);
+    else
+        k_noise_tiles_adaptive<false><<<grid, kNoiseBlock, 0, r->stream>>>(a);
+    NoiseResolveArgs v;
+    v.records = s.records.p;
+    v.recordCount = (uint32_t)groups;
+    v.result = s.result.p;
+    v.tilesX = tilesX;
+    v.tilesY = tilesY;
+    v.calls = s.calls + 1u;
+    k_noise_resolve<<<1, kNoiseResolveBlock, 0, r->stream>>>(v);
+    HIP_TRY(r, hipGetLastError());
+    s.calls += 1u;
+    s.tilesX = tilesX;
+    s.tilesY = tilesY;
+    s.tileShift = sh;
+    return PTX_OK;
+}
+
 // What ptx_resize does to the output stage: the output is not ready, G and the grid of ptx_local_exposure go with the extent they were
 // made for, as do the halves of ptx_noise_halves and the count of ptx_noise_meter calls, and the meter starts over, its exposure having
 // been metered on an image of the old extent.  The present image, the LUT and the kept grade desc stay: they belong to the window and
@@ -702,7 +907,8 @@ static int outputResized(PtxRenderer *r)
     o.localGrid.release();
     o.localReady = false;
     dropNoiseHalves(r);
+    dropAdaptive(r);
     o.noise.calls = 0u;
-    o.noise.tilesX = o.noise.tilesY = 0u;
+    o.noise.tilesX = o.noise.tilesY = o.noise.tileShift = 0u;
     return meterReset(r);
 }

@@ -494,6 +494,22 @@ static int renderWavefront(PtxRenderer *r, RenderPlan &pl, uint32_t sampleCount)
     return endLaunch(r, { PendingLaunch::kWavefront, pl.bounces, pl.tailBelow, canonical ? p.numSlots : 0u, p.numSlots - p.ownedPixels * p.frames, epoch, r->env.verbose });
 }
 
+// The launch covers the tiles of the adaptive plan in force (ptx_adaptive_plan, pt_output_host.hpp), in the plan's own tile size:
+// slotPixel takes slot k's tile from the list.  Only renderImpl does this; every other launch keeps the frame.
+static void coverPlan(LaunchParams &p, const OutputState::AdaptiveState &s)
+{
+    p.tileSize = 1u << s.tileShift;
+    p.tilesX = s.plan.tilesX;
+    p.numTiles = s.plan.tilesX * s.plan.tilesY;
+    p.rank = 0u;
+    p.worldSize = 1u;
+    p.ownedTiles = s.plan.activeTiles;
+    p.slotsPerFrame = s.plan.activeTiles * p.tileSize * p.tileSize;
+    p.ownedPixels = s.plan.activePixels;
+    p.numSlots = p.slotsPerFrame * p.frames;
+    p.tileList = s.list.p;
+}
+
 static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const PtxLightsUbo *lights, uint32_t firstFrame, uint32_t frames)
 {
     if (!r || !uniform || !lights)
@@ -506,6 +522,8 @@ static int renderImpl(PtxRenderer *r, const PtxRaygenUniformData *uniform, const
         return fail(r, PTX_ERROR_INVALID_ARGUMENT, "ptx_render: LightCount %u exceeds MaxLightCount", lights->LightCount);
     RenderPlan pl;
     pl.p = makeParams(r, uniform, firstFrame, frames);
+    if (r->output.adaptive.planned) // an adaptive plan is in force: its tiles, as the one shard of the frame
+        coverPlan(pl.p, r->output.adaptive);
     if (const int rc = beginLaunch(r, lights, pl.p, (uint64_t)pl.p.slotsPerFrame * frames))
         return rc;
     if (pl.p.numSlots == 0)

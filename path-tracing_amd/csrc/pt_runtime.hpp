@@ -42,6 +42,7 @@
 #include "pt_local_exposure.hpp"
 #include "pt_upscale.hpp"
 #include "pt_noise.hpp"
+#include "pt_adaptive.hpp"
 
 // =====================================================================================
 // Host side: the renderer object behind the C-ABI
@@ -297,9 +298,25 @@ struct OutputState
         DevBuf<NoiseTile> tiles;        // (Q_t, n_t, converged) per tile ...
         DevBuf<float> tileErrors;       // ... and E_t, the map ptx_read_noise copies out
         DevBuf<uint32_t> records;       // kNoiseRecordWords words per workgroup of k_noise_tiles
-        uint32_t tilesX = 0, tilesY = 0; // of the last accepted call
+        uint32_t tilesX = 0, tilesY = 0, tileShift = 0; // of the last accepted call
         uint32_t calls = 0;             // accepted calls since creation or ptx_resize
     } noise;
+    // adaptive sampling (ptx_adaptive_plan, ptx_noise_meter_adaptive, docs/NEXT_ROWS.md section 27): everything is made by the first
+    // accepted ptx_adaptive_plan and released by ptx_resize, a change of the tile shard and ptx_noise_halves(0) (dropAdaptive)
+    struct AdaptiveState
+    {
+        DevBuf<uint32_t> counts;        // countA[numTiles], then countB[numTiles]: frames per tile and half
+        DevBuf<uint32_t> list;          // the active tile ids of the plan in force, ascending: what slotPixel reads
+        DevBuf<uint8_t> active, seed;   // a flag per tile: in the plan in force / a seed of the last call
+        DevBuf<uint8_t> mask;           // the device copy of a PTX_ADAPTIVE_FROM_MASK call's mask
+        DevBuf<PtxAdaptivePlan> result; // written whole by every call
+        PtxAdaptivePlan plan = {};      // the host's copy of it
+        uint32_t tileShift = 0;         // of the counts; 0: there are none
+        uint32_t generation = 0;        // accepted ptx_adaptive_plan calls since the counts were made
+        bool planned = false;           // a plan is in force: renderImpl covers `list`
+        bool counted = false;           // some count may be non-zero
+        uint32_t numTiles() const { return plan.tilesX * plan.tilesY; }
+    } adaptive;
     void invalidate() { ready = false; } // the present image stays: it belongs to the window, not to the render extent
 };
 

@@ -108,6 +108,7 @@ struct LaunchParams
     uint32_t numSlots;
     uint32_t ownedPixels; // slots of one frame that map to a pixel inside the image
     uint32_t framesPerWave; // 1, 2, 4 or 8 (divides frames): a wave of 64 slots = 64 / framesPerWave pixels x framesPerWave frames
+    const uint32_t *tileList; // null, or the ownedTiles tile ids of an adaptive plan, ascending (ptx_adaptive_plan): rank 0 of 1 then
 };
 
 // slot <-> (frame of the batch, slot inside the frame).  The samples a batch adds to ONE pixel sit in neighbouring lanes: their
@@ -125,11 +126,17 @@ PT_DEV void slotFrame(const LaunchParams &p, uint32_t slot, uint32_t &f, uint32_
 
 // slot -> pixel.  Owned tiles are rank, rank+world, ...; inside a tile pixels are laid
 // out in 8x8 blocks so that one wave64 = one 8x8 pixel block (coherent primary rays).
-PT_DEV uint32_t slotPixel(const LaunchParams &p, uint32_t slotInFrame)
+// PLANNED: the kernels of ptx_render (k_generate, the first bounce's, k_restart, k_finish_restarts, k_megakernel, k_accumulate), whose
+// launch may cover the list of an adaptive plan instead (LaunchParams::tileList, ptx_adaptive_plan): slot k's tile is then the list's
+// entry k.  Every other kernel keeps the frame and never reads the field.
+template <bool PLANNED>
+PT_DEV uint32_t slotPixelOf(const LaunchParams &p, uint32_t slotInFrame)
 {
     const uint32_t ts = p.tileSize, perTile = ts * ts;
     const uint32_t k = slotInFrame / perTile, o = slotInFrame % perTile;
-    const uint32_t tile = p.rank + k * p.worldSize;
+    uint32_t tile = p.rank + k * p.worldSize;
+    if (PLANNED && p.tileList)
+        tile = k < p.ownedTiles ? p.tileList[k] : p.numTiles;
     const uint32_t bpr = ts / 8, blk = o / 64, ib = o % 64;
     const uint32_t x = (tile % p.tilesX) * ts + (blk % bpr) * 8 + (ib % 8);
     const uint32_t y = (tile / p.tilesX) * ts + (blk / bpr) * 8 + (ib / 8);
@@ -137,6 +144,8 @@ PT_DEV uint32_t slotPixel(const LaunchParams &p, uint32_t slotInFrame)
         return kNoPixel;
     return y * p.width + x;
 }
+PT_DEV uint32_t slotPixel(const LaunchParams &p, uint32_t slotInFrame) { return slotPixelOf<false>(p, slotInFrame); }
+PT_DEV uint32_t slotPixelPlanned(const LaunchParams &p, uint32_t slotInFrame) { return slotPixelOf<true>(p, slotInFrame); }
 
 // raygen.rgen:44-60: start one sample of a slot (jitter draws, primary ray; with DIFF also the
 // offset rays of raygen.rgen:56-58)
@@ -247,7 +256,7 @@ PT_DEV uint32_t pixelOfSlot(const LaunchParams &p, uint32_t slot)
 {
     uint32_t f, s;
     slotFrame(p, slot, f, s);
-    return slotPixel(p, s);
+    return slotPixelPlanned(p, s);
 }
 // ... and what k_generate, the first bounce's kernels and the megakernel start a slot from: its pixel and the RNG state of its
 // first sample (raygen.rgen:38).  The state is of no use where the pixel is kNoPixel.
@@ -255,7 +264,7 @@ PT_DEV void slotStart(const LaunchParams &p, uint32_t slot, uint32_t &pixel, uin
 {
     uint32_t f, s;
     slotFrame(p, slot, f, s);
-    pixel = slotPixel(p, s);
+    pixel = slotPixelPlanned(p, s);
     rng = initRng(pixel % p.width, pixel / p.width, p.width, p.firstFrame + f);
 }
 
@@ -934,7 +943,7 @@ __global__ void __launch_bounds__(kBlock) k_accumulate(LaunchParams p, const flo
     for (uint32_t base = (blockIdx.x * blockDim.x + threadIdx.x) & ~63u; base < chunks * 64u; base += gridDim.x * blockDim.x)
     {
         const uint32_t chunk = base >> 6, s = chunk * pixelsPerWave + lane / g;
-        const uint32_t pixel = slotPixel(p, s);
+        const uint32_t pixel = slotPixelPlanned(p, s);
         const bool owner = sub == 0u && pixel != kNoPixel;
         const uint32_t at = shardMajor ? s : pixel;
         float4 acc = owner ? image[at] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);

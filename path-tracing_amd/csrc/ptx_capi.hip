@@ -451,6 +451,26 @@ int ptx_read_noise(PtxRenderer *r, PtxNoiseResult *out, float *tileErrors, size_
     return readNoise(r, out, tileErrors, bytes);
 }
 
+int ptx_adaptive_plan(PtxRenderer *r, const PtxAdaptiveDesc *desc, PtxAdaptivePlan *out)
+{
+    return adaptivePlan(r, desc, out);
+}
+
+int ptx_read_adaptive(PtxRenderer *r, PtxAdaptivePlan *out, uint32_t *tiles, size_t tileBytes, uint32_t *counts, size_t countBytes)
+{
+    return readAdaptive(r, out, tiles, tileBytes, counts, countBytes);
+}
+
+int ptx_adaptive_clear(PtxRenderer *r)
+{
+    return adaptiveClear(r);
+}
+
+int ptx_noise_meter_adaptive(PtxRenderer *r, const PtxAdaptiveMeterDesc *desc)
+{
+    return noiseMeterAdaptive(r, desc);
+}
+
 int ptx_read_moments(PtxRenderer *r, void *host, size_t bytes)
 {
     return readMoments(r, host, bytes);

@@ -25,9 +25,19 @@ uint32_t s_NoiseCalls = 0;             // render calls since the accumulation re
 PtxNoiseResult s_NoiseResult = {};     // of the last metered check, once read
 bool s_NoisePending = false;           // a ptx_noise_meter has been enqueued since s_NoiseResult was read
 
+// adaptive sampling (ptx.h "Adaptive sampling"): the checks plan the render calls that follow
+RendererHip::AdaptiveSettings s_AdaptiveSettings;
+uint32_t s_AdaptivePending[2] = { 0, 0 }; // samples rendered into half 0 / half 1 since the last ptx_adaptive_plan
+bool s_AdaptiveCounts = false;            // the handle holds counts: a ptx_adaptive_plan has been accepted since Init or OnResize
+
 bool NoiseIsOn()
 {
     return s_NoiseSettings.Enabled && !s_DebugPipeline;
+}
+
+bool AdaptiveIsOn()
+{
+    return s_AdaptiveSettings.Enabled && s_NoiseSettings.Enabled;
 }
 
 int BindNoiseHalf(uint32_t which)
@@ -38,10 +48,34 @@ int BindNoiseHalf(uint32_t which)
 // the check of Render, and with PTX_NOISE_WRITE_SUM what SaveOutput, Present and ReadAccumulationImage do first
 int MeterNoise(uint32_t flags)
 {
+    if (AdaptiveIsOn() && s_AdaptiveCounts) // every tile by its own counts; the sum scaled to the samples of all render calls
+    {
+        const PtxAdaptiveMeterDesc adaptive = { s_AdaptivePending[0], s_AdaptivePending[1], s_NoiseSamples[0] + s_NoiseSamples[1], PostProcessExposure(),
+                                                s_NoiseSettings.Threshold, s_NoiseSettings.TileShift, flags, { 0u, 0u } };
+        const int rc = ptx_noise_meter_adaptive(s_Renderer, &adaptive);
+        if (rc == PTX_OK)
+            s_NoisePending = true;
+        return rc;
+    }
     const PtxNoiseDesc desc = { s_NoiseSamples[0], s_NoiseSamples[1], PostProcessExposure(), s_NoiseSettings.Threshold, s_NoiseSettings.TileShift, flags, { 0u, 0u } };
     const int rc = ptx_noise_meter(s_Renderer, &desc);
     if (rc == PTX_OK)
         s_NoisePending = true;
+    return rc;
+}
+
+// behind the check of Render: the samples since the last plan are committed and the tiles the check left open are planned
+int PlanAdaptive()
+{
+    const PtxAdaptiveDesc desc = { s_NoiseSettings.TileShift, PTX_ADAPTIVE_FROM_NOISE, nullptr, s_AdaptiveSettings.Dilate, s_AdaptivePending[0], s_AdaptivePending[1], 0u,
+                                   { 0u, 0u } };
+    PtxAdaptivePlan plan;
+    const int rc = ptx_adaptive_plan(s_Renderer, &desc, &plan);
+    if (rc == PTX_OK)
+    {
+        s_AdaptivePending[0] = s_AdaptivePending[1] = 0;
+        s_AdaptiveCounts = true;
+    }
     return rc;
 }
 }
@@ -92,6 +126,7 @@ void RendererHip::OnResize(uint32_t width, uint32_t height)
     s_Width = width;
     s_Height = height;
     Check(ptx_resize(s_Renderer, width, height));
+    s_AdaptiveCounts = false; // ptx_resize drops them
     ResetAccumulationImage();
 }
 
@@ -110,6 +145,12 @@ void RendererHip::SetTileShard(uint32_t rank, uint32_t worldSize, uint32_t tileS
 {
     const PtxTileShard shard = { rank, worldSize, tileSize };
     Check(ptx_set_tile_shard(s_Renderer, &shard));
+    if (s_AdaptiveCounts) // a change of the shard drops plan and counts: ask, and start over
+    {
+        PtxAdaptivePlan plan;
+        s_AdaptiveCounts = ptx_read_adaptive(s_Renderer, &plan, nullptr, 0, nullptr, 0) == PTX_OK;
+        ResetAccumulationImage();
+    }
 }
 
 // Renderer.cpp:801-808
@@ -119,9 +160,12 @@ void RendererHip::ResetAccumulationImage()
     s_AccumulationRestarted = true;
     s_NoiseSamples[0] = s_NoiseSamples[1] = 0;
     s_NoiseCalls = 0;
+    s_AdaptivePending[0] = s_AdaptivePending[1] = 0;
     if (s_Renderer && s_Width && s_NoiseSettings.Enabled) // makes the halves, or zeroes them again; the sum is formed from them when it is needed
     {
-        Check(ptx_noise_halves(s_Renderer, 1u));
+        Check(ptx_noise_halves(s_Renderer, 1u)); // (the counts of an adaptive render are zeroed with them)
+        if (s_AdaptiveCounts)
+            Check(ptx_adaptive_clear(s_Renderer));
         return;
     }
     if (s_Renderer && s_Width)
@@ -169,9 +213,18 @@ void RendererHip::Render()
     Check(ptx_render(s_Renderer, &rgenData, &lights));
     s_NoiseSamples[which] += s_SamplesPerFrame;
     s_NoiseCalls++;
-    const uint32_t every = s_NoiseSettings.CheckEvery ? s_NoiseSettings.CheckEvery : 1u;
+    uint32_t every = s_NoiseSettings.CheckEvery ? s_NoiseSettings.CheckEvery : 1u;
+    if (AdaptiveIsOn())
+    {
+        s_AdaptivePending[which] += s_SamplesPerFrame;
+        every += every & 1u; // both halves receive the same samples under one plan
+    }
     if (s_NoiseCalls % every == 0u && s_NoiseSamples[1] && s_NoiseSamples[0] + s_NoiseSamples[1] >= s_NoiseSettings.MinSamples)
+    {
         Check(MeterNoise(0u));
+        if (AdaptiveIsOn())
+            Check(PlanAdaptive());
+    }
 }
 
 // With the NoiseSettings on the running sum is A + B: ptx_noise_meter forms it in the internal image (PTX_NOISE_WRITE_SUM), which is then
@@ -196,14 +249,36 @@ static int RebindNoiseHalf()
 void RendererHip::SetSettings(const NoiseSettings &settings)
 {
     const bool change = settings.Enabled != s_NoiseSettings.Enabled;
+    // the counts of an adaptive render are per tile of the old size: the accumulation starts over with the new one
+    const bool retile = !change && settings.Enabled && settings.TileShift != s_NoiseSettings.TileShift && s_AdaptiveCounts;
     s_NoiseSettings = settings;
+    if (retile)
+    {
+        ResetAccumulationImage(); // zeroes the counts and clears the plan: the first plan of the new tile size makes them anew
+        s_AdaptiveCounts = false; // ... and until then the checks are ptx_noise_meter's
+    }
     if (!change)
         return;
     if (!settings.Enabled && s_Renderer) // the binding returns to the internal image
+    {
         Check(ptx_noise_halves(s_Renderer, 0u));
+        s_AdaptiveCounts = false; // they go with the halves
+    }
     s_NoiseResult = {};
     s_NoisePending = false;
     ResetAccumulationImage(); // the samples so far are in the other kind of image
+}
+
+void RendererHip::SetSettings(const AdaptiveSettings &settings)
+{
+    const bool change = settings.Enabled != s_AdaptiveSettings.Enabled;
+    s_AdaptiveSettings = settings;
+    if (!change)
+        return;
+    if (s_Renderer && s_AdaptiveCounts) // render calls cover the frame again
+        Check(ptx_adaptive_clear(s_Renderer));
+    if (s_NoiseSettings.Enabled)
+        ResetAccumulationImage(); // the tiles start over with equal counts
 }
 
 PtxNoiseResult RendererHip::GetNoise()

@@ -210,6 +210,24 @@ public:
     static void SetSettings(const NoiseSettings &settings);
     static bool IsConverged();
     static PtxNoiseResult GetNoise();
+    // Adaptive sampling (ptx.h "Adaptive sampling", docs/NEXT_ROWS.md section 27).  It has effect only together with
+    // NoiseSettings::Enabled.  Enabled: at every check Render() enqueues ptx_noise_meter_adaptive with the samples rendered since the
+    // last check as the pending counts (ptx_noise_meter at the first check after Init or OnResize, when the handle holds no counts yet
+    // and every tile has received every sample) and then ptx_adaptive_plan(PTX_ADAPTIVE_FROM_NOISE, Dilate) with the same counts as
+    // framesA and framesB; the render calls that follow cover the tiles that check left open, and their margin.  The two halves must
+    // receive equal samples under one plan, so CheckEvery is rounded up to an even number.  IsConverged() is unchanged: every tile of
+    // the last check is converged -- not "no tile is active", because the margin keeps converged tiles active.  SaveOutput, Present
+    // and ReadAccumulationImage meter with PTX_NOISE_WRITE_SUM and normalizeTo = the samples of all render calls so far, so that every
+    // tile shows its own mean.  ResetAccumulationImage clears the plan and zeroes the counts, and so does a change of
+    // NoiseSettings::TileShift, whose tiles the counts are.  GetTotalSamples() counts render calls'
+    // samples; ptx_get_stats' pathSamples says what a call traced.  Sharded frames are refused.  Disabled (the default): every call
+    // enqueues exactly what it did.  The default is ADAPTIVE_DEFAULTS of the Python package; nobody has tuned it.
+    struct AdaptiveSettings
+    {
+        bool Enabled = false;
+        uint32_t Dilate = 1;
+    };
+    static void SetSettings(const AdaptiveSettings &settings);
     // Variance-guided denoising (ptx.h "Variance-guided denoising").  Enabled together with the denoiser and the temporal
     // accumulation: SaveOutput and Present run ptx_render_guides -> ptx_temporal_accumulate_moments -> ptx_denoise_variance ->
     // ptx_postprocess_denoised; the normal and position sigmas are the DenoiserSettings'.  Disabled (the default), or without either
